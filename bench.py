@@ -17,12 +17,17 @@ data-parallel over 8 x MI355X" = 30 sequences per GPU; `"scaling": "strong"`); `
 before the timed region; weights are random-init at the full bert_base_6layer_6conect.json config.
 The optimizer step is outside the metric ("fwd+bwd", BASELINE.json) and is not run.
 
-Extra blocks:
+A plain run sets up, warms up, times the --steps steps, writes the outputs of the last timed step when
+--dump-outputs DIR is given, and prints the line.  Everything else is measured only with --full:
   roofline     - the dominant kernel (largest summed launch time among the GEMM variants), timed live
                  with HIP events on its launch stream over the timed region, priced in algorithmic
-                 FLOPs (2*M*N*K per launch) against the dense bf16 MFMA peak.
+                 FLOPs (2*M*N*K per launch) against the dense bf16 MFMA peak; the kernel ranking, the
+                 co-attention GEMMs and the exclusive (single-stream) figures from extra steps after it.
+  padded       - config.padded_schedule_value: the step on all 256 token rows (train workload, N = 1).
+  comm         - N > 1: the gradient exchange alone and the part of it the step does not hide.
   cpu_baseline - the CPU oracle (PyTorch fp32 restatement pinned to the reference's goldens) on a
                  bounded sample: BASELINE config 1 (1 image x 6 sequences), fwd+bwd, on the host cores.
+  (scoring workload: the roofline block and the per-candidate schedule beside the shared-context one.)
 """
 from __future__ import annotations
 
@@ -41,6 +46,8 @@ GRAPHS_AUTO_MAX_SEQ = 90           # --graphs auto: replayed hipGraphs up to thi
 PEAK_BF16_TFLOPS = 2500.0          # dense bf16 MFMA peak, MI355X (MI355X_MICROARCH.md: ~2.5 PF dense)
 F_FWD_BASE_GF = 76.808             # GFLOP / sequence forward without the vocab decoder
 F_DEC_ROW_GF = 0.04688             # GFLOP per decoded row (768 x 30522)
+DUMP_GRAD_SAMPLE = 4096            # --dump-outputs: gradient elements sampled per parameter tensor (seeded, the same every run)
+DUMP_SEED = 20240                  # --dump-outputs: seed of that sample
 
 
 def parse():
@@ -87,7 +94,7 @@ def parse():
                          "per 240 sequences; with --compact-inputs: descriptors + per-image tensors).  prefetch: the same "
                          "host batches through unimm_amd.inputs.DevicePrefetcher (pinned, copied one step ahead on a copy stream)")
     ap.add_argument("--gemm-profile", choices=["all", "dominant"], default="dominant",
-                    help="HIP-event timing inside the timed region: dominant (default) = the weight-gradient kernel only, which is "
+                    help="--full: HIP-event timing inside the timed region: dominant (default) = the weight-gradient kernel only, which is "
                          "what the roofline block needs; all = every GEMM launch (adds the all_gemm_* fields).  Two event records "
                          "around each of ~340 GEMM launches are not free: measured 1.3 ms of a 56 ms step at bs=240 (drain + "
                          "timestamp between back-to-back kernels) and 2 ms of 16 ms at 30 sequences per GPU (host launch rate)")
@@ -138,6 +145,14 @@ def parse():
                     help="N > 1: all-reduce per bucket, or reduce-scatter + all-gather per bucket")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--config", default=os.path.join(ROOT, "unimm_amd", "config", "bert_base_6layer_6conect.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (see the module docstring): GEMM event timing in the "
+                         "timed region and the roofline block, the padded schedule, the exchange figures (N > 1), the CPU baseline "
+                         "(unless --no-cpu-baseline), the per-candidate scoring schedule.  Off: only the timed steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, rank 0): "
+                         "the losses and scores the step returned and a fixed seeded sample of every parameter gradient "
+                         "(%d elements per tensor) with the full gradient norms" % DUMP_GRAD_SAMPLE)
     return ap.parse_args()
 
 
@@ -166,6 +181,37 @@ def host_cores():
 
 def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, arrays, module=None):
+    """--dump-outputs: every array as <path>/<name>.npy (float32, or float64 when it already is); with `module`, also
+    grad_sample = DUMP_GRAD_SAMPLE elements of every parameter gradient at seeded positions (all of a smaller tensor), the
+    tensors in named_parameters() order, and grad_norm = the fp64 norm of every such gradient."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        out[k] = v.double() if v.dtype == torch.float64 else v.float()
+    if module is not None:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        samples, norms = [], []
+        for _, p in module.named_parameters():
+            if p.grad is None:
+                continue
+            flat = p.grad.detach().reshape(-1)
+            n = flat.numel()
+            idx = torch.randint(0, n, (DUMP_GRAD_SAMPLE,), generator=g) if n > DUMP_GRAD_SAMPLE else torch.arange(n)
+            samples.append(flat[idx.to(flat.device)].float())
+            norms.append(flat.double().norm())
+        out["grad_sample"] = torch.cat(samples)
+        out["grad_norm"] = torch.stack(norms)
+    total = 0
+    for k, v in out.items():
+        a = v.cpu().numpy()
+        np.save(os.path.join(path, k + ".npy"), a)
+        total += a.nbytes
+    log(f"outputs of the last timed step: {len(out)} arrays, {total / 1e6:.1f} MB in {path}")
 
 
 def cpu_baseline(cfg_path, steps):
@@ -211,7 +257,7 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
     The 100 candidates of a round share image, history and question (dataloader/dataloader_visdial.py builds them so;
     synth.make_scoring_batch); with --shared-context on (default, bf16 engine) the context rows and the image stream are
     computed once per round and chunk (unimm_amd/scoring.py) -- the per-candidate schedule, which recomputes them 100 times as
-    the reference does, is timed beside it (`config.per_candidate_value`).  Ranks process different images (weak scaling, no
+    the reference does, is timed beside it with --full (`config.per_candidate_value`).  Ranks process different images (weak scaling, no
     collective)."""
     from unimm_amd import harness
     model = enc.bert_pretrained
@@ -239,6 +285,8 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
     n_rows = int((img["masked_lm_labels"] != -1).sum())
     shared = args.shared_context == "on" and args.compute == "bf16"
 
+    last = {}                                     # what the latest step returned (--dump-outputs)
+
     def step(shared=shared):
         sc = []
         for b in chunks:
@@ -248,7 +296,10 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
                                                  co_attention_mask=b["co_attention_mask"], image_index=b.get("image_index"),
                                                  shared_context=b["context_group"] if shared else None)
             sc.append(s)
-        return harness.scores_to_ranks(torch.cat(sc).view(1, 10, 100))
+        scores = torch.cat(sc)
+        ranks = harness.scores_to_ranks(scores.view(1, 10, 100))
+        last.update(scores=scores, ranks=ranks)
+        return ranks
 
     log(f"scoring: {len(chunks)} chunks x {ck} sequences ready on {dev}, {n_rows} decoded rows per image, shared context {'on' if shared else 'off'}")
     for _ in range(max(args.warmup, 2) if host else args.warmup):
@@ -261,16 +312,21 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
         torch.cuda.synchronize()
 
     fence()
-    lib.prof_enable(True)
+    if args.full:
+        lib.prof_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ranks = step()
     fence()
     dt = time.perf_counter() - t0
-    prof = lib.prof_collect()
-    lib.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    prof = None
+    if args.full:
+        prof = lib.prof_collect()
+        lib.prof_enable(False)
     per_cand = None
-    if shared:                                    # the reference's schedule (every candidate recomputes context and image), same inputs
+    if shared and args.full:                      # the reference's schedule (every candidate recomputes context and image), same inputs
         step(False)
         fence()
         t1 = time.perf_counter()
@@ -285,10 +341,6 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
     dt = float(t)
     value = 1000 * world * args.steps / dt
     if rank == 0:
-        name, (ms, fl, cnt) = max(prof.items(), key=lambda kv: kv[1][0])
-        gemm_ms = sum(v[0] for v in prof.values())
-        gemm_fl = sum(v[1] for v in prof.values())
-        achieved = fl / (ms * 1e-3) / 1e12
         f_fwd = F_FWD_BASE_GF + F_DEC_ROW_GF * n_rows / 1000
         out = {"metric": "candidate dialog-sequences/sec (forward + sequence log-likelihood + ranks) at chunk=250 seq=256 regions=36(+1 <IMG>)",
                "value": round(value, 2), "unit": "dialog-sequences/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -307,14 +359,19 @@ def scoring(args, world, rank, dev, enc, lib, synth, dist):
                           "seq_len": 256, "regions": 37,
                           "parallelism": f"dp{world}", "lm_rows_decoded_per_seq": round(n_rows / 1000, 2),
                           "gflop_per_seq_fwd_padded_equivalent": round(f_fwd, 3),
-                          "gemm_gflop_per_seq_executed": round(gemm_fl / args.steps / 1000 / 1e9, 3),
-                          "rank_checksum": int(ranks.sum())},
-               "roofline": {"bound": "mfma", "kernel": name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
-                            "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": None,
-                            "launches_per_step": cnt // args.steps, "avg_launch_us": round(ms * 1e3 / cnt, 2),
-                            "all_gemm_tflops": round(gemm_fl / (gemm_ms * 1e-3) / 1e12, 1),
-                            "gemm_share_of_step": round(gemm_ms * 1e-3 / dt, 3),
-                            "padded_equivalent_tflops": round(f_fwd * 1e9 * value / 1e12, 1)}}
+                          "rank_checksum": int(ranks.sum())}}
+        if args.full:
+            name, (ms, fl, cnt) = max(prof.items(), key=lambda kv: kv[1][0])
+            gemm_ms = sum(v[0] for v in prof.values())
+            gemm_fl = sum(v[1] for v in prof.values())
+            achieved = fl / (ms * 1e-3) / 1e12
+            out["config"]["gemm_gflop_per_seq_executed"] = round(gemm_fl / args.steps / 1000 / 1e9, 3)
+            out["roofline"] = {"bound": "mfma", "kernel": name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
+                               "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": None,
+                               "launches_per_step": cnt // args.steps, "avg_launch_us": round(ms * 1e3 / cnt, 2),
+                               "all_gemm_tflops": round(gemm_fl / (gemm_ms * 1e-3) / 1e12, 1),
+                               "gemm_share_of_step": round(gemm_ms * 1e-3 / dt, 3),
+                               "padded_equivalent_tflops": round(f_fwd * 1e9 * value / 1e12, 1)}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -484,6 +541,12 @@ def main():
             batch.update(next(src))
 
     fused_step = [False]                        # set below, once it is known whether the graph executor runs the step
+    last = {}                                   # --dump-outputs: what the latest step returned (detached views, no copies)
+
+    def keep(**outs):
+        if args.dump_outputs:
+            last.clear()
+            last.update((k, v.detach()) for k, v in outs.items())
 
     def combine(lm, nsp, img):                  # train.py:164-168, as unimm_amd.harness.forward combines them
         if args.plain_loss:
@@ -503,6 +566,7 @@ def main():
             loss, _ = ranking.dense_finetune_loss(nsp_scores, batch["next_sentence_label"], relevance, lm, coeff["nsp"],
                                                   num_options=per_gpu)
             loss.backward()
+            keep(loss=loss, lm_loss=lm, img_loss=img, nsp_loss=nsp, nsp_scores=nsp_scores)
             return loss
         if args.compact_inputs and args.workload == "train":
             lm, img, nsp = net(batch["input_ids"], batch["image_feat_unique"], batch["image_loc_unique"],
@@ -514,16 +578,19 @@ def main():
                                image_index=batch["image_index"])
             loss = combine(lm, nsp, img)
             loss.backward()
+            keep(loss=loss, lm_loss=lm, img_loss=img, nsp_loss=nsp)
             return loss
         if fused_step[0]:
-            return net.forward_backward(
+            loss, lm, img, nsp, nsp_logits = net.forward_backward(
                 batch["input_ids"], batch["image_feat"], batch["image_loc"], (coeff["lm"], coeff["nsp"], coeff["img"]),
                 sep_indices=batch["sep_indices"], sep_len=batch["sep_len"], token_type_ids=batch["token_type_ids"],
                 token_position_ids=batch["token_position_ids"], attention_mask=batch["attention_mask"],
                 masked_lm_labels=batch["masked_lm_labels"], next_sentence_label=batch["next_sentence_label"],
                 image_attention_mask=batch["image_attention_mask"], co_attention_mask=batch["co_attention_mask"],
                 image_label=batch["image_label"], image_target=batch["image_target"], nsp_weight=nsp_w,
-                lm_weight=batch["lm_weight"])[0]
+                lm_weight=batch["lm_weight"])
+            keep(loss=loss, lm_loss=lm, img_loss=img, nsp_loss=nsp, nsp_logits=nsp_logits)
+            return loss
         lm, img, nsp = net(batch["input_ids"], batch["image_feat"], batch["image_loc"], sep_indices=batch["sep_indices"],
                            sep_len=batch["sep_len"], token_type_ids=batch["token_type_ids"],
                            token_position_ids=batch["token_position_ids"], attention_mask=batch["attention_mask"],
@@ -533,6 +600,7 @@ def main():
                            lm_weight=batch["lm_weight"])
         loss = combine(lm, nsp, img)
         loss.backward()
+        keep(loss=loss, lm_loss=lm, img_loss=img, nsp_loss=nsp)
         return loss
 
     opt = sched = None
@@ -655,7 +723,7 @@ def main():
     if world > 1:
         net.comm_stats(reset=True)
     prof_all = args.gemm_profile == "all"
-    if not use_graphs:
+    if not use_graphs and args.full:
         lib.prof_enable(1 if prof_all else 2)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -666,6 +734,70 @@ def main():
         st_timed = net.comm_stats()
         assert st_timed["buckets"] == st_timed["n_buckets_expected"] * args.steps, st_timed
     graph_stats = dict(model.engine.graphs.stats) if use_graphs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, enc)
+    loss_val = float(loss.detach())
+    log(f"timed region: {dt / args.steps * 1e3:.2f} ms/step")
+    if getattr(model.engine, "_stager", None) is not None:
+        st_ = model.engine._stager.stats
+        log(f"host staging: {st_['steps']} steps, {st_.get('host_ms', 0.0) / max(1, st_['steps']):.2f} ms of host time per step, "
+            f"{st_['bytes_h2d'] / max(1, st_['steps']) / 1e6:.1f} MB per step over PCIe, pinned {model.engine._stager.pinned_bytes() / 1e6:.0f} MB; "
+            + ", ".join(f"{k} {st_.get(k, 0.0) / max(1, st_['steps']):.2f}" for k in ("wait_ms", "pack_ms", "copy_ms")))
+
+    def headline(dt):
+        """The fields of the result line that every run prints (dt: seconds of the timed steps, slowest rank)."""
+        value = global_batch * args.steps / dt
+        f_fwd = F_FWD_BASE_GF + F_DEC_ROW_GF * n_lm_rows / per_gpu     # reference-equivalent (padded to 256 tokens)
+        plan = plan_default
+        valid_rows = plan["Mv"] if plan is not None else per_gpu * 256
+        if args.workload == "dense":
+            metric = f"dialog-sequences/sec (fwd+bwd) dense-annotation fine-tune micro-step at bs={per_gpu} seq=256 regions=36(+1 <IMG>)"
+            wl = ("dense-annotation fine-tune micro-step (BASELINE configs[3]): bert_base_6layer_6conect, discriminative inputs, "
+                  "sequences_per_image=2, nsp_loss_coeff=0, batch_multiply=16 (gradient exchange every 16th step), " + args.compute + ", "
+                  "fwd+bwd, " + ("objective = NeuralNDCG^T over the step's options + LM loss (dense_annotation_finetuning.py:263-293), "
+                              "optimizer not included" if args.dense_objective == "ranking"
+                              else "LM + region-KL proxy objective, ranking loss and optimizer not included"))
+        else:
+            metric = "dialog-sequences/sec (fwd+bwd) at bs=240 seq=256 regions=36(+1 <IMG>)"
+            wl = ("UniMM-UL sparse training step (BASELINE configs[1]): bert_base_6layer_6conect, "
+                  "sequences_per_image=6, num_negative_samples=5, mask_prob=0.15, dropout on, "
+                  "MLM+UL / NSP / region-KL losses, fwd+bwd, " +
+                  ("PLUS the fused AdamW step and weight-copy refresh (--with-optimizer)" if args.with_optimizer
+                   else "optimizer step not included") +
+                  ("; compact inputs (mask descriptors, per-image tensors)" if args.compact_inputs else "") +
+                  ("" if args.host_inputs == "off" else
+                   f"; inputs start in HOST memory every step ({args.host_inputs}: "
+                   + ("CPU tensors handed to forward()" + ("" if args.host_staging == "on" else ", plain .to(device) path") if args.host_inputs == "direct" else "pinned + copied one step ahead by DevicePrefetcher")
+                   + f", {h2d_bytes / 1e6:.0f} MB per step, 3 batches cycled) -- NOT the contract's resident-input metric"))
+        return {
+            "metric": metric,
+            "value": round(value, 2), "unit": "dialog-sequences/sec", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "bf16" if args.compute == "bf16" else "fp32x3 (bf16 MFMA over split operands hi+lo, fp32 accumulate; fp32 attention / activations / gradients)",
+            "data": "synthetic",
+            "config": {"workload": wl + ("" if args.compute == "bf16" else "; compute_dtype=fp32x3 (the reference's no-autocast arithmetic class)"),
+                       "global_batch": global_batch, "per_gpu_batch": per_gpu, "seq_len": 256, "regions": 37,
+                       "parallelism": f"dp{world}", "lm_rows_decoded_per_seq": round(n_lm_rows / per_gpu, 2),
+                       "executor": ("hipGraph replay (unimm_amd/graphs.py): " + json.dumps(graph_stats)) if graph_stats else "eager launches",
+                       "step_api": ("forward_backward(batch, loss_weights): forward and backward enqueued back to back (--fused-step)"
+                                    if fused_step[0] else "loss = combine(losses); loss.backward() (autograd, as train.py:164-168, :315)"),
+                       "valid_token_rows": valid_rows, "token_rows_padded": per_gpu * 256,
+                       "gflop_per_seq_fwd_padded_equivalent": round(f_fwd, 3),
+                       "loss": round(loss_val, 4)},
+        }, value, f_fwd
+
+    plan_default = model.engine.last_plan          # (the padded steps of --full replace engine.last_plan)
+    if not args.full:                              # a plain run: the timed steps are all it measures
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        if rank == 0:
+            print(json.dumps(headline(float(t))[0]), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     prof_steps = args.steps                    # steps the launch profile `prof` covers
     if use_graphs:                             # the per-kernel figures below come from eager steps
         model.engine.graphs = None
@@ -675,13 +807,6 @@ def main():
         prof_steps = 2
     prof = lib.prof_collect()
     lib.prof_enable(False)
-    loss_val = float(loss.detach())
-    log(f"timed region: {dt / args.steps * 1e3:.2f} ms/step")
-    if getattr(model.engine, "_stager", None) is not None:
-        st_ = model.engine._stager.stats
-        log(f"host staging: {st_['steps']} steps, {st_.get('host_ms', 0.0) / max(1, st_['steps']):.2f} ms of host time per step, "
-            f"{st_['bytes_h2d'] / max(1, st_['steps']) / 1e6:.1f} MB per step over PCIe, pinned {model.engine._stager.pinned_bytes() / 1e6:.0f} MB; "
-            + ", ".join(f"{k} {st_.get(k, 0.0) / max(1, st_['steps']):.2f}" for k in ("wait_ms", "pack_ms", "copy_ms")))
     # Outside the timed region (N=1 only): the same kernel with the chip to itself.  In the production schedule the image
     # side runs on its own stream, so a weight-gradient launch shares CUs with image-layer kernels and its in-situ
     # duration (the `achieved` / `frac` above) is not an exclusive one; two single-stream steps give that figure.
@@ -751,7 +876,6 @@ def main():
 
     # the padded schedule (every sequence computed on all 256 token rows, as the reference does) beside the default one
     padded_value = None
-    plan_default = model.engine.last_plan          # (the padded steps below replace engine.last_plan)
     if world == 1 and args.workload == "train" and not args.no_padded:
         model.engine.unpad = False
         step()
@@ -802,10 +926,9 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
-    total_seq = global_batch * args.steps
-    value = total_seq / dt
 
     if rank == 0:
+        out, value, f_fwd = headline(dt)
         dom = max(prof.items(), key=lambda kv: kv[1][0])
         name, (ms, fl, cnt) = dom
         achieved = fl / (ms * 1e-3) / 1e12
@@ -829,65 +952,26 @@ def main():
                 traffic_commit = tj.get("commit")      # the commit the PMC passes were taken at
             elif tj.get("kernel") == name:
                 traffic_src = "stale: csrc/gemm.hip changed since " + str(tj.get("commit")) + " (re-run tools/profile_round.sh)"
-        f_fwd = F_FWD_BASE_GF + F_DEC_ROW_GF * n_lm_rows / per_gpu     # reference-equivalent (padded to 256 tokens)
-        plan = plan_default
-        valid_rows = plan["Mv"] if plan is not None else per_gpu * 256
         exec_gf_seq = exec_fl_step / per_gpu / 1e9          # GEMM FLOPs actually executed per sequence, fwd+bwd
-        if args.workload == "dense":
-            metric = f"dialog-sequences/sec (fwd+bwd) dense-annotation fine-tune micro-step at bs={per_gpu} seq=256 regions=36(+1 <IMG>)"
-            wl = ("dense-annotation fine-tune micro-step (BASELINE configs[3]): bert_base_6layer_6conect, discriminative inputs, "
-                  "sequences_per_image=2, nsp_loss_coeff=0, batch_multiply=16 (gradient exchange every 16th step), " + args.compute + ", "
-                  "fwd+bwd, " + ("objective = NeuralNDCG^T over the step's options + LM loss (dense_annotation_finetuning.py:263-293), "
-                              "optimizer not included" if args.dense_objective == "ranking"
-                              else "LM + region-KL proxy objective, ranking loss and optimizer not included"))
-        else:
-            metric = "dialog-sequences/sec (fwd+bwd) at bs=240 seq=256 regions=36(+1 <IMG>)"
-            wl = ("UniMM-UL sparse training step (BASELINE configs[1]): bert_base_6layer_6conect, "
-                  "sequences_per_image=6, num_negative_samples=5, mask_prob=0.15, dropout on, "
-                  "MLM+UL / NSP / region-KL losses, fwd+bwd, " +
-                  ("PLUS the fused AdamW step and weight-copy refresh (--with-optimizer)" if args.with_optimizer
-                   else "optimizer step not included") +
-                  ("; compact inputs (mask descriptors, per-image tensors)" if args.compact_inputs else "") +
-                  ("" if args.host_inputs == "off" else
-                   f"; inputs start in HOST memory every step ({args.host_inputs}: "
-                   + ("CPU tensors handed to forward()" + ("" if args.host_staging == "on" else ", plain .to(device) path") if args.host_inputs == "direct" else "pinned + copied one step ahead by DevicePrefetcher")
-                   + f", {h2d_bytes / 1e6:.0f} MB per step, 3 batches cycled) -- NOT the contract's resident-input metric"))
-        out = {
-            "metric": metric,
-            "value": round(value, 2), "unit": "dialog-sequences/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "bf16" if args.compute == "bf16" else "fp32x3 (bf16 MFMA over split operands hi+lo, fp32 accumulate; fp32 attention / activations / gradients)",
-            "data": "synthetic",
-            "config": {"workload": wl + ("" if args.compute == "bf16" else "; compute_dtype=fp32x3 (the reference's no-autocast arithmetic class)"),
-                       "global_batch": global_batch, "per_gpu_batch": per_gpu, "seq_len": 256, "regions": 37,
-                       "parallelism": f"dp{world}", "lm_rows_decoded_per_seq": round(n_lm_rows / per_gpu, 2),
-                       "executor": ("hipGraph replay (unimm_amd/graphs.py): " + json.dumps(graph_stats)) if graph_stats else "eager launches",
-                       "step_api": ("forward_backward(batch, loss_weights): forward and backward enqueued back to back (--fused-step)"
-                                    if fused_step[0] else "loss = combine(losses); loss.backward() (autograd, as train.py:164-168, :315)"),
-                       "valid_token_rows": valid_rows, "token_rows_padded": per_gpu * 256,
-                       "gflop_per_seq_fwd_padded_equivalent": round(f_fwd, 3),
-                       "gemm_gflop_per_seq_executed_fwd_bwd": round(exec_gf_seq, 3),
-                       "padded_schedule_value": round(padded_value, 2) if padded_value is not None else None,
-                       "padded_schedule_note": "the same step with engine.unpad = False: every sequence computed on all 256 "
-                                               "token rows as the reference does (2 steps after the timed region)",
-                       "loss": round(loss_val, 4)},
-            "roofline": {"bound": "mfma", "kernel": name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-                         "traffic_unit": "HBM bytes per launch (2 x FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
-                         "traffic_measured_at_commit": traffic_commit,
-                         "launches_per_step": cnt // prof_steps, "avg_launch_us": round(ms * 1e3 / cnt, 2),
-                         "event_timed_launches": "every GEMM" if prof_all else "the weight-gradient kernels only (in the timed region); every GEMM in 2 extra steps",
-                         "whole_step_executed_gemm_tflops": round(exec_fl_step / (dt / args.steps) / 1e12, 1),
-                         "whole_step_frac": round(exec_fl_step / (dt / args.steps) / 1e12 / PEAK_BF16_TFLOPS, 4),
-                         "gemm_kernels_by_time": [{"kernel": k, "ms_per_step": round(kms, 3), "tflops": round(kfl / (kms * 1e-3) / 1e12, 1) if kms > 0 else None,
-                                                   "launches_per_step": kcnt} for k, kms, kfl, kcnt in ranking[:6]],
-                         "schedule": ("two streams (image side beside text side): in-situ durations are shared-chip durations"
-                                      if model.engine.dual_stream else "single stream"),
-                         "coattention_gemms": coatt,
-                         "exclusive": exclusive,
-                         "padded_equivalent_tflops": round(3 * f_fwd * 1e9 * value / 1e12, 1)},
-        }
+        out["config"].update({"gemm_gflop_per_seq_executed_fwd_bwd": round(exec_gf_seq, 3),
+                              "padded_schedule_value": round(padded_value, 2) if padded_value is not None else None,
+                              "padded_schedule_note": "the same step with engine.unpad = False: every sequence computed on all 256 "
+                                                      "token rows as the reference does (2 steps after the timed region)"})
+        out["roofline"] = {"bound": "mfma", "kernel": name, "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS,
+                           "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                           "traffic_unit": "HBM bytes per launch (2 x FETCH_SIZE + WRITE_SIZE)", "traffic_source": traffic_src,
+                           "traffic_measured_at_commit": traffic_commit,
+                           "launches_per_step": cnt // prof_steps, "avg_launch_us": round(ms * 1e3 / cnt, 2),
+                           "event_timed_launches": "every GEMM" if prof_all else "the weight-gradient kernels only (in the timed region); every GEMM in 2 extra steps",
+                           "whole_step_executed_gemm_tflops": round(exec_fl_step / (dt / args.steps) / 1e12, 1),
+                           "whole_step_frac": round(exec_fl_step / (dt / args.steps) / 1e12 / PEAK_BF16_TFLOPS, 4),
+                           "gemm_kernels_by_time": [{"kernel": k, "ms_per_step": round(kms, 3), "tflops": round(kfl / (kms * 1e-3) / 1e12, 1) if kms > 0 else None,
+                                                     "launches_per_step": kcnt} for k, kms, kfl, kcnt in ranking[:6]],
+                           "schedule": ("two streams (image side beside text side): in-situ durations are shared-chip durations"
+                                        if model.engine.dual_stream else "single stream"),
+                           "coattention_gemms": coatt,
+                           "exclusive": exclusive,
+                           "padded_equivalent_tflops": round(3 * f_fwd * 1e9 * value / 1e12, 1)}
         if args.compute != "bf16":
             out["roofline"]["note"] = ("fp32x3: every GEMM runs over three bf16 planes (hi hi + lo hi + hi lo): the FLOPs priced here are the "
                                        "EXECUTED bf16 MFMA FLOPs, 3x the algorithmic fp32 FLOPs of the layer")

@@ -1,6 +1,7 @@
 """bench.py prints ONE JSON line with the fields the contract names (a small batch, one step; run as a child process).  N > 1 is
 run in both launch forms: `python bench.py --gpus 2` (bench.self_launch starts the ranks) and under an external
-torch.distributed.run."""
+torch.distributed.run.  The extra blocks (roofline, padded schedule, comm) come with --full; a plain run prints the headline
+fields only and, with --dump-outputs, writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "12",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -38,6 +39,38 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert j["config"]["padded_schedule_value"] > 0
 
 
+def test_plain_bench_times_only_its_steps_and_dumps_the_last_one(tmp_path):
+    """No --full: the headline fields and nothing measured beside them; --steps is the number of timed steps; --dump-outputs
+    writes the losses and the gradient sample of the last timed step as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "12",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "dialog-sequences/sec" and j["dtype"] == "bf16"
+    assert abs(j["value"] - 12 / (j["ms_per_step"] * 1e-3)) <= 0.01 * j["value"]
+    for k in ("roofline", "cpu_baseline", "comm"):
+        assert k not in j, k
+    assert "padded_schedule_value" not in j["config"]
+    files = sorted(p.name for p in out.iterdir())
+    for name in ("loss.npy", "lm_loss.npy", "img_loss.npy", "nsp_loss.npy", "grad_sample.npy", "grad_norm.npy"):
+        assert name in files, files
+    total = 0
+    for name in files:
+        a = np.load(out / name)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        assert np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(out / "loss.npy")) - j["config"]["loss"]) <= 1e-3 * max(1.0, abs(j["config"]["loss"]))
+    assert (np.load(out / "grad_norm.npy") > 0).any()
+
+
 def test_bench_two_ranks_rehearsal_with_the_graph_executor():
     """The N > 1 path of bench.py under an external torch.distributed.run (one JSON line from rank 0), rehearsed on
     one GPU: UNIMM_BENCH_REHEARSAL=1 puts both ranks on device 0 and exchanges over gloo (RCCL refuses two ranks on one
@@ -48,7 +81,7 @@ def test_bench_two_ranks_rehearsal_with_the_graph_executor():
     env = dict(os.environ, UNIMM_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", "24", "--graphs", "on", "--no-cpu-baseline", "--no-padded"],
+                        "--batch", "24", "--graphs", "on", "--full", "--no-cpu-baseline", "--no-padded"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -68,7 +101,7 @@ def test_bench_two_ranks_rehearsal_launched_as_plain_python():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "24",
-                        "--no-cpu-baseline", "--no-padded"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--full", "--no-cpu-baseline", "--no-padded"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), lines

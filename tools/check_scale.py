@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Self-check of a multi-GPU bench line against DESIGN.md section 6's predictions.
 
-    python bench.py --gpus N ... > line.json          (starts its own ranks; or under python -m torch.distributed.run --nproc-per-node N)
+    python bench.py --gpus N --full ... > line.json   (starts its own ranks; or under python -m torch.distributed.run --nproc-per-node N)
     python tools/check_scale.py line.json [more.json ...]        (or: ... | python tools/check_scale.py -)
 
 No N > 1 box was available to this build in any round, so the first real RCCL run has to check itself: the line must say

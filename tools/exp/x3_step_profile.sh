@@ -1,7 +1,7 @@
 # kernel stats of the dense fine-tune micro-step in fp32x3: bash tools/exp/x3_step_profile.sh <tag>
 tag=$1; out=gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python bench.py --workload dense --compute fp32x3 --steps 8 --warmup 2 --no-cpu-baseline --no-padded > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o run -- python bench.py --full --workload dense --compute fp32x3 --steps 8 --warmup 2 --no-cpu-baseline --no-padded > $out/bench.log 2>&1
 python - <<PY
 import csv
 rows=list(csv.DictReader(open("$out/run_kernel_stats.csv")))
