@@ -572,6 +572,61 @@ int unimm_x3_attn_bwd(const unimm_attn_bwd_args* args, const unimm_x3_attn_plane
  * (v_mfma_f32_16x16x4_f32, exact fp32 operands), 0 = the vector-ALU kernels of the first version (kept for A/B runs). */
 int unimm_x3_attn_set_impl(int32_t impl);
 
+/* ---------------------------------------------------------------------------------------------
+ * Answer generation (unimm_amd/generation.py; ABI 19).  Under the generative mask (utils/data_utils.py:199-210) the context
+ * rows [1, c) and the image stream never see the answer, answer row c+k attends [1, c+k] and the [MASK]-copy row of answer
+ * token k attends [1, c+k) + itself: the sequence is a prefix-LM, so a decode step pushes only the NEW text rows of every
+ * hypothesis through the blocks and reads everything older from a key/value cache.
+ * ------------------------------------------------------------------------------------------- */
+/* Text self-attention (models/vilbert_dialog.py:390-410) of the new rows of G groups x `beams` hypothesis slots, D = 64,
+ * H * D <= 1024.  Hypothesis slot s = g * beams + b owns the new rows [s * nr, s * nr + nr) of q / k / v / out (nr = 1 or 2:
+ * answer row k-1, then copy row k).  New row i of slot s attends, in this order: the group's SHARED context rows
+ * [ctx_off[g], ctx_off[g] + ctx_len[g]) of ctx_k / ctx_v, the slot's PRIVATE cached answer rows [0, plen[s]) (row r at
+ * priv_k / priv_v + (s * pcap + r) * ldp), and its own new rows [0, i] (k / v of the same call).  That is exactly the
+ * generative mask: a masked key's exp(-10000 + s) underflows to 0 in fp32 in the reference, so no mask words are read.
+ * One workgroup per (group, head) takes all nr * beams <= 32 query rows, so the context K / V of a group is read once;
+ * K / V rows go straight to VGPRs (kernel guide: attention decode / GEMV, M <= 16), dot products and P.V on the vector ALU
+ * in fp32.  No split over keys: one head's context is at most 255 x 64 x 2 x 2 B = 65 KB, microseconds at one CU's bandwidth
+ * (revisit if a profile disagrees; measured at 80 dialogs x 4 beams: ~69 us per launch, second to the NT GEMMs in a decode step --
+ * a matrix-instruction form of the score and P.V products is the next step).  ctx_len[g] <= 256 and ctx_len[g] + plen[s] + nr <= 320; out is written in the layout of unimm_attn_fwd
+ * (row, head * 64 + d).  Row strides in elements, multiples of 8; every pointer 16-byte aligned. */
+typedef struct {
+  const void* q; const void* k; const void* v;   /* bf16, the new rows' fused projection (row strides ldq / ldk / ldv) */
+  void* out;                                     /* bf16 [G * beams * nr, ldo] */
+  const void* ctx_k; const void* ctx_v;          /* bf16 shared context rows, row stride ldc */
+  const int32_t* ctx_off; const int32_t* ctx_len; /* int32 [G], device */
+  const void* priv_k; const void* priv_v;        /* bf16 private caches [G * beams][pcap] rows, row stride ldp (or NULL when pcap = 0) */
+  const int32_t* plen;                           /* int32 [G * beams], device: cached answer rows of each slot (<= pcap) */
+  int32_t G, beams, nr, H, D, pcap;
+  int32_t ldq, ldk, ldv, ldo, ldc, ldp;
+  float scale;
+} unimm_attn_decode_args;
+int unimm_attn_decode(const unimm_attn_decode_args* args, void* stream);
+
+/* Per-step maintenance of the private caches of all `layers` text layers in one launch, after beam selection:
+ * for every slot s with parent p = parent[s] (a slot of the previous step), dst rows [0, plen[p]) of s = src rows of p, and dst
+ * row plen[p] of s = p's new answer row: new_kv + layer * new_layer_stride + (p * new_row_mul) * ld_new (width elements, the K
+ * and V columns of one layer are `width` contiguous elements, e.g. K | V of the fused projection); plen_out[s] = plen[p] + 1.
+ * Cache layout: src / dst + ((layer * slots + s) * pcap + r) * ldp, width <= ldp.  src and dst must not overlap (the
+ * reorder is a gather); bit-exact copies.  plen[p] + 1 <= pcap, width % 8 == 0, strides % 8 == 0. */
+typedef struct {
+  const void* src; void* dst;                    /* bf16 [layers][slots][pcap][ldp] */
+  const void* new_kv;                            /* bf16 */
+  const int32_t* parent; const int32_t* plen; int32_t* plen_out;   /* int32 [slots], device */
+  int32_t layers, slots, pcap, ldp, width;
+  int64_t new_layer_stride;                      /* elements */
+  int32_t ld_new, new_row_mul;
+} unimm_kv_update_args;
+int unimm_kv_cache_update(const unimm_kv_update_args* args, void* stream);
+
+/* Log-softmax + top-K of fp32 logits [rows, ldl] (models/vilbert_dialog.py:1023-1026 decoder output), one row per
+ * workgroup, the vocabulary streamed once with an online log-sum-exp.  logp = logit - lse over ALL V ids (no renormalisation
+ * after banning).  Then -inf for: the `nbanned` ids of `banned` (int32, device), id `sep` when flags[row] & 1, every id other
+ * than `sep` when flags[row] & 2 (flags int32 [rows] or NULL).  Returns the K <= 16 largest (vals fp32 [rows, K], ids int32
+ * [rows, K]) ordered by (value desc, id asc) -- -inf entries included, by the same rule; lse fp32 [rows] or NULL. */
+int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                  const int32_t* flags, int32_t sep, int32_t K, float* vals, int32_t* ids, float* lse, void* stream);
+
 /* Launch profiler for bench.py's `roofline` block: HIP events around every GEMM launch on its own
  * stream while enabled.  Variant index: 0..11 = unimm_gemm_nt (epilogue * 2 + out_f32), 12 = unimm_gemm_tn.
  * unimm_prof_collect synchronises the events and returns per-variant summed milliseconds, algorithmic

@@ -1,0 +1,176 @@
+"""Answer generation throughput at the full config (seeded weights): prefill, decode step, answers/s and tokens/s for
+(G, beams) in {(1, 1), (1, 5), (80, 1), (80, 4)}, every answer exactly 20 tokens + [SEP] (min_answer_len = max_answer_len = 20),
+against the recompute lower bound: sequence_log_likelihood of the same G * beams sequences at answer lengths 1 .. 20 summed
+(a generator that re-runs the encoder per token pays at least that) -- with shared_context=<dialog> where that path applies
+(answers of <= 14 tokens: it takes <= 32 private rows per sequence), the per-sequence path for the longer ones.
+
+    python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile]
+
+--profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
+process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CFG_PATH = os.path.join(ROOT, "unimm_amd", "config", "bert_base_6layer_6conect.json")
+ANS = 20
+T, R, F = 256, 37, 2048
+
+
+def build_model():
+    from oracle import vilbert_ref as RF
+    from unimm_amd import BertConfig, BertForMultiModalPreTraining
+    model = BertForMultiModalPreTraining(BertConfig.from_json_file(CFG_PATH))
+    model.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    return model.cuda().eval()
+
+
+def dialogs(G, seed):
+    """G contexts of 60 .. 180 tokens ([CLS] utterances [SEP] ..., segments toggling), random regions, on the device."""
+    rng = np.random.default_rng(seed)
+    ids = np.zeros((G, T), dtype=np.int64)
+    tt = np.zeros((G, T), dtype=np.int64)
+    c = np.zeros(G, dtype=np.int64)
+    for g in range(G):
+        target, toks, segs, s = int(rng.integers(60, 181)), [101], [0], 0
+        while len(toks) < target:
+            u = rng.integers(1000, 30522, int(rng.integers(3, 12))).tolist() + [102]
+            toks += u
+            segs += [s] * len(u)
+            s ^= 1
+        ids[g, :len(toks)], tt[g, :len(toks)], c[g] = toks, segs, len(toks)
+    pp = np.tile(np.arange(T), (G, 1))
+    d = dict(input_ids=ids, token_type_ids=tt, position_ids=pp)
+    d = {k: torch.from_numpy(v).cuda() for k, v in d.items()}
+    d["image_feat"] = torch.from_numpy(rng.standard_normal((G, R, F)).astype(np.float32)).cuda()
+    d["image_loc"] = torch.from_numpy(rng.random((G, R, 5)).astype(np.float32)).cuda()
+    d["image_attention_mask"] = torch.ones((G, R), dtype=torch.int64, device="cuda")
+    return d, c
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        best = min(best, (time.perf_counter() - t0) * 1e3)
+    return best
+
+
+def generate(model, d, c, beams, n):
+    return model.generate_answers(d["input_ids"], d["image_feat"], d["image_loc"], c, d["token_type_ids"], d["position_ids"],
+                                  d["image_attention_mask"], beams=beams, max_answer_len=n, min_answer_len=n)
+
+
+def recompute_bound(model, d, c, G, beams, reps):
+    """Summed ms of scoring G * beams sequences with answers of 1 .. ANS tokens (shared context up to 14 answer tokens)."""
+    from unimm_amd.inputs import DialogMaskSpec
+    B = G * beams
+    gi = np.repeat(np.arange(G), beams)
+    rng = np.random.default_rng(1)
+    total = 0.0
+    for n in range(1, ANS + 1):
+        ids = d["input_ids"][gi].clone()
+        tt = d["token_type_ids"][gi].clone()
+        pp = d["position_ids"][gi].clone()
+        lab = torch.full((B, T), -1, dtype=torch.int64, device="cuda")
+        ans = torch.from_numpy(rng.integers(1000, 30522, (B, n))).cuda()
+        for b in range(B):
+            cb = int(c[gi[b]])
+            L = cb + n + 1
+            seq = torch.cat([ans[b], torch.tensor([102], device="cuda")])
+            ids[b, cb:L] = seq
+            ids[b, L:L + n + 1] = 103
+            lab[b, L:L + n + 1] = seq
+            tt[b, cb:L + n + 1] = tt[b, cb - 1] ^ 1
+            pp[b, cb:L] = torch.arange(cb, L, device="cuda")
+            pp[b, L:L + n + 1] = torch.arange(cb, L, device="cuda")
+        spec = DialogMaskSpec(np.ones(B), c[gi] + n + 1, np.full(B, n + 1))
+        grp = torch.from_numpy(gi).cuda() if 2 * (n + 1) + 1 <= 32 else None
+        total += timed(lambda: model.sequence_log_likelihood(ids, d["image_feat"][gi], d["image_loc"][gi], lab, shared_context=grp,
+                                                             token_type_ids=tt, position_ids=pp, attention_mask=spec,
+                                                             image_attention_mask=d["image_attention_mask"][gi]), reps)
+    return total
+
+
+def measure(model, G, beams, reps, recompute=True):
+    d, c = dialogs(G, seed=G * 10 + beams)
+    prefill = timed(lambda: generate(model, d, c, beams, 0), reps)
+    full = timed(lambda: generate(model, d, c, beams, ANS), reps)
+    res = generate(model, d, c, beams, ANS)
+    assert bool((res.lengths == ANS + 1).all())
+    step = (full - prefill) / ANS
+    row = dict(G=G, beams=beams, prefill_ms=round(prefill, 3), decode_step_ms=round(step, 3), call_ms=round(full, 3),
+               answers_per_s=round(G * beams / full * 1e3, 1), tokens_per_s=round(G * beams * (ANS + 1) / full * 1e3, 1))
+    if recompute:
+        rb = recompute_bound(model, d, c, G, beams, reps)
+        row.update(recompute_bound_ms=round(rb, 3), speedup_vs_recompute=round(rb / full, 2))
+    return row
+
+
+def profile():
+    """Kernel mix of one (80, 4) call from rocprofv3 --kernel-trace --stats on a child process."""
+    out = tempfile.mkdtemp(prefix="bench_generate_prof_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "gen", "--", sys.executable, os.path.abspath(__file__),
+           "--shapes", "80,4", "--reps", "1", "--no-recompute", "--quiet"]
+    subprocess.run(cmd, check=True, timeout=900)
+    stats = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
+    if not stats:
+        raise RuntimeError(f"no kernel_stats.csv under {out}")
+    rows = list(csv.DictReader(open(stats[0])))
+    # the profiled process ran the (80, 4) call 1 (warm-up) + 1 (timed) times at 0 and at ANS tokens, + 1 checked call at ANS
+    calls_ans = 3
+    mix = []
+    for r in rows:
+        name = r.get("Name") or r.get("KernelName")
+        n = int(r.get("Calls", 0))
+        ms = float(r.get("TotalDurationNs", 0)) / 1e6
+        mix.append(dict(kernel=name[:90], calls_per_step=round(n / (calls_ans * ANS), 2), ms_per_step=round(ms / (calls_ans * ANS), 4)))
+    mix.sort(key=lambda m: -m["ms_per_step"])
+    return mix[:20]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--shapes", nargs="*", default=["1,1", "1,5", "80,1", "80,4"])
+    ap.add_argument("--no-recompute", action="store_true")
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--quiet", action="store_true")
+    a = ap.parse_args()
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    model = build_model()
+    rows = [measure(model, *map(int, s.split(",")), a.reps, recompute=not a.no_recompute) for s in a.shapes]
+    if a.quiet:
+        return
+    print(f"{'G':>3} {'beams':>5} {'prefill ms':>10} {'ms/step':>8} {'call ms':>8} {'answers/s':>10} {'tokens/s':>9} {'recompute ms':>12} {'x':>6}")
+    for r in rows:
+        print(f"{r['G']:>3} {r['beams']:>5} {r['prefill_ms']:>10.2f} {r['decode_step_ms']:>8.2f} {r['call_ms']:>8.1f} "
+              f"{r['answers_per_s']:>10.1f} {r['tokens_per_s']:>9.1f} {r.get('recompute_bound_ms', float('nan')):>12.1f} "
+              f"{r.get('speedup_vs_recompute', float('nan')):>6.2f}")
+    result = dict(rows=rows)
+    if a.profile:
+        result["kernel_mix_80x4"] = profile()
+        for m in result["kernel_mix_80x4"]:
+            print(f"  {m['ms_per_step']:8.4f} ms  {m['calls_per_step']:6.2f} x  {m['kernel']}")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,361 @@
+// Answer generation kernels (include/unimm_hip.h, ABI 19): text self-attention of the decode rows against a shared context
+// cache plus per-hypothesis private caches, the per-step private-cache append + reorder, and log-softmax + top-K of the
+// decoder logits.  unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int NTHREADS = 256;
+constexpr int DH = 64;          // head size of the text stream
+constexpr int QMAX = 32;        // nr * beams query rows per (group, head)
+constexpr int KMAX = 320;       // keys per query row: context (<= 256) + private + own new rows (T <= 256 bounds the sum)
+constexpr int TOPK_MAX = 16;
+constexpr int VMAX = 65536;     // vocabulary bound of the banned-id bitmask
+
+struct DecodeParams {
+  const bf16_t *q, *k, *v;
+  bf16_t* out;
+  const bf16_t *ctx_k, *ctx_v;
+  const int32_t *ctx_off, *ctx_len;
+  const bf16_t *priv_k, *priv_v;
+  const int32_t* plen;
+  int G, beams, nr, H, pcap;
+  int ldq, ldk, ldv, ldo, ldc, ldp;
+  float scale;
+};
+
+// 64 bf16 of one key row -> fp32 registers (eight 16-byte loads)
+__device__ __forceinline__ void load_row64(const bf16_t* p, float (&f)[DH]) {
+  const uint4* p4 = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+  for (int c = 0; c < DH / 8; ++c) {
+    const uint4 w = p4[c];
+    const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f[c * 8 + 2 * e] = __uint_as_float(u[e] << 16);
+      f[c * 8 + 2 * e + 1] = __uint_as_float(u[e] & 0xffff0000u);
+    }
+  }
+}
+
+__device__ __forceinline__ float dot64(const float* q, const float (&k)[DH]) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+  for (int d = 0; d < DH; d += 4) {
+    a0 = fmaf(q[d], k[d], a0);
+    a1 = fmaf(q[d + 1], k[d + 1], a1);
+    a2 = fmaf(q[d + 2], k[d + 2], a2);
+    a3 = fmaf(q[d + 3], k[d + 3], a3);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+__global__ __launch_bounds__(NTHREADS) void attn_decode_kernel(DecodeParams p) {
+  __shared__ float Qs[QMAX * DH];
+  __shared__ float S[QMAX * KMAX];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  const int nq = p.beams * p.nr;
+  const int row0 = g * nq;                       // first new row of the group
+  const int slot0 = g * p.beams;
+  const int c = min(max(p.ctx_len[g], 0), 256);
+  const int co = p.ctx_off[g];
+  // cached rows of slot s, bounded so that every key index stays inside the LDS score row
+  auto plen_of = [&](int s) { return min(min(max(p.plen[s], 0), p.pcap), KMAX - p.nr - c); };
+
+  for (int idx = tid; idx < nq * DH; idx += NTHREADS) {
+    const int r = idx / DH, d = idx % DH;
+    Qs[idx] = bf2f(p.q[(int64_t)(row0 + r) * p.ldq + h * DH + d]) * p.scale;
+  }
+  __syncthreads();
+
+  // scores against the shared context: one key row per thread, every query row of the group
+  for (int j = tid; j < c; j += NTHREADS) {
+    float kf[DH];
+    load_row64(p.ctx_k + (int64_t)(co + j) * p.ldc + h * DH, kf);
+    for (int r = 0; r < nq; ++r) S[r * KMAX + j] = dot64(Qs + r * DH, kf);
+  }
+  // scores against each slot's private rows, then its own new rows (causal among the new rows)
+  const int npk = p.pcap + p.nr;
+  for (int t = tid; t < p.beams * npk; t += NTHREADS) {
+    const int b = t / npk, j = t % npk;
+    const int s = slot0 + b;
+    const int pl = plen_of(s);
+    if (j >= pl + p.nr) continue;
+    float kf[DH];
+    if (j < pl)
+      load_row64(p.priv_k + ((int64_t)s * p.pcap + j) * p.ldp + h * DH, kf);
+    else
+      load_row64(p.k + (int64_t)(s * p.nr + (j - pl)) * p.ldk + h * DH, kf);
+    for (int i = 0; i < p.nr; ++i)
+      if (j < pl || j - pl <= i) S[(b * p.nr + i) * KMAX + c + j] = dot64(Qs + (b * p.nr + i) * DH, kf);
+  }
+  __syncthreads();
+
+  // softmax of every row over its key prefix [0, c + plen + i + 1): one wave per row
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int r = wave; r < nq; r += NTHREADS / 64) {
+    const int b = r / p.nr, i = r % p.nr;
+    const int nk = c + plen_of(slot0 + b) + i + 1;
+    float* Sr = S + r * KMAX;
+    float m = -INFINITY;
+    for (int j = lane; j < nk; j += 64) m = fmaxf(m, Sr[j]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < nk; j += 64) {
+      const float e = expf(Sr[j] - m);
+      Sr[j] = e;
+      sum += e;
+    }
+    const float inv = 1.0f / wave_sum(sum);
+    for (int j = lane; j < nk; j += 64) Sr[j] *= inv;
+  }
+  __syncthreads();
+
+  // P.V: thread = (output column d, row group rg); the context V rows are read once per row group
+  const int d = tid & (DH - 1), rg = tid >> 6;
+  constexpr int RPT = QMAX / (NTHREADS / DH);    // 8 rows per thread
+  float acc[RPT];
+#pragma unroll
+  for (int u = 0; u < RPT; ++u) acc[u] = 0.f;
+  // eight V rows in flight per iteration: one dependent load per key left this loop latency-bound (~200 us per launch)
+  const bf16_t* vcol = p.ctx_v + (int64_t)co * p.ldc + h * DH + d;
+  constexpr int VU = 8;
+  int j = 0;
+  for (; j + VU <= c; j += VU) {
+    float v[VU];
+#pragma unroll
+    for (int e = 0; e < VU; ++e) v[e] = bf2f(vcol[(int64_t)(j + e) * p.ldc]);
+#pragma unroll
+    for (int u = 0; u < RPT; ++u) {
+      const int r = rg + 4 * u;
+      if (r < nq) {
+#pragma unroll
+        for (int e = 0; e < VU; ++e) acc[u] = fmaf(S[r * KMAX + j + e], v[e], acc[u]);
+      }
+    }
+  }
+  for (; j < c; ++j) {
+    const float v = bf2f(vcol[(int64_t)j * p.ldc]);
+#pragma unroll
+    for (int u = 0; u < RPT; ++u) {
+      const int r = rg + 4 * u;
+      if (r < nq) acc[u] = fmaf(S[r * KMAX + j], v, acc[u]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < RPT; ++u) {
+    const int r = rg + 4 * u;
+    if (r >= nq) continue;
+    const int b = r / p.nr, i = r % p.nr, s = slot0 + b;
+    const int pl = plen_of(s);
+    float a = acc[u];
+    const bf16_t* pcol = p.priv_v + (int64_t)s * p.pcap * p.ldp + h * DH + d;
+    int j = 0;
+    for (; j + 4 <= pl; j += 4) {
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = bf2f(pcol[(int64_t)(j + e) * p.ldp]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a = fmaf(S[r * KMAX + c + j + e], v[e], a);
+    }
+    for (; j < pl; ++j) a = fmaf(S[r * KMAX + c + j], bf2f(pcol[(int64_t)j * p.ldp]), a);
+    for (int e = 0; e <= i; ++e)
+      a = fmaf(S[r * KMAX + c + pl + e], bf2f(p.v[(int64_t)(s * p.nr + e) * p.ldv + h * DH + d]), a);
+    p.out[(int64_t)(row0 + r) * p.ldo + h * DH + d] = f2bf(a);
+  }
+}
+
+struct KvParams {
+  const bf16_t* src; bf16_t* dst; const bf16_t* nkv;
+  const int32_t *parent, *plen; int32_t* plen_out;
+  int layers, slots, pcap, ldp, width;
+  int64_t nls;
+  int ld_new, row_mul;
+};
+
+// grid (slots, layers): slot s of layer l <- rows [0, plen[p]) of parent p, then p's new answer row
+__global__ __launch_bounds__(NTHREADS) void kv_update_kernel(KvParams a) {
+  const int s = blockIdx.x, l = blockIdx.y;
+  const int par = min(max(a.parent[s], 0), a.slots - 1);
+  const int pl = min(max(a.plen[par], 0), a.pcap - 1);
+  const int vec = a.width / 8;
+  const bf16_t* src = a.src + ((int64_t)l * a.slots + par) * a.pcap * a.ldp;
+  bf16_t* dst = a.dst + ((int64_t)l * a.slots + s) * a.pcap * a.ldp;
+  const bf16_t* nrow = a.nkv + l * a.nls + (int64_t)par * a.row_mul * a.ld_new;
+  for (int t = threadIdx.x; t < (pl + 1) * vec; t += NTHREADS) {
+    const int r = t / vec, c = t % vec;
+    const uint4* from = reinterpret_cast<const uint4*>(r < pl ? src + (int64_t)r * a.ldp : nrow) + c;
+    reinterpret_cast<uint4*>(dst + (int64_t)r * a.ldp)[c] = *from;
+  }
+  if (l == 0 && threadIdx.x == 0) a.plen_out[s] = pl + 1;
+}
+
+struct TopkParams {
+  const float* logits; const int32_t* banned; const int32_t* flags;
+  float* vals; int32_t* ids; float* lse;
+  int rows, V, ldl, nbanned, sep, K;
+};
+
+// (va, ia) ranks before (vb, ib): value desc, id asc
+__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
+
+__global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
+  __shared__ uint32_t ban[VMAX / 32];
+  __shared__ float lv[TOPK_MAX * NTHREADS];
+  __shared__ int li[TOPK_MAX * NTHREADS];
+  __shared__ float rm[NTHREADS / 64], rs[NTHREADS / 64];
+  __shared__ int wi[NTHREADS / 64];
+  __shared__ float wv[NTHREADS / 64];
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const int nw = (a.V + 31) / 32;
+  for (int w = tid; w < nw; w += NTHREADS) ban[w] = 0u;
+  __syncthreads();
+  for (int b = tid; b < a.nbanned; b += NTHREADS) {
+    const int id = a.banned[b];
+    if (id >= 0 && id < a.V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+  }
+  __syncthreads();
+  const int f = a.flags != nullptr ? a.flags[row] : 0;
+  const float* x = a.logits + (int64_t)row * a.ldl;
+  const int K = a.K;
+
+  float m = -INFINITY, s = 0.f;
+  int n = 0;                                     // entries of this thread's list (value desc, id asc)
+  float tv = 0.f;
+  int ti = 0;                                    // its last entry once full
+  for (int j = tid; j < a.V; j += NTHREADS) {
+    const float xv = x[j];
+    if (xv > -INFINITY) {
+      if (xv > m) {
+        s = s * expf(m - xv) + 1.f;
+        m = xv;
+      } else {
+        s += expf(xv - m);
+      }
+    }
+    const bool banned = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == a.sep) || ((f & 2) && j != a.sep);
+    const float cv = banned ? -INFINITY : xv;
+    if (n < K || better(cv, j, tv, ti)) {
+      int pos = n < K ? n : K - 1;
+      while (pos > 0 && better(cv, j, lv[(pos - 1) * NTHREADS + tid], li[(pos - 1) * NTHREADS + tid])) {
+        lv[pos * NTHREADS + tid] = lv[(pos - 1) * NTHREADS + tid];
+        li[pos * NTHREADS + tid] = li[(pos - 1) * NTHREADS + tid];
+        --pos;
+      }
+      lv[pos * NTHREADS + tid] = cv;
+      li[pos * NTHREADS + tid] = j;
+      if (n < K) ++n;
+      tv = lv[(n - 1) * NTHREADS + tid];
+      ti = li[(n - 1) * NTHREADS + tid];
+    }
+  }
+
+  // log-sum-exp of the row: combine the (max, scaled sum) pairs
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    const float M = fmaxf(m, m2);
+    s = (M == -INFINITY) ? 0.f : s * expf(m - M) + s2 * expf(m2 - M);
+    m = M;
+  }
+  if (lane == 0) { rm[wave] = m; rs[wave] = s; }
+  __syncthreads();
+  float M = rm[0];
+  for (int w = 1; w < NTHREADS / 64; ++w) M = fmaxf(M, rm[w]);
+  float tot = 0.f;
+  for (int w = 0; w < NTHREADS / 64; ++w)
+    if (rm[w] > -INFINITY) tot += rs[w] * expf(rm[w] - M);
+  const float lse = M + logf(tot);
+
+  // merge the 256 sorted lists: K rounds of a block-wide arg-best over the list heads
+  int hd = 0;
+  for (int r = 0; r < K; ++r) {
+    float bv = hd < n ? lv[hd * NTHREADS + tid] : -INFINITY;
+    int bi = hd < n ? li[hd * NTHREADS + tid] : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(bv, o, 64);
+      const int i2 = __shfl_xor(bi, o, 64);
+      if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+    }
+    if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+    __syncthreads();
+    bv = wv[0];
+    bi = wi[0];
+    for (int w = 1; w < NTHREADS / 64; ++w)
+      if (better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+    __syncthreads();
+    if (hd < n && li[hd * NTHREADS + tid] == bi) ++hd;
+    if (tid == 0) {
+      a.vals[(int64_t)row * K + r] = bv - lse;
+      a.ids[(int64_t)row * K + r] = bi;
+    }
+  }
+  if (tid == 0 && a.lse != nullptr) a.lse[row] = lse;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+extern "C" int unimm_attn_decode(const unimm_attn_decode_args* a, void* stream) {
+  if (a == nullptr || a->q == nullptr || a->k == nullptr || a->v == nullptr || a->out == nullptr || a->ctx_k == nullptr ||
+      a->ctx_v == nullptr || a->ctx_off == nullptr || a->ctx_len == nullptr || a->plen == nullptr)
+    return UNIMM_E_ARG;
+  if (a->pcap > 0 && (a->priv_k == nullptr || a->priv_v == nullptr)) return UNIMM_E_ARG;
+  if (a->D != DH || a->H < 1 || a->H * DH > 1024 || a->G < 1 || a->beams < 1 || (a->nr != 1 && a->nr != 2) ||
+      a->beams * a->nr > QMAX || a->pcap < 0)
+    return UNIMM_E_SHAPE;
+  if (!al16(a->q) || !al16(a->k) || !al16(a->v) || !al16(a->ctx_k) || !al16(a->ctx_v) ||
+      (a->pcap > 0 && (!al16(a->priv_k) || !al16(a->priv_v) || a->ldp % 8)) ||
+      a->ldq % 8 || a->ldk % 8 || a->ldv % 8 || a->ldc % 8)
+    return UNIMM_E_ALIGN;
+  DecodeParams p;
+  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v; p.out = (bf16_t*)a->out;
+  p.ctx_k = (const bf16_t*)a->ctx_k; p.ctx_v = (const bf16_t*)a->ctx_v; p.ctx_off = a->ctx_off; p.ctx_len = a->ctx_len;
+  p.priv_k = (const bf16_t*)a->priv_k; p.priv_v = (const bf16_t*)a->priv_v; p.plen = a->plen;
+  p.G = a->G; p.beams = a->beams; p.nr = a->nr; p.H = a->H; p.pcap = a->pcap;
+  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.ldc = a->ldc; p.ldp = a->ldp;
+  p.scale = a->scale;
+  hipLaunchKernelGGL(attn_decode_kernel, dim3((unsigned)(a->G * a->H)), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+extern "C" int unimm_kv_cache_update(const unimm_kv_update_args* a, void* stream) {
+  if (a == nullptr || a->src == nullptr || a->dst == nullptr || a->new_kv == nullptr || a->parent == nullptr ||
+      a->plen == nullptr || a->plen_out == nullptr)
+    return UNIMM_E_ARG;
+  if (a->layers < 1 || a->slots < 1 || a->pcap < 1 || a->width < 8 || a->width > a->ldp || a->new_row_mul < 1)
+    return UNIMM_E_SHAPE;
+  if (a->src == a->dst || a->plen == a->plen_out) return UNIMM_E_ARG;
+  if (!al16(a->src) || !al16(a->dst) || !al16(a->new_kv) || a->width % 8 || a->ldp % 8 || a->ld_new % 8 ||
+      a->new_layer_stride % 8)
+    return UNIMM_E_ALIGN;
+  KvParams p;
+  p.src = (const bf16_t*)a->src; p.dst = (bf16_t*)a->dst; p.nkv = (const bf16_t*)a->new_kv;
+  p.parent = a->parent; p.plen = a->plen; p.plen_out = a->plen_out;
+  p.layers = a->layers; p.slots = a->slots; p.pcap = a->pcap; p.ldp = a->ldp; p.width = a->width;
+  p.nls = a->new_layer_stride; p.ld_new = a->ld_new; p.row_mul = a->new_row_mul;
+  hipLaunchKernelGGL(kv_update_kernel, dim3((unsigned)a->slots, (unsigned)a->layers), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+extern "C" int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                             const int32_t* flags, int32_t sep, int32_t K, float* vals, int32_t* ids, float* lse, void* stream) {
+  if (logits == nullptr || vals == nullptr || ids == nullptr || (nbanned > 0 && banned == nullptr)) return UNIMM_E_ARG;
+  if (rows < 0 || V < 1 || V > VMAX || ldl < V || K < 1 || K > TOPK_MAX || K > V || nbanned < 0) return UNIMM_E_SHAPE;
+  if (rows == 0) return UNIMM_OK;
+  TopkParams p;
+  p.logits = logits; p.banned = banned; p.flags = flags; p.vals = vals; p.ids = ids; p.lse = lse;
+  p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.K = K;
+  hipLaunchKernelGGL(lm_topk_kernel, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}

@@ -346,10 +346,11 @@ class Engine:
             return DR.drop_arg(p, DR.site_key(self.seed, _site(name))) + (self.salt_word,)
         return DR.drop_arg(p, DR.make_key(self.seed, self.step, _site(name)))
 
-    def _linear(self, x, lin, epi=L.EPI_BIAS, aux=None, want_u=False, drop=None, out_f32=False, ldo=None, M=None):
+    def _linear(self, x, lin, epi=L.EPI_BIAS, aux=None, want_u=False, drop=None, out_f32=False, ldo=None, M=None, out=None):
         M = x.shape[0] if M is None else M
         ldo = ldo or lin.N
-        out = torch.empty((M, ldo), dtype=F32 if out_f32 else BF16, device=x.device)
+        if out is None:                              # or a caller's [M, ldo] buffer (answer generation's per-layer K / V stash)
+            out = torch.empty((M, ldo), dtype=F32 if out_f32 else BF16, device=x.device)
         u = torch.empty((M, ldo), dtype=BF16, device=x.device) if want_u else None
         aux_ln = None
         if isinstance(aux, _LazyLN):

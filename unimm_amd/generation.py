@@ -1,0 +1,340 @@
+"""Answer generation: beam search over the generative (prefix-LM) mask with a per-layer key/value cache.
+
+Why a cache is exact.  Under the generative mask (utils/data_utils.py:199-210; `oracle/masks.py` restates it), with context
+length c (dialog `[CLS] caption [SEP] q1 [SEP] a1 ... q_r [SEP]` in positions [0, c)):
+
+    context rows [1, c)   attend [1, c)                       -- never column 0, never the answer
+    answer row c + k      attends [1, c + k]                  -- causal
+    copy row of token k   attends [1, c + k) + itself         -- a [MASK] with answer token k's position id; predicts token k
+    regions               attend text [1, c)                  (co-attention mask)
+    column 0 (CLS)        is attended by nobody but CLS itself
+
+so the image stream and the context rows never depend on the answer, answer row k depends on earlier answer rows only and
+the copy row of token k on the context and answer rows < k.  A dialog is PREFILLED once (context + image through the whole
+encoder: the shared-context pass of `scoring.py`, which keeps every text layer's context K / V and every connection layer's
+region K1 / V1), and decode step k pushes exactly two new text rows per hypothesis through the blocks: answer row k-1 (its
+K / V joins the hypothesis's private cache afterwards) and copy row k (its logits choose token k).  Step 0 needs no decode:
+the prefill runs the one-token sequence `context [SEP] [MASK]`, whose copy row IS copy row 0.  Consequently the log p of a
+generated answer equals `sequence_log_likelihood` of the completed sequence.
+
+Answer token k of dialog g has position id position_ids[g, c-1] + 1 + k and segment token_type_ids[g, c-1] ^ 1
+(`oracle/masks.py::_layout`: the segment toggles for the answer); the copy rows are [MASK] (103) with the same ids.
+
+Search semantics (k = tokens generated so far, excluding [SEP]):
+
+* Step k: for each live hypothesis, log-softmax over the vocabulary of its copy row's logits; then -inf for the ids in
+  `banned_tokens`, for [SEP] (102) while k < min_answer_len, and for every id other than [SEP] once k reaches the dialog's
+  limit min(max_answer_len, (T - c) // 2 - 1) (so that the completed sequence fits in T untruncated), which forces the end.
+  No renormalisation after banning: scores stay comparable with `sequence_log_likelihood`.
+* Candidates: each live hypothesis proposes its top `beams` tokens (value desc, id asc); a candidate's score is the parent's
+  cumulative log p plus the token's log p (fp32).  Candidates are ordered by (score desc, parent slot asc, token id asc);
+  candidates of score -inf are never taken.
+* The walk over the ordered candidates: a [SEP] candidate becomes a finished hypothesis (final score
+  logp / (k + 1) ** length_penalty) while the dialog has fewer than `beams` finished ones; any other candidate takes a live
+  slot; the walk ends when `beams` live slots are filled.
+* A dialog stops when it has `beams` finished hypotheses or no live hypothesis left.
+* Output: the `beams` best finished hypotheses by (final score desc, finishing step asc, walk order); a dialog that finished
+  fewer pads with zero tokens, length 0 and score / logp -inf.
+* beams = 1 is greedy decoding; length_penalty = 0 returns the summed log p of val_lm.py, 1 the token mean of val_avg_lm.py.
+
+`beam_search` is written against an abstract step function (tests drive it with a table model on the CPU); `generate_answers`
+supplies the engine's: the decode step runs the existing NT GEMM / LayerNorm kernels on M = 2 * slots rows,
+`unimm_attn_decode` for text self-attention, `unimm_attn_fwd` (variable-length) against the cached regions for the
+text-attends-regions half of a connection layer, the MLM head on the copy rows, `unimm_lm_topk` on the fp32 logits, and
+`unimm_kv_cache_update` (append + reorder of the private caches of all text layers) between steps.  Beam selection runs as
+torch ops on the [G, beams * beams] candidates; the only device->host synchronisation of a step is the "all dialogs
+stopped" flag.  Inference only, bf16 engine with the connection layers.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import params as PM
+from .inputs import DialogMaskSpec
+
+SEP, MASK = 102, 103
+BF16, F32 = torch.bfloat16, torch.float32
+MAX_BEAMS = 16
+SEP_BANNED, SEP_FORCED = 1, 2                  # per-row flags of unimm_lm_topk
+
+
+@dataclass
+class GeneratedAnswers:
+    tokens: torch.Tensor    # int64 [G, beams, max_answer_len + 1]: answer tokens then [SEP], zero-padded
+    lengths: torch.Tensor   # int64 [G, beams], including the [SEP]
+    scores: torch.Tensor    # fp32 [G, beams]: logp / lengths ** length_penalty
+    logp: torch.Tensor      # fp32 [G, beams]: summed log p
+    step_logp: torch.Tensor  # fp32 [G, beams, max_answer_len + 1]: the log p of each token (an extension: per-step checks)
+
+
+def answer_limits(context_len, T, max_answer_len):
+    """Tokens dialog g may generate before its [SEP]: min(max_answer_len, (T - c) // 2 - 1)."""
+    c = np.asarray(context_len, dtype=np.int64).reshape(-1)
+    return np.minimum(max_answer_len, (T - c) // 2 - 1)
+
+
+def check_request(context_len, T, beams, max_answer_len, min_answer_len):
+    """The refused cases (ValueError): -> per-dialog limits (np.int64 [G])."""
+    if not 1 <= int(beams) <= MAX_BEAMS:
+        raise ValueError(f"generate_answers: beams must be in [1, {MAX_BEAMS}], got {beams}")
+    if max_answer_len < 0 or min_answer_len < 0 or min_answer_len > max_answer_len:
+        raise ValueError(f"generate_answers: need 0 <= min_answer_len <= max_answer_len (got {min_answer_len}, {max_answer_len})")
+    c = np.asarray(context_len, dtype=np.int64).reshape(-1)
+    if (c < 2).any() or (c > T).any():
+        raise ValueError("generate_answers: every context must hold [CLS] and at least one token (2 <= context_len <= T)")
+    lim = answer_limits(c, T, max_answer_len)
+    bad = np.nonzero(lim < min_answer_len)[0]
+    if bad.size:
+        g = int(bad[0])
+        raise ValueError(f"generate_answers: dialog {g} (context {int(c[g])} of T = {T}) has room for {max(int(lim[g]), 0)} answer "
+                         f"tokens, fewer than min_answer_len = {min_answer_len}")
+    return lim
+
+
+def answer_ids(pos_last, seg_last, k):
+    """(position id, segment id) of answer token k (and of its [MASK] copy) after a context whose last token has them."""
+    return pos_last + 1 + k, seg_last ^ 1
+
+
+def step_flags(k, limits, beams, min_answer_len):
+    """int32 [G * beams] flags of step k: SEP_BANNED while k < min_answer_len, SEP_FORCED once k reaches the dialog's limit."""
+    f = torch.where(limits <= k, SEP_FORCED, 0).to(torch.int32)
+    if k < min_answer_len:
+        f = f | SEP_BANNED
+    return f.repeat_interleave(beams)
+
+
+def beam_search(step, G, beams, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
+    """Run the search of the module docstring.  step(k, parent, token, flags) -> (vals fp32 [G*beams, beams], ids [G*beams, beams]):
+    the top-`beams` log p (value desc, id asc; banned ids -inf) of every hypothesis slot at step k, where slot s continues slot
+    parent[s] of the previous step with answer token k-1 = token[s] (k = 0: one root per dialog, slot g * beams; the other
+    slots' rows are ignored).  limits: per-dialog token limits (answer_limits)."""
+    S, W, NEG = G * beams, max_answer_len + 1, float("-inf")
+    dev = torch.device(device)
+    limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev)
+    cum = torch.full((G, beams), NEG, dtype=F32, device=dev)
+    cum[:, 0] = 0.0
+    hist = torch.zeros((S, W), dtype=torch.int64, device=dev)
+    hist_lp = torch.zeros((S, W), dtype=F32, device=dev)
+    parent = torch.arange(S, device=dev)
+    token = torch.zeros(S, dtype=torch.int64, device=dev)
+    alive = torch.ones(G, dtype=torch.bool, device=dev)
+    # finished hypotheses, in finishing order; entry `beams` of each dialog is a sink for the candidates not accepted
+    fin_tok = torch.zeros((G, beams + 1, W), dtype=torch.int64, device=dev)
+    fin_lp = torch.zeros((G, beams + 1, W), dtype=F32, device=dev)
+    fin_len = torch.zeros((G, beams + 1), dtype=torch.int64, device=dev)
+    fin_logp = torch.full((G, beams + 1), NEG, dtype=F32, device=dev)
+    fin_score = torch.full((G, beams + 1), NEG, dtype=F32, device=dev)
+    nfin = torch.zeros(G, dtype=torch.int64, device=dev)
+    gbase = (torch.arange(G, device=dev) * beams)[:, None]
+    for k in range(max_answer_len + 1):
+        vals, ids = step(k, parent, token, step_flags(k, limits, beams, min_answer_len).to(dev))
+        vals = vals.to(dev, F32).view(G, beams, beams)
+        ids = ids.to(dev, torch.int64).view(G, beams, beams)
+        score = (cum[:, :, None] + vals).masked_fill(~alive[:, None, None], NEG).view(G, beams * beams)
+        order = torch.sort(score, dim=1, descending=True, stable=True).indices   # (score desc, parent asc, rank = id asc)
+        sc = score.gather(1, order)
+        tk = ids.view(G, beams * beams).gather(1, order)
+        tv = vals.reshape(G, beams * beams).gather(1, order)
+        par = order // beams                                                  # parent slot inside the dialog
+        finite = sc > NEG
+        is_sep = finite & (tk == SEP)
+        is_live = finite & (tk != SEP)
+        nlive = torch.cumsum(is_live.to(torch.int64), 1)
+        reached = (nlive - is_live.to(torch.int64)) < beams                   # the walk ends at the beams-th live candidate
+        take = is_live & (nlive <= beams)
+        cand_fin = is_sep & reached
+        frank = nfin[:, None] + torch.cumsum(cand_fin.to(torch.int64), 1) - 1
+        accept = cand_fin & (frank < beams)
+        # finished: the parent's history + [SEP] at position k
+        ftok = hist.view(G, beams, W).gather(1, par[:, :, None].expand(-1, -1, W)).clone()
+        ftok[:, :, k] = SEP
+        flp = hist_lp.view(G, beams, W).gather(1, par[:, :, None].expand(-1, -1, W)).clone()
+        flp[:, :, k] = tv
+        fidx = torch.where(accept, frank, beams)
+        fin_tok.scatter_(1, fidx[:, :, None].expand(-1, -1, W), ftok)
+        fin_lp.scatter_(1, fidx[:, :, None].expand(-1, -1, W), flp)
+        fin_len.scatter_(1, fidx, torch.full_like(fidx, k + 1))
+        fin_logp.scatter_(1, fidx, sc)
+        fin_score.scatter_(1, fidx, sc / float((k + 1) ** length_penalty))
+        nfin = nfin + accept.sum(1)
+        # live: slot rank = order among the taken candidates
+        lidx = torch.where(take, nlive - 1, beams)
+        new_par = torch.cat([gbase.expand(G, beams) + torch.arange(beams, device=dev), gbase], 1)
+        new_par = new_par.scatter(1, lidx, gbase + par)[:, :beams]
+        new_tok = torch.zeros((G, beams + 1), dtype=torch.int64, device=dev).scatter(1, lidx, tk)[:, :beams]
+        new_cum = torch.full((G, beams + 1), NEG, dtype=F32, device=dev).scatter(1, lidx, sc)[:, :beams]
+        new_lp = torch.zeros((G, beams + 1), dtype=F32, device=dev).scatter(1, lidx, tv)[:, :beams]
+        parent, token = new_par.reshape(S), new_tok.reshape(S)
+        hist, hist_lp = hist[parent], hist_lp[parent]
+        hist[:, k] = token
+        hist_lp[:, k] = new_lp.reshape(S)
+        cum = new_cum
+        alive = alive & (nfin < beams) & take.any(1)
+        if not bool(alive.any()):                                             # the step's one device -> host synchronisation
+            break
+    fs = fin_score[:, :beams]
+    order = torch.sort(fs, dim=1, descending=True, stable=True).indices
+    return GeneratedAnswers(tokens=fin_tok[:, :beams].gather(1, order[:, :, None].expand(-1, -1, W)),
+                            lengths=fin_len[:, :beams].gather(1, order), scores=fs.gather(1, order),
+                            logp=fin_logp[:, :beams].gather(1, order),
+                            step_logp=fin_lp[:, :beams].gather(1, order[:, :, None].expand(-1, -1, W)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the engine's step function
+# ---------------------------------------------------------------------------------------------------------------------------
+def generate_answers(model, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
+                     image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
+                     length_penalty=0.0, banned_tokens=(0, 101, 103)):
+    """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
+    if getattr(model, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError("generate_answers runs on the bf16 engine")
+    cfg = model.config
+    if not cfg.with_coattention:
+        raise NotImplementedError("generate_answers needs the connection layers (with_coattention)")
+    G, T = input_ids.shape
+    c_h = (context_len.cpu().numpy() if torch.is_tensor(context_len) else np.asarray(context_len)).astype(np.int64).reshape(-1)
+    if c_h.shape[0] != G:
+        raise ValueError(f"generate_answers: {c_h.shape[0]} context lengths for {G} dialogs")
+    limits = check_request(c_h, T, beams, max_answer_len, min_answer_len)
+    eng = model._engine
+    eng.ensure(model._device())
+    inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
+               position_ids=position_ids, image_attention_mask=image_attention_mask, image_index=image_index)
+    inp = {k: v for k, v in inp.items() if v is not None}
+    eng.stage_host_inputs(inp, pack=("attention_mask", "co_attention_mask"))   # the [G, R] image key mask stays a tensor
+    return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
+                               tuple(int(t) for t in banned_tokens))
+
+
+def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens):
+    from .scoring import _forward_shared
+    cfg = eng.cfg
+    dev = eng.arena.device
+    ids = inp["input_ids"].to(dev, non_blocking=True)
+    G, T = ids.shape
+    S = G * beams
+    H, Hb, V = cfg.hidden_size, cfg.bi_hidden_size, cfg.vocab_size
+    heads, nh = cfg.num_attention_heads, cfg.bi_num_attention_heads
+    D, Db = H // heads, Hb // nh
+    if D != 64:
+        raise ValueError(f"generate_answers: text head size {D} (unimm_attn_decode takes 64)")
+    R = inp["image_feat"].shape[1]
+    ar = torch.arange(G, device=dev)
+    c_d = torch.from_numpy(c_h).to(dev)
+    tt = inp.get("token_type_ids")
+    tt = tt.to(dev, non_blocking=True).long() if tt is not None else torch.zeros((G, T), dtype=torch.int64, device=dev)
+    pp = inp.get("position_ids")
+    pp = pp.to(dev, non_blocking=True).long() if pp is not None else torch.arange(T, device=dev).repeat(G, 1)
+    pos_last, seg_last = pp[ar, c_d - 1], tt[ar, c_d - 1]
+    apos, aseg = answer_ids(pos_last, seg_last, 0)
+
+    # ---- prefill: `context [SEP] [MASK]` per dialog through the shared-context pass, keeping the caches ---------------------
+    pid, ptt, ppp = ids.long().clone(), tt.clone(), pp.clone()
+    lab = torch.full((G, T), -1, dtype=torch.int64, device=dev)
+    for j, tok in ((0, SEP), (1, MASK)):
+        pid[ar, c_d + j] = tok
+        ptt[ar, c_d + j] = aseg
+        ppp[ar, c_d + j] = apos
+    lab[ar, c_d + 1] = SEP
+    pin = dict(input_ids=pid, image_feat=inp["image_feat"], image_loc=inp["image_loc"], token_type_ids=ptt, position_ids=ppp,
+               masked_lm_labels=lab, attention_mask=DialogMaskSpec(np.ones(G), c_h + 1, np.ones(G)))
+    for k in ("image_attention_mask", "image_index"):
+        if k in inp:
+            pin[k] = inp[k]
+    cache = {}
+    pre = _forward_shared(eng, pin, np.arange(G), False, cache)
+    plan = pre["plan"]
+    s_off, s_len = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (plan.s_off, plan.s_len))
+    vwords = cache["vwords"]
+    nwv = vwords.shape[1]
+
+    sched = PM.encoder_schedule(cfg)
+    tkeys = [f"t{i}" for kind, i in sched if kind == "t"]
+    nt = len(tkeys)
+    lidx = {key: n for n, key in enumerate(tkeys)}
+    pcap = max(int(limits.max()), 1)
+    priv = [torch.zeros((nt, S, pcap, 2 * H), dtype=BF16, device=dev) for _ in range(2)]
+    plen = [torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2)]
+    M = 2 * S
+    stash = torch.empty((nt, M, 3 * H), dtype=BF16, device=dev)               # the step's fused projections, per text layer
+    banned = torch.tensor(banned_tokens, dtype=torch.int32, device=dev) if banned_tokens else None
+    vals = torch.empty((S, beams), dtype=F32, device=dev)
+    tops = torch.empty((S, beams), dtype=torch.int32, device=dev)
+    q_off = (ar * 2 * beams).to(torch.int32)
+    q_len = torch.full((G,), 2 * beams, dtype=torch.int32, device=dev)
+    k_off = (ar * R).to(torch.int32)
+    k_len = torch.full((G,), R, dtype=torch.int32, device=dev)
+    copy_rows = torch.arange(1, M, 2, device=dev, dtype=torch.int32)
+    slot_pos = apos.repeat_interleave(beams)
+    slot_seg = aseg.repeat_interleave(beams)
+    gmm, bta, _, _ = eng.ln["emb_t"]
+    NO = L.NO_DROP
+    st = dict(cur=0)
+
+    def text_block(key, x32, x):
+        qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
+        li = lidx[key]
+        qkv = eng._linear(x, qkv_l, out=stash[li])
+        ctxq = cache[key]
+        ctx = torch.empty((M, H), dtype=BF16, device=dev)
+        pv = priv[st["cur"]][li].view(S * pcap, 2 * H)
+        L.attn_decode(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, ctxq[:, H:2 * H], ctxq[:, 2 * H:], s_off, s_len,
+                      pv[:, :H], pv[:, H:], plen[st["cur"]], G, beams, 2, heads, pcap, 1.0 / math.sqrt(D))
+        pre1 = eng._linear(ctx, so, L.EPI_BIAS_DROP_RESID, aux=x32, drop=NO, out_f32=True)
+        x1_32, x1, _, _ = eng._layernorm(pre1, key + ".ln1", False, lazy=True)
+        h = eng._linear(x1, ff1, L.EPI_BIAS_GELU)
+        pre2 = eng._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=NO, out_f32=True)
+        x2_32, x2, _, _ = eng._layernorm(pre2, key + ".ln2", False, lazy=True)
+        return x2_32, x2
+
+    def conn_block(key, xt32, xt):
+        """The text half of a connection layer: the regions' side is the prefill's (they never attend the answer)."""
+        lq2, d2, tff1, tff2 = (eng.lin[key + s] for s in (".qkv2", ".d2", ".tff1", ".tff2"))
+        qkv1 = cache[key]
+        qkv2 = eng._linear(xt, lq2)
+        ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
+        L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, G, nh, T, R, Db, 1.0 / math.sqrt(Db),
+                   0, nwv, NO, qvar=(q_off, q_len), kvar=(k_off, k_len))
+        pret = eng._linear(ctx_t, d2, L.EPI_BIAS_DROP_RESID, aux=xt32, drop=NO, out_f32=True)
+        at32, at, _, _ = eng._layernorm(pret, key + ".lnb2", False, lazy=True)
+        ht = eng._linear(at, tff1, L.EPI_BIAS_GELU)
+        pret2 = eng._linear(ht, tff2, L.EPI_BIAS_DROP_RESID, aux=at32, drop=NO, out_f32=True)
+        ot32, ot, _, _ = eng._layernorm(pret2, key + ".lnt", False, lazy=True)
+        return ot32, ot
+
+    def step(k, parent, token, flags):
+        if k == 0:                                         # copy row 0 is the prefill's decoded row
+            L.lm_topk(pre["logits"], G, V, banned, flags[::beams].contiguous(), SEP, beams, vals[:G], tops[:G])
+            return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
+        if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
+            cur = st["cur"]
+            L.kv_cache_update(priv[cur], priv[1 - cur], stash[0][:, H:], parent.to(torch.int32), plen[cur], plen[1 - cur],
+                              nt, S, pcap, 2 * H, M * 3 * H, 2)
+            st["cur"] = 1 - cur
+        # new rows: (answer row k-1, copy row k) per slot
+        ids32 = torch.stack([token, torch.full_like(token, MASK)], 1).reshape(M).to(torch.int32)
+        pos32 = torch.stack([slot_pos + (k - 1), slot_pos + k], 1).reshape(M).to(torch.int32)
+        typ32 = slot_seg.repeat_interleave(2).to(torch.int32)
+        xt = torch.empty((M, H), dtype=BF16, device=dev)
+        xt32 = torch.empty((M, H), dtype=F32, device=dev)
+        L.embed_fwd(ids32, pos32, typ32, eng.tab["word"], eng.tab["pos"], eng.tab["type"], eng.tab["ext"], gmm, bta, xt32, xt, M, H,
+                    cfg.type_vocab_size)
+        for kind, i in sched:
+            if kind == "t":
+                xt32, xt = text_block(f"t{i}", xt32, xt)
+            elif kind == "c":
+                xt32, xt = conn_block(f"c{i}", xt32, xt)
+        xs = torch.empty((S, H), dtype=BF16, device=dev)
+        L.gather_rows(xt, copy_rows, xs, S, H)
+        logits = eng.decode_rows(xs, S)
+        L.lm_topk(logits, S, V, banned, flags, SEP, beams, vals, tops)
+        return vals, tops
+
+    return beam_search(step, G, beams, limits, max_answer_len, min_answer_len, length_penalty, device=dev)

@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -74,6 +74,9 @@ def lib():
     L.unimm_x3_attn_fwd.argtypes = [VP, VP, VP]
     L.unimm_x3_attn_bwd.argtypes = [VP, VP, VP]
     L.unimm_attn_probs.argtypes = [VP, VP, VP]
+    L.unimm_attn_decode.argtypes = [VP, VP]
+    L.unimm_kv_cache_update.argtypes = [VP, VP]
+    L.unimm_lm_topk.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, I32, VP, VP, VP, VP]
     L.unimm_gemm_tn_grouped.argtypes = [VP, I32, VP]
     L.unimm_gemm_tn_grouped_ws.argtypes = [VP, I32, I32, VP, I64, VP]
     L.unimm_colpartials_finish_grouped.argtypes = [VP, I32, VP]
@@ -96,7 +99,9 @@ SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "uni
            # the fp32-accuracy mode (csrc/x3ops.hip)
            "unimm_x3_split", "unimm_x3_split_wt", "unimm_x3_layernorm_bwd_partials", "unimm_embed_bwd_f32", "unimm_x3_lm_loss_bwd",
            "unimm_x3_kl_loss_bwd", "unimm_x3_rows_add", "unimm_x3_attn_fwd", "unimm_x3_attn_bwd", "unimm_x3_attn_set_impl", "unimm_x3_layernorm_fwd", "unimm_prof_tag", "unimm_prof_tagged",
-           "unimm_sum_dropout", "unimm_sum_dropout_bwd", "unimm_mse_loss_fwd", "unimm_mse_loss_bwd", "unimm_host_mask_pack", "unimm_host_memcpy"]
+           "unimm_sum_dropout", "unimm_sum_dropout_bwd", "unimm_mse_loss_fwd", "unimm_mse_loss_bwd", "unimm_host_mask_pack", "unimm_host_memcpy",
+           # answer generation (csrc/generate.hip, ABI 19)
+           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk"]
 
 
 def _check(rc, what):
@@ -310,6 +315,61 @@ def attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mas
     rc = fn(addr, _stream())
     if rc != 0:
         _check(rc, "unimm_attn_fwd")
+
+
+class AttnDecodeArgs(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("out", C.c_void_p),
+                ("ctx_k", C.c_void_p), ("ctx_v", C.c_void_p), ("ctx_off", C.c_void_p), ("ctx_len", C.c_void_p),
+                ("priv_k", C.c_void_p), ("priv_v", C.c_void_p), ("plen", C.c_void_p),
+                ("G", C.c_int32), ("beams", C.c_int32), ("nr", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("pcap", C.c_int32),
+                ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32), ("ldo", C.c_int32), ("ldc", C.c_int32), ("ldp", C.c_int32),
+                ("scale", C.c_float)]
+
+
+class KvUpdateArgs(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("new_kv", C.c_void_p),
+                ("parent", C.c_void_p), ("plen", C.c_void_p), ("plen_out", C.c_void_p),
+                ("layers", C.c_int32), ("slots", C.c_int32), ("pcap", C.c_int32), ("ldp", C.c_int32), ("width", C.c_int32),
+                ("new_layer_stride", C.c_int64), ("ld_new", C.c_int32), ("new_row_mul", C.c_int32)]
+
+
+def attn_decode(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen, G, beams, nr, H, pcap, scale, D=64):
+    """Text self-attention of the decode rows (unimm_attn_decode): q / k / v / out / ctx_k / ctx_v are 2-D bf16 views (row stride =
+    stride(0)); priv_k / priv_v: 2-D views whose row (slot * pcap + r) is cached answer row r of a slot (or None when pcap = 0)."""
+    _dev(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen)
+    a = AttnDecodeArgs()
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.ctx_k, a.ctx_v, a.ctx_off, a.ctx_len = ctx_k.data_ptr(), ctx_v.data_ptr(), ctx_off.data_ptr(), ctx_len.data_ptr()
+    a.priv_k, a.priv_v, a.plen = _P(priv_k), _P(priv_v), plen.data_ptr()
+    a.G, a.beams, a.nr, a.H, a.D, a.pcap = G, beams, nr, H, D, pcap
+    a.ldq, a.ldk, a.ldv, a.ldo, a.ldc = q.stride(0), k.stride(0), v.stride(0), out.stride(0), ctx_k.stride(0)
+    if ctx_v.stride(0) != ctx_k.stride(0):
+        raise UnimmHipError("attn_decode: ctx_k and ctx_v need one row stride")
+    a.ldp = priv_k.stride(0) if priv_k is not None else 0
+    if priv_v is not None and priv_v.stride(0) != a.ldp:
+        raise UnimmHipError("attn_decode: priv_k and priv_v need one row stride")
+    a.scale = scale
+    _check(lib().unimm_attn_decode(C.byref(a), _stream()), "unimm_attn_decode")
+
+
+def kv_cache_update(src, dst, new_kv, parent, plen, plen_out, layers, slots, pcap, width, new_layer_stride, new_row_mul):
+    """Private-cache append + reorder (unimm_kv_cache_update).  src / dst: bf16 [layers, slots, pcap, ldp]; new_kv: 2-D bf16 view
+    (row stride = stride(0)) at the first K column of layer 0's new rows; the new answer row of slot p is row p * new_row_mul."""
+    _dev(src, dst, new_kv, parent, plen, plen_out)
+    a = KvUpdateArgs()
+    a.src, a.dst, a.new_kv = src.data_ptr(), dst.data_ptr(), new_kv.data_ptr()
+    a.parent, a.plen, a.plen_out = parent.data_ptr(), plen.data_ptr(), plen_out.data_ptr()
+    a.layers, a.slots, a.pcap, a.ldp, a.width = layers, slots, pcap, src.shape[-1], width
+    a.new_layer_stride, a.ld_new, a.new_row_mul = new_layer_stride, new_kv.stride(0), new_row_mul
+    _check(lib().unimm_kv_cache_update(C.byref(a), _stream()), "unimm_kv_cache_update")
+
+
+def lm_topk(logits, rows, V, banned, flags, sep, K, vals, ids, lse=None):
+    """log-softmax + top-K of fp32 logits [rows, >= V] (unimm_lm_topk): vals fp32 [rows, K], ids int32 [rows, K]."""
+    _dev(logits, banned, flags, vals, ids, lse)
+    nb = 0 if banned is None else banned.numel()
+    _check(lib().unimm_lm_topk(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, K,
+                               vals.data_ptr(), ids.data_ptr(), _P(lse), _stream()), "unimm_lm_topk")
 
 
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):

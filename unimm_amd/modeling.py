@@ -327,6 +327,18 @@ class BertForMultiModalPreTraining(nn.Module):
                 scores = scores / cnt
         return scores, out["nsp"]
 
+    @torch.no_grad()
+    def generate_answers(self, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
+                         image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
+                         length_penalty=0.0, banned_tokens=(0, 101, 103)):
+        """Beam-search answers for the dialogs whose first context_len[g] tokens are `[CLS] caption [SEP] ... q_r [SEP]`, with the
+        context and image computed once and a per-layer key/value cache (an extension; unimm_amd/generation.py states the
+        semantics).  -> GeneratedAnswers(tokens, lengths, scores, logp).  bf16 engine."""
+        from .generation import generate_answers
+        return generate_answers(self, input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids,
+                                image_attention_mask, image_index, beams=beams, max_answer_len=max_answer_len,
+                                min_answer_len=min_answer_len, length_penalty=length_penalty, banned_tokens=banned_tokens)
+
 
 class VisualDialogEncoder(nn.Module):
     """Drop-in for models/visual_dialog_encoder.py:8-50 (what train.py / val_lm.py instantiate)."""
@@ -362,6 +374,15 @@ class VisualDialogEncoder(nn.Module):
         if output_lm_scores:
             out = out + (prediction_scores_t,)
         return out
+
+    def generate_answers(self, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
+                         image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
+                         length_penalty=0.0, banned_tokens=(0, 101, 103)):
+        """BertForMultiModalPreTraining.generate_answers."""
+        return self.bert_pretrained.generate_answers(
+            input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids, image_attention_mask, image_index,
+            beams=beams, max_answer_len=max_answer_len, min_answer_len=min_answer_len, length_penalty=length_penalty,
+            banned_tokens=banned_tokens)
 
     def forward_backward(self, input_ids, image_feat, image_loc, loss_weights, sep_indices=None, sep_len=None, token_type_ids=None,
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,

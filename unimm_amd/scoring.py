@@ -109,14 +109,18 @@ def _i64(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=torch.int64, non_blocking=True)
 
 
-def forward_shared(eng, inp: dict, groups, want_nsp=True):
+def forward_shared(eng, inp: dict, groups, want_nsp=True, cache=None):
     """-> dict(rownll [n_lm] fp32, lm_seq [n_lm] int32 (sequence of each decoded row), nsp [B, 2] | None, ok [B] bool, plan).
     `ok[b]` is False where sequence b's context tokens / segments / positions differ from its group's representative (checked on
-    the device, no host synchronisation): the caller poisons those scores."""
-    return eng._on_text_stream(_forward_shared, eng, inp, groups, want_nsp)
+    the device, no host synchronisation): the caller poisons those scores.
+    cache (a dict, or None): also retain what answer generation reads back (unimm_amd/generation.py) -- per text layer key
+    't<i>' its fused Q|K|V projection of the packed rows (the S rows are the groups' context K / V), per connection layer key
+    'c<i>' the regions' fused projection (K1 / V1), 'vwords' the groups' packed image key masks, and the decoder logits of the
+    copy rows in out['logits'].  Nothing computed changes."""
+    return eng._on_text_stream(_forward_shared, eng, inp, groups, want_nsp, cache)
 
 
-def _forward_shared(eng, inp, groups, want_nsp):
+def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     cfg = eng.cfg
     dev = eng.arena.device
     if getattr(eng, "compute_dtype", "bf16") != "bf16":
@@ -265,6 +269,8 @@ def _forward_shared(eng, inp, groups, want_nsp):
         """BertLayer (models/vilbert_dialog.py:385-483) on the packed rows, inference."""
         qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
         qkv = eng._linear(x, qkv_l)
+        if cache is not None:
+            cache[key] = qkv
         q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
         ctx = torch.empty((M, H), dtype=BF16, device=dev)
         sc = 1.0 / math.sqrt(D)
@@ -288,6 +294,8 @@ def _forward_shared(eng, inp, groups, want_nsp):
         qkv2 = eng._linear(xt, lq2)
         eng._to_txt(qkv1)
         eng._to_img(qkv2)
+        if cache is not None:
+            cache[key] = qkv1
         q1, k1, v1 = qkv1[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:]
         q2, k2, v2 = qkv2[:, :Hb], qkv2[:, Hb:2 * Hb], qkv2[:, 2 * Hb:]
         with eng._img():
@@ -322,6 +330,8 @@ def _forward_shared(eng, inp, groups, want_nsp):
     eng._to_txt(xv32, xv)
 
     out = dict(plan=plan, ok=same)
+    if cache is not None:
+        cache["vwords"] = vmask[0].view(G, nwv)
     # ---- poolers + NSP (models/vilbert_dialog.py:946-967, 1064-1070): row 0 of every sequence, region 0 of its group -------
     if want_nsp:
         xt32d, xv32d = eng._dense32(xt32), eng._dense32(xv32)
@@ -346,6 +356,8 @@ def _forward_shared(eng, inp, groups, want_nsp):
     L.gather_rows(xt, lm_idx, xs, n, H)
     lm = eng._lm_head(xs, n, lab_sel, w_sel, False)
     out["rownll"] = lm["rownll"]
+    if cache is not None:
+        out["logits"] = lm["logits"]
     out["lm_seq"] = (lm_pos // T).to(torch.int32)
     return out
 
