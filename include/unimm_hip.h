@@ -154,6 +154,8 @@ int unimm_gemm_tn_grouped_ws(const unimm_gemm_tn_args* args, int32_t count, int3
  * Tq / Tk remain the PADDED lengths that index mask, lse and the dropout counters.  Padding rows
  * (fully masked queries that no valid row attends, models/vilbert_dialog.py:1418) are then never
  * computed at all.
+ * Keys at positions >= k_len[b] (+ ks_len[b] when a shared segment is spliced in) do not exist, whatever their mask bits say,
+ * and bits past Tk in a row's last word are ignored: only ceil(Tk/32) words of a mask row are read.
  * Alignment: q, k, v, out (and dq, dk, dv, dout of the backward) 16-byte aligned, every row stride a multiple of 8
  * elements: operand fragments are 16-byte loads and result rows leave as 16-byte stores; UNIMM_E_ALIGN otherwise.
  * ------------------------------------------------------------------------------------------- */

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnParams p) {
     const bf16_t* qg_ = p.q + (qbase + qrow) * p.ldq + head * D;                                             \
     _Pragma("unroll") for (int ks = 0; ks < D / 16; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qg_ + 16 * ks + 8 * h); \
     const uint32_t* mp_ = p.mask + (size_t)b * p.mask_b_stride + (size_t)qrow * p.mask_q_stride;            \
-    _Pragma("unroll") for (int t = 0; t < NKT; ++t) mw[t] = mp_[t];                                          \
+    _Pragma("unroll") for (int t = 0; t < NKT; ++t) mw[t] = 32 * t < p.Tk ? mp_[t] : 0u;   /* a row has ceil(Tk / 32) words */ \
   }
   UNIMM_LOAD_QTILE()
   stage_wait();
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   {
     const uint32_t* mp = p.mask + (size_t)b * p.mask_b_stride + (size_t)qrow * p.mask_q_stride;
 #pragma unroll
-    for (int t = 0; t < NKT; ++t) mw[t] = mp[t];
+    for (int t = 0; t < NKT; ++t) mw[t] = 32 * t < p.Tk ? mp[t] : 0u;   // a row has ceil(Tk / 32) words: tiles past them are skipped
   }
   stage_wait();
   __syncthreads();
@@ -470,6 +470,14 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   store_acc_row<D>(p.dq + (qvalid ? grow : 0) * p.lddq + head * D, dq, 1.0f, h, qvalid);
 }
 
+// Keys past the sequence's end do not exist, whatever the mask bits say.  The key-on-the-lane forms compute their lanes anyway (from
+// the last key's row), and a set bit would give such a lane P = 2^(s - lse): +inf on a fully masked query row (lse ~ -10000), which
+// the zero K^T rows of dQ turn into NaN (0 * inf).  Their inverted words therefore mark those keys masked: P stays finite there.
+__device__ __forceinline__ uint32_t pad_key_bits(int Tk_b, int kt) {
+  const int n = Tk_b - 32 * kt;                                 // keys of tile kt that exist (>= 1 for the tiles that are staged)
+  return n >= 32 ? 0u : ~0u << n;
+}
+
 // ------------------------------------------------------------------------------------------------
 // backward, part 2: dK, dV (key on the lane; one wave = one 32-key tile, walks all query tiles)
 //   S = Q . K^T and dP = dO . V^T land as [query regs][key lane]; P / dS feed
@@ -512,7 +520,7 @@ __global__ __launch_bounds__(MAXT, MAXT == 256 ? 1 : 2) void attn_bwd_dkv_kernel
     for (int i = tid; i < nkt_b * qpad_b; i += blockDim.x) {
       const int kt = i / qpad_b, qi = i - kt * qpad_b;
       const int qc = qi < Tq_b ? qi : Tq_b - 1;
-      mw_s[kt * QPAD + qi] = ~mb[(size_t)qc * p.mask_q_stride + kt];   // INVERTED: bit set = masked
+      mw_s[kt * QPAD + qi] = ~mb[(size_t)qc * p.mask_q_stride + kt] | pad_key_bits(Tk_b, kt);   // INVERTED: bit set = masked
     }
   }
 
@@ -685,7 +693,7 @@ __device__ __forceinline__ void bwd_stage_row_stats(const AttnBwdParams& p, int 
   for (int i = tid; i < nkt_b * qpad_b; i += nthreads) {
     const int kt = i / qpad_b, qi = i - kt * qpad_b;
     const int qc = qi < Tq_b ? qi : Tq_b - 1;
-    mw_s[kt * mstride + qi] = ~mb[(size_t)qc * p.mask_q_stride + kt];
+    mw_s[kt * mstride + qi] = ~mb[(size_t)qc * p.mask_q_stride + kt] | pad_key_bits(Tk_b, kt);
   }
 }
 
@@ -840,7 +848,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_fewq128_kernel(AttnParams p) 
     int q = 32 * qt + r;
     q = q < Tq_b ? q : Tq_b - 1;
     qrow[qt] = q;
-    mw[qt] = p.mask[(size_t)b * p.mask_b_stride + (size_t)q * p.mask_q_stride + wt];
+    mw[qt] = 32 * wt < p.Tk ? p.mask[(size_t)b * p.mask_b_stride + (size_t)q * p.mask_q_stride + wt] : 0u;   // (ceil(Tk / 32) words a row)
   }
   stage_wait();
   __syncthreads();
