@@ -297,7 +297,8 @@ int unimm_layernorm_bwd(const void* dy, const float* x, const float* mean, const
  * this call until it is reduced) holds [blocks][3][H] = per-block sums for dgamma, dbeta, dbias; *blocks_out (host)
  * receives the block count.  unimm_colpartials_finish_grouped then adds the column sums of up to many pending calls
  * into their destinations in one launch (dst[q] == NULL skips quantity q): the engine reduces a block's LayerNorm
- * partials once at the end of the block instead of between two dependent kernels each time. */
+ * partials once at the end of the block instead of between two dependent kernels each time.  m_dev (or NULL): device word with
+ * the rows actually present (M = capacity); rows at or past it are neither read nor written and add nothing to the partials. */
 int unimm_layernorm_bwd_partials(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                                  void* dx, void* dx_drop, float* partials, int32_t M, int32_t H, uint32_t drop_key,
                                  uint32_t drop_thr, float drop_scale, uint32_t odrop_key, uint32_t odrop_thr,
@@ -321,7 +322,7 @@ typedef struct {
   int32_t M, H, type_vocab;
   float eps;
   uint32_t drop_key, drop_thr; float drop_scale;
-  const int32_t* m_dev; /* or NULL: device word with the rows actually present (M = capacity) */
+  const int32_t* m_dev; /* or NULL: device word with the rows actually present (M = capacity); later rows are not read or written */
   const int64_t* rows;  /* or NULL: row r takes ids / pos / typ at index rows[r] (the unpadded schedule's row map) */
   const uint32_t* drop_salt; /* or NULL (see unimm_gemm_nt_args.drop_salt) */
 } unimm_embed_args;
@@ -399,7 +400,8 @@ int unimm_rows_add_f32(void* dst, const int32_t* idx, const float* src, int32_t 
 int unimm_gelu_bwd(const void* dt, const void* u, void* du, int64_t n, void* stream);
 /* scatter == 0: dst[i,:] = src[idx[i],:]; scatter != 0: dst[idx[i],:] = src[i,:]  (bf16 rows of H, idx unique).
  * Selects the labelled token rows the decoder runs on (the reference decodes all 256 rows and then
- * boolean-gathers, models/vilbert_dialog.py:1583-1584). */
+ * boolean-gathers, models/vilbert_dialog.py:1583-1584).  n_dev (or NULL): device word with the rows actually present (n = capacity);
+ * rows i at or past it are not read, and the rows they would write are left untouched. */
 int unimm_gather_rows(const void* src, const int32_t* idx, void* dst, int32_t n, int32_t H, int32_t scatter,
                       const int32_t* n_dev, void* stream);
 
@@ -410,11 +412,12 @@ int unimm_gather_rows(const void* src, const int32_t* idx, void* dst, int32_t n,
 /* Token-level likelihood / unlikelihood (models/vilbert_dialog.py:1577-1595): per decoded row with
  * label y (-1 = ignore) and integer weight w: w>0 -> -w*log p_y; w==-1 -> -log(clamp(1-p_y, 1e-6)).
  * rowloss is the un-normalised contribution, rownll = -log p_y (generative scoring, val_lm.py:131-136),
- * lse the row's log-sum-exp.  The :1600-1604 CrossEntropy fallback is this with w = [y != -1]. */
+ * lse the row's log-sum-exp.  The :1600-1604 CrossEntropy fallback is this with w = [y != -1].  n_dev (or NULL): device word with
+ * the rows actually present (n = capacity); rows at or past it are neither read nor written. */
 int unimm_lm_loss_fwd(const float* logits, const int32_t* labels, const int32_t* weights, float* rowloss,
                       float* rownll, float* lse, int32_t n, int32_t V, int32_t ld, const int32_t* n_dev, void* stream);
 /* dlogits (bf16 [n, ldd], columns >= V zero-filled) = g * inv_denom * d(rowloss)/d(logits); inv_dev (or NULL): the
- * denominator's reciprocal as a device word instead of the host float */
+ * denominator's reciprocal as a device word instead of the host float; n_dev as for the forward (rows past it: dlogits untouched) */
 int unimm_lm_loss_bwd(const float* logits, const int32_t* labels, const int32_t* weights, const float* lse,
                       const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld,
                       int32_t ldd, const int32_t* n_dev, const float* inv_dev, void* stream);
@@ -440,7 +443,8 @@ int unimm_nsp_loss_fwd(const float* logits, const int32_t* labels, float w0, flo
  * through the returned NSP scores (the ranking loss of dense_annotation_finetuning.py:263-293) */
 int unimm_nsp_loss_bwd(const float* logits, const int32_t* labels, float w0, float w1, const float* g, const float* extra,
                        float* dlogits, int32_t B, int32_t ld, int32_t ldd, void* stream);
-/* dst[0] = scale * sum(src) (fixed order, deterministic); dst[seg[i]] += sign * src[i] */
+/* dst[0] = scale * sum(src) (fixed order, deterministic); dst[seg[i]] += sign * src[i].  n_dev (or NULL): only src[0 .. min(n, *n_dev))
+ * is read; scale_dev (or NULL): a device word that replaces scale */
 int unimm_reduce_sum(const float* src, int64_t n, float* dst, float scale, const int32_t* n_dev, const float* scale_dev,
                      void* stream);
 int unimm_segment_sum(const float* src, const int32_t* seg, float* dst, int64_t n, float sign, void* stream);
@@ -548,7 +552,8 @@ int unimm_x3_layernorm_fwd(const float* x, const float* gamma, const float* beta
 /* unimm_embed_bwd with an fp32 upstream gradient */
 int unimm_embed_bwd_f32(const unimm_embed_args* args, const float* dy, float* dword, float* dpos, float* dtype, float* dext,
                         float* dgamma, float* dbeta, float* partials, void* stream);
-/* unimm_lm_loss_bwd / unimm_kl_loss_bwd writing x-type split operands [rows, 3 cp] (cp % 64 == 0, cp >= V / C) */
+/* unimm_lm_loss_bwd / unimm_kl_loss_bwd writing x-type split operands [rows, 3 cp] (cp % 64 == 0, cp >= V / C); unlike
+ * unimm_lm_loss_bwd, rows of out3 at or past *n_dev (below n) are written as zeros */
 int unimm_x3_lm_loss_bwd(const float* logits, const int32_t* labels, const int32_t* weights, const float* lse, const float* g,
                          float inv_denom, void* out3, int32_t n, int32_t V, int32_t ld, int32_t cp, const int32_t* n_dev,
                          const float* inv_dev, void* stream);
