@@ -35,7 +35,10 @@ const char* unimm_arch(void);     /* "gfx950" */
  * 515-517, 552, 582, 595, 659-661, 670-672, 745-748, 950, 965, 983, 1002, 1025, 1070, 1087,
  * 1488-1489) with the elementwise op that follows it fused in, and -- called with the transposed
  * bf16 weight copy -- the input-gradient half of their autograd backward.
- * K % 64 == 0; ldx, ldw % 8 == 0; ldo, ldaux % 4 == 0; x, w, out 16-byte aligned.
+ * K % 64 == 0; ldx, ldw % 8 == 0; ldo, ldaux % 4 == 0; x, w, out and -- where given -- aux and out2 16-byte aligned
+ * (UNIMM_E_ALIGN otherwise: the epilogue reads aux and writes out2 sixteen bytes at a time wherever the row stride keeps rows
+ * aligned; every caller in this repository passes whole allocations or row slices of them).  bias and the aux_* vectors are
+ * read one fp32 at a time and need only their natural 4-byte alignment.
  * ------------------------------------------------------------------------------------------- */
 enum {
   UNIMM_EPI_BIAS = 0,            /* out = acc + bias                                            */
@@ -62,7 +65,8 @@ typedef struct {
   uint32_t drop_key; /* dropout (UNIMM_EPI_BIAS_DROP_RESID): element (m, n) is kept iff the 16-bit field (n & 1) of
                       * drop_word(key, m * ceil(N / 2) + n / 2) is >= thr -- one counter-based hash per two neighbouring
                       * columns (csrc/common.h: drop_word; unimm_amd/dropout.py is the bit-exact host mirror)  */
-  uint32_t drop_thr; /* p * 2^16; 0 disables                                                    */
+  uint32_t drop_thr; /* p * 2^32 (dropout.py: drop_arg); the kernels compare each 16-bit field with thr >> 16, so p is
+                      * resolved to 2^-16; 0 disables                                           */
   float drop_scale;  /* 1 / (1 - p)                                                             */
   /* UNIMM_EPI_BIAS_DROP_RESID only, all four or none: the residual operand is LayerNorm(aux) evaluated on
    * the fly, (aux[m,n] - aux_mean[m]) * aux_rstd[m] * aux_gamma[n] + aux_beta[n] -- the fp32 output of the
@@ -92,8 +96,12 @@ typedef struct {
    * workgroups per output tile, each reducing a slice of K; -1 = the library's choice (as many as stay resident at once, <= 4,
    * >= 8 K-steps each).  Partial tiles meet in the caller's workspace and the last arriver of a tile runs the epilogue, so the
    * fused epilogues work unchanged.  splitk_ws: 256-byte aligned device memory, ZERO-FILLED ONCE by the caller and then private
-   * to launches of ONE stream (the kernel leaves its counters zero); 16 KiB + tiles * splits * tile bytes (a 64 x 128 tile is
-   * 32 KiB); too small for a launch = that launch runs unsplit.  Ring-loop tiles only (64x128, 128x128). */
+   * to launches of ONE stream (the kernel leaves its counters zero); 16 KiB of counters (one int32 ticket per output tile, so at
+   * most 4096 tiles) + tiles * splits * tile bytes, a tile being BM x BN fp32 partial sums (a 64 x 128 tile is 32 KiB, 128 x 128
+   * 64 KiB), `splits` the number the launch settles on; too small for that = the launch runs unsplit (not with fewer splits).
+   * A split request (splitk other than 0 / 1) with no workspace or fewer than 32 KiB of it is rejected with UNIMM_E_ARG.
+   * Four-wave ring-loop tiles only (64x128: 7, 9, 15; 128x128: 1, 10, 14); on every other tile the request is ignored.
+   * oracle/gemm_ref.py (splits, ws_bytes) restates these rules for the tests. */
   void* splitk_ws;
   int64_t splitk_ws_bytes;
   int32_t splitk;

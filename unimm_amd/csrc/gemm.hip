@@ -749,6 +749,8 @@ extern "C" int unimm_gemm_nt(const unimm_gemm_nt_args* a, void* stream) {
                          a->epilogue == UNIMM_EPI_ADD || a->epilogue == UNIMM_EPI_MUL;
   if (needs_aux && (a->aux == nullptr || (a->ldaux % 4) || a->ldaux < a->N)) return UNIMM_E_ARG;
   if (a->epilogue == UNIMM_EPI_BIAS_DROP_RESID && !a->out_f32) return UNIMM_E_ARG;  // residual stream is fp32
+  // the epilogue's 16-byte paths (taken wherever the row stride keeps rows aligned) assume aligned bases of aux and out2 too
+  if (((needs_aux ? (uintptr_t)a->aux : 0) | (uintptr_t)a->out2) & 15) return UNIMM_E_ALIGN;
   GemmNtParams p;
   p.x = (const bf16_t*)a->x; p.w = (const bf16_t*)a->w; p.bias = a->bias; p.aux = a->aux;
   p.out = a->out; p.out2 = (bf16_t*)a->out2;

@@ -736,7 +736,13 @@ __device__ __forceinline__ bool nt_split_join(const GemmNtParams& p, f32x4 (&acc
 #pragma unroll
     for (int j = 0; j < MT; ++j) {
       f32x4* dst = mine + ((wave * 4 + i) * MT + j) * 64 + lane;
-      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(acc[i][j]) : "memory");
+      // s_nop 1: the data registers of a VMEM store wider than 64 bits must not be rewritten within two wait states, and the
+      // compiler's hazard recognizer does not look inside an asm statement.  Where the accumulators themselves are the store's
+      // operands nothing rewrites them; but the 128x128 tile on a three-slot ring (one workgroup per CU, hence a 512-register
+      // budget) keeps them in AGPRs, every store's data is then a temporary copied out of them (v_accvgpr_read_b32 v4..v7) and
+      // REUSED by the copy for the next store in the very next instruction: the first dword of lanes 12-15 of every 16 reached
+      // the slab wrong, and tile 10 with split-K was off by O(1) in one element of 16 (tests/test_gpu_gemm_edges.py, section D).
+      asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(acc[i][j]) : "memory");
     }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                                               // (every wave has left the ring: smem[0..3] carries the ticket)
