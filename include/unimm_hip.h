@@ -604,7 +604,13 @@ int unimm_x3_attn_set_impl(int32_t impl);
  * in fp32.  No split over keys: one head's context is at most 255 x 64 x 2 x 2 B = 65 KB, microseconds at one CU's bandwidth
  * (revisit if a profile disagrees; measured at 80 dialogs x 4 beams: ~69 us per launch, second to the NT GEMMs in a decode step --
  * a matrix-instruction form of the score and P.V products is the next step).  ctx_len[g] <= 256 and ctx_len[g] + plen[s] + nr <= 320; out is written in the layout of unimm_attn_fwd
- * (row, head * 64 + d).  Row strides in elements, multiples of 8; every pointer 16-byte aligned. */
+ * (row, head * 64 + d).  Row strides in elements, multiples of 8; every pointer 16-byte aligned.
+ * Values outside those bounds are clamped, never followed out of the buffers: ctx_len[g] is taken as min(max(ctx_len[g], 0), 256),
+ * and plen[s] as min(max(plen[s], 0), pcap, 320 - nr - ctx_len[g]) -- a negative plen is 0, plen > pcap is pcap, and with
+ * ctx_len = 256, nr = 2 a slot sees its first 62 private rows whatever pcap is.  Nothing else is read: not the rows between the
+ * groups' contexts, not the private rows at and past the clamped plen[s], not a column outside [0, H * 64) of any row; of `out`
+ * exactly the columns [0, H * 64) of the G * beams * nr rows are written.  ctx_len[g] = 0 is allowed (a row then attends the
+ * private and new rows only); ctx_off need not be ascending. */
 typedef struct {
   const void* q; const void* k; const void* v;   /* bf16, the new rows' fused projection (row strides ldq / ldk / ldv) */
   void* out;                                     /* bf16 [G * beams * nr, ldo] */
@@ -623,7 +629,12 @@ int unimm_attn_decode(const unimm_attn_decode_args* args, void* stream);
  * row plen[p] of s = p's new answer row: new_kv + layer * new_layer_stride + (p * new_row_mul) * ld_new (width elements, the K
  * and V columns of one layer are `width` contiguous elements, e.g. K | V of the fused projection); plen_out[s] = plen[p] + 1.
  * Cache layout: src / dst + ((layer * slots + s) * pcap + r) * ldp, width <= ldp.  src and dst must not overlap (the
- * reorder is a gather); bit-exact copies.  plen[p] + 1 <= pcap, width % 8 == 0, strides % 8 == 0. */
+ * reorder is a gather); bit-exact copies.  plen[p] + 1 <= pcap, width % 8 == 0, strides % 8 == 0.
+ * Clamps: parent[s] is taken as min(max(parent[s], 0), slots - 1) and plen[p] as min(max(plen[p], 0), pcap - 1), so a full
+ * parent (plen[p] = pcap) keeps its first pcap - 1 rows, gets the new row as its last and reports plen_out = pcap.  Of dst
+ * exactly the columns [0, width) of the rows [0, plen_out[s]) of every slot are written; columns past `width` of src and of the
+ * new rows are not read.  src == dst or plen == plen_out returns UNIMM_E_ARG, a misaligned pointer / width / stride
+ * UNIMM_E_ALIGN, both before any launch. */
 typedef struct {
   const void* src; void* dst;                    /* bf16 [layers][slots][pcap][ldp] */
   const void* new_kv;                            /* bf16 */
@@ -638,7 +649,12 @@ int unimm_kv_cache_update(const unimm_kv_update_args* args, void* stream);
  * workgroup, the vocabulary streamed once with an online log-sum-exp.  logp = logit - lse over ALL V ids (no renormalisation
  * after banning).  Then -inf for: the `nbanned` ids of `banned` (int32, device), id `sep` when flags[row] & 1, every id other
  * than `sep` when flags[row] & 2 (flags int32 [rows] or NULL).  Returns the K <= 16 largest (vals fp32 [rows, K], ids int32
- * [rows, K]) ordered by (value desc, id asc) -- -inf entries included, by the same rule; lse fp32 [rows] or NULL. */
+ * [rows, K]) ordered by (value desc, id asc) -- -inf entries included, by the same rule; lse fp32 [rows] or NULL.
+ * The order is decided on the raw fp32 logits (exact ties by id), not on the rounded logp.  V <= 65536, K <= V, ldl >= V (no
+ * alignment asked of ldl); columns past V are not read.  Banned ids outside [0, V) and duplicates are ignored, `banned` may be
+ * NULL when nbanned = 0, and nbanned is not bounded by the block size.  -inf logits are candidates like any other (they add
+ * nothing to lse and rank last, by id); a row whose logits are ALL -inf has lse = -inf and NaN values.  rows = 0 returns
+ * UNIMM_OK without a launch and leaves the outputs untouched. */
 int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
                   const int32_t* flags, int32_t sep, int32_t K, float* vals, int32_t* ids, float* lse, void* stream);
 
