@@ -726,6 +726,32 @@ class Engine:
             self.attn_sink[tag] = probs
         return out, lse
 
+    def _post_attn(self, ctx, res32, proj, ff1, ff2, ln_mid, ln_out, d_proj, d_ffn, save, m_dev=None):
+        """What follows the attention in every encoder block: BertSelfOutput or one side of BertBiOutput
+        (models/vilbert_dialog.py:744-754), then BertIntermediate, then BertOutput.
+        ctx: the attention context; res32: the fp32 residual stream entering the block (possibly a `_LazyLN`); proj, ff1,
+        ff2: the three linears; ln_mid, ln_out: keys of `self.ln`; d_proj, d_ffn: the dropout triples of the two residual
+        joins; m_dev: device word with the valid rows, when the row dimension is a capacity.
+        -> (y32, y, bwd): the fp32 residual stream leaving the block and its bf16 copy; bwd (None unless save) maps dy to
+        (dctx, dres), dres being the gradient w.r.t. the first pre-LayerNorm sum: the caller adds it in the epilogue of
+        its QKV input-gradient GEMM."""
+        pre1 = self._linear(ctx, proj, L.EPI_BIAS_DROP_RESID, aux=res32, drop=d_proj, out_f32=True)
+        x1_32, x1, m1, r1 = self._layernorm(pre1, ln_mid, save, lazy=True)
+        # training keeps GELU'(u) (not u): the backward epilogue is then a plain multiply
+        h, u = self._linear(x1, ff1, L.EPI_BIAS_GELU_DG, want_u=True) if save else (self._linear(x1, ff1, L.EPI_BIAS_GELU), None)
+        pre2 = self._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_ffn, out_f32=True)
+        x2_32, x2, m2, r2 = self._layernorm(pre2, ln_out, save, lazy=True)
+        if not save:
+            return x2_32, x2, None
+
+        def bwd(dx2):
+            dpre2, dpre2d = self._layernorm_bwd(dx2, pre2, m2, r2, ln_out, dbias=ff2.gb, drop=d_ffn, m_dev=m_dev)
+            du = self._linear_bwd(dpre2d, h, ff2, L.EPI_MUL, aux=u, bias_grad=False, m_dev=m_dev)
+            dx1 = self._linear_bwd(du, x1, ff1, L.EPI_ADD, aux=dpre2, m_dev=m_dev)
+            dpre1, dpre1d = self._layernorm_bwd(dx1, pre1, m1, r1, ln_mid, dbias=proj.gb, drop=d_proj, m_dev=m_dev)
+            return self._linear_bwd(dpre1d, ctx, proj, bias_grad=False, m_dev=m_dev), dpre1
+        return x2_32, x2, bwd
+
     def _self_block(self, key, x32, x, mask, B, T, heads, pname, p_attn, p_hid, st, var=None):
         """BertLayer / BertImageLayer (models/vilbert_dialog.py:385-483, :514-612).
         (x32, x): fp32 residual stream and its bf16 copy (the GEMM operand)."""
@@ -739,21 +765,12 @@ class Engine:
         d_attn = self._drop(pname + "attn", p_attn, train)
         ctx, lse = self._attn(q, k, v, mask, B, heads, T, T, D, d_attn, save, qvar=var, kvar=var, tag=key)
         d_so = self._drop(pname + "so", p_hid, train)
-        pre1 = self._linear(ctx, so, L.EPI_BIAS_DROP_RESID, aux=x32, drop=d_so, out_f32=True)
-        x1_32, x1, m1, r1 = self._layernorm(pre1, key + ".ln1", save, lazy=True)
-        # training keeps GELU'(u) (not u): the backward epilogue is then a plain multiply
-        h, u = self._linear(x1, ff1, L.EPI_BIAS_GELU_DG, want_u=True) if save else (self._linear(x1, ff1, L.EPI_BIAS_GELU), None)
         d_out = self._drop(pname + "out", p_hid, train)
-        pre2 = self._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_out, out_f32=True)
-        x2_32, x2, m2, r2 = self._layernorm(pre2, key + ".ln2", save, lazy=True)
         md = var[2] if var is not None else None      # device word: valid rows, when the row dimension is a capacity
+        x2_32, x2, post_bwd = self._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
         if save:
             def bwd(dx2):
-                dpre2, dpre2d = self._layernorm_bwd(dx2, pre2, m2, r2, key + ".ln2", dbias=ff2.gb, drop=d_out, m_dev=md)
-                du = self._linear_bwd(dpre2d, h, ff2, L.EPI_MUL, aux=u, bias_grad=False, m_dev=md)
-                dx1 = self._linear_bwd(du, x1, ff1, L.EPI_ADD, aux=dpre2, m_dev=md)
-                dpre1, dpre1d = self._layernorm_bwd(dx1, pre1, m1, r1, key + ".ln1", dbias=so.gb, drop=d_so, m_dev=md)
-                dctx = self._linear_bwd(dpre1d, ctx, so, bias_grad=False, m_dev=md)
+                dctx, dpre1 = post_bwd(dx2)
                 dqkv = torch.empty_like(qkv)
                 delta = torch.empty_like(lse)
                 words, mq, mb = mask
@@ -790,24 +807,10 @@ class Engine:
         dto = self._drop(pn + "tout", cfg.hidden_dropout_prob, train)
         with self._img():
             ctx_v, lse_v = self._attn(q1, k2, v2, comask, B, nh, R, T, D, da2, save, kvar=var, tag=key + "/2")    # regions attend text (:701-721)
-            prev = self._linear(ctx_v, d1, L.EPI_BIAS_DROP_RESID, aux=xv32, drop=db1, out_f32=True)   # BertBiOutput (:744-754, call order :775)
-            av32, av, mv1, rv1 = self._layernorm(prev, key + ".lnb1", save, lazy=True)
-            if save:
-                hv, uv = self._linear(av, vff1, L.EPI_BIAS_GELU_DG, want_u=True)
-            else:
-                hv, uv = self._linear(av, vff1, L.EPI_BIAS_GELU), None
-            prev2 = self._linear(hv, vff2, L.EPI_BIAS_DROP_RESID, aux=av32, drop=dvo, out_f32=True)
-            ov32, ov, mv2, rv2 = self._layernorm(prev2, key + ".lnv", save, lazy=True)
-        ctx_t, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")     # text attends regions (:681-698)
-        pret = self._linear(ctx_t, d2, L.EPI_BIAS_DROP_RESID, aux=xt32, drop=db2, out_f32=True)
-        at32, at, mt1, rt1 = self._layernorm(pret, key + ".lnb2", save, lazy=True)
-        if save:
-            ht, ut = self._linear(at, tff1, L.EPI_BIAS_GELU_DG, want_u=True)
-        else:
-            ht, ut = self._linear(at, tff1, L.EPI_BIAS_GELU), None
-        pret2 = self._linear(ht, tff2, L.EPI_BIAS_DROP_RESID, aux=at32, drop=dto, out_f32=True)
-        ot32, ot, mt2, rt2 = self._layernorm(pret2, key + ".lnt", save, lazy=True)
+            ov32, ov, bwd_v = self._post_attn(ctx_v, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)   # BertBiOutput (:744-754, call order :775)
         md = var[2] if var is not None else None      # device word: valid text rows (capacity-sized text tensors)
+        ctx_t, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")     # text attends regions (:681-698)
+        ot32, ot, bwd_t = self._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save, m_dev=md)
         if save:
             def bwd(dov, dot):
                 sc = 1.0 / math.sqrt(D)
@@ -819,20 +822,12 @@ class Engine:
                 self._to_txt(dqkv1)
                 self._to_img(dqkv2)
                 with self._img():                                   # image half: FFN, bi-output
-                    dp, dpd = self._layernorm_bwd(dov, prev2, mv2, rv2, key + ".lnv", dbias=vff2.gb, drop=dvo)
-                    duv = self._linear_bwd(dpd, hv, vff2, L.EPI_MUL, aux=uv, bias_grad=False)
-                    dav = self._linear_bwd(duv, av, vff1, L.EPI_ADD, aux=dp)
-                    dprev, dprevd = self._layernorm_bwd(dav, prev, mv1, rv1, key + ".lnb1", dbias=d1.gb, drop=db1)
-                    dctx_v = self._linear_bwd(dprevd, ctx_v, d1, bias_grad=False)
+                    dctx_v, dprev = bwd_v(dov)
                     delta_v = torch.empty_like(lse_v)
                     w, mq, mb = comask
                     L.attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, delta_v, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:],
                                w, B, nh, R, T, D, sc, mq, mb, da2, kvar=var)
-                dp, dpd = self._layernorm_bwd(dot, pret2, mt2, rt2, key + ".lnt", dbias=tff2.gb, drop=dto, m_dev=md)   # text half
-                dut = self._linear_bwd(dpd, ht, tff2, L.EPI_MUL, aux=ut, bias_grad=False, m_dev=md)
-                dat = self._linear_bwd(dut, at, tff1, L.EPI_ADD, aux=dp, m_dev=md)
-                dpret, dpretd = self._layernorm_bwd(dat, pret, mt1, rt1, key + ".lnb2", dbias=d2.gb, drop=db2, m_dev=md)
-                dctx_t = self._linear_bwd(dpretd, ctx_t, d2, bias_grad=False, m_dev=md)
+                dctx_t, dpret = bwd_t(dot)                          # text half: FFN, bi-output
                 delta_t = torch.empty_like(lse_t)
                 w, mq, mb = vmask
                 L.attn_bwd(q2, k1, v1, ctx_t, dctx_t, lse_t, delta_t, dqkv2[:, :Hb], dqkv1[:, Hb:2 * Hb], dqkv1[:, 2 * Hb:],
@@ -1097,12 +1092,8 @@ class Engine:
         return dict(ids32=ids32, typ32=typ32, pos32=pos32, labels=labels, lab32=lab32, w32=w32, il32=il32, plan=plan, sel=sel,
                     n_img=n_img, dyn=dyn, st_nspw=st_nspw, var=var, Mt=Mt)
 
-    def _forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
-        """Runs the trunk + heads.  Returns a dict of outputs and (when save) the tape for backward.
-        lm_rows: 'labelled' (decode only rows that carry a label / weight), 'all', or 'none'."""
-        cfg = self.cfg
-        dev = self.arena.device
-        self.refresh_weights()
+    def _batch_dims(self, inp, dev):
+        """Checks the step's shapes -> (B, T, R, image_index as int64 [B] on the device | None)."""
         ids = inp["input_ids"]
         B, T = ids.shape
         feat = inp["image_feat"]
@@ -1116,6 +1107,38 @@ class Engine:
             raise ValueError(f"image_feat has {feat.shape[0]} rows for {B} sequences and no image_index was given")
         if T > 256 or R > 256:
             raise ValueError("sequence / region count above 256 is not supported by the attention kernels")
+        return B, T, R, img_idx
+
+    def _pooled_heads(self, xt32, xv32, cls_idx_t, cls_idx_v, B, train):
+        """Poolers + NSP head (models/vilbert_dialog.py:946-967, 1064-1070) on rows cls_idx_t / cls_idx_v of the two fp32
+        residual streams -> dict of what the heads' backward reads; the logits are `nsp_pad[:, :2]`.
+        Everything above the encoder's last LayerNorm runs in fp32 from the fp32 residual stream and the fp32 master
+        weights (unimm_linear_f32): 0.4 GFLOP, but with bf16 operands ReLU units of the B pooled rows switched with the
+        last bit of the forward and the pooler gradients were 8-16 % off the reference's (round 2)."""
+        dev = xt32.device
+        H, Hv = xt32.shape[1], xv32.shape[1]
+        cls_t = torch.empty((B, H), dtype=F32, device=dev)         # first-token rows (:949, :964)
+        cls_v = torch.empty((B, Hv), dtype=F32, device=dev)
+        L.gather_rows(xt32.view(BF16), cls_idx_t, cls_t.view(BF16), B, 2 * H)      # fp32 rows moved as 2 H 16-bit elements
+        L.gather_rows(xv32.view(BF16), cls_idx_v, cls_v.view(BF16), B, 2 * Hv)
+        pooled_t = self._linear32(cls_t, "tpool", relu=True)
+        pooled_v = self._linear32(cls_v, "vpool", relu=True)
+        d_fuse = self._drop("fuse", 0.1, train)
+        fused = torch.empty_like(pooled_t)
+        L.mul_dropout(pooled_t, pooled_v, fused, fused.numel(), d_fuse, fusion_sum=self.cfg.fusion_method == "sum")
+        nsp = torch.zeros((B, 4), dtype=F32, device=dev)
+        self._linear32(fused, "nsp", out=nsp)
+        return dict(pooled_t=pooled_t, pooled_v=pooled_v, fused=fused, d_fuse=d_fuse, nsp_pad=nsp, cls_t=cls_t, cls_v=cls_v,
+                    cls_idx_t=cls_idx_t, cls_idx_v=cls_idx_v)
+
+    def _forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
+        """Runs the trunk + heads.  Returns a dict of outputs and (when save) the tape for backward.
+        lm_rows: 'labelled' (decode only rows that carry a label / weight), 'all', or 'none'."""
+        cfg = self.cfg
+        dev = self.arena.device
+        self.refresh_weights()
+        B, T, R, img_idx = self._batch_dims(inp, dev)
+        feat = inp["image_feat"]
         H, Hv = cfg.hidden_size, cfg.v_hidden_size
         st = dict(train=train, tape=[] if save else None)
         tape = st["tape"]
@@ -1237,21 +1260,8 @@ class Engine:
         # ---- poolers + NSP (models/vilbert_dialog.py:946-967, 1064-1070) -------------------------
         cls_idx_t = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
         cls_idx_v = torch.arange(0, B * R, R, dtype=torch.int32, device=dev)
-        # Everything above the encoder's last LayerNorm runs in fp32 from the fp32 residual stream and the fp32 master
-        # weights (unimm_linear_f32): 0.4 GFLOP, but with bf16 operands ReLU units of the B pooled rows switched with the
-        # last bit of the forward and the pooler gradients were 8-16 % off the reference's (round 2).
-        cls_t = torch.empty((B, H), dtype=F32, device=dev)         # first-token rows (:949, :964)
-        cls_v = torch.empty((B, Hv), dtype=F32, device=dev)
-        L.gather_rows(xt32.view(BF16), cls_idx_t, cls_t.view(BF16), B, 2 * H)      # fp32 rows moved as 2 H 16-bit elements
-        L.gather_rows(xv32.view(BF16), cls_idx_v, cls_v.view(BF16), B, 2 * Hv)
-        pooled_t = self._linear32(cls_t, "tpool", relu=True)
-        pooled_v = self._linear32(cls_v, "vpool", relu=True)
-        d_fuse = self._drop("fuse", 0.1, train)
-        fused = torch.empty_like(pooled_t)
-        L.mul_dropout(pooled_t, pooled_v, fused, fused.numel(), d_fuse, fusion_sum=cfg.fusion_method == "sum")
-        nsp = torch.zeros((B, 4), dtype=F32, device=dev)
-        self._linear32(fused, "nsp", out=nsp)
-        out["nsp"] = nsp[:, :2]
+        heads = self._pooled_heads(xt32, xv32, cls_idx_t, cls_idx_v, B, train)
+        out["nsp"] = heads["nsp_pad"][:, :2]
 
         # ---- MLM head: transform + tied decoder on the selected rows (:982-986, :1023-1026) -------
         V = cfg.vocab_size
@@ -1270,9 +1280,7 @@ class Engine:
             out["pred_t"] = self.decode_rows(self.padded(out, seq_t), B * T).view(B, T, Vp)[:, :, :V]
 
         if save:
-            out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, pooled_t=pooled_t, pooled_v=pooled_v, fused=fused,
-                              d_fuse=d_fuse, nsp_pad=nsp, cls_t=cls_t, cls_v=cls_v, cls_idx_t=cls_idx_t,
-                              cls_idx_v=cls_idx_v)
+            out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, **heads)
         return out
 
     @staticmethod

@@ -223,6 +223,26 @@ class EngineX3(Engine):
     # ------------------------------------------------------------------------------------------
     # blocks
     # ------------------------------------------------------------------------------------------
+    def _post_attn(self, ctx3, res32, proj, ff1, ff2, ln_mid, ln_out, d_proj, d_ffn, save, m_dev=None):
+        """The base engine's contract on split operands: ctx3 is the attention context as a split operand, the result is
+        (y32, y3 split operand, bwd); bwd(dy) -> (dctx, dres), both fp32."""
+        pre1 = self._lin3(ctx3, proj, L.EPI_BIAS_DROP_RESID, aux=res32, drop=d_proj)
+        x1_32, x1_3, m1, r1 = self._ln3(pre1, ln_mid, save)
+        u = self._lin3(x1_3, ff1)                                   # pre-activation, fp32
+        h3 = self._op3(u, op=L.X3_GELU)[0]
+        pre2 = self._lin3(h3, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_ffn)
+        x2_32, x2_3, m2, r2 = self._ln3(pre2, ln_out, save)
+        if not save:
+            return x2_32, x2_3, None
+
+        def bwd(dx2):
+            dpre2, dpre2d3 = self._ln3_bwd(dx2, pre2, m2, r2, ln_out, dbias=ff2.gb, drop=d_ffn, m_dev=m_dev)
+            du3 = self._op3(self._lin3_bwd(dpre2d3, h3, ff2, bias_grad=False, m_dev=m_dev), op=L.X3_MUL_DGELU, b=u)[0]
+            dx1 = self._lin3_bwd(du3, x1_3, ff1, m_dev=m_dev, add=dpre2)
+            dpre1, dpre1d3 = self._ln3_bwd(dx1, pre1, m1, r1, ln_mid, dbias=proj.gb, drop=d_proj, m_dev=m_dev)
+            return self._lin3_bwd(dpre1d3, ctx3, proj, bias_grad=False, m_dev=m_dev), dpre1
+        return x2_32, x2_3, bwd
+
     def _self_block(self, key, x32, x3, mask, B, T, heads, pname, p_attn, p_hid, st, var=None):
         """BertLayer / BertImageLayer (models/vilbert_dialog.py:385-483, :514-612).  (x32, x3): the fp32 residual stream and
         its split copy (the GEMM operand)."""
@@ -236,22 +256,12 @@ class EngineX3(Engine):
         d_attn = self._drop(pname + "attn", p_attn, train)
         ctx, ctx3, lse = self._attn(q, k, v, mask, B, heads, T, T, D, d_attn, save, qvar=var, kvar=var, tag=key)
         d_so = self._drop(pname + "so", p_hid, train)
-        pre1 = self._lin3(ctx3, so, L.EPI_BIAS_DROP_RESID, aux=x32, drop=d_so)
-        x1_32, x1_3, m1, r1 = self._ln3(pre1, key + ".ln1", save)
-        u = self._lin3(x1_3, ff1)                                   # pre-activation, fp32
-        h3 = self._op3(u, op=L.X3_GELU)[0]
         d_out = self._drop(pname + "out", p_hid, train)
-        pre2 = self._lin3(h3, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_out)
-        x2_32, x2_3, m2, r2 = self._ln3(pre2, key + ".ln2", save)
         md = var[2] if var is not None else None
+        x2_32, x2_3, post_bwd = self._post_attn(ctx3, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
         if save:
             def bwd(dx2):
-                dpre2, dpre2d3 = self._ln3_bwd(dx2, pre2, m2, r2, key + ".ln2", dbias=ff2.gb, drop=d_out, m_dev=md)
-                du_t = self._lin3_bwd(dpre2d3, h3, ff2, bias_grad=False, m_dev=md)
-                du3 = self._op3(du_t, op=L.X3_MUL_DGELU, b=u)[0]
-                dx1 = self._lin3_bwd(du3, x1_3, ff1, m_dev=md, add=dpre2)
-                dpre1, dpre1d3 = self._ln3_bwd(dx1, pre1, m1, r1, key + ".ln1", dbias=so.gb, drop=d_so, m_dev=md)
-                dctx = self._lin3_bwd(dpre1d3, ctx3, so, bias_grad=False, m_dev=md)
+                dctx, dpre1 = post_bwd(dx2)
                 dqkv = self._qkv_grad(qkv)
                 self._attn_bwd(q, k, v, ctx, dctx, lse, mask, dqkv[:, :Hd], dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:3 * Hd], 3 * Hd,
                                B, heads, T, T, D, d_attn, qvar=var, kvar=var)
@@ -287,21 +297,11 @@ class EngineX3(Engine):
         # image half: regions attend text (:701-721), BertBiOutput (:744-754, call order :775), image FFN
         with self._img():
             ctx_v, ctx_v3, lse_v = self._attn(q1, k2, v2, comask, B, nh, R, T, D, da2, save, kvar=var, tag=key + "/2")
-            prev = self._lin3(ctx_v3, d1, L.EPI_BIAS_DROP_RESID, aux=xv32, drop=db1)
-            av32, av3, mv1, rv1 = self._ln3(prev, key + ".lnb1", save)
-            uv = self._lin3(av3, vff1)
-            hv3 = self._op3(uv, op=L.X3_GELU)[0]
-            prev2 = self._lin3(hv3, vff2, L.EPI_BIAS_DROP_RESID, aux=av32, drop=dvo)
-            ov32, ov3, mv2, rv2 = self._ln3(prev2, key + ".lnv", save)
+            ov32, ov3, bwd_v = self._post_attn(ctx_v3, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)
+        md = var[2] if var is not None else None
         # text half: text attends regions (:681-698)
         ctx_t, ctx_t3, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")
-        pret = self._lin3(ctx_t3, d2, L.EPI_BIAS_DROP_RESID, aux=xt32, drop=db2)
-        at32, at3, mt1, rt1 = self._ln3(pret, key + ".lnb2", save)
-        ut = self._lin3(at3, tff1)
-        ht3 = self._op3(ut, op=L.X3_GELU)[0]
-        pret2 = self._lin3(ht3, tff2, L.EPI_BIAS_DROP_RESID, aux=at32, drop=dto)
-        ot32, ot3, mt2, rt2 = self._ln3(pret2, key + ".lnt", save)
-        md = var[2] if var is not None else None
+        ot32, ot3, bwd_t = self._post_attn(ctx_t3, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save, m_dev=md)
         if save:
             def bwd(dov, dot):
                 # gradient buffers of the two projections: each is written by BOTH attention backward kernels (every slice exactly
@@ -312,19 +312,11 @@ class EngineX3(Engine):
                 self._to_txt(dqkv1)
                 self._to_img(dqkv2)
                 with self._img():                                   # image half
-                    dp, dpd3 = self._ln3_bwd(dov, prev2, mv2, rv2, key + ".lnv", dbias=vff2.gb, drop=dvo)
-                    duv3 = self._op3(self._lin3_bwd(dpd3, hv3, vff2, bias_grad=False), op=L.X3_MUL_DGELU, b=uv)[0]
-                    dav = self._lin3_bwd(duv3, av3, vff1, add=dp)
-                    dprev, dprevd3 = self._ln3_bwd(dav, prev, mv1, rv1, key + ".lnb1", dbias=d1.gb, drop=db1)
-                    dctx_v = self._lin3_bwd(dprevd3, ctx_v3, d1, bias_grad=False)
+                    dctx_v, dprev = bwd_v(dov)
                     self._attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, comask, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:3 * Hb],
                                    3 * Hb, B, nh, R, T, D, da2, kvar=var)
                 # text half
-                dp, dpd3 = self._ln3_bwd(dot, pret2, mt2, rt2, key + ".lnt", dbias=tff2.gb, drop=dto, m_dev=md)
-                dut3 = self._op3(self._lin3_bwd(dpd3, ht3, tff2, bias_grad=False, m_dev=md), op=L.X3_MUL_DGELU, b=ut)[0]
-                dat = self._lin3_bwd(dut3, at3, tff1, m_dev=md, add=dp)
-                dpret, dpretd3 = self._ln3_bwd(dat, pret, mt1, rt1, key + ".lnb2", dbias=d2.gb, drop=db2, m_dev=md)
-                dctx_t = self._lin3_bwd(dpretd3, ctx_t3, d2, bias_grad=False, m_dev=md)
+                dctx_t, dpret = bwd_t(dot)
                 self._attn_bwd(q2, k1, v1, ctx_t, dctx_t, lse_t, vmask, dqkv2[:, :Hb], dqkv1[:, Hb:2 * Hb], dqkv1[:, 2 * Hb:3 * Hb],
                                3 * Hb, B, nh, T, R, D, da1, qvar=var)
                 self._to_img()                                      # dK1 / dV1 written by the text side
@@ -345,19 +337,8 @@ class EngineX3(Engine):
             raise NotImplementedError("fixed_t_layer / fixed_v_layer / with_coattention=False run on the bf16 engine only")
         dev = self.arena.device
         self.refresh_weights()
-        ids = inp["input_ids"]
-        B, T = ids.shape
+        B, T, R, img_idx = self._batch_dims(inp, dev)
         feat = inp["image_feat"]
-        R = feat.shape[1]
-        img_idx = inp.get("image_index")
-        if img_idx is not None:
-            img_idx = img_idx.to(dev, dtype=torch.int64, non_blocking=True).reshape(-1)
-            if img_idx.numel() != B:
-                raise ValueError("image_index needs one entry per sequence")
-        elif feat.shape[0] != B:
-            raise ValueError(f"image_feat has {feat.shape[0]} rows for {B} sequences and no image_index was given")
-        if T > 256 or R > 256:
-            raise ValueError("sequence / region count above 256 is not supported by the attention kernels")
         H, Hv = cfg.hidden_size, cfg.v_hidden_size
         st = dict(train=train, tape=[] if save else None)
         tape = st["tape"]
@@ -448,18 +429,8 @@ class EngineX3(Engine):
         # ---- poolers + NSP (:946-967, :1064-1070): the base engine's fp32 heads -----------------------------------------
         cls_idx_t = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
         cls_idx_v = torch.arange(0, B * R, R, dtype=torch.int32, device=dev)
-        cls_t = torch.empty((B, H), dtype=F32, device=dev)
-        cls_v = torch.empty((B, Hv), dtype=F32, device=dev)
-        L.gather_rows(xt32.view(BF16), cls_idx_t, cls_t.view(BF16), B, 2 * H)
-        L.gather_rows(xv32.view(BF16), cls_idx_v, cls_v.view(BF16), B, 2 * Hv)
-        pooled_t = self._linear32(cls_t, "tpool", relu=True)
-        pooled_v = self._linear32(cls_v, "vpool", relu=True)
-        d_fuse = self._drop("fuse", 0.1, train)
-        fused = torch.empty_like(pooled_t)
-        L.mul_dropout(pooled_t, pooled_v, fused, fused.numel(), d_fuse, fusion_sum=cfg.fusion_method == "sum")
-        nsp = torch.zeros((B, 4), dtype=F32, device=dev)
-        self._linear32(fused, "nsp", out=nsp)
-        out["nsp"] = nsp[:, :2]
+        heads = self._pooled_heads(xt32, xv32, cls_idx_t, cls_idx_v, B, train)
+        out["nsp"] = heads["nsp_pad"][:, :2]
         # ---- MLM head on the selected rows (:982-986, :1023-1026) --------------------------------------------------------
         V = cfg.vocab_size
         Vp = _rup(V, 64)
@@ -475,8 +446,7 @@ class EngineX3(Engine):
         elif lm_rows == "all":
             out["pred_t"] = self.decode_rows(self.padded(out, xt3), B * T).view(B, T, Vp)[:, :, :V]
         if save:
-            out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, pooled_t=pooled_t, pooled_v=pooled_v, fused=fused,
-                              d_fuse=d_fuse, nsp_pad=nsp, cls_t=cls_t, cls_v=cls_v, cls_idx_t=cls_idx_t, cls_idx_v=cls_idx_v)
+            out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, **heads)
         return out
 
     def _lm_head(self, xs3, n, lab_sel, w_sel, save, n_dev=None):

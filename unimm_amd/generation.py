@@ -38,7 +38,8 @@ Search semantics (k = tokens generated so far, excluding [SEP]):
 * beams = 1 is greedy decoding; length_penalty = 0 returns the summed log p of val_lm.py, 1 the token mean of val_avg_lm.py.
 
 `beam_search` is written against an abstract step function (tests drive it with a table model on the CPU); `generate_answers`
-supplies the engine's: the decode step runs the existing NT GEMM / LayerNorm kernels on M = 2 * slots rows,
+supplies the engine's: the decode step runs the existing NT GEMM / LayerNorm kernels on M = 2 * slots rows (after each
+attention, the engine's `_post_attn`),
 `unimm_attn_decode` for text self-attention, `unimm_attn_fwd` (variable-length) against the cached regions for the
 text-attends-regions half of a connection layer, the MLM head on the copy rows, `unimm_lm_topk` on the fp32 logits, and
 `unimm_kv_cache_update` (append + reorder of the private caches of all text layers) between steps.  Beam selection runs as
@@ -287,12 +288,7 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         pv = priv[st["cur"]][li].view(S * pcap, 2 * H)
         L.attn_decode(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, ctxq[:, H:2 * H], ctxq[:, 2 * H:], s_off, s_len,
                       pv[:, :H], pv[:, H:], plen[st["cur"]], G, beams, 2, heads, pcap, 1.0 / math.sqrt(D))
-        pre1 = eng._linear(ctx, so, L.EPI_BIAS_DROP_RESID, aux=x32, drop=NO, out_f32=True)
-        x1_32, x1, _, _ = eng._layernorm(pre1, key + ".ln1", False, lazy=True)
-        h = eng._linear(x1, ff1, L.EPI_BIAS_GELU)
-        pre2 = eng._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=NO, out_f32=True)
-        x2_32, x2, _, _ = eng._layernorm(pre2, key + ".ln2", False, lazy=True)
-        return x2_32, x2
+        return eng._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
 
     def conn_block(key, xt32, xt):
         """The text half of a connection layer: the regions' side is the prefill's (they never attend the answer)."""
@@ -302,12 +298,7 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
         L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, G, nh, T, R, Db, 1.0 / math.sqrt(Db),
                    0, nwv, NO, qvar=(q_off, q_len), kvar=(k_off, k_len))
-        pret = eng._linear(ctx_t, d2, L.EPI_BIAS_DROP_RESID, aux=xt32, drop=NO, out_f32=True)
-        at32, at, _, _ = eng._layernorm(pret, key + ".lnb2", False, lazy=True)
-        ht = eng._linear(at, tff1, L.EPI_BIAS_GELU)
-        pret2 = eng._linear(ht, tff2, L.EPI_BIAS_DROP_RESID, aux=at32, drop=NO, out_f32=True)
-        ot32, ot, _, _ = eng._layernorm(pret2, key + ".lnt", False, lazy=True)
-        return ot32, ot
+        return eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)[:2]
 
     def step(k, parent, token, flags):
         if k == 0:                                         # copy row 0 is the prefill's decoded row

@@ -15,7 +15,8 @@ restates it) with L = length incl. candidate + [SEP], n = len(candidate) + 1, c 
 so in EVERY layer the context rows [1, c) and the whole image stream see nothing that depends on the candidate: they are the
 same for the 100 sequences of a round.  This module runs them once per group (S rows: c - 1 text rows + the 37 regions) and
 only the rows that do depend on the candidate -- row 0, the answer rows and the copy rows: 1 + 2 n of ~140 -- per sequence
-(P rows).  All GEMMs / LayerNorms run on one packed row matrix [S_0 | S_1 | ... | P_0 | P_1 | ...]; attention is
+(P rows).  All GEMMs / LayerNorms run on one packed row matrix [S_0 | S_1 | ... | P_0 | P_1 | ...] (what follows each
+attention is the engine's `_post_attn`, the heads its `_pooled_heads`); attention is
 
     text self-attention     S_g x S_g  (all-ones mask)               one launch over the groups
                             P_b x [CLS_b | S_g(b) | answer_b, copy_b]  one launch over the sequences: the group's K / V rows are
@@ -277,12 +278,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
         L.attn_fwd(q, k, v, ctx, None, ones_t, G, heads, T, T, D, sc, 0, nw, NO, qvar=(s_off, s_len), kvar=(s_off, s_len))
         L.attn_fwd(q, k, v, ctx, None, pwords, B, heads, 32, T, D, sc, nw, 32 * nw, NO, qvar=(p_off, p_len, None, p_ord),
                    kvar=(p_off, p_len), kshared=(ks_off, ks_len, 1))
-        pre1 = eng._linear(ctx, so, L.EPI_BIAS_DROP_RESID, aux=x32, drop=NO, out_f32=True)
-        x1_32, x1, _, _ = eng._layernorm(pre1, key + ".ln1", False, lazy=True)
-        h = eng._linear(x1, ff1, L.EPI_BIAS_GELU)
-        pre2 = eng._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=NO, out_f32=True)
-        x2_32, x2, _, _ = eng._layernorm(pre2, key + ".ln2", False, lazy=True)
-        return x2_32, x2
+        return eng._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
 
     def conn_block(key, xv32, xv, xt32, xt):
         """BertConnectionLayer (models/vilbert_dialog.py:655-783), inference: the image half once per group."""
@@ -302,19 +298,11 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
             ctx_v = torch.empty((G * R, Hb), dtype=BF16, device=dev)
             # regions attend text (:701-721): the co-attention mask is 1 on the context [1, c) = all of S_g
             L.attn_fwd(q1, k2, v2, ctx_v, None, ones_t, G, nh, R, T, Db, sc, 0, nw, NO, kvar=(s_off, s_len))
-            prev = eng._linear(ctx_v, d1, L.EPI_BIAS_DROP_RESID, aux=xv32, drop=NO, out_f32=True)
-            av32, av, _, _ = eng._layernorm(prev, key + ".lnb1", False, lazy=True)
-            hv = eng._linear(av, vff1, L.EPI_BIAS_GELU)
-            prev2 = eng._linear(hv, vff2, L.EPI_BIAS_DROP_RESID, aux=av32, drop=NO, out_f32=True)
-            ov32, ov, _, _ = eng._layernorm(prev2, key + ".lnv", False, lazy=True)
+            ov32, ov, _ = eng._post_attn(ctx_v, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", NO, NO, False)
         ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
         # text attends regions (:681-698): every packed text block against its group's regions
         L.attn_fwd(q2, k1, v1, ctx_t, None, it_vwords, G + B, nh, T, R, Db, sc, 0, nwv, NO, qvar=(it_off, it_len), kvar=(it_koff, it_klen))
-        pret = eng._linear(ctx_t, d2, L.EPI_BIAS_DROP_RESID, aux=xt32, drop=NO, out_f32=True)
-        at32, at, _, _ = eng._layernorm(pret, key + ".lnb2", False, lazy=True)
-        ht = eng._linear(at, tff1, L.EPI_BIAS_GELU)
-        pret2 = eng._linear(ht, tff2, L.EPI_BIAS_DROP_RESID, aux=at32, drop=NO, out_f32=True)
-        ot32, ot, _, _ = eng._layernorm(pret2, key + ".lnt", False, lazy=True)
+        ot32, ot, _ = eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)
         return ov32, ov, ot32, ot
 
     # ---- encoder (schedule of models/vilbert_dialog.py:842-929) ---------------------------------------------------------
@@ -335,17 +323,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     # ---- poolers + NSP (models/vilbert_dialog.py:946-967, 1064-1070): row 0 of every sequence, region 0 of its group -------
     if want_nsp:
         xt32d, xv32d = eng._dense32(xt32), eng._dense32(xv32)
-        cls_t = torch.empty((B, H), dtype=F32, device=dev)
-        cls_v = torch.empty((B, Hv), dtype=F32, device=dev)
-        L.gather_rows(xt32d.view(BF16), p_off, cls_t.view(BF16), B, 2 * H)
-        L.gather_rows(xv32d.view(BF16), (gid * R).to(torch.int32), cls_v.view(BF16), B, 2 * Hv)
-        pooled_t = eng._linear32(cls_t, "tpool", relu=True)
-        pooled_v = eng._linear32(cls_v, "vpool", relu=True)
-        fused = torch.empty_like(pooled_t)
-        L.mul_dropout(pooled_t, pooled_v, fused, fused.numel(), NO, fusion_sum=cfg.fusion_method == "sum")
-        nsp = torch.zeros((B, 4), dtype=F32, device=dev)
-        eng._linear32(fused, "nsp", out=nsp)
-        out["nsp"] = nsp[:, :2]
+        out["nsp"] = eng._pooled_heads(xt32d, xv32d, p_off, (gid * R).to(torch.int32), B, False)["nsp_pad"][:, :2]
     # ---- MLM head on the copy rows (:982-986, :1023-1026) ------------------------------------------------------------------
     n = plan.n_lm
     lm_idx = _i32(plan.lm_idx, dev)
