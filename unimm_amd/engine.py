@@ -713,6 +713,17 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # blocks
     # ------------------------------------------------------------------------------------------
+    # What a compute mode overrides -- these hooks, `_post_attn` and `_transform_head`; the blocks below, their stream
+    # brackets, dropout sites and tape entries are written once, against them:
+    #   _proj(x, lin)            the fused QKV projection of a block input (x: the GEMM operand of the residual stream)
+    #   _attn(...)               -> (ctx, ctx_op, lse): ctx is what the attention backward reads as `out`, ctx_op the operand
+    #                            handed to `_post_attn`
+    #   _qkv_grad(qkv)           the gradient buffer of a projection output
+    #   _attn_bwd(...)           the attention backward into column slices of `_qkv_grad` buffers
+    #   _proj_bwd(dqkv, x, lin, add, m_dev)   weight / bias gradients of the projection; returns dx = dqkv @ W + add
+    def _proj(self, x, lin):
+        return self._linear(x, lin)
+
     def _attn(self, q, k, v, mask, B, H, Tq, Tk, D, drop, save, qvar=None, kvar=None, tag=None):
         out = torch.empty((q.shape[0], H * D), dtype=BF16, device=q.device)
         lse = torch.empty((B, H, Tq), dtype=F32, device=q.device) if save else None
@@ -724,7 +735,20 @@ class Engine:
             probs = torch.empty((B, H, Tq, Tk), dtype=F32, device=q.device)
             L.attn_probs(q, k, probs, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop)
             self.attn_sink[tag] = probs
-        return out, lse
+        return out, out, lse
+
+    def _qkv_grad(self, qkv):
+        return torch.empty_like(qkv)
+
+    def _attn_bwd(self, q, k, v, ctx, dctx, lse, mask, dq, dk, dv, N, B, H, Tq, Tk, D, drop, qvar=None, kvar=None):
+        """dq / dk / dv: column slices of `_qkv_grad` buffers (N: their projection width, not needed here)."""
+        delta = torch.empty_like(lse)
+        words, mq, mb = mask
+        L.attn_bwd(q, k, v, ctx, dctx, lse, delta, dq, dk, dv, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop,
+                   qvar=qvar, kvar=kvar)
+
+    def _proj_bwd(self, dqkv, x, lin, add, m_dev=None):
+        return self._linear_bwd(dqkv, x, lin, L.EPI_ADD, aux=add, m_dev=m_dev)
 
     def _post_attn(self, ctx, res32, proj, ff1, ff2, ln_mid, ln_out, d_proj, d_ffn, save, m_dev=None):
         """What follows the attention in every encoder block: BertSelfOutput or one side of BertBiOutput
@@ -754,29 +778,27 @@ class Engine:
 
     def _self_block(self, key, x32, x, mask, B, T, heads, pname, p_attn, p_hid, st, var=None):
         """BertLayer / BertImageLayer (models/vilbert_dialog.py:385-483, :514-612).
-        (x32, x): fp32 residual stream and its bf16 copy (the GEMM operand)."""
+        (x32, x): fp32 residual stream and its copy as a GEMM operand (bf16, or the split operand of the fp32x3 mode)."""
         train, tape = st["train"], st["tape"]
         save = tape is not None
-        Hd = x.shape[1]
-        D = Hd // heads
         qkv_l, so, ff1, ff2 = (self.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
-        qkv = self._linear(x, qkv_l)
+        Hd = qkv_l.N // 3
+        D = Hd // heads
+        qkv = self._proj(x, qkv_l)
         q, k, v = qkv[:, :Hd], qkv[:, Hd:2 * Hd], qkv[:, 2 * Hd:]
         d_attn = self._drop(pname + "attn", p_attn, train)
-        ctx, lse = self._attn(q, k, v, mask, B, heads, T, T, D, d_attn, save, qvar=var, kvar=var, tag=key)
+        ctx, ctx_op, lse = self._attn(q, k, v, mask, B, heads, T, T, D, d_attn, save, qvar=var, kvar=var, tag=key)
         d_so = self._drop(pname + "so", p_hid, train)
         d_out = self._drop(pname + "out", p_hid, train)
         md = var[2] if var is not None else None      # device word: valid rows, when the row dimension is a capacity
-        x2_32, x2, post_bwd = self._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
+        x2_32, x2, post_bwd = self._post_attn(ctx_op, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
         if save:
             def bwd(dx2):
                 dctx, dpre1 = post_bwd(dx2)
-                dqkv = torch.empty_like(qkv)
-                delta = torch.empty_like(lse)
-                words, mq, mb = mask
-                L.attn_bwd(q, k, v, ctx, dctx, lse, delta, dqkv[:, :Hd], dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:], words,
-                           B, heads, T, T, D, 1.0 / math.sqrt(D), mq, mb, d_attn, qvar=var, kvar=var)
-                return self._linear_bwd(dqkv, x, qkv_l, L.EPI_ADD, aux=dpre1, m_dev=md)
+                dqkv = self._qkv_grad(qkv)
+                self._attn_bwd(q, k, v, ctx, dctx, lse, mask, dqkv[:, :Hd], dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:3 * Hd], 3 * Hd,
+                               B, heads, T, T, D, d_attn, qvar=var, kvar=var)
+                return self._proj_bwd(dqkv, x, qkv_l, dpre1, m_dev=md)
             tape.append((key, bwd))
         return x2_32, x2
 
@@ -793,8 +815,8 @@ class Engine:
         # The two halves run on their own streams (`_img()` = image side, otherwise the text side); the only
         # exchanges are the other side's K/V for the two co-attention directions.
         with self._img():
-            qkv1 = self._linear(xv, lq1)      # image side  [B*R, 3Hb]
-        qkv2 = self._linear(xt, lq2)          # text side   [B*T, 3Hb]
+            qkv1 = self._proj(xv, lq1)        # image side  [B*R, 3Hb]
+        qkv2 = self._proj(xt, lq2)            # text side   [B*T, 3Hb]
         self._to_txt(qkv1)
         self._to_img(qkv2)
         q1, k1, v1 = qkv1[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:]
@@ -806,37 +828,32 @@ class Engine:
         dvo = self._drop(pn + "vout", cfg.v_hidden_dropout_prob, train)
         dto = self._drop(pn + "tout", cfg.hidden_dropout_prob, train)
         with self._img():
-            ctx_v, lse_v = self._attn(q1, k2, v2, comask, B, nh, R, T, D, da2, save, kvar=var, tag=key + "/2")    # regions attend text (:701-721)
-            ov32, ov, bwd_v = self._post_attn(ctx_v, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)   # BertBiOutput (:744-754, call order :775)
+            ctx_v, ctx_v_op, lse_v = self._attn(q1, k2, v2, comask, B, nh, R, T, D, da2, save, kvar=var, tag=key + "/2")    # regions attend text (:701-721)
+            ov32, ov, bwd_v = self._post_attn(ctx_v_op, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)   # BertBiOutput (:744-754, call order :775)
         md = var[2] if var is not None else None      # device word: valid text rows (capacity-sized text tensors)
-        ctx_t, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")     # text attends regions (:681-698)
-        ot32, ot, bwd_t = self._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save, m_dev=md)
+        ctx_t, ctx_t_op, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")     # text attends regions (:681-698)
+        ot32, ot, bwd_t = self._post_attn(ctx_t_op, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save, m_dev=md)
         if save:
             def bwd(dov, dot):
-                sc = 1.0 / math.sqrt(D)
                 # gradient buffers of the two projections: each is written by BOTH attention backward kernels (every
                 # slice exactly once), i.e. from both streams -> allocate first and let each stream see the other's
                 with self._img():
-                    dqkv1 = torch.empty_like(qkv1)
-                dqkv2 = torch.empty_like(qkv2)
+                    dqkv1 = self._qkv_grad(qkv1)
+                dqkv2 = self._qkv_grad(qkv2)
                 self._to_txt(dqkv1)
                 self._to_img(dqkv2)
                 with self._img():                                   # image half: FFN, bi-output
                     dctx_v, dprev = bwd_v(dov)
-                    delta_v = torch.empty_like(lse_v)
-                    w, mq, mb = comask
-                    L.attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, delta_v, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:],
-                               w, B, nh, R, T, D, sc, mq, mb, da2, kvar=var)
+                    self._attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, comask, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:3 * Hb],
+                                   3 * Hb, B, nh, R, T, D, da2, kvar=var)
                 dctx_t, dpret = bwd_t(dot)                          # text half: FFN, bi-output
-                delta_t = torch.empty_like(lse_t)
-                w, mq, mb = vmask
-                L.attn_bwd(q2, k1, v1, ctx_t, dctx_t, lse_t, delta_t, dqkv2[:, :Hb], dqkv1[:, Hb:2 * Hb], dqkv1[:, 2 * Hb:],
-                           w, B, nh, T, R, D, sc, mq, mb, da1, qvar=var)
+                self._attn_bwd(q2, k1, v1, ctx_t, dctx_t, lse_t, vmask, dqkv2[:, :Hb], dqkv1[:, Hb:2 * Hb], dqkv1[:, 2 * Hb:3 * Hb],
+                               3 * Hb, B, nh, T, R, D, da1, qvar=var)
                 self._to_img()                                      # dK1/dV1 written by the text side
                 self._to_txt()                                      # dK2/dV2 written by the image side
                 with self._img():
-                    dxv = self._linear_bwd(dqkv1, xv, lq1, L.EPI_ADD, aux=dprev)
-                dxt = self._linear_bwd(dqkv2, xt, lq2, L.EPI_ADD, aux=dpret, m_dev=md)
+                    dxv = self._proj_bwd(dqkv1, xv, lq1, dprev)
+                dxt = self._proj_bwd(dqkv2, xt, lq2, dpret, m_dev=md)
                 return dxv, dxt
             tape.append((key, bwd))
         return ov32, ov, ot32, ot
@@ -1238,15 +1255,10 @@ class Engine:
         img = None
         pred_v_out = None
         if want_pred_v or inp.get("image_target") is not None:
+            C = cfg.v_target_size
             with self._img_if(self.image_head_side):
-                itr, idec = self.lin["imgtr"], self.lin["imgdec"]
-                C = cfg.v_target_size
-                if save:
-                    tv, uvh = self._linear(xv, itr, L.EPI_BIAS_GELU, want_u=True, out_f32=True)
-                else:
-                    tv, uvh = self._linear(xv, itr, L.EPI_BIAS_GELU, out_f32=True), None
-                _, hvn, mh, rh = self._layernorm(tv, "imgtr", save, want32=False)
-                pred_v = self._linear(hvn, idec, out_f32=True, ldo=_rup(C, 4))
+                tv, uvh, hvn, mh, rh, pred_v = self._transform_head(xv, self.lin["imgtr"], "imgtr", self.lin["imgdec"],
+                                                                    _rup(C, 4), save)
             pred_v_out = pred_v.view(B, R, -1)[:, :, :C]
             img = dict(tv=tv, u=uvh, hn=hvn, mean=mh, rstd=rh, pred=pred_v)
         self._to_txt(xv32, xv, img["pred"] if img is not None else None)                # the heads read both streams
@@ -1298,27 +1310,28 @@ class Engine:
                       w * x.shape[1], scatter=True, n_dev=plan["var"][2])
         return full
 
-    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None):
-        cfg = self.cfg
-        V = cfg.vocab_size
-        Vp = _rup(V, 64)
-        lmtr, dec = self.lin["lmtr"], self.lin["dec"]
+    def _transform_head(self, x, tr, ln_key, dec, ldo, save, M=None):
+        """transform -> GELU -> LayerNorm -> decoder of the MLM and image heads (models/vilbert_dialog.py:982-986, :1001-1005)
+        on M rows of the GEMM operand x -> (t, u, hn, mean, rstd, out): the fp32 GELU output, the transform's pre-activation
+        (None unless save), the normalised decoder operand, the LayerNorm statistics (None unless save), fp32 out [M, ldo]."""
         if save:
-            t1, u = self._linear(xs, lmtr, L.EPI_BIAS_GELU, want_u=True, out_f32=True)
+            t, u = self._linear(x, tr, L.EPI_BIAS_GELU, want_u=True, out_f32=True, M=M)
         else:
-            t1, u = self._linear(xs, lmtr, L.EPI_BIAS_GELU, out_f32=True), None
-        _, hn, mean, rstd = self._layernorm(t1, "lmtr", save, want32=False)
-        logits = self._linear(hn, dec, out_f32=True, ldo=Vp)
+            t, u = self._linear(x, tr, L.EPI_BIAS_GELU, out_f32=True, M=M), None
+        _, hn, mean, rstd = self._layernorm(t, ln_key, save, want32=False)
+        return t, u, hn, mean, rstd, self._linear(hn, dec, out_f32=True, ldo=ldo)
+
+    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None):
+        V = self.cfg.vocab_size
+        t1, u, hn, mean, rstd, logits = self._transform_head(xs, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(V, 64), save)
         rowloss, rownll, lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
         L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
         return dict(xs=xs, t1=t1, u=u, hn=hn, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll,
                     lse=lse, labels=lab_sel, weights=w_sel)
 
     def decode_rows(self, x, n):
-        """MLM transform + decoder for n rows of x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
-        t1 = self._linear(x, self.lin["lmtr"], L.EPI_BIAS_GELU, M=n, out_f32=True)
-        _, hn, _, _ = self._layernorm(t1, "lmtr", False, want32=False)
-        return self._linear(hn, self.lin["dec"], out_f32=True, ldo=_rup(self.cfg.vocab_size, 64))
+        """MLM transform + decoder for n rows of the GEMM operand x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
+        return self._transform_head(x, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(self.cfg.vocab_size, 64), False, M=n)[5]
 
     # ------------------------------------------------------------------------------------------
     # losses + backward

@@ -1,4 +1,4 @@
-"""The fp32-accuracy engine ("fp32x3"): the same launch schedule as `unimm_amd.engine.Engine` with fp32 activations,
+"""The fp32-accuracy engine ("fp32x3"): the launch schedule of `unimm_amd.engine.Engine` with fp32 activations,
 fp32 gradients and fp32-grade GEMMs, for callers that run the reference WITHOUT autocast
 (dense_annotation_finetuning.py:253 calls `forward` in fp32 end to end; north_star gates fp32 results at 1e-3).
 
@@ -10,8 +10,11 @@ residual-join that the bf16 path fuses into GEMM epilogues), run LayerNorm / emb
 and compute the attention cores in fp32 on the vector ALUs.  Masks, the unpadded schedule, dropout counters, the row-sparse
 decoder, the fp32 pooler / NSP heads, the loss kernels and the flat gradient arena are the base engine's.
 
-The base engine's two-stream schedule (image side beside the text side), eager launches or the graph executor, no lazy
-LayerNorm: this is the accuracy mode, ~0.3 of the bf16 engine's throughput.  There is no CPU / eager-PyTorch fallback here either."""
+The encoder blocks, the MLM head and `decode_rows` are the base engine's own code, not a copy: this class overrides the
+operand hooks they are written against (`_proj`, `_attn`, `_qkv_grad`, `_attn_bwd`, `_proj_bwd`, `_post_attn`,
+`_transform_head`) and keeps its own `_forward` / `_backward` around them.  The base engine's two-stream schedule (image
+side beside the text side), eager launches or the graph executor, no lazy LayerNorm: this is the accuracy mode, ~0.3 of the
+bf16 engine's throughput.  There is no CPU / eager-PyTorch fallback here either."""
 from __future__ import annotations
 
 import math
@@ -210,8 +213,11 @@ class EngineX3(Engine):
             return torch.empty((qkv.shape[0], 3 * qkv.shape[1]), dtype=BF16, device=qkv.device)
         return torch.empty_like(qkv)
 
-    def _qkv_grad3(self, g):
-        return g if self.attn_planes else self._split(g)
+    def _proj(self, x3, lin):
+        return self._lin3(x3, lin)
+
+    def _proj_bwd(self, dqkv, x3, lin, add, m_dev=None):
+        return self._lin3_bwd(dqkv if self.attn_planes else self._split(dqkv), x3, lin, m_dev=m_dev, add=add)
 
     def _attn_bwd(self, q, k, v, ctx, dctx, lse, mask, dq, dk, dv, N, B, H, Tq, Tk, D, drop, qvar=None, kvar=None):
         """dq / dk / dv: column slices [:, c0:c1] of `_qkv_grad` buffers (N = their projection width = the plane stride)."""
@@ -243,90 +249,12 @@ class EngineX3(Engine):
             return self._lin3_bwd(dpre1d3, ctx3, proj, bias_grad=False, m_dev=m_dev), dpre1
         return x2_32, x2_3, bwd
 
-    def _self_block(self, key, x32, x3, mask, B, T, heads, pname, p_attn, p_hid, st, var=None):
-        """BertLayer / BertImageLayer (models/vilbert_dialog.py:385-483, :514-612).  (x32, x3): the fp32 residual stream and
-        its split copy (the GEMM operand)."""
-        train, tape = st["train"], st["tape"]
-        save = tape is not None
-        Hd = x32.shape[1]
-        D = Hd // heads
-        qkv_l, so, ff1, ff2 = (self.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
-        qkv = self._lin3(x3, qkv_l)
-        q, k, v = qkv[:, :Hd], qkv[:, Hd:2 * Hd], qkv[:, 2 * Hd:]
-        d_attn = self._drop(pname + "attn", p_attn, train)
-        ctx, ctx3, lse = self._attn(q, k, v, mask, B, heads, T, T, D, d_attn, save, qvar=var, kvar=var, tag=key)
-        d_so = self._drop(pname + "so", p_hid, train)
-        d_out = self._drop(pname + "out", p_hid, train)
-        md = var[2] if var is not None else None
-        x2_32, x2_3, post_bwd = self._post_attn(ctx3, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
-        if save:
-            def bwd(dx2):
-                dctx, dpre1 = post_bwd(dx2)
-                dqkv = self._qkv_grad(qkv)
-                self._attn_bwd(q, k, v, ctx, dctx, lse, mask, dqkv[:, :Hd], dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:3 * Hd], 3 * Hd,
-                               B, heads, T, T, D, d_attn, qvar=var, kvar=var)
-                return self._lin3_bwd(self._qkv_grad3(dqkv), x3, qkv_l, m_dev=md, add=dpre1)
-            tape.append((key, bwd))
-        return x2_32, x2_3
-
-    def _conn_block(self, key, i, xv32, xv3, xt32, xt3, B, R, T, vmask, comask, st, var=None):
-        """BertConnectionLayer (models/vilbert_dialog.py:655-783)."""
-        cfg = self.cfg
-        train, tape = st["train"], st["tape"]
-        save = tape is not None
-        pn = f"bert.encoder.c_layer.{i}."
-        Hb, nh = cfg.bi_hidden_size, cfg.bi_num_attention_heads
-        D = Hb // nh
-        lq1, lq2, d1, d2 = (self.lin[key + s] for s in (".qkv1", ".qkv2", ".d1", ".d2"))
-        vff1, vff2, tff1, tff2 = (self.lin[key + s] for s in (".vff1", ".vff2", ".tff1", ".tff2"))
-        # The two halves run on their own streams (`_img()` = image side, otherwise the text side); the only exchanges are the
-        # other side's K / V for the two co-attention directions (the base engine's schedule).
-        with self._img():
-            qkv1 = self._lin3(xv3, lq1)       # image side  [B*R, 3Hb]
-        qkv2 = self._lin3(xt3, lq2)           # text side   [rows, 3Hb]
-        self._to_txt(qkv1)
-        self._to_img(qkv2)
-        q1, k1, v1 = qkv1[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:]
-        q2, k2, v2 = qkv2[:, :Hb], qkv2[:, Hb:2 * Hb], qkv2[:, 2 * Hb:]
-        da1 = self._drop(pn + "attn1", cfg.v_attention_probs_dropout_prob, train)
-        da2 = self._drop(pn + "attn2", cfg.attention_probs_dropout_prob, train)
-        db1 = self._drop(pn + "bo1", cfg.v_hidden_dropout_prob, train)
-        db2 = self._drop(pn + "bo2", cfg.hidden_dropout_prob, train)
-        dvo = self._drop(pn + "vout", cfg.v_hidden_dropout_prob, train)
-        dto = self._drop(pn + "tout", cfg.hidden_dropout_prob, train)
-        # image half: regions attend text (:701-721), BertBiOutput (:744-754, call order :775), image FFN
-        with self._img():
-            ctx_v, ctx_v3, lse_v = self._attn(q1, k2, v2, comask, B, nh, R, T, D, da2, save, kvar=var, tag=key + "/2")
-            ov32, ov3, bwd_v = self._post_attn(ctx_v3, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)
-        md = var[2] if var is not None else None
-        # text half: text attends regions (:681-698)
-        ctx_t, ctx_t3, lse_t = self._attn(q2, k1, v1, vmask, B, nh, T, R, D, da1, save, qvar=var, tag=key + "/1")
-        ot32, ot3, bwd_t = self._post_attn(ctx_t3, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save, m_dev=md)
-        if save:
-            def bwd(dov, dot):
-                # gradient buffers of the two projections: each is written by BOTH attention backward kernels (every slice exactly
-                # once), i.e. from both streams -> allocate first and let each stream see the other's
-                with self._img():
-                    dqkv1 = self._qkv_grad(qkv1)
-                dqkv2 = self._qkv_grad(qkv2)
-                self._to_txt(dqkv1)
-                self._to_img(dqkv2)
-                with self._img():                                   # image half
-                    dctx_v, dprev = bwd_v(dov)
-                    self._attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, comask, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:3 * Hb],
-                                   3 * Hb, B, nh, R, T, D, da2, kvar=var)
-                # text half
-                dctx_t, dpret = bwd_t(dot)
-                self._attn_bwd(q2, k1, v1, ctx_t, dctx_t, lse_t, vmask, dqkv2[:, :Hb], dqkv1[:, Hb:2 * Hb], dqkv1[:, 2 * Hb:3 * Hb],
-                               3 * Hb, B, nh, T, R, D, da1, qvar=var)
-                self._to_img()                                      # dK1 / dV1 written by the text side
-                self._to_txt()                                      # dK2 / dV2 written by the image side
-                with self._img():
-                    dxv = self._lin3_bwd(self._qkv_grad3(dqkv1), xv3, lq1, add=dprev)
-                dxt = self._lin3_bwd(self._qkv_grad3(dqkv2), xt3, lq2, m_dev=md, add=dpret)
-                return dxv, dxt
-            tape.append((key, bwd))
-        return ov32, ov3, ot32, ot3
+    def _transform_head(self, x3, tr, ln_key, dec, ldo, save, M=None):
+        """The base engine's contract on split operands; u (fp32) is returned whether or not save."""
+        u = self._lin3(x3, tr, M=M)
+        t = self._op3(u, op=L.X3_GELU, want3=False, want32=True)[1]
+        _, hn3, mean, rstd = self._ln3(t, ln_key, save)
+        return t, u, hn3, mean, rstd, self._lin3(hn3, dec, ldo=ldo)
 
     # ------------------------------------------------------------------------------------------
     # forward
@@ -412,13 +340,10 @@ class EngineX3(Engine):
         img = None
         pred_v_out = None
         if want_pred_v or inp.get("image_target") is not None:
-            itr, idec = self.lin["imgtr"], self.lin["imgdec"]
             C = cfg.v_target_size
             with self._img():
-                uvh = self._lin3(xv3, itr)
-                tv = self._op3(uvh, op=L.X3_GELU, want3=False, want32=True)[1]
-                _, hvn3, mh, rh = self._ln3(tv, "imgtr", save)
-                pred_v = self._lin3(hvn3, idec, ldo=_rup(C, 4))
+                tv, uvh, hvn3, mh, rh, pred_v = self._transform_head(xv3, self.lin["imgtr"], "imgtr", self.lin["imgdec"],
+                                                                     _rup(C, 4), save)
             pred_v_out = pred_v.view(B, R, -1)[:, :, :C]
             img = dict(tv=tv, u=uvh, hn=hvn3, mean=mh, rstd=rh, pred=pred_v)
         self._to_txt(xv32, xv3, img["pred"] if img is not None else None)       # the heads read both streams
@@ -448,27 +373,6 @@ class EngineX3(Engine):
         if save:
             out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, **heads)
         return out
-
-    def _lm_head(self, xs3, n, lab_sel, w_sel, save, n_dev=None):
-        cfg = self.cfg
-        V = cfg.vocab_size
-        Vp = _rup(V, 64)
-        lmtr, dec = self.lin["lmtr"], self.lin["dec"]
-        u = self._lin3(xs3, lmtr)
-        t1 = self._op3(u, op=L.X3_GELU, want3=False, want32=True)[1]
-        _, hn3, mean, rstd = self._ln3(t1, "lmtr", save)
-        logits = self._lin3(hn3, dec, ldo=Vp)
-        rowloss, rownll, lse = (torch.empty(n, dtype=F32, device=xs3.device) for _ in range(3))
-        L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
-        return dict(xs=xs3, t1=t1, u=u, hn=hn3, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll,
-                    lse=lse, labels=lab_sel, weights=w_sel)
-
-    def decode_rows(self, x3, n):
-        """MLM transform + decoder for n rows given as a split operand [n, 3 H]: fp32 logits [n, Vpad]."""
-        u = self._lin3(x3, self.lin["lmtr"], M=n)
-        t1 = self._op3(u, op=L.X3_GELU, want3=False, want32=True)[1]
-        _, hn3, _, _ = self._ln3(t1, "lmtr", False)
-        return self._lin3(hn3, self.lin["dec"], ldo=_rup(self.cfg.vocab_size, 64))
 
     # ------------------------------------------------------------------------------------------
     # backward

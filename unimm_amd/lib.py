@@ -287,6 +287,19 @@ def _item_order(qvar, kvar):
 NO_DROP = (0, 0, 1.0)
 
 
+def _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar=None, kvar=None):
+    """The fields `AttnArgs` and `AttnBwdArgs` share, for every attention wrapper (v = None: the launch reads no values)."""
+    a.q, a.k, a.v, a.mask = q.data_ptr(), k.data_ptr(), _P(v), mask.data_ptr()
+    a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
+    a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
+    a.order = _item_order(qvar, kvar)
+    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
+    a.ldq, a.ldk, a.ldv = q.stride(0), k.stride(0), (v.stride(0) if v is not None else 0)
+    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
+    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
+    a.drop_salt = _salt(drop)
+
+
 def attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP,
              qvar=None, kvar=None, kshared=None):
     """q/k/v/out: 2-D bf16 views [rows, >=H*D] (row stride = stride(0)); mask: packed uint32 words.
@@ -299,19 +312,12 @@ def attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mas
         a = AttnArgs()
         st = _tls.af = (a, C.addressof(a), lib().unimm_attn_fwd)
     a, addr, fn = st
-    a.q, a.k, a.v, a.out, a.lse, a.mask = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _P(lse), mask.data_ptr()
-    a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
-    a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
     if kshared is not None:
         a.ks_off, a.ks_len, a.ks_ins = kshared[0].data_ptr(), kshared[1].data_ptr(), int(kshared[2])
     else:
         a.ks_off, a.ks_len, a.ks_ins = None, None, 0
-    a.order = _item_order(qvar, kvar)
-    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
-    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
-    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
-    a.drop_salt = _salt(drop)
     rc = fn(addr, _stream())
     if rc != 0:
         _check(rc, "unimm_attn_fwd")
@@ -375,17 +381,8 @@ def lm_topk(logits, rows, V, banned, flags, sep, K, vals, ids, lse=None):
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):
     """probs: fp32 [B, H, Tq, Tk] = dropout(softmax(q k^T scale + additive mask)); fixed row layout (diagnostic output)."""
     _dev(q, k, probs, mask)
-    a = AttnArgs()
-    a.q, a.k, a.v, a.out, a.lse, a.mask = q.data_ptr(), k.data_ptr(), None, None, None, mask.data_ptr()
-    a.q_off = a.q_len = a.k_off = a.k_len = None
-    a.ks_off = a.ks_len = None
-    a.ks_ins = 0
-    a.order = None
-    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
-    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), 0, 0
-    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
-    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
-    a.drop_salt = _salt(drop)
+    a = AttnArgs()                  # out / lse / ldo / ks_* stay zero
+    _attn_common(a, q, k, None, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop)
     _check(lib().unimm_attn_probs(C.byref(a), _ptr(probs), _stream()), "unimm_attn_probs")
 
 
@@ -397,18 +394,11 @@ def attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, mask, B, H, Tq, Tk, D, 
         a = AttnBwdArgs()
         st = _tls.ab = (a, C.addressof(a), lib().unimm_attn_bwd)
     a, addr, fn = st
-    a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
-    a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
-    a.q, a.k, a.v, a.out, a.dout = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr()
-    a.lse, a.delta, a.dq, a.dk, a.dv, a.mask = (lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                                                mask.data_ptr())
-    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
-    a.ldq, a.ldk, a.ldv, a.ldo, a.lddo = q.stride(0), k.stride(0), v.stride(0), out.stride(0), dout.stride(0)
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.out, a.dout, a.lse, a.delta = out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr()
+    a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    a.ldo, a.lddo = out.stride(0), dout.stride(0)
     a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
-    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
-    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
-    a.drop_salt = _salt(drop)
-    a.order = _item_order(qvar, kvar)
     rc = fn(addr, _stream())
     if rc != 0:
         _check(rc, "unimm_attn_bwd")
@@ -989,15 +979,8 @@ def x3_attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, 
         pl = X3AttnPlanes()
         pl.out3, pl.ld3, pl.cp3 = out3.data_ptr(), out3.stride(0), out3.shape[1] // 3
     a = AttnArgs()
-    a.q, a.k, a.v, a.out, a.lse, a.mask = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _P(lse), mask.data_ptr()
-    a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
-    a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
-    a.order = _item_order(qvar, kvar)
-    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
-    a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
-    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
-    a.drop_salt = _salt(drop)
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
     _check(lib().unimm_x3_attn_fwd(C.byref(a), C.byref(pl) if pl is not None else None, _stream()), "unimm_x3_attn_fwd")
 
 
@@ -1011,19 +994,12 @@ def x3_attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, mask, B, H, Tq, Tk, 
     if planes is not None:
         pl = X3AttnPlanes()
         pl.dq3, pl.dk3, pl.dv3, pl.cp3, pl.ld3 = dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), planes[0], planes[1]
-    a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
-    a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
-    a.order = _item_order(qvar, kvar)
-    a.q, a.k, a.v, a.out, a.dout = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr()
-    a.lse, a.delta, a.mask = lse.data_ptr(), delta.data_ptr(), mask.data_ptr()
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.out, a.dout, a.lse, a.delta = out.data_ptr(), dout.data_ptr(), lse.data_ptr(), delta.data_ptr()
+    a.ldo, a.lddo = out.stride(0), dout.stride(0)
     if pl is None:
         a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
         a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
-    a.B, a.H, a.Tq, a.Tk, a.D = B, H, Tq, Tk, D
-    a.ldq, a.ldk, a.ldv, a.ldo, a.lddo = q.stride(0), k.stride(0), v.stride(0), out.stride(0), dout.stride(0)
-    a.mask_q_stride, a.mask_b_stride, a.scale = mask_q_stride, mask_b_stride, scale
-    a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
-    a.drop_salt = _salt(drop)
     _check(lib().unimm_x3_attn_bwd(C.byref(a), C.byref(pl) if pl is not None else None, _stream()), "unimm_x3_attn_bwd")
 
 
