@@ -179,10 +179,13 @@ typedef struct {
   float scale;
   uint32_t drop_key, drop_thr; float drop_scale;
   const uint32_t* drop_salt; /* or NULL (see unimm_gemm_nt_args.drop_salt) */ /* element index = ((b*H+h)*Tq+q)*Tk+k */
-  /* unimm_attn_fwd only (NULL elsewhere), with k_off / k_len given and dropout off: a SHARED key/value segment -- rows
+  /* unimm_attn_fwd and unimm_x3_attn_fwd only (NULL elsewhere), with k_off / k_len given and dropout off: a SHARED key/value segment -- rows
    * [ks_off[b], ks_off[b] + ks_len[b]) of the same k / v matrices -- spliced into sequence b's keys after its first ks_ins
    * private rows.  Key position j of sequence b is private row j (j < ks_ins), shared row j - ks_ins (j < ks_ins + ks_len[b]),
    * else private row j - ks_len[b]; the sequence has k_len[b] + ks_len[b] <= 256 keys and the mask words index key positions.
+   * The position count is clamped to Tk, ks_len[b] < 0 is taken as 0, and nothing outside the two row ranges is read.
+   * ks_off and ks_len come together or not at all; a segment without k_off / k_len, with ks_ins < 0 or with drop_thr != 0 is
+   * UNIMM_E_ARG before any launch.  Both backward entry points have no such fields and never take a segment.
    * Generative scoring (val_lm.py:52-121): the 100 candidate answers of a dialog round attend the round's context rows,
    * which are computed once (utils/data_utils.py:199-210: context rows never see the answer).  ABI 16. */
   const int32_t* ks_off; const int32_t* ks_len;
@@ -580,7 +583,11 @@ typedef struct {
   int32_t cp3;                     /* plane stride = columns per plane (multiple of 8, >= H * D); buffers 16-byte aligned, ld3 % 8 == 0 */
 } unimm_x3_attn_planes;
 /* planes (or NULL): what the next GEMM reads, written by the attention kernel itself instead of a unimm_x3_split pass over its
- * fp32 result.  Matrix-instruction kernels only (UNIMM_E_ARG under unimm_x3_attn_set_impl(0)). */
+ * fp32 result.  Matrix-instruction kernels only (UNIMM_E_ARG under unimm_x3_attn_set_impl(0)).
+ * unimm_x3_attn_fwd takes the spliced shared key/value segment (ks_off / ks_len / ks_ins of the argument struct, same meaning
+ * and same checks as in unimm_attn_fwd) in its matrix-instruction kernels: out, lse and the split planes are bit-identical to a
+ * launch over the same rows gathered into position order.  UNIMM_E_ARG under unimm_x3_attn_set_impl(0); unimm_x3_attn_bwd
+ * has no way to pass one. */
 int unimm_x3_attn_fwd(const unimm_attn_args* args, const unimm_x3_attn_planes* planes, void* stream);
 int unimm_x3_attn_bwd(const unimm_attn_bwd_args* args, const unimm_x3_attn_planes* planes, void* stream);
 /* Which kernels the two entry points above launch: 1 (default) = the fp32 matrix-instruction kernels

@@ -376,6 +376,8 @@ struct AttnF32 {
   // optional x-type split outputs (planes of `cp3` columns, row stride ld3): the forward's context, the backward's dQ / dK / dV
   bf16_t* o3; bf16_t* dq3; bf16_t* dk3; bf16_t* dv3;
   int ld3, cp3;
+  // forward, matrix kernels only: the shared key/value segment spliced into the keys (unimm_attn_args.ks_*), or NULL
+  const int* ks_off; const int* ks_len; int ks_ins;
 };
 
 #ifndef UNIMM_X3_ATTN_BWD_DH
@@ -665,6 +667,22 @@ __device__ __forceinline__ void xm_load_b(const float* __restrict__ g, int grp, 
     reg[4 * J] = t[0]; reg[4 * J + 1] = t[1]; reg[4 * J + 2] = t[2]; reg[4 * J + 3] = t[3];
   }
 }
+// A shared key/value segment spliced into a sequence's keys (unimm_attn_args.ks_*): key position j is private row j below
+// `ins`, shared row j - ins below `end` = ins + ks_len[b], else private row j - ks_len[b].  All five words are
+// workgroup-uniform: the row of a position is the position plus the tail's displacement, plus one uniform step below each
+// boundary.  The position itself comes from threadIdx, so this is two vector compares and two conditional adds per staged
+// row and lane against scalar operands, not per element (written as a three-way select the compiler made it a table in
+// scratch memory).  `ins` is clamped to the private length (and the caller clamps both lengths to >= 0), so no
+// position below k_len[b] + ks_len[b] maps outside [k_off[b], k_off[b] + k_len[b]) and [ks_off[b], ks_off[b] + ks_len[b]).
+struct XmSplice {
+  int ins, end, d_tail, up_shared, up_head;
+  __device__ __forceinline__ int row(int j) const { return j + d_tail + (j < end ? up_shared : 0) + (j < ins ? up_head : 0); }
+};
+__device__ __forceinline__ XmSplice xm_splice(int koff, int klen, int soff, int slen, int ks_ins) {
+  const int ins = ks_ins < klen ? ks_ins : klen;
+  const int d_head = koff, d_shared = soff - ins, d_tail = koff - slen;
+  return XmSplice{ins, ins + slen, d_tail, d_shared - d_tail, d_head - d_shared};
+}
 // Staging: rows [r0, r0 + NR) of the other side (zeros past `len`) into LDS rows of D + 4 floats, in two halves, so that a
 // chunk's global loads are in flight while the previous chunk is being multiplied:
 // load() requests rows [r0, r0 + NR) into registers, store() puts them into LDS (between two barriers).
@@ -678,6 +696,15 @@ template <int D, int NR> struct XmChunk {
       const int i = n * XM_T + threadIdx.x, r = i / (D / 4), c = (i - r * (D / 4)) * 4;
       t[n] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (r0 + r < len) t[n] = *reinterpret_cast<const f32x4*>(g + (size_t)(row_base + r0 + r) * ld + col0 + c);
+    }
+  }
+  // the same request over key POSITIONS [r0, r0 + NR) of a sequence with a spliced shared segment (zeros past `npos`)
+  __device__ __forceinline__ void load(const float* __restrict__ g, const XmSplice sp, int r0, int npos, int ld, int col0) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+      const int i = n * XM_T + threadIdx.x, r = i / (D / 4), c = (i - r * (D / 4)) * 4;
+      t[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (r0 + r < npos) t[n] = *reinterpret_cast<const f32x4*>(g + (size_t)sp.row(r0 + r) * ld + col0 + c);
     }
   }
   __device__ __forceinline__ void store(float* __restrict__ lds) const {
@@ -786,7 +813,11 @@ __device__ __forceinline__ float xm_groups_sum(float v) { v += __shfl_xor(v, 16,
 
 // Forward.  NT = 16-key tiles a query row can have (4 / 8 / 16): the whole score row of a query lives in registers
 // (exact two-pass softmax), K streams through LDS 64 keys at a time, then V.
-template <int D, int NT>
+// SPLICED: a shared key/value segment sits inside the keys (XmSplice).  Only the staging differs: `klen` becomes the number
+// of key POSITIONS (clamped to Tk), a chunk's rows come through the position -> row map, and the products, the softmax and
+// P V consume positions in the same order and chunks as a launch over physically gathered rows: bit-identical results.
+// The unspliced instantiations are the training kernels; they compile to what they were before the flag existed.
+template <int D, int NT, bool SPLICED>
 __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_fwd_kernel(AttnF32 p) {
   constexpr bool OWN_Q = true;
   constexpr int LD = D + 4, KC = 64;
@@ -795,9 +826,19 @@ __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_fwd_kernel
   int blk, head, b;
   if (!xm_decode(OWN_Q ? (p.Tq + XM_R - 1) / XM_R : (p.Tk + XM_R - 1) / XM_R, p.H, p.B, p.order, blk, head, b)) return;
   const int qlen = p.q_len != nullptr ? p.q_len[b] : p.Tq, qoff = p.q_off != nullptr ? p.q_off[b] : b * p.Tq;
-  const int klen = p.k_len != nullptr ? p.k_len[b] : p.Tk, koff = p.k_off != nullptr ? p.k_off[b] : b * p.Tk;
+  const int kpriv = p.k_len != nullptr ? p.k_len[b] : p.Tk, koff = p.k_off != nullptr ? p.k_off[b] : b * p.Tk;
   const int r0 = blk * XM_R;
   if (r0 >= qlen) return;                                  // workgroup-uniform
+  // SPLICED: klen counts key positions, private + shared (either length below 0 is 0; positions at or past Tk do not exist)
+  const int npriv = kpriv > 0 ? kpriv : 0, slen = SPLICED ? (p.ks_len[b] > 0 ? p.ks_len[b] : 0) : 0;
+  const XmSplice sp = SPLICED ? xm_splice(koff, npriv, p.ks_off[b], slen, p.ks_ins) : XmSplice{0, 0, 0, 0, 0};
+  const int klen = SPLICED ? (npriv + slen < p.Tk ? npriv + slen : p.Tk) : kpriv;
+  XmChunk<D, KC> pre;
+  // request key positions [k0, k0 + KC) of K or V
+  auto request = [&](const float* __restrict__ g, int k0, int ld) {
+    if constexpr (SPLICED) pre.load(g, sp, k0, klen, ld, head * D);
+    else pre.load(g, koff, k0, klen, ld, head * D);
+  };
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, grp = lane >> 4;
   const bool live = r0 + wave * 16 < qlen;                 // wave-uniform: some of the wave's queries exist
   const bool valid = r0 + wave * 16 + r < qlen;
@@ -812,16 +853,15 @@ __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_fwd_kernel
 #pragma unroll
   for (int w = 0; w < NT / 2; ++w) mws[w] = mrow[w < nmw ? w : nmw - 1];
   f32x4 s[NT];
-  XmChunk<D, KC> pre;
-  pre.load(p.k, koff, 0, klen, p.ldk, head * D);
+  request(p.k, 0, p.ldk);
 #pragma unroll
   for (int ch = 0; ch < NT / 4; ++ch) {
     if (ch * KC < klen) {
       __syncthreads();
       pre.store(Xs);
       __syncthreads();
-      if ((ch + 1) * KC < klen) pre.load(p.k, koff, (ch + 1) * KC, klen, p.ldk, head * D);   // next K chunk, or V's first
-      else pre.load(p.v, koff, 0, klen, p.ldv, head * D);
+      if ((ch + 1) * KC < klen) request(p.k, (ch + 1) * KC, p.ldk);   // next K chunk, or V's first
+      else request(p.v, 0, p.ldv);
       if (live) {
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
@@ -869,7 +909,7 @@ __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_fwd_kernel
       __syncthreads();
       pre.store(Xs);
       __syncthreads();
-      if ((ch + 1) * KC < klen) pre.load(p.v, koff, (ch + 1) * KC, klen, p.ldv, head * D);
+      if ((ch + 1) * KC < klen) request(p.v, (ch + 1) * KC, p.ldv);
       if (live) {
 #pragma unroll
         for (int tt = 0; tt < 4; ++tt)
@@ -1098,7 +1138,10 @@ int fill_attn(const unimm_attn_args* a, AttnF32& p) {
   if ((a->ldq % 4) || (a->ldk % 4) || (a->ldv % 4) || (a->ldo % 4)) return UNIMM_E_ALIGN;
   if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) & 15) return UNIMM_E_ALIGN;
   if ((a->q_off == nullptr) != (a->q_len == nullptr) || (a->k_off == nullptr) != (a->k_len == nullptr)) return UNIMM_E_ARG;
-  if (a->ks_off != nullptr || a->ks_len != nullptr) return UNIMM_E_ARG;      // the spliced shared key segment is a bf16-kernel feature
+  // a spliced shared key segment: both words or neither, variable-length keys, inference (the forward's matrix kernels
+  // only: unimm_x3_attn_fwd checks which kernels are selected, unimm_x3_attn_bwd never passes one)
+  if ((a->ks_off == nullptr) != (a->ks_len == nullptr)) return UNIMM_E_ARG;
+  if (a->ks_off != nullptr && (a->k_off == nullptr || a->ks_ins < 0 || a->drop_thr != 0u)) return UNIMM_E_ARG;
   p = AttnF32{};
   p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.out = (float*)a->out; p.lse = a->lse;
   p.mask = a->mask; p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
@@ -1107,6 +1150,7 @@ int fill_attn(const unimm_attn_args* a, AttnF32& p) {
   p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
   p.mqs = a->mask_q_stride; p.mbs = a->mask_b_stride; p.scale = a->scale;
   p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt; p.drop.key2 = 0u;
+  p.ks_off = a->ks_off; p.ks_len = a->ks_len; p.ks_ins = a->ks_off != nullptr ? a->ks_ins : 0;
   return UNIMM_OK;
 }
 
@@ -1207,6 +1251,7 @@ extern "C" int unimm_x3_attn_fwd(const unimm_attn_args* a, const unimm_x3_attn_p
   AttnF32 p;
   const int rc = fill_attn(a, p);
   if (rc != UNIMM_OK) return rc;
+  if (p.ks_off != nullptr && g_x3_attn_impl == 0) return UNIMM_E_ARG;  // a shared key segment: the matrix kernels only
   if (pl != nullptr && pl->out3 != nullptr) {
     if (g_x3_attn_impl == 0) return UNIMM_E_ARG;                       // split outputs: the matrix kernels only
     if ((((uintptr_t)pl->out3) & 15) || (pl->ld3 % 8) || (pl->cp3 % 8) || pl->cp3 < a->H * a->D || pl->ld3 < 3 * pl->cp3) return UNIMM_E_ALIGN;
@@ -1216,7 +1261,11 @@ extern "C" int unimm_x3_attn_fwd(const unimm_attn_args* a, const unimm_x3_attn_p
   if (g_x3_attn_impl != 0) {
     const dim3 grid(xm_grid((a->Tq + XM_R - 1) / XM_R, a->H, a->B));
     const int nt = (a->Tk + 15) / 16;
-#define UNIMM_X3M_FWD(D_, NT_) hipLaunchKernelGGL((x3m_attn_fwd_kernel<D_, NT_>), grid, dim3(XM_T), 0, s, p)
+#define UNIMM_X3M_FWD(D_, NT_)                                                                                     \
+  do {                                                                                                            \
+    if (p.ks_off != nullptr) hipLaunchKernelGGL((x3m_attn_fwd_kernel<D_, NT_, true>), grid, dim3(XM_T), 0, s, p);  \
+    else hipLaunchKernelGGL((x3m_attn_fwd_kernel<D_, NT_, false>), grid, dim3(XM_T), 0, s, p);                     \
+  } while (0)
     if (a->D == 64) { if (nt <= 4) UNIMM_X3M_FWD(64, 4); else if (nt <= 8) UNIMM_X3M_FWD(64, 8); else UNIMM_X3M_FWD(64, 16); }
     else { if (nt <= 4) UNIMM_X3M_FWD(128, 4); else if (nt <= 8) UNIMM_X3M_FWD(128, 8); else UNIMM_X3M_FWD(128, 16); }
 #undef UNIMM_X3M_FWD

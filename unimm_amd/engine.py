@@ -737,6 +737,44 @@ class Engine:
             self.attn_sink[tag] = probs
         return out, out, lse
 
+    # Inference-only hooks of the shared-context pass (unimm_amd/scoring.py), which launches several attention cores into
+    # disjoint row ranges of ONE context buffer (the S rows, then the P rows with the group's rows spliced into their keys)
+    # and embeds rows chosen by its own plan:
+    #   _ctx_rows(rows, width, device)   an uninitialised context buffer
+    #   _attn_rows(q, k, v, ctx, mask, ..., kshared)   one launch into it, no dropout, no lse
+    #   _ctx_operand(ctx)                what `_post_attn` takes, once every row is written
+    #   _embed_image_rows / _embed_text_rows   -> (fp32 residual stream, its GEMM operand)
+    def _ctx_rows(self, rows, width, device):
+        return torch.empty((rows, width), dtype=BF16, device=device)
+
+    def _attn_rows(self, q, k, v, ctx, mask, B, H, Tq, Tk, D, qvar=None, kvar=None, kshared=None):
+        words, mq, mb = mask
+        L.attn_fwd(q, k, v, ctx, None, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, L.NO_DROP, qvar=qvar, kvar=kvar,
+                   kshared=kshared)
+
+    def _ctx_operand(self, ctx):
+        return ctx
+
+    def _embed_image_rows(self, featd, locd, n):
+        """Image embedding (models/vilbert_dialog.py:1487-1493) of n regions: featd fp32 [n, F], locd fp32 [n, 5]
+        (the fp32x3 engine's override takes the same fp32 inputs)."""
+        Hv, dev = self.cfg.v_hidden_size, featd.device
+        packed = torch.empty((n, self.vemb_k), dtype=BF16, device=dev)
+        L.pack_image(featd, locd, packed, n, self.cfg.v_feature_size, self.vemb_k)
+        prev = torch.empty((n, Hv), dtype=F32, device=dev)
+        L.gemm_nt(packed, self.vemb_w, prev, bias=self.vemb_b, M=n, N=Hv, K=self.vemb_k)
+        return self._layernorm(prev, "emb_v", False)[:2]
+
+    def _embed_text_rows(self, ids32, pos32, typ32, M, rows):
+        """Text embeddings (:326-356) of the M padded rows `rows` (int64 [M]: b * T + t)."""
+        H, dev = self.cfg.hidden_size, ids32.device
+        gmm, bta, _, _ = self.ln["emb_t"]
+        xt = torch.empty((M, H), dtype=BF16, device=dev)
+        xt32 = torch.empty((M, H), dtype=F32, device=dev)
+        L.embed_fwd(ids32, pos32, typ32, self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"], gmm, bta, xt32, xt, M, H,
+                    self.cfg.type_vocab_size, rows=rows)
+        return xt32, xt
+
     def _qkv_grad(self, qkv):
         return torch.empty_like(qkv)
 

@@ -206,6 +206,39 @@ class EngineX3(Engine):
             self.attn_sink[tag] = probs
         return out, out3, lse
 
+    # the shared-context pass's inference hooks (unimm_amd/engine.py) on fp32 rows and split operands
+    def _ctx_rows(self, rows, width, device):
+        """-> (context fp32, the same rows as a split operand | None): the two outputs of one attention launch"""
+        out3 = torch.empty((rows, 3 * _rup(width, 64)), dtype=BF16, device=device) if self.attn_planes else None
+        return torch.empty((rows, width), dtype=F32, device=device), out3
+
+    def _attn_rows(self, q, k, v, ctx, mask, B, H, Tq, Tk, D, qvar=None, kvar=None, kshared=None):
+        words, mq, mb = mask
+        L.x3_attn_fwd(q, k, v, ctx[0], None, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, L.NO_DROP, qvar=qvar, kvar=kvar,
+                      out3=ctx[1], kshared=kshared)
+
+    def _ctx_operand(self, ctx):
+        return ctx[1] if ctx[1] is not None else self._split(ctx[0])
+
+    def _embed_image_rows(self, featd, locd, n):
+        """One group-row GEMM over the split of [feat | loc | 0] with the w-type split of [W_feat | W_loc | 0]."""
+        F, Hv, dev = self.cfg.v_feature_size, self.cfg.v_hidden_size, featd.device
+        packed32 = torch.zeros((n, self.vemb_k), dtype=F32, device=dev)
+        packed32[:, :F].copy_(featd)
+        packed32[:, F:F + 5].copy_(locd)
+        prev = torch.empty((n, Hv), dtype=F32, device=dev)
+        L.gemm_nt(self._split(packed32), self.vemb_w3, prev, bias=self.vemb_b, M=n, N=Hv, K=3 * self.vemb_k)
+        return self._ln3(prev, "emb_v", False)[:2]
+
+    def _embed_text_rows(self, ids32, pos32, typ32, M, rows):
+        H, dev = self.cfg.hidden_size, ids32.device
+        gmm, bta, _, _ = self.ln["emb_t"]
+        scratch16 = torch.empty((M, H), dtype=BF16, device=dev)
+        xt32 = torch.empty((M, H), dtype=F32, device=dev)
+        L.embed_fwd(ids32, pos32, typ32, self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"], gmm, bta, xt32, scratch16,
+                    M, H, self.cfg.type_vocab_size, rows=rows)
+        return xt32, self._split(xt32)
+
     def _qkv_grad(self, qkv):
         """Gradient buffer of a fused projection output qkv (fp32 [rows, N], N % 64 == 0): with the matrix attention kernels a
         split operand [rows, 3 N] whose planes the attention backward fills directly, otherwise fp32 (split afterwards)."""

@@ -970,9 +970,10 @@ class X3AttnPlanes(C.Structure):
 
 
 def x3_attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP, qvar=None, kvar=None,
-                out3=None):
+                out3=None, kshared=None):
     """unimm_attn_fwd on fp32 q / k / v / out (2-D views, row stride = stride(0)).  out3 (bf16 [rows, 3 cp]): the context also
-    as an x-type split operand."""
+    as an x-type split operand.  kshared: (offsets, lengths, ins) as in `attn_fwd` (needs kvar, inference only, the
+    matrix-instruction kernels)."""
     _dev(q, k, v, out, lse, mask, out3)
     pl = None
     if out3 is not None:
@@ -981,6 +982,8 @@ def x3_attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, 
     a = AttnArgs()
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
     a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
+    if kshared is not None:
+        a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
     _check(lib().unimm_x3_attn_fwd(C.byref(a), C.byref(pl) if pl is not None else None, _stream()), "unimm_x3_attn_fwd")
 
 

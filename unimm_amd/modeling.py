@@ -303,8 +303,9 @@ class BertForMultiModalPreTraining(nn.Module):
         shared_context (an extension): one group id per sequence -- sequences of a group share image and dialog context and
         differ only in the candidate answer, as the 100 options of a round in val_lm.py:52-121 do (pass the round index).  The
         context rows and the image stream are then computed once per group (unimm_amd/scoring.py); a sequence whose context does
-        not match its group comes back as NaN.  bf16 engine; the fp32x3 engine takes the per-sequence path."""
-        if shared_context is not None and self.compute_dtype == "bf16":
+        not match its group comes back as NaN.  Both engines; on fp32x3 the two schedules differ only by the summation order
+        inside the attention kernels (one unit in the last place of the scores in tests/test_gpu_x3_scoring.py)."""
+        if shared_context is not None:
             from .scoring import sequence_log_likelihood_shared
             return sequence_log_likelihood_shared(self, input_ids, image_feat, image_loc, masked_lm_labels, shared_context,
                                                   average=average, **kw)

@@ -15,8 +15,7 @@ restates it) with L = length incl. candidate + [SEP], n = len(candidate) + 1, c 
 so in EVERY layer the context rows [1, c) and the whole image stream see nothing that depends on the candidate: they are the
 same for the 100 sequences of a round.  This module runs them once per group (S rows: c - 1 text rows + the 37 regions) and
 only the rows that do depend on the candidate -- row 0, the answer rows and the copy rows: 1 + 2 n of ~140 -- per sequence
-(P rows).  All GEMMs / LayerNorms run on one packed row matrix [S_0 | S_1 | ... | P_0 | P_1 | ...] (what follows each
-attention is the engine's `_post_attn`, the heads its `_pooled_heads`); attention is
+(P rows).  All GEMMs / LayerNorms run on one packed row matrix [S_0 | S_1 | ... | P_0 | P_1 | ...]; attention is
 
     text self-attention     S_g x S_g  (all-ones mask)               one launch over the groups
                             P_b x [CLS_b | S_g(b) | answer_b, copy_b]  one launch over the sequences: the group's K / V rows are
@@ -26,12 +25,15 @@ attention is the engine's `_post_attn`, the heads its `_pooled_heads`); attentio
     regions attend text     regions_g x S_g                          (co-attention mask = the context = all of S_g)
     text attends regions    (S_g | P_b) x regions_g(b)               one launch over groups + sequences
 
-Inference only (no tape, no dropout), bf16 engine.  Results equal the per-sequence path up to the summation order inside the
-attention kernels (tests/test_gpu_fullsize.py).  The decoder runs on the copy rows only, as before.
+Inference only (no tape, no dropout), on either engine: the pass is written once against the engine's operand hooks
+(unimm_amd/engine.py: `_proj`, `_post_attn`, `_self_block`, `_lm_head`, `_pooled_heads`, and the inference hooks `_ctx_rows` /
+`_attn_rows` / `_ctx_operand` / `_embed_image_rows` / `_embed_text_rows`), so on the bf16 engine the rows are bf16 tensors and
+on the fp32x3 engine fp32 rows with their split operands (the spliced launch is then unimm_x3_attn_fwd's).  Results equal the
+per-sequence path up to the summation order inside the attention kernels (tests/test_gpu_fullsize.py,
+tests/test_gpu_x3_scoring.py).  The decoder runs on the copy rows only, as before.  The key/value caches (`cache=`) are
+answer generation's and stay with the bf16 engine.
 """
 from __future__ import annotations
-
-import math
 
 import numpy as np
 import torch
@@ -124,8 +126,8 @@ def forward_shared(eng, inp: dict, groups, want_nsp=True, cache=None):
 def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     cfg = eng.cfg
     dev = eng.arena.device
-    if getattr(eng, "compute_dtype", "bf16") != "bf16":
-        raise NotImplementedError("shared-context scoring runs on the bf16 engine")
+    if cache is not None and getattr(eng, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError("the key/value caches of the shared pass are answer generation's, which runs on the bf16 engine")
     if not cfg.with_coattention:
         raise NotImplementedError("shared-context scoring needs the connection layers (with_coattention)")
     eng.refresh_weights()
@@ -133,7 +135,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     B, T = ids.shape
     feat = inp["image_feat"]
     R = feat.shape[1]
-    H, Hv, Hb = cfg.hidden_size, cfg.v_hidden_size, cfg.bi_hidden_size
+    H, Hb = cfg.hidden_size, cfg.bi_hidden_size
     labels = inp.get("masked_lm_labels")
     if labels is None:
         raise ValueError("shared_context scoring needs masked_lm_labels (the copy rows)")
@@ -230,11 +232,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     with eng._img():
         featd = feat_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, F)
         locd = loc_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, 5)
-        packed = torch.empty((G * R, eng.vemb_k), dtype=BF16, device=dev)
-        L.pack_image(featd, locd, packed, G * R, F, eng.vemb_k)
-        prev = torch.empty((G * R, Hv), dtype=F32, device=dev)
-        L.gemm_nt(packed, eng.vemb_w, prev, bias=eng.vemb_b, M=G * R, N=Hv, K=eng.vemb_k)
-        xv32, xv, _, _ = eng._layernorm(prev, "emb_v", False)
+        xv32, xv = eng._embed_image_rows(featd, locd, G * R)
     if im is None:
         im = torch.ones((B, R), dtype=torch.uint8, device=dev)
     imd = im.to(dev, non_blocking=True)
@@ -251,11 +249,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     ids32 = eng._i32(ids.reshape(-1), dev)
     typ32 = eng._i32(tt.reshape(-1), dev) if tt is not None else torch.zeros(B * T, dtype=torch.int32, device=dev)
     pos32 = eng._i32(pp.reshape(-1), dev) if pp is not None else torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-    gmm, bta, _, _ = eng.ln["emb_t"]
-    xt = torch.empty((M, H), dtype=BF16, device=dev)
-    xt32 = torch.empty((M, H), dtype=F32, device=dev)
-    L.embed_fwd(ids32, pos32, typ32, eng.tab["word"], eng.tab["pos"], eng.tab["type"], eng.tab["ext"], gmm, bta, xt32, xt, M, H,
-                cfg.type_vocab_size, rows=rows)
+    xt32, xt = eng._embed_text_rows(ids32, pos32, typ32, M, rows)
 
     heads, D = cfg.num_attention_heads, H // cfg.num_attention_heads
     nh, Db = cfg.bi_num_attention_heads, Hb // cfg.bi_num_attention_heads
@@ -266,28 +260,27 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     it_klen = torch.full_like(it_koff, R)
     it_vwords = vmask[0].view(G, nwv)[it_img.long()].contiguous()                                  # [G + B, nwv]
 
+    # (x32, x) below: an fp32 residual stream and its copy as the engine's GEMM operand, as in `Engine._self_block`
     def text_block(key, x32, x):
         """BertLayer (models/vilbert_dialog.py:385-483) on the packed rows, inference."""
         qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
-        qkv = eng._linear(x, qkv_l)
+        qkv = eng._proj(x, qkv_l)
         if cache is not None:
             cache[key] = qkv
         q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
-        ctx = torch.empty((M, H), dtype=BF16, device=dev)
-        sc = 1.0 / math.sqrt(D)
-        L.attn_fwd(q, k, v, ctx, None, ones_t, G, heads, T, T, D, sc, 0, nw, NO, qvar=(s_off, s_len), kvar=(s_off, s_len))
-        L.attn_fwd(q, k, v, ctx, None, pwords, B, heads, 32, T, D, sc, nw, 32 * nw, NO, qvar=(p_off, p_len, None, p_ord),
-                   kvar=(p_off, p_len), kshared=(ks_off, ks_len, 1))
-        return eng._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
+        ctx = eng._ctx_rows(M, H, dev)
+        eng._attn_rows(q, k, v, ctx, (ones_t, 0, nw), G, heads, T, T, D, qvar=(s_off, s_len), kvar=(s_off, s_len))
+        eng._attn_rows(q, k, v, ctx, (pwords, nw, 32 * nw), B, heads, 32, T, D, qvar=(p_off, p_len, None, p_ord),
+                       kvar=(p_off, p_len), kshared=(ks_off, ks_len, 1))
+        return eng._post_attn(eng._ctx_operand(ctx), x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
 
     def conn_block(key, xv32, xv, xt32, xt):
         """BertConnectionLayer (models/vilbert_dialog.py:655-783), inference: the image half once per group."""
         lq1, lq2, d1, d2 = (eng.lin[key + s] for s in (".qkv1", ".qkv2", ".d1", ".d2"))
         vff1, vff2, tff1, tff2 = (eng.lin[key + s] for s in (".vff1", ".vff2", ".tff1", ".tff2"))
-        sc = 1.0 / math.sqrt(Db)
         with eng._img():
-            qkv1 = eng._linear(xv, lq1)
-        qkv2 = eng._linear(xt, lq2)
+            qkv1 = eng._proj(xv, lq1)
+        qkv2 = eng._proj(xt, lq2)
         eng._to_txt(qkv1)
         eng._to_img(qkv2)
         if cache is not None:
@@ -295,14 +288,14 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
         q1, k1, v1 = qkv1[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:]
         q2, k2, v2 = qkv2[:, :Hb], qkv2[:, Hb:2 * Hb], qkv2[:, 2 * Hb:]
         with eng._img():
-            ctx_v = torch.empty((G * R, Hb), dtype=BF16, device=dev)
+            ctx_v = eng._ctx_rows(G * R, Hb, dev)
             # regions attend text (:701-721): the co-attention mask is 1 on the context [1, c) = all of S_g
-            L.attn_fwd(q1, k2, v2, ctx_v, None, ones_t, G, nh, R, T, Db, sc, 0, nw, NO, kvar=(s_off, s_len))
-            ov32, ov, _ = eng._post_attn(ctx_v, xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", NO, NO, False)
-        ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
+            eng._attn_rows(q1, k2, v2, ctx_v, (ones_t, 0, nw), G, nh, R, T, Db, kvar=(s_off, s_len))
+            ov32, ov, _ = eng._post_attn(eng._ctx_operand(ctx_v), xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", NO, NO, False)
+        ctx_t = eng._ctx_rows(M, Hb, dev)
         # text attends regions (:681-698): every packed text block against its group's regions
-        L.attn_fwd(q2, k1, v1, ctx_t, None, it_vwords, G + B, nh, T, R, Db, sc, 0, nwv, NO, qvar=(it_off, it_len), kvar=(it_koff, it_klen))
-        ot32, ot, _ = eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)
+        eng._attn_rows(q2, k1, v1, ctx_t, (it_vwords, 0, nwv), G + B, nh, T, R, Db, qvar=(it_off, it_len), kvar=(it_koff, it_klen))
+        ot32, ot, _ = eng._post_attn(eng._ctx_operand(ctx_t), xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)
         return ov32, ov, ot32, ot
 
     # ---- encoder (schedule of models/vilbert_dialog.py:842-929) ---------------------------------------------------------
@@ -330,8 +323,8 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     lm_pos = _i64(plan.lm_pos, dev)
     lab_sel = lab_d.reshape(-1)[lm_pos].to(torch.int32)
     w_sel = torch.ones(n, dtype=torch.int32, device=dev)
-    xs = torch.empty((n, H), dtype=BF16, device=dev)
-    L.gather_rows(xt, lm_idx, xs, n, H)
+    xs = torch.empty((n, xt.shape[1]), dtype=BF16, device=dev)             # rows of the GEMM operand: H, or the split's 3 H, bf16 words
+    L.gather_rows(xt, lm_idx, xs, n, xt.shape[1])
     lm = eng._lm_head(xs, n, lab_sel, w_sel, False)
     out["rownll"] = lm["rownll"]
     if cache is not None:
