@@ -255,7 +255,8 @@ def test_gemm_tn_grouped_matches_single_launches():
     shapes = [(9000, 768, 768, True), (9000, 2304, 768, True), (4133, 1024, 1024, False), (9000, 768, 3072, False),
               (500, 200, 136, True), (37 * 7, 1601, 1024, True), (240, 2, 768, False), (5000, 512, 256, False),
               (4096, 256, 512, True), (7777, 320, 264, False), (6000, 1024, 768, True), (4100, 768, 1024, False),
-              (8192, 3072, 768, True), (64, 64, 64, False)]            # 14 > 12: the big class needs two launches
+              (8192, 3072, 768, True), (64, 64, 64, False)]            # both tile classes in one call (the cut at 48 problems per launch:
+                                                                        # tests/test_gpu_gemm_tn_edges.py section C)
     probs, refs = [], []
     for (M, N, K, wb) in shapes:
         dy = torch.zeros((M, (N + 7) // 8 * 8), device="cuda", dtype=torch.bfloat16)

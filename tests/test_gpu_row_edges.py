@@ -30,6 +30,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import gemm_tn_ref as GT
 from oracle import rows_ref as RR
 
 pytestmark = pytest.mark.gpu
@@ -432,18 +433,8 @@ def test_layernorm_bwd_partials_device_count(count):
 # ----------------------------------------------------------------------------------------------
 def tn_rows_per_split(M, N, K):
     """The split heuristic of launch_tn_group (csrc/gemm.hip) for one problem alone on the chip: the row ranges whose
-    edges a device count must be tested at."""
-    big = N >= 256 and K >= 256 and M >= 1024
-    tb, slots = (256, 256) if big else (128, 512)
-    tiles = -(-N // tb) * -(-K // tb)
-    max_s = min(max(M // 1024, 1), 32)
-    splits, best = 1, 1e30
-    for sp in range(1, max_s + 1):
-        cost = -(-(tiles * sp) // slots) * (M / 64 / sp + 8.0)
-        if cost < best * 0.98:
-            best, splits = cost, sp
-    rps = -(-M // splits)                                          # ceil(M / splits), rounded up to whole 64-row steps
-    return -(-rps // 64) * 64
+    edges a device count must be tested at (oracle/gemm_tn_ref.py restates the launcher's rules)."""
+    return GT.single_rows_per_split(M, N, K)
 
 
 TN_FORMS = {"pp": (4096, 384, 320), "small": (3000, 200, 136)}     # gemm_tn_pp_kernel / gemm_tn_kernel<2,2,4>

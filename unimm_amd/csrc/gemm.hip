@@ -846,6 +846,16 @@ int launch_tn_group(const unimm_gemm_tn_args* const* a, int count, bool big, boo
     g.pr[i].rows_per_split = ((rps + TK - 1) / TK) * TK;
     g.pr[i].nsplit = (g.pr[i].M + g.pr[i].rows_per_split - 1) / g.pr[i].rows_per_split;
   }
+  // The ping-pong loop reaches a split's rows through buffer descriptors and per-lane / per-step byte offsets of 32 bits
+  // (gemm_tn_pp_kernel: num_records = rows * ld * 2): a split whose rows span 4 GiB of either operand would wrap them and
+  // read that operand as zeros, so a launch that holds such a problem takes the lock-step loop (size_t math in stage_one_tn).
+  // Same guard as launch_nt's for configuration 8.
+  if (big && !legacy_loop) {
+    for (int i = 0; i < count; ++i) {
+      const size_t ld = (size_t)(g.pr[i].lddy > g.pr[i].ldx ? g.pr[i].lddy : g.pr[i].ldx);
+      if ((size_t)g.pr[i].rows_per_split * ld * 2 >= ((size_t)1 << 32)) legacy_loop = true;
+    }
+  }
   // workspace layout: [counters: one int per tile in a FIXED 16 KiB region: launches with different tile counts share
   // the workspace, and the slabs of one must never cover the (zero-between-launches) counters of another]
   // [slabs: tiles x splits partial tiles of tb x tb floats]

@@ -224,7 +224,7 @@ def gemm_tn(dy, x, dw, M=None, N=None, K=None, dbias=None, m_dev=None):
 
 def gemm_tn_grouped(problems, shared=None, ws=None):
     """problems: list of (dy, x, dw, M, N, K, dbias[, m_dev[, overwrite]]) -- every dw[N,K] += dy[:M,:N]^T @ x[:M,:K] in as few
-    launches as possible (one per <= 12 problems of the same tile class).  overwrite: dw is known to be zero and has no other
+    launches as possible (one per <= 48 problems of the same tile class: csrc/gemm.hip TN_MAXG).  overwrite: dw is known to be zero and has no other
     contributor -> plain stores instead of atomics (unimm_gemm_tn_args.overwrite).
     shared: the launches run beside another stream's kernels (split heuristic hint; None = the process-wide default).
     ws: zero-initialised uint8 device tensor private to the launch stream (partial-tile slabs + arrival counters);
