@@ -232,14 +232,15 @@ def _call(model, b):
         next_sentence_label=b["next_sentence_label"], nsp_weight=b["nsp_weight"], lm_weight=b["lm_weight"], _want_lm_scores=False)
 
 
-@pytest.mark.parametrize("executor", ["eager", "graphs"])
-def test_two_forwards_before_one_backward(golden_dir, executor):
+@pytest.mark.parametrize("executor, compute", [pytest.param("eager", "bf16", id="eager"), pytest.param("graphs", "bf16", id="graphs"),
+                                               pytest.param("eager", "fp32x3", id="eager-fp32x3")])
+def test_two_forwards_before_one_backward(golden_dir, executor, compute):
     """`loss = model(b1) + model(b2); loss.backward()` (and an eval forward between a step's forward and its backward): each
     backward must read ITS step's row counts, loss denominators, activations and dropout salt.  Eagerly the row counts live in
     per-forward device words; under the graph executor an entry whose forward has not been back-propagated yet is not replayed
-    again (the second forward runs eagerly)."""
+    again (the second forward runs eagerly).  Both engines eagerly: the step's backward is one definition (Engine._backward)."""
     from unimm_amd import synth
-    ref, m = _build(golden_dir), _build(golden_dir)
+    ref, m = _build(golden_dir, compute), _build(golden_dir, compute)
     cfg = ref.config
     b1 = synth.make_batch(n_seq=12, T=64, R=37, cfg=cfg, seed=5, device="cuda")
     b2 = synth.make_batch(n_seq=12, T=64, R=37, cfg=cfg, seed=9, device="cuda")     # same shapes, other lengths / label counts

@@ -40,6 +40,11 @@ def _rup(x, m):
     return (x + m - 1) // m * m
 
 
+def _rows16(x):
+    """-> (x as rows of 16-bit elements, their number per row): the row-moving kernels take fp32 rows as 2 H such elements"""
+    return (x.view(BF16), 2 * x.shape[1]) if x.dtype == F32 else (x, x.shape[1])
+
+
 # inputs that `stage_host_inputs` moves to the device (nsp_weight stays on the host: it is read there)
 _STAGED_KEYS = ("input_ids", "token_type_ids", "position_ids", "masked_lm_labels", "lm_weight", "next_sentence_label", "image_label",
                 "image_attention_mask", "attention_mask", "co_attention_mask", "image_loc", "image_feat", "image_target", "image_index")
@@ -404,15 +409,18 @@ class Engine:
             return None
         if K < 2048 or N > 1024 or ((M + 127) // 128) * ((N + 127) // 128) > 256:
             return None
+        return 1, 2, self._splitk_workspace()
+
+    def _splitk_workspace(self):
+        """The split-K workspace (slabs + zero-between-launches tickets) is private to launches of ONE stream: keyed by the
+        stream the launch goes to (the caller's stream in eager steps, the capturing stream under graph capture), so a
+        text-side GEMM issued from another stream can never share tickets with one in flight."""
         dev = self.arena.flat.device
-        # The workspace (slabs + zero-between-launches tickets) is private to launches of ONE stream: key it by the stream the
-        # launch goes to (the caller's stream in eager steps, the capturing stream under graph capture), so a text-side GEMM
-        # issued from another stream can never share tickets with one in flight
         key = int(torch.cuda.current_stream(dev).cuda_stream)
         ws = self._splitk_ws.get(key)
         if ws is None:
             ws = self._splitk_ws[key] = torch.zeros(self.splitk_ws_bytes, dtype=torch.uint8, device=dev)
-        return 1, 2, ws
+        return ws
 
     def _linear32(self, x, key, relu=False, out=None):
         """y = act(x W^T + b) in fp32 from the fp32 master weights (poolers, NSP head; models/vilbert_dialog.py:946-967, :1070)."""
@@ -713,8 +721,10 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # blocks
     # ------------------------------------------------------------------------------------------
-    # What a compute mode overrides -- these hooks, `_post_attn` and `_transform_head`; the blocks below, their stream
-    # brackets, dropout sites and tape entries are written once, against them:
+    # What a compute mode overrides -- these hooks, `_post_attn`, `_transform_head`, the two embeddings (`_embed_image`,
+    # `_embed_text`) and the hooks of the heads' backward (listed above `_transform_head_bwd`); the blocks below and the step
+    # around them (`_forward`, `_backward`), their stream brackets, dropout sites and tape entries are written once, against
+    # them:
     #   _proj(x, lin)            the fused QKV projection of a block input (x: the GEMM operand of the residual stream)
     #   _attn(...)               -> (ctx, ctx_op, lse): ctx is what the attention backward reads as `out`, ctx_op the operand
     #                            handed to `_post_attn`
@@ -743,7 +753,7 @@ class Engine:
     #   _ctx_rows(rows, width, device)   an uninitialised context buffer
     #   _attn_rows(q, k, v, ctx, mask, ..., kshared)   one launch into it, no dropout, no lse
     #   _ctx_operand(ctx)                what `_post_attn` takes, once every row is written
-    #   _embed_image_rows / _embed_text_rows   -> (fp32 residual stream, its GEMM operand)
+    #   _embed_image / _embed_text       the step's embeddings, without dropout and without a backward
     def _ctx_rows(self, rows, width, device):
         return torch.empty((rows, width), dtype=BF16, device=device)
 
@@ -755,25 +765,54 @@ class Engine:
     def _ctx_operand(self, ctx):
         return ctx
 
-    def _embed_image_rows(self, featd, locd, n):
-        """Image embedding (models/vilbert_dialog.py:1487-1493) of n regions: featd fp32 [n, F], locd fp32 [n, 5]
-        (the fp32x3 engine's override takes the same fp32 inputs)."""
-        Hv, dev = self.cfg.v_hidden_size, featd.device
+    # The two embeddings, for the step and for inference on rows of the caller's choosing (scoring, answer generation call
+    # them with L.NO_DROP, save=False) -> (fp32 residual stream, its GEMM operand, bwd | None):
+    def _embed_image(self, featd, locd, n, drop, save):
+        """Image embedding (models/vilbert_dialog.py:1487-1493) of n regions, featd fp32 [n, F], locd fp32 [n, 5]: one GEMM
+        over [feat | loc | 0] with W_cat = [W_feat | W_loc | 0], then LayerNorm."""
+        F, Hv, dev = self.cfg.v_feature_size, self.cfg.v_hidden_size, featd.device
         packed = torch.empty((n, self.vemb_k), dtype=BF16, device=dev)
-        L.pack_image(featd, locd, packed, n, self.cfg.v_feature_size, self.vemb_k)
+        L.pack_image(featd, locd, packed, n, F, self.vemb_k)
         prev = torch.empty((n, Hv), dtype=F32, device=dev)
         L.gemm_nt(packed, self.vemb_w, prev, bias=self.vemb_b, M=n, N=Hv, K=self.vemb_k)
-        return self._layernorm(prev, "emb_v", False)[:2]
+        xv32, xv, mv, rv = self._layernorm(prev, "emb_v", save, drop=drop)
+        if not save:
+            return xv32, xv, None
+        A, v = self.arena, "bert.v_embeddings."
 
-    def _embed_text_rows(self, ids32, pos32, typ32, M, rows):
-        """Text embeddings (:326-356) of the M padded rows `rows` (int64 [M]: b * T + t)."""
+        def bwd(dxv):
+            dbias = A.grad(v + "image_embeddings.bias")
+            before = dbias.clone()
+            dpre, _ = self._layernorm_bwd(dxv, prev, mv, rv, "emb_v", dbias=dbias, out_drop=drop, defer=False)
+            A.grad(v + "image_location_embeddings.bias").add_(dbias - before)
+            self._wgrad(dpre, packed, A.grad(v + "image_embeddings.weight"), n, Hv, F, sole=True)
+            self._wgrad(dpre, packed[:, F:], A.grad(v + "image_location_embeddings.weight"), n, Hv, 5, sole=True)
+        return xv32, xv, bwd
+
+    def _embed_text(self, ids32, pos32, typ32, M, rows, drop, save, m_dev):
+        """Text embeddings (:326-356) of M rows; rows (int64 [M]: b * T + t, or None = the first M): the entries of ids32 /
+        pos32 / typ32 they embed; m_dev: device word with the valid rows, when M is a capacity."""
         H, dev = self.cfg.hidden_size, ids32.device
-        gmm, bta, _, _ = self.ln["emb_t"]
         xt = torch.empty((M, H), dtype=BF16, device=dev)
         xt32 = torch.empty((M, H), dtype=F32, device=dev)
-        L.embed_fwd(ids32, pos32, typ32, self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"], gmm, bta, xt32, xt, M, H,
-                    self.cfg.type_vocab_size, rows=rows)
-        return xt32, xt
+        emb = self._embed_text_args(ids32, pos32, typ32)
+        L.embed_fwd(*emb, xt32, xt, M, H, self.cfg.type_vocab_size, drop=drop, m_dev=m_dev, rows=rows)
+        return xt32, xt, (self._embed_text_bwd(L.embed_bwd, emb, M, rows, drop, m_dev) if save else None)
+
+    def _embed_text_args(self, ids32, pos32, typ32):
+        gmm, bta, _, _ = self.ln["emb_t"]
+        return (ids32, pos32, typ32, self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"], gmm, bta)
+
+    def _embed_text_bwd(self, kernel, emb, M, rows, drop, m_dev):
+        """kernel: L.embed_bwd (bf16 gradient rows) or L.embed_bwd_f32"""
+        A, e, H = self.arena, "bert.embeddings.", self.cfg.hidden_size
+        _, _, ggm, gbt = self.ln["emb_t"]
+
+        def bwd(dxt):
+            kernel(*emb, dxt, A.grad(e + "word_embeddings.weight"), A.grad(e + "position_embeddings.weight"),
+                   A.grad(e + "token_type_embeddings.weight"), A.grad(e + "token_type_embeddings_extension.weight"), ggm, gbt,
+                   self.part[H], M, H, self.cfg.type_vocab_size, drop=drop, m_dev=m_dev, rows=rows)
+        return bwd
 
     def _qkv_grad(self, qkv):
         return torch.empty_like(qkv)
@@ -999,15 +1038,22 @@ class Engine:
         tmask = self._pack_mask(am, dev, T)
         comask = self._pack_mask(cm, dev, R)
         self._dev_masks = []
+        return self._plan_header(inp, B, T, R, tmask, comask, dev)[0].tolist()
+
+    def _plan_header(self, inp, B, T, R, tmask, comask, dev, need=True):
+        """Conversions of the inputs the plan reads + unimm_plan_lengths -> (header | None, lab32, w32, nw_dev, il32).  Without
+        `need` the header is computed only when the NSP class weights live on the device or regions are to be counted."""
         labels, weights = inp.get("masked_lm_labels"), inp.get("lm_weight")
         lab32 = self._i32(labels.reshape(B, T), dev) if labels is not None else None
         w32 = self._i32(weights.reshape(B, T), dev) if (weights is not None and labels is not None) else None
-        il = inp.get("image_label")
-        il32 = self._i32(il.reshape(B, R), dev) if (il is not None and inp.get("image_target") is not None) else None
         nw_in = inp.get("nsp_weight")
         nw_dev = nw_in.reshape(-1)[:2].to(F32).contiguous() if (torch.is_tensor(nw_in) and nw_in.is_cuda) else None
-        header = L.plan_lengths(tmask, comask, R, lab32, w32, nw_dev, B, T, image_label=il32)
-        return header.tolist()
+        il = inp.get("image_label")
+        il32 = self._i32(il.reshape(B, R), dev) if (il is not None and inp.get("image_target") is not None) else None
+        header = None
+        if need or nw_dev is not None or il32 is not None:
+            header = L.plan_lengths(tmask, comask, R, lab32, w32, nw_dev, B, T, image_label=il32)
+        return header, lab32, w32, nw_dev, il32
 
     def forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
         return self._on_text_stream(self._forward, inp, train, save, lm_rows, want_pred_v)
@@ -1094,18 +1140,12 @@ class Engine:
         pos = inp.get("position_ids")
         pos32 = self._i32(pos.reshape(-1), dev) if pos is not None else \
             torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-        labels, weights = inp.get("masked_lm_labels"), inp.get("lm_weight")
+        labels = inp.get("masked_lm_labels")
         want_sel = lm_rows == "labelled" and labels is not None
-        lab32 = self._i32(labels.reshape(B, T), dev) if labels is not None else None
-        w32 = self._i32(weights.reshape(B, T), dev) if (weights is not None and labels is not None) else None
-        nw_in = inp.get("nsp_weight")
-        nw_dev = nw_in.reshape(-1)[:2].to(F32).contiguous() if (torch.is_tensor(nw_in) and nw_in.is_cuda) else None
-        il = inp.get("image_label")
-        il32 = self._i32(il.reshape(B, R), dev) if (il is not None and inp.get("image_target") is not None) else None
+        header, lab32, w32, nw_dev, il32 = self._plan_header(inp, B, T, R, tmask, comask, dev, need=self.unpad or want_sel)
         plan, sel, n_img = None, None, None
         dyn = None
-        if self.unpad or want_sel or nw_dev is not None or il32 is not None:
-            header = L.plan_lengths(tmask, comask, R, lab32, w32, nw_dev, B, T, image_label=il32)
+        if header is not None:
             # the step's one host sync (the graph executor has read the same header in its pre-pass and injects the values:
             # a captured launch sequence cannot synchronise)
             hh = self._inject_header if self._inject_header is not None else header.tolist()
@@ -1194,14 +1234,12 @@ class Engine:
         self.refresh_weights()
         B, T, R, img_idx = self._batch_dims(inp, dev)
         feat = inp["image_feat"]
-        H, Hv = cfg.hidden_size, cfg.v_hidden_size
         st = dict(train=train, tape=[] if save else None)
         tape = st["tape"]
 
         tmask, vmask, comask = self._prep_masks(inp, B, T, R, dev)
         # ---- image embedding first: it does not depend on the plan, so the image stream already has work while the
         # host waits for the header below (models/vilbert_dialog.py:360-383)
-        A = self.arena
         F = cfg.v_feature_size
         self._to_img()                        # masks are packed (and the previous step is behind us): the image side may start
         with self._img():                     # image embedding: beside the first text layers
@@ -1210,22 +1248,7 @@ class Engine:
             if img_idx is not None:             # one entry per image on the wire, expanded on the device (train.py:413-432)
                 featd, locd = featd.index_select(0, img_idx), locd.index_select(0, img_idx)
             featd, locd = featd.contiguous().view(B * R, F), locd.contiguous().view(B * R, 5)
-            packed = torch.empty((B * R, self.vemb_k), dtype=BF16, device=dev)
-            L.pack_image(featd, locd, packed, B * R, F, self.vemb_k)
-            prev = torch.empty((B * R, Hv), dtype=F32, device=dev)
-            L.gemm_nt(packed, self.vemb_w, prev, bias=self.vemb_b, M=B * R, N=Hv, K=self.vemb_k)
-            d_embv = self._drop("emb_v", cfg.hidden_dropout_prob, train)
-            xv32, xv, mv, rv = self._layernorm(prev, "emb_v", save, drop=d_embv)
-            if save:
-                v = "bert.v_embeddings."
-
-                def bwd_embv(dxv):
-                    dbias = A.grad(v + "image_embeddings.bias")
-                    before = dbias.clone()
-                    dpre, _ = self._layernorm_bwd(dxv, prev, mv, rv, "emb_v", dbias=dbias, out_drop=d_embv, defer=False)
-                    A.grad(v + "image_location_embeddings.bias").add_(dbias - before)
-                    self._wgrad(dpre, packed, A.grad(v + "image_embeddings.weight"), B * R, Hv, F, sole=True)
-                    self._wgrad(dpre, packed[:, F:], A.grad(v + "image_location_embeddings.weight"), B * R, Hv, 5, sole=True)
+            xv32, xv, bwd_embv = self._embed_image(featd, locd, B * R, self._drop("emb_v", cfg.hidden_dropout_prob, train), save)
 
         pl = self._prep_plan(inp, B, T, R, tmask, comask, lm_rows, dev)
         ids32, typ32, pos32, labels = pl["ids32"], pl["typ32"], pl["pos32"], pl["labels"]
@@ -1233,20 +1256,8 @@ class Engine:
         # ---- embeddings --------------------------------------------------------------------------
         erows = plan["rows"] if plan is not None else None      # packed row -> padded row (the kernels gather through it)
         emd = plan["var"][2] if plan is not None else None
-        gmm, bta, ggm, gbt = self.ln["emb_t"]
-        d_embt = self._drop("emb_t", cfg.hidden_dropout_prob, train)
-        xt = torch.empty((Mt, H), dtype=BF16, device=dev)
-        xt32 = torch.empty((Mt, H), dtype=F32, device=dev)
-        tabs = (self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"])
-        L.embed_fwd(ids32, pos32, typ32, *tabs, gmm, bta, xt32, xt, Mt, H, cfg.type_vocab_size, drop=d_embt, m_dev=emd, rows=erows)
-        A = self.arena
-        e = "bert.embeddings."
-        if save:
-            def bwd_embt(dxt):
-                L.embed_bwd(ids32, pos32, typ32, *tabs, gmm, bta, dxt, A.grad(e + "word_embeddings.weight"),
-                            A.grad(e + "position_embeddings.weight"), A.grad(e + "token_type_embeddings.weight"),
-                            A.grad(e + "token_type_embeddings_extension.weight"), ggm, gbt, self.part[H], Mt, H,
-                            cfg.type_vocab_size, drop=d_embt, m_dev=emd, rows=erows)
+        xt32, xt, bwd_embt = self._embed_text(ids32, pos32, typ32, Mt, erows, self._drop("emb_t", cfg.hidden_dropout_prob, train),
+                                              save, emd)
 
         # ---- encoder (schedule of models/vilbert_dialog.py:842-929) ------------------------------
         # Two streams: the image stream (embedding, image layers, the image half of every connection layer) and the
@@ -1298,7 +1309,7 @@ class Engine:
                 tv, uvh, hvn, mh, rh, pred_v = self._transform_head(xv, self.lin["imgtr"], "imgtr", self.lin["imgdec"],
                                                                     _rup(C, 4), save)
             pred_v_out = pred_v.view(B, R, -1)[:, :, :C]
-            img = dict(tv=tv, u=uvh, hn=hvn, mean=mh, rstd=rh, pred=pred_v)
+            img = dict(t1=tv, u=uvh, hn=hvn, mean=mh, rstd=rh, pred=pred_v)
         self._to_txt(xv32, xv, img["pred"] if img is not None else None)                # the heads read both streams
         seq_t, seq_v = xt, xv
 
@@ -1316,13 +1327,13 @@ class Engine:
         # ---- MLM head: transform + tied decoder on the selected rows (:982-986, :1023-1026) -------
         V = cfg.vocab_size
         Vp = _rup(V, 64)
-        lmtr, dec = self.lin["lmtr"], self.lin["dec"]
         lm = None
         if lm_rows == "labelled" and labels is not None:
             n = sel["n"]                                          # rows chosen by the plan kernels at the start of forward (a capacity)
             if n > 0:
-                xs = torch.empty((n, H), dtype=BF16, device=dev)
-                L.gather_rows(seq_t, sel["idx"], xs, n, H, n_dev=dyn["n_lm"])
+                W = seq_t.shape[1]                                # the operand's own width: split rows move as 3 H 16-bit elements
+                xs = torch.empty((n, W), dtype=BF16, device=dev)
+                L.gather_rows(seq_t, sel["idx"], xs, n, W, n_dev=dyn["n_lm"])
                 lm = self._lm_head(xs, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"])
                 lm.update(idx=sel["idx"], pos_idx=sel["pos"], n=n, n_dev=dyn["n_lm"], inv_dev=dyn["inv_lm"])
             out["lm"] = lm
@@ -1342,10 +1353,9 @@ class Engine:
         full = torch.zeros((out["B"] * out["T"], x.shape[1]), dtype=x.dtype, device=x.device)
         if "rows32" not in plan:
             plan["rows32"] = plan["rows"].to(torch.int32)
-        w = 2 if x.dtype == F32 else 1                  # fp32 rows move as 2 H 16-bit elements
+        src, w = _rows16(x)
         # the row dimension of x is a capacity: only the step's real rows are scattered (device-side count)
-        L.gather_rows(x.view(BF16) if w == 2 else x, plan["rows32"], full.view(BF16) if w == 2 else full, x.shape[0],
-                      w * x.shape[1], scatter=True, n_dev=plan["var"][2])
+        L.gather_rows(src, plan["rows32"], _rows16(full)[0], x.shape[0], w, scatter=True, n_dev=plan["var"][2])
         return full
 
     def _transform_head(self, x, tr, ln_key, dec, ldo, save, M=None):
@@ -1370,6 +1380,52 @@ class Engine:
     def decode_rows(self, x, n):
         """MLM transform + decoder for n rows of the GEMM operand x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
         return self._transform_head(x, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(self.cfg.vocab_size, 64), False, M=n)[5]
+
+    # The heads' backward, like the blocks, is written once (`_backward`) against what a compute mode overrides:
+    #   grad_dtype               element type of the gradient of the residual streams
+    #   _lm_loss_grad / _img_loss_grad   the loss gradient w.r.t. a head's output, as the operand of its decoder's backward
+    #   _transform_head_bwd      the mirror of `_transform_head`
+    #   _rows_add                fp32 rows added onto rows of a gradient stream (the poolers' input gradients)
+    grad_dtype = BF16
+
+    def _gvec(self, g):
+        """A loss's incoming gradient as an fp32 [1] device tensor (None: the loss does not take part)."""
+        dev = self.arena.device
+        return torch.zeros(1, dtype=F32, device=dev) if g is None else g.detach().to(F32).reshape(1).contiguous()
+
+    def _lm_loss_grad(self, lm, g_lm):
+        n, V = lm["n"], self.cfg.vocab_size          # n is a capacity: the real count lives on the device (n_dev)
+        dlog = torch.empty((n, _rup(V, 64)), dtype=BF16, device=self.arena.device)
+        L.lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], self._gvec(g_lm), 1.0 / n, dlog, n, V,
+                      n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
+        return dlog
+
+    def _img_loss_grad(self, img, gimg, rows):
+        C = self.cfg.v_target_size
+        dpred = torch.empty((rows, self.lin["imgdec"].wt.shape[1]), dtype=BF16, device=self.arena.device)
+        if self.cfg.predict_feature:
+            L.mse_loss_bwd(img["pred"], img["target"], img["label"], gimg, img["inv"], dpred, rows, C)
+        else:
+            L.kl_loss_bwd(img["pred"], img["target"], img["label"], img["lse"], gimg, img["inv"], dpred, rows, C,
+                          inv_dev=img.get("inv_dev"))
+        return dpred
+
+    def _transform_head_bwd(self, dout, hs, x, tr, ln_key, dec, M=None, N=None, m_dev=None):
+        """dout: the loss gradient w.r.t. the head's output (M rows, N valid columns); hs: what `_transform_head` returned, by
+        name (t1, u, hn, mean, rstd); x: the head's input operand.  Accumulates the head's parameter gradients -> dx."""
+        M = dout.shape[0] if M is None else M
+        if dec is self.lin["dec"] and M <= self.skinny_dx_rows:      # dE += dlog^T hn ; dbias ; dhn = dlog @ E
+            self._linear_bwd(dout, hs["hn"], dec, M=M, N=N, m_dev=m_dev, need_dx=False)
+            dhn = self._decoder_dx(dout, dec, M, N)
+        else:
+            dhn = self._linear_bwd(dout, hs["hn"], dec, M=M, N=N, m_dev=m_dev)
+        dt, _ = self._layernorm_bwd(dhn, hs["t1"], hs["mean"], hs["rstd"], ln_key, m_dev=m_dev)
+        du = torch.empty_like(dt)
+        L.gelu_bwd(dt, hs["u"], du, du.numel())
+        return self._linear_bwd(du, x, tr, m_dev=m_dev)
+
+    def _rows_add(self, dst, idx, src, n):
+        L.rows_add_f32(dst, idx, src, n, src.shape[1])
 
     # ------------------------------------------------------------------------------------------
     # losses + backward
@@ -1430,9 +1486,7 @@ class Engine:
         cfg = self.cfg
         dev = self.arena.device
         bw = out["bwd"]
-        B, T, R = out["B"], out["T"], out["R"]
-        H, Hv = cfg.hidden_size, cfg.v_hidden_size
-        seq_t, seq_v = out["seq_out_t"], out["seq_out_v"]
+        B, R = out["B"], out["R"]
         self.arena.attach_grads()
         self._bwd_fresh = bool(self.arena.fresh)   # gradients known to be zero: sole contributors may write instead of add (_wgrad)
         self._reported = set()                     # gradient buckets reported done in this pass (_bucket_done)
@@ -1442,68 +1496,41 @@ class Engine:
                                "`model.engine.arena.fresh` (INTEGRATION.md, 'Gradient arena')")
         self._step_rows = out["Mt"]              # the tile rule follows THIS step's rows (another forward may have run since)
 
-        def gvec(g):
-            return torch.zeros(1, dtype=F32, device=dev) if g is None else g.detach().to(F32).reshape(1).contiguous()
-
-        dseq_t = torch.zeros((out["Mt"], H), dtype=BF16, device=dev)
+        dseq_t = torch.zeros((out["Mt"], cfg.hidden_size), dtype=self.grad_dtype, device=dev)
         # ---- image head: on the image stream, beside the MLM head's backward -------------------------
         img = out["img"]
-        C = cfg.v_target_size
-        itr, idec = self.lin["imgtr"], self.lin["imgdec"]
-        Cp = idec.wt.shape[1]
-        gimg = gvec(g_img)
+        gimg = self._gvec(g_img)
         self._to_img(gimg, img["target"], img["lse"], img["label"])
         with self._img_if(self.image_head_side):
-            dpred = torch.empty((B * R, Cp), dtype=BF16, device=dev)
-            if cfg.predict_feature:
-                L.mse_loss_bwd(img["pred"], img["target"], img["label"], gimg, img["inv"], dpred, B * R, C)
-            else:
-                L.kl_loss_bwd(img["pred"], img["target"], img["label"], img["lse"], gimg, img["inv"], dpred, B * R, C,
-                              inv_dev=img.get("inv_dev"))
-            dhn_v = self._linear_bwd(dpred, img["hn"], idec, M=B * R, N=C)
-            dtv, _ = self._layernorm_bwd(dhn_v, img["tv"], img["mean"], img["rstd"], "imgtr")
-            duv = torch.empty_like(dtv)
-            L.gelu_bwd(dtv, img["u"], duv, duv.numel())
-            dseq_v = self._linear_bwd(duv, seq_v, itr)
+            dpred = self._img_loss_grad(img, gimg, B * R)
+            dseq_v = self._transform_head_bwd(dpred, img, out["seq_out_v"], self.lin["imgtr"], "imgtr", self.lin["imgdec"], M=B * R,
+                                              N=cfg.v_target_size)
         # ---- MLM head ---------------------------------------------------------------------------
         lm = out.get("lm")
         if lm is not None:
-            n, V = lm["n"], cfg.vocab_size
-            Vp = _rup(V, 64)
-            lmtr, dec = self.lin["lmtr"], self.lin["dec"]
-            dlog = torch.empty((n, Vp), dtype=BF16, device=dev)
-            nd = lm.get("n_dev")                                              # n is a capacity: the real count lives on the device
-            L.lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], gvec(g_lm), 1.0 / n, dlog, n, V, n_dev=nd,
-                          inv_dev=lm.get("inv_dev"))
-            # dE += dlog^T hn ; dbias ; dhn = dlog @ E
-            if n <= self.skinny_dx_rows:
-                self._linear_bwd(dlog, lm["hn"], dec, M=n, N=V, m_dev=nd, need_dx=False)
-                dhn = self._decoder_dx(dlog, dec, n, V)
-            else:
-                dhn = self._linear_bwd(dlog, lm["hn"], dec, M=n, N=V, m_dev=nd)
-            dt1, _ = self._layernorm_bwd(dhn, lm["t1"], lm["mean"], lm["rstd"], "lmtr", m_dev=nd)
-            du = torch.empty_like(dt1)
-            L.gelu_bwd(dt1, lm["u"], du, du.numel())
-            dxs = self._linear_bwd(du, lm["xs"], lmtr, m_dev=nd)
-            L.gather_rows(dxs, lm["idx"], dseq_t, n, H, scatter=True, n_dev=nd)
+            n, nd = lm["n"], lm.get("n_dev")
+            dxs = self._transform_head_bwd(self._lm_loss_grad(lm, g_lm), lm, lm["xs"], self.lin["lmtr"], "lmtr", self.lin["dec"],
+                                           M=n, N=cfg.vocab_size, m_dev=nd)
+            src, w = _rows16(dxs)
+            L.gather_rows(src, lm["idx"], _rows16(dseq_t)[0], n, w, scatter=True, n_dev=nd)
         # ---- NSP + poolers ------------------------------------------------------------------------
         nlab, w0, w1 = out["nsp_state"]
         dnsp = torch.empty((B, 2), dtype=F32, device=dev)
         extra = None                      # gradient arriving through the returned NSP scores (dense fine-tune ranking loss)
         if g_nsp_scores is not None:
             extra = g_nsp_scores.detach().to(device=dev, dtype=F32).reshape(B, 2).contiguous()
-        L.nsp_loss_bwd(bw["nsp_pad"], nlab, w0, w1, gvec(g_nsp), dnsp, B, extra=extra)
+        L.nsp_loss_bwd(bw["nsp_pad"], nlab, w0, w1, self._gvec(g_nsp), dnsp, B, extra=extra)
         dfused = self._linear32_bwd(dnsp, bw["fused"], "nsp")
         dpt, dpv = torch.empty_like(dfused), torch.empty_like(dfused)
         L.mul_dropout_bwd(bw["pooled_t"], bw["pooled_v"], dfused, dpt, dpv, dfused.numel(), bw["d_fuse"],
                           fusion_sum=cfg.fusion_method == "sum")
         # pooler input gradients land on the first-token rows
         dcls_t = self._linear32_bwd(dpt, bw["cls_t"], "tpool")
-        L.rows_add_f32(dseq_t, bw["cls_idx_t"], dcls_t, B, dcls_t.shape[1])
+        self._rows_add(dseq_t, bw["cls_idx_t"], dcls_t, B)
         dcls_v = self._linear32_bwd(dpv, bw["cls_v"], "vpool")
         self._to_img(dcls_v)                     # the image pooler's input gradient joins the image head's on the image stream
         with self._img_if(self.image_head_side):
-            L.rows_add_f32(dseq_v, bw["cls_idx_v"], dcls_v, B, dcls_v.shape[1])
+            self._rows_add(dseq_v, bw["cls_idx_v"], dcls_v, B)
         self._bucket_done("heads")
         # ---- encoder blocks in reverse -------------------------------------------------------------
         gt, gv = dseq_t, dseq_v

@@ -12,9 +12,12 @@ decoder, the fp32 pooler / NSP heads, the loss kernels and the flat gradient are
 
 The encoder blocks, the MLM head and `decode_rows` are the base engine's own code, not a copy: this class overrides the
 operand hooks they are written against (`_proj`, `_attn`, `_qkv_grad`, `_attn_bwd`, `_proj_bwd`, `_post_attn`,
-`_transform_head`) and keeps its own `_forward` / `_backward` around them.  The base engine's two-stream schedule (image
-side beside the text side), eager launches or the graph executor, no lazy LayerNorm: this is the accuracy mode, ~0.3 of the
-bf16 engine's throughput.  There is no CPU / eager-PyTorch fallback here either."""
+`_transform_head`).  So is the step: `_forward`, `_backward` and `_backward_encoder` exist in the base engine only, written
+against the embedding hooks (`_embed_image`, `_embed_text`) and the hooks of the heads' backward (`grad_dtype`,
+`_lm_loss_grad`, `_img_loss_grad`, `_transform_head_bwd`, `_rows_add`); `_forward` here only refuses the encoder options
+this mode does not run.  The base engine's two-stream schedule (image side beside the text side), eager launches or the
+graph executor, no lazy LayerNorm: this is the accuracy mode, ~0.3 of the bf16 engine's throughput.  There is no CPU /
+eager-PyTorch fallback here either."""
 from __future__ import annotations
 
 import math
@@ -22,7 +25,6 @@ import math
 import torch
 
 from . import lib as L
-from . import params as PM
 from .engine import BF16, F32, Engine, _rup
 
 
@@ -101,12 +103,7 @@ class EngineX3(Engine):
             return None
         t128 = ((M + 127) // 128) * ((N + 127) // 128)
         if K >= 6144 and 2 * t128 <= 512:
-            dev = self.arena.flat.device
-            key = int(torch.cuda.current_stream(dev).cuda_stream)
-            ws = self._splitk_ws.get(key)
-            if ws is None:
-                ws = self._splitk_ws[key] = torch.zeros(self.splitk_ws_bytes, dtype=torch.uint8, device=dev)
-            return 1, (4 if 4 * t128 <= 512 else 2), ws
+            return 1, (4 if 4 * t128 <= 512 else 2), self._splitk_workspace()
         if ((M + 63) // 64) * ((N + 127) // 128) <= 512:
             return 9, 0, None
         return None
@@ -220,24 +217,35 @@ class EngineX3(Engine):
     def _ctx_operand(self, ctx):
         return ctx[1] if ctx[1] is not None else self._split(ctx[0])
 
-    def _embed_image_rows(self, featd, locd, n):
-        """One group-row GEMM over the split of [feat | loc | 0] with the w-type split of [W_feat | W_loc | 0]."""
+    def _embed_image(self, featd, locd, n, drop, save):
+        """One GEMM over the split of [feat | loc | 0] with the w-type split of [W_feat | W_loc | 0], then LayerNorm."""
         F, Hv, dev = self.cfg.v_feature_size, self.cfg.v_hidden_size, featd.device
         packed32 = torch.zeros((n, self.vemb_k), dtype=F32, device=dev)
         packed32[:, :F].copy_(featd)
         packed32[:, F:F + 5].copy_(locd)
+        packed3 = self._split(packed32)
         prev = torch.empty((n, Hv), dtype=F32, device=dev)
-        L.gemm_nt(self._split(packed32), self.vemb_w3, prev, bias=self.vemb_b, M=n, N=Hv, K=3 * self.vemb_k)
-        return self._ln3(prev, "emb_v", False)[:2]
+        L.gemm_nt(packed3, self.vemb_w3, prev, bias=self.vemb_b, M=n, N=Hv, K=3 * self.vemb_k)
+        xv32, xv3, mv, rv = self._ln3(prev, "emb_v", save, drop=drop)
+        if not save:
+            return xv32, xv3, None
+        A, v, K3 = self.arena, "bert.v_embeddings.", self.vemb_k
 
-    def _embed_text_rows(self, ids32, pos32, typ32, M, rows):
+        def bwd(dxv):
+            _, dpre3 = self._ln3_bwd(dxv, prev, mv, rv, "emb_v", dbias=A.grad(v + "image_embeddings.bias"), out_drop=drop,
+                                     want32=False, dbias2=A.grad(v + "image_location_embeddings.bias"))
+            self._wgrad3(dpre3, packed3, A.grad(v + "image_embeddings.weight"), n, Hv, F, Hv, K3)
+            self._wgrad3(dpre3, packed3, A.grad(v + "image_location_embeddings.weight"), n, Hv, 5, Hv, K3, xcol0=F)
+        return xv32, xv3, bwd
+
+    def _embed_text(self, ids32, pos32, typ32, M, rows, drop, save, m_dev):
         H, dev = self.cfg.hidden_size, ids32.device
-        gmm, bta, _, _ = self.ln["emb_t"]
         scratch16 = torch.empty((M, H), dtype=BF16, device=dev)
         xt32 = torch.empty((M, H), dtype=F32, device=dev)
-        L.embed_fwd(ids32, pos32, typ32, self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"], gmm, bta, xt32, scratch16,
-                    M, H, self.cfg.type_vocab_size, rows=rows)
-        return xt32, self._split(xt32)
+        emb = self._embed_text_args(ids32, pos32, typ32)
+        L.embed_fwd(*emb, xt32, scratch16, M, H, self.cfg.type_vocab_size, drop=drop, m_dev=m_dev, rows=rows)
+        del scratch16
+        return xt32, self._split(xt32), (self._embed_text_bwd(L.embed_bwd_f32, emb, M, rows, drop, m_dev) if save else None)
 
     def _qkv_grad(self, qkv):
         """Gradient buffer of a fused projection output qkv (fp32 [rows, N], N % 64 == 0): with the matrix attention kernels a
@@ -290,190 +298,38 @@ class EngineX3(Engine):
         return t, u, hn3, mean, rstd, self._lin3(hn3, dec, ldo=ldo)
 
     # ------------------------------------------------------------------------------------------
-    # forward
+    # the step: the base engine's `_forward` / `_backward`, with fp32 gradient streams and split loss gradients
     # ------------------------------------------------------------------------------------------
+    grad_dtype = F32
+
     def _forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
         cfg = self.cfg
         if cfg.fixed_t_layer or cfg.fixed_v_layer or not cfg.with_coattention:
             raise NotImplementedError("fixed_t_layer / fixed_v_layer / with_coattention=False run on the bf16 engine only")
-        dev = self.arena.device
-        self.refresh_weights()
-        B, T, R, img_idx = self._batch_dims(inp, dev)
-        feat = inp["image_feat"]
-        H, Hv = cfg.hidden_size, cfg.v_hidden_size
-        st = dict(train=train, tape=[] if save else None)
-        tape = st["tape"]
-        tmask, vmask, comask = self._prep_masks(inp, B, T, R, dev)
-        pl = self._prep_plan(inp, B, T, R, tmask, comask, lm_rows, dev)
-        ids32, typ32, pos32, labels = pl["ids32"], pl["typ32"], pl["pos32"], pl["labels"]
-        il32, plan, sel, n_img, dyn, st_nspw, var, Mt = (pl[k] for k in ("il32", "plan", "sel", "n_img", "dyn", "st_nspw", "var", "Mt"))
-        A = self.arena
-        F = cfg.v_feature_size
+        return super()._forward(inp, train, save, lm_rows, want_pred_v)
 
-        # ---- image embedding (models/vilbert_dialog.py:1487-1493): one GEMM over [feat | loc | 0], on the image stream -
-        self._to_img()                        # masks / plan are enqueued (and the previous step is behind us)
-        with self._img():
-            featd = feat.to(dev, dtype=F32, non_blocking=True)
-            locd = inp["image_loc"].to(dev, dtype=F32, non_blocking=True)
-            if img_idx is not None:
-                featd, locd = featd.index_select(0, img_idx), locd.index_select(0, img_idx)
-            packed32 = torch.zeros((B * R, self.vemb_k), dtype=F32, device=dev)
-            packed32[:, :F].copy_(featd.reshape(B * R, F))
-            packed32[:, F:F + 5].copy_(locd.reshape(B * R, 5))
-            packed3 = self._split(packed32)
-            prev = torch.empty((B * R, Hv), dtype=F32, device=dev)
-            L.gemm_nt(packed3, self.vemb_w3, prev, bias=self.vemb_b, M=B * R, N=Hv, K=3 * self.vemb_k)
-            d_embv = self._drop("emb_v", cfg.hidden_dropout_prob, train)
-            xv32, xv3, mv, rv = self._ln3(prev, "emb_v", save, drop=d_embv)
-            if save:
-                v = "bert.v_embeddings."
+    def _lm_loss_grad(self, lm, g_lm):
+        n, dec = lm["n"], self.lin["dec"]
+        dlog3 = torch.empty((n, 3 * dec.Np), dtype=BF16, device=self.arena.device)
+        L.x3_lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], self._gvec(g_lm), 1.0 / n, dlog3, n, self.cfg.vocab_size,
+                         n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
+        return dlog3
 
-                def bwd_embv(dxv):
-                    _, dpre3 = self._ln3_bwd(dxv, prev, mv, rv, "emb_v", dbias=A.grad(v + "image_embeddings.bias"), out_drop=d_embv,
-                                             want32=False, dbias2=A.grad(v + "image_location_embeddings.bias"))
-                    K3 = self.vemb_k
-                    self._wgrad3(dpre3, packed3, A.grad(v + "image_embeddings.weight"), B * R, Hv, F, Hv, K3)
-                    self._wgrad3(dpre3, packed3, A.grad(v + "image_location_embeddings.weight"), B * R, Hv, 5, Hv, K3, xcol0=F)
+    def _img_loss_grad(self, img, gimg, rows):
+        C = self.cfg.v_target_size
+        dpred3 = torch.empty((rows, 3 * self.lin["imgdec"].Np), dtype=BF16, device=self.arena.device)
+        if self.cfg.predict_feature:
+            L.mse_loss_bwd(img["pred"], img["target"], img["label"], gimg, img["inv"], dpred3, rows, C, split=True)
+        else:
+            L.x3_kl_loss_bwd(img["pred"], img["target"], img["label"], img["lse"], gimg, img["inv"], dpred3, rows, C,
+                             inv_dev=img.get("inv_dev"))
+        return dpred3
 
-        # ---- text embeddings (:326-356) --------------------------------------------------------------------------------
-        erows = plan["rows"] if plan is not None else None
-        emd = plan["var"][2] if plan is not None else None
-        gmm, bta, ggm, gbt = self.ln["emb_t"]
-        d_embt = self._drop("emb_t", cfg.hidden_dropout_prob, train)
-        scratch16 = torch.empty((Mt, H), dtype=BF16, device=dev)
-        xt32 = torch.empty((Mt, H), dtype=F32, device=dev)
-        tabs = (self.tab["word"], self.tab["pos"], self.tab["type"], self.tab["ext"])
-        L.embed_fwd(ids32, pos32, typ32, *tabs, gmm, bta, xt32, scratch16, Mt, H, cfg.type_vocab_size, drop=d_embt, m_dev=emd, rows=erows)
-        del scratch16
-        xt3 = self._split(xt32)
-        e = "bert.embeddings."
-        if save:
-            def bwd_embt(dxt):
-                L.embed_bwd_f32(ids32, pos32, typ32, *tabs, gmm, bta, dxt, A.grad(e + "word_embeddings.weight"),
-                                A.grad(e + "position_embeddings.weight"), A.grad(e + "token_type_embeddings.weight"),
-                                A.grad(e + "token_type_embeddings_extension.weight"), ggm, gbt, self.part[H], Mt, H,
-                                cfg.type_vocab_size, drop=d_embt, m_dev=emd, rows=erows)
+    def _transform_head_bwd(self, dout3, hs, x3, tr, ln_key, dec, M=None, N=None, m_dev=None):
+        dhn = self._lin3_bwd(dout3, hs["hn"], dec, M=M, m_dev=m_dev)       # dE += dlog^T hn ; dbias ; dhn = dlog @ E
+        dt, _ = self._ln3_bwd(dhn, hs["t1"], hs["mean"], hs["rstd"], ln_key, m_dev=m_dev, want3=False)
+        du3 = self._op3(dt, op=L.X3_MUL_DGELU, b=hs["u"])[0]
+        return self._lin3_bwd(du3, x3, tr, m_dev=m_dev)
 
-        # ---- encoder (schedule of :842-929) ------------------------------------------------------------------------------
-        for kind, i in PM.encoder_schedule(cfg):
-            if kind == "v":
-                with self._img():
-                    xv32, xv3 = self._self_block(f"v{i}", xv32, xv3, vmask, B, R, cfg.v_num_attention_heads, f"bert.encoder.v_layer.{i}.",
-                                                 cfg.v_attention_probs_dropout_prob, cfg.v_hidden_dropout_prob, st)
-            elif kind == "t":
-                xt32, xt3 = self._self_block(f"t{i}", xt32, xt3, tmask, B, T, cfg.num_attention_heads, f"bert.encoder.layer.{i}.",
-                                             cfg.attention_probs_dropout_prob, cfg.hidden_dropout_prob, st, var=var)
-            else:
-                with self._conn_tag():
-                    xv32, xv3, xt32, xt3 = self._conn_block(f"c{i}", i, xv32, xv3, xt32, xt3, B, R, T, vmask, comask, st, var=var)
-            if save:
-                tape[-1] = (kind, tape[-1][0], tape[-1][1])
-
-        # ---- image head (:1001-1005, :1085-1088) -------------------------------------------------------------------------
-        img = None
-        pred_v_out = None
-        if want_pred_v or inp.get("image_target") is not None:
-            C = cfg.v_target_size
-            with self._img():
-                tv, uvh, hvn3, mh, rh, pred_v = self._transform_head(xv3, self.lin["imgtr"], "imgtr", self.lin["imgdec"],
-                                                                     _rup(C, 4), save)
-            pred_v_out = pred_v.view(B, R, -1)[:, :, :C]
-            img = dict(tv=tv, u=uvh, hn=hvn3, mean=mh, rstd=rh, pred=pred_v)
-        self._to_txt(xv32, xv3, img["pred"] if img is not None else None)       # the heads read both streams
-        out = dict(seq_out_t=xt3, seq_out_v=xv3, seq32_t=xt32, seq32_v=xv32, B=B, T=T, R=R, plan=plan, Mt=Mt,
-                   nsp_weight_host=st_nspw, n_img=n_img, img_label32=il32, dyn=dyn, img=img)
-        if pred_v_out is not None:
-            out["pred_v"] = pred_v_out
-        # ---- poolers + NSP (:946-967, :1064-1070): the base engine's fp32 heads -----------------------------------------
-        cls_idx_t = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
-        cls_idx_v = torch.arange(0, B * R, R, dtype=torch.int32, device=dev)
-        heads = self._pooled_heads(xt32, xv32, cls_idx_t, cls_idx_v, B, train)
-        out["nsp"] = heads["nsp_pad"][:, :2]
-        # ---- MLM head on the selected rows (:982-986, :1023-1026) --------------------------------------------------------
-        V = cfg.vocab_size
-        Vp = _rup(V, 64)
-        lm = None
-        if lm_rows == "labelled" and labels is not None:
-            n = sel["n"]
-            if n > 0:
-                xs3 = torch.empty((n, 3 * H), dtype=BF16, device=dev)
-                L.gather_rows(xt3, sel["idx"], xs3, n, 3 * H, n_dev=dyn["n_lm"])      # split rows move as 3 H 16-bit elements
-                lm = self._lm_head(xs3, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"])
-                lm.update(idx=sel["idx"], pos_idx=sel["pos"], n=n, n_dev=dyn["n_lm"], inv_dev=dyn["inv_lm"])
-            out["lm"] = lm
-        elif lm_rows == "all":
-            out["pred_t"] = self.decode_rows(self.padded(out, xt3), B * T).view(B, T, Vp)[:, :, :V]
-        if save:
-            out["bwd"] = dict(tape=tape, embt=bwd_embt, embv=bwd_embv, **heads)
-        return out
-
-    # ------------------------------------------------------------------------------------------
-    # backward
-    # ------------------------------------------------------------------------------------------
-    def _backward(self, out, g_lm, g_img, g_nsp, g_nsp_scores=None):
-        cfg = self.cfg
-        dev = self.arena.device
-        bw = out["bwd"]
-        B, T, R = out["B"], out["T"], out["R"]
-        H, Hv = cfg.hidden_size, cfg.v_hidden_size
-        self.arena.attach_grads()
-
-        def gvec(g):
-            return torch.zeros(1, dtype=F32, device=dev) if g is None else g.detach().to(F32).reshape(1).contiguous()
-
-        dseq_t = torch.zeros((out["Mt"], H), dtype=F32, device=dev)
-        # ---- image head ---------------------------------------------------------------------------------------------
-        img = out["img"]
-        C = cfg.v_target_size
-        itr, idec = self.lin["imgtr"], self.lin["imgdec"]
-        gimg = gvec(g_img)
-        self._to_img(gimg, img["target"], img["lse"], img["label"])
-        with self._img():                                    # image head: on the image stream, beside the MLM head's backward
-            dpred3 = torch.empty((B * R, 3 * idec.Np), dtype=BF16, device=dev)
-            if cfg.predict_feature:
-                L.mse_loss_bwd(img["pred"], img["target"], img["label"], gimg, img["inv"], dpred3, B * R, C, split=True)
-            else:
-                L.x3_kl_loss_bwd(img["pred"], img["target"], img["label"], img["lse"], gimg, img["inv"], dpred3, B * R, C,
-                                 inv_dev=img.get("inv_dev"))
-            dhn_v = self._lin3_bwd(dpred3, img["hn"], idec)
-            dtv, _ = self._ln3_bwd(dhn_v, img["tv"], img["mean"], img["rstd"], "imgtr", want3=False)
-            duv3 = self._op3(dtv, op=L.X3_MUL_DGELU, b=img["u"])[0]
-            dseq_v = self._lin3_bwd(duv3, out["seq_out_v"], itr)
-        # ---- MLM head -----------------------------------------------------------------------------------------------
-        lm = out.get("lm")
-        if lm is not None:
-            n, V = lm["n"], cfg.vocab_size
-            lmtr, dec = self.lin["lmtr"], self.lin["dec"]
-            nd = lm.get("n_dev")
-            dlog3 = torch.empty((n, 3 * dec.Np), dtype=BF16, device=dev)
-            L.x3_lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], gvec(g_lm), 1.0 / n, dlog3, n, V, n_dev=nd,
-                             inv_dev=lm.get("inv_dev"))
-            dhn = self._lin3_bwd(dlog3, lm["hn"], dec, m_dev=nd)       # dE += dlog^T hn ; dbias ; dhn = dlog @ E
-            dt1, _ = self._ln3_bwd(dhn, lm["t1"], lm["mean"], lm["rstd"], "lmtr", m_dev=nd, want3=False)
-            du3 = self._op3(dt1, op=L.X3_MUL_DGELU, b=lm["u"])[0]
-            dxs = self._lin3_bwd(du3, lm["xs"], lmtr, m_dev=nd)
-            L.gather_rows(dxs.view(BF16), lm["idx"], dseq_t.view(BF16), n, 2 * H, scatter=True, n_dev=nd)
-        # ---- NSP + poolers (fp32 heads of the base engine) ----------------------------------------------------------
-        nlab, w0, w1 = out["nsp_state"]
-        dnsp = torch.empty((B, 2), dtype=F32, device=dev)
-        extra = None
-        if g_nsp_scores is not None:
-            extra = g_nsp_scores.detach().to(device=dev, dtype=F32).reshape(B, 2).contiguous()
-        L.nsp_loss_bwd(bw["nsp_pad"], nlab, w0, w1, gvec(g_nsp), dnsp, B, extra=extra)
-        dfused = self._linear32_bwd(dnsp, bw["fused"], "nsp")
-        dpt, dpv = torch.empty_like(dfused), torch.empty_like(dfused)
-        L.mul_dropout_bwd(bw["pooled_t"], bw["pooled_v"], dfused, dpt, dpv, dfused.numel(), bw["d_fuse"],
-                          fusion_sum=cfg.fusion_method == "sum")
-        dcls_t = self._linear32_bwd(dpt, bw["cls_t"], "tpool")
-        L.x3_rows_add(dseq_t, bw["cls_idx_t"], dcls_t, B, H)
-        dcls_v = self._linear32_bwd(dpv, bw["cls_v"], "vpool")
-        self._to_img(dcls_v)                     # the image pooler's input gradient joins the image head's on the image stream
-        with self._img():
-            L.x3_rows_add(dseq_v, bw["cls_idx_v"], dcls_v, B, Hv)
-        self._bucket_done("heads")
-        # ---- encoder blocks in reverse --------------------------------------------------------------------------------
-        gt, gv = dseq_t, dseq_v
-        entries = list(reversed(bw["tape"]))
-        self._backward_encoder(bw, entries, gt, gv)      # the base engine's block loop and bucket order
-        self._to_txt()                                       # everything joined before the caller continues
-        self._bucket_done("text_embeddings")
+    def _rows_add(self, dst, idx, src, n):
+        L.x3_rows_add(dst, idx, src, n, src.shape[1])

@@ -275,7 +275,6 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     copy_rows = torch.arange(1, M, 2, device=dev, dtype=torch.int32)
     slot_pos = apos.repeat_interleave(beams)
     slot_seg = aseg.repeat_interleave(beams)
-    gmm, bta, _, _ = eng.ln["emb_t"]
     NO = L.NO_DROP
     st = dict(cur=0)
 
@@ -313,10 +312,7 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         ids32 = torch.stack([token, torch.full_like(token, MASK)], 1).reshape(M).to(torch.int32)
         pos32 = torch.stack([slot_pos + (k - 1), slot_pos + k], 1).reshape(M).to(torch.int32)
         typ32 = slot_seg.repeat_interleave(2).to(torch.int32)
-        xt = torch.empty((M, H), dtype=BF16, device=dev)
-        xt32 = torch.empty((M, H), dtype=F32, device=dev)
-        L.embed_fwd(ids32, pos32, typ32, eng.tab["word"], eng.tab["pos"], eng.tab["type"], eng.tab["ext"], gmm, bta, xt32, xt, M, H,
-                    cfg.type_vocab_size)
+        xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, None, NO, False, None)
         for kind, i in sched:
             if kind == "t":
                 xt32, xt = text_block(f"t{i}", xt32, xt)

@@ -27,7 +27,7 @@ only the rows that do depend on the candidate -- row 0, the answer rows and the 
 
 Inference only (no tape, no dropout), on either engine: the pass is written once against the engine's operand hooks
 (unimm_amd/engine.py: `_proj`, `_post_attn`, `_self_block`, `_lm_head`, `_pooled_heads`, and the inference hooks `_ctx_rows` /
-`_attn_rows` / `_ctx_operand` / `_embed_image_rows` / `_embed_text_rows`), so on the bf16 engine the rows are bf16 tensors and
+`_attn_rows` / `_ctx_operand` / `_embed_image` / `_embed_text`), so on the bf16 engine the rows are bf16 tensors and
 on the fp32x3 engine fp32 rows with their split operands (the spliced launch is then unimm_x3_attn_fwd's).  Results equal the
 per-sequence path up to the summation order inside the attention kernels (tests/test_gpu_fullsize.py,
 tests/test_gpu_x3_scoring.py).  The decoder runs on the copy rows only, as before.  The key/value caches (`cache=`) are
@@ -232,7 +232,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     with eng._img():
         featd = feat_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, F)
         locd = loc_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, 5)
-        xv32, xv = eng._embed_image_rows(featd, locd, G * R)
+        xv32, xv, _ = eng._embed_image(featd, locd, G * R, NO, False)
     if im is None:
         im = torch.ones((B, R), dtype=torch.uint8, device=dev)
     imd = im.to(dev, non_blocking=True)
@@ -249,7 +249,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     ids32 = eng._i32(ids.reshape(-1), dev)
     typ32 = eng._i32(tt.reshape(-1), dev) if tt is not None else torch.zeros(B * T, dtype=torch.int32, device=dev)
     pos32 = eng._i32(pp.reshape(-1), dev) if pp is not None else torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-    xt32, xt = eng._embed_text_rows(ids32, pos32, typ32, M, rows)
+    xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, rows, NO, False, None)
 
     heads, D = cfg.num_attention_heads, H // cfg.num_attention_heads
     nh, Db = cfg.bi_num_attention_heads, Hb // cfg.bi_num_attention_heads
