@@ -595,7 +595,7 @@ int unimm_x3_attn_bwd(const unimm_attn_bwd_args* args, const unimm_x3_attn_plane
 int unimm_x3_attn_set_impl(int32_t impl);
 
 /* ---------------------------------------------------------------------------------------------
- * Answer generation (unimm_amd/generation.py; ABI 19).  Under the generative mask (utils/data_utils.py:199-210) the context
+ * Answer generation (unimm_amd/generation.py; ABI 19, sampling ABI 20).  Under the generative mask (utils/data_utils.py:199-210) the context
  * rows [1, c) and the image stream never see the answer, answer row c+k attends [1, c+k] and the [MASK]-copy row of answer
  * token k attends [1, c+k) + itself: the sequence is a prefix-LM, so a decode step pushes only the NEW text rows of every
  * hypothesis through the blocks and reads everything older from a key/value cache.
@@ -664,6 +664,37 @@ int unimm_kv_cache_update(const unimm_kv_update_args* args, void* stream);
  * UNIMM_OK without a launch and leaves the outputs untouched. */
 int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
                   const int32_t* flags, int32_t sep, int32_t K, float* vals, int32_t* ids, float* lse, void* stream);
+
+/* Sampling from fp32 logits [rows, ldl] (ABI 20): temperature, top-k and nucleus filtering and one draw per row, one workgroup
+ * per row; logits / V / ldl / banned / nbanned / flags / sep as in unimm_lm_topk.  Per row, in this order:
+ *  1. ELIGIBLE ids: [0, V) without the banned ids, without `sep` when flags[row] & 1, without every id other than `sep` when
+ *     flags[row] & 2 (with a finite logit of `sep` that row returns token = sep, logq = 0 whatever the other arguments are),
+ *     and without the ids whose logit is not > -inf.  Nothing eligible: token = -1, logp = logq = -inf (lse is still written).
+ *  2. RANK by (raw fp32 logit desc, id asc), the order of unimm_lm_topk (-0 ties +0).  top_k > 0 keeps exactly the first
+ *     min(top_k, #eligible) ids of that order (an exact radix select on the order-preserving integer image of the fp32 bits, a
+ *     second one on the id among the logits tied at the boundary); top_k = 0 keeps all, and top_k is not bounded by 16.
+ *  3. TEMPERATURE: y_i = x_i / temperature, q_i ~ exp(y_i - max y) over the kept ids; the kernel evaluates y_i - max y as
+ *     (x_i - x_max) / temperature, so that its rounding does not grow with an offset common to the row.
+ *  4. NUCLEUS, top_p < 1: keep {i : x_i >= theta}, theta the largest logit of the row whose mass sum{q_i : x_i >= theta} is
+ *     >= top_p * sum q.  Ids tied with theta all stay; the top-ranked id always stays.  Masses are summed in 2^-40 fixed point
+ *     (q_i <= 1) in 64-bit integers, whose sum does not depend on the order of the additions; the comparison is
+ *     mass >= ceil((double)top_p * (double)total) in those units.
+ *  5. DRAW by Gumbel-max: token = argmax over the kept ids of y_i + g_i (ties to the smaller id), g_i = -log(-log u_i),
+ *     u_i = ((h_i >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1)),
+ *     h_i = mix32(mix32(key ^ (stream_ids[row] * 0x9E3779B1 + 0x7F4A7C15)) + i * 0x85EBCA77), mix32 the hash of csrc/common.h
+ *     (host mirror: unimm_amd/dropout.py mix32_int); logf is the accurate one.  A draw depends on (key, stream_ids[row], the
+ *     row's logits and flags) alone: not on the row's position, the number of rows or an earlier launch.
+ *  6. logq[row] = y_t - logsumexp over the kept ids of y: the log-probability under the distribution sampled from.
+ * logp[row] = x_t - logsumexp(x[0:V]), the value unimm_lm_topk reports for that id (the same online log-sum-exp), lse fp32 [rows]
+ * or NULL.  token int32 [rows], logp / logq fp32 [rows], stream_ids int32 [rows] (device).
+ * Which path a V takes: V <= 36864 stages the row's keys once in LDS (4 V bytes of dynamic LDS: 119 KiB at V = 30522) and runs
+ * every selection pass over LDS; a larger V (<= 65536) re-reads the L2-resident row in every pass.  Same results either way.
+ * V <= 65536, ldl >= V, columns past V are not read; banned ids outside [0, V) and duplicates are ignored; rows = 0 returns
+ * UNIMM_OK without a launch and leaves the outputs untouched.  temperature <= 0 (or not finite), top_p outside (0, 1] and
+ * top_k < 0 return UNIMM_E_ARG before any launch. */
+int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                    const int32_t* flags, int32_t sep, float temperature, int32_t top_k, float top_p, uint32_t key,
+                    const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse, void* stream);
 
 /* Launch profiler for bench.py's `roofline` block: HIP events around every GEMM launch on its own
  * stream while enabled.  Variant index: 0..11 = unimm_gemm_nt (epilogue * 2 + out_f32), 12 = unimm_gemm_tn.

@@ -4,7 +4,12 @@ against the recompute lower bound: sequence_log_likelihood of the same G * beams
 (a generator that re-runs the encoder per token pays at least that) -- with shared_context=<dialog> where that path applies
 (answers of <= 14 tokens: it takes <= 32 private rows per sequence), the per-sequence path for the longer ones.
 
-    python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile]
+    python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile] [--samples N]
+
+--samples N adds, for G = 80 dialogs: ms/step of sampling N answers per dialog (temperature 0.8, top_k 50, top_p 0.9) against a
+beam run with the same number of hypothesis slots (beams = N) in the same process, the time of one unimm_lm_sample launch against
+one unimm_lm_topk launch on the same [80 N, 30522] logits, and the two ways of appending a step's K | V rows to the private caches
+(tensor indexing in place, which the sampler uses, against unimm_kv_cache_update under an identity parent).
 
 --profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
 process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
@@ -73,9 +78,64 @@ def timed(fn, reps):
     return best
 
 
-def generate(model, d, c, beams, n):
+def generate(model, d, c, beams, n, **kw):
     return model.generate_answers(d["input_ids"], d["image_feat"], d["image_loc"], c, d["token_type_ids"], d["position_ids"],
-                                  d["image_attention_mask"], beams=beams, max_answer_len=n, min_answer_len=n)
+                                  d["image_attention_mask"], beams=beams, max_answer_len=n, min_answer_len=n, **kw)
+
+
+def launch_us(fn, n=50):
+    """Microseconds per launch: n launches between two events, after a warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+def measure_sampling(model, G, N, reps):
+    """Sampling N answers per dialog against beams = N (the same 2 G N decode rows), and the selection kernels alone."""
+    from unimm_amd import lib as L
+    d, c = dialogs(G, seed=G * 10 + N)
+    skw = dict(samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1)
+    row = dict(G=G, slots=N)
+    for name, beams, kw in (("beam", N, {}), ("sample", 1, skw)):
+        prefill = timed(lambda: generate(model, d, c, beams, 0, **kw), reps)
+        full = timed(lambda: generate(model, d, c, beams, ANS, **kw), reps)
+        assert bool((generate(model, d, c, beams, ANS, **kw).lengths == ANS + 1).all())
+        row[name + "_prefill_ms"], row[name + "_call_ms"] = round(prefill, 3), round(full, 3)
+        row[name + "_ms_per_step"] = round((full - prefill) / ANS, 3)
+    S, V = G * N, 30522
+    logits = torch.randn((S, V), generator=torch.Generator().manual_seed(0)).cuda() * 3
+    banned = torch.tensor([0, 101, 103], dtype=torch.int32, device="cuda")
+    flags = torch.zeros(S, dtype=torch.int32, device="cuda")
+    streams = torch.arange(S, dtype=torch.int32, device="cuda")
+    vals = torch.empty((S, N), dtype=torch.float32, device="cuda")
+    ids = torch.empty((S, N), dtype=torch.int32, device="cuda")
+    tok = torch.empty(S, dtype=torch.int32, device="cuda")
+    lp, lq = torch.empty(S, device="cuda"), torch.empty(S, device="cuda")
+    row["lm_topk_us"] = round(launch_us(lambda: L.lm_topk(logits, S, V, banned, flags, 102, N, vals, ids)), 1)
+    for name, (t, k, p) in (("lm_sample_us", (0.8, 50, 0.9)), ("lm_sample_plain_us", (1.0, 0, 1.0)), ("lm_sample_top_k_us", (1.0, 50, 1.0)),
+                            ("lm_sample_top_p_us", (1.0, 0, 0.9))):
+        row[name] = round(launch_us(lambda: L.lm_sample(logits, S, V, banned, flags, 102, t, k, p, 12345, streams, tok, lp, lq)), 1)
+    # appending one K | V row per slot and text layer: in place against the copying kernel under an identity parent
+    nt, H, pcap = 12, 768, ANS
+    priv = [torch.zeros((nt, S, pcap, 2 * H), dtype=torch.bfloat16, device="cuda") for _ in range(2)]
+    plen = [torch.full((S,), pcap // 2, dtype=torch.int32, device="cuda") for _ in range(2)]
+    stash = torch.randn((nt, 2 * S, 3 * H), device="cuda").to(torch.bfloat16)
+    ident = torch.arange(S, dtype=torch.int32, device="cuda")
+
+    def in_place():
+        priv[0][:, :, pcap // 2] = stash[:, 0::2, H:]
+        plen[0].add_(0)
+
+    row["append_in_place_us"] = round(launch_us(in_place), 1)
+    row["append_kv_cache_update_us"] = round(launch_us(lambda: L.kv_cache_update(priv[0], priv[1], stash[0][:, H:], ident, plen[0], plen[1],
+                                                                                nt, S, pcap, 2 * H, 2 * S * 3 * H, 2)), 1)
+    return row
 
 
 def recompute_bound(model, d, c, G, beams, reps):
@@ -153,6 +213,7 @@ def main():
     ap.add_argument("--no-recompute", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--samples", type=int, default=0, help="add the sampling comparison at G = 80 with this many samples per dialog")
     a = ap.parse_args()
     torch.set_num_threads(min(16, torch.get_num_threads()))
     model = build_model()
@@ -165,6 +226,12 @@ def main():
               f"{r['answers_per_s']:>10.1f} {r['tokens_per_s']:>9.1f} {r.get('recompute_bound_ms', float('nan')):>12.1f} "
               f"{r.get('speedup_vs_recompute', float('nan')):>6.2f}")
     result = dict(rows=rows)
+    if a.samples:
+        result["sampling"] = r = measure_sampling(model, 80, a.samples, a.reps)
+        print(f"G = {r['G']}, {r['slots']} slots per dialog: ms/step sampling {r['sample_ms_per_step']:.2f} against beams {r['beam_ms_per_step']:.2f}; "
+              f"one launch on [{r['G'] * r['slots']}, 30522]: unimm_lm_sample {r['lm_sample_us']:.1f} us (no filter {r['lm_sample_plain_us']:.1f}, "
+              f"top-k only {r['lm_sample_top_k_us']:.1f}, nucleus only {r['lm_sample_top_p_us']:.1f}) against unimm_lm_topk {r['lm_topk_us']:.1f} us; "
+              f"cache append in place {r['append_in_place_us']:.1f} us against unimm_kv_cache_update {r['append_kv_cache_update_us']:.1f} us")
     if a.profile:
         result["kernel_mix_80x4"] = profile()
         for m in result["kernel_mix_80x4"]:

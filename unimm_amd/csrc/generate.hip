@@ -1,6 +1,7 @@
-// Answer generation kernels (include/unimm_hip.h, ABI 19): text self-attention of the decode rows against a shared context
-// cache plus per-hypothesis private caches, the per-step private-cache append + reorder, and log-softmax + top-K of the
-// decoder logits.  unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
+// Answer generation kernels (include/unimm_hip.h, ABI 19-20): text self-attention of the decode rows against a shared context
+// cache plus per-hypothesis private caches, the per-step private-cache append + reorder, log-softmax + top-K of the
+// decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20).
+// unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
 #include <math.h>
 
 #include "common.h"
@@ -299,6 +300,251 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
   if (tid == 0 && a.lse != nullptr) a.lse[row] = lse;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// unimm_lm_sample: one workgroup per logits row.  Every id gets a KEY: 0 when it is not eligible (banned, a flag, a logit that
+// is not > -inf), otherwise the order-preserving integer image of its fp32 bits (> 0), so that "logit desc, id asc" is "key desc,
+// id asc" and every selection below is an exact radix select on integers.  V <= STAGE_MAX: the keys are staged in LDS once and
+// every later pass reads LDS; larger V: the passes recompute the key from the (L2-resident) row.  Masses are summed as
+// 2^-40 fixed point in 64-bit integers: an integer sum does not depend on the order of the atomics, so a launch is reproducible.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int STAGE_MAX = 36864;               // 144 KiB of keys + 12.3 KiB of static LDS <= 160 KiB
+constexpr float FIX_ONE = 1099511627776.f;     // 2^40
+static_assert(NTHREADS == 256, "one histogram bin per thread");
+
+struct SampleParams {
+  const float* logits; const int32_t* banned; const int32_t* flags; const int32_t* stream;
+  int32_t* token; float* logp; float* logq; float* lse;
+  int rows, V, ldl, nbanned, sep, top_k;
+  float temperature, top_p;
+  uint32_t key;
+};
+
+struct SelScratch {
+  unsigned long long hist[256], scan[256], tgt, own;
+  uint32_t sel;
+};
+
+__device__ __forceinline__ uint32_t ord_key(float x) {
+  uint32_t u = __float_as_uint(x);
+  if ((u << 1) == 0u) u = 0u;                  // -0 ties +0, as the float comparison of lm_topk has it
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_val(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// The largest w (top_shift + 8 bits wide) with sum{wt_j : active j, w_j >= w} >= target, by 8-bit digits from the top:
+// f(j, w, wt) -> active.  *rem = target minus the weight strictly above w, *at = the weight at w.  Every thread calls it.
+template <class F>
+__device__ uint32_t radix_select(F f, int V, int top_shift, unsigned long long target, SelScratch& s, unsigned long long* rem,
+                                 unsigned long long* at) {
+  const int tid = threadIdx.x;
+  uint32_t prefix = 0u, pmask = 0u;
+  unsigned long long own_sel = 0ull;
+  for (int shift = top_shift; shift >= 0; shift -= 8) {
+    s.hist[tid] = 0ull;
+    if (tid == 0) { s.sel = 0u; s.tgt = target; s.own = 0ull; }
+    __syncthreads();
+    for (int j = tid; j < V; j += NTHREADS) {
+      uint32_t w;
+      unsigned long long wt;
+      if (f(j, w, wt) && (w & pmask) == prefix) atomicAdd(&s.hist[(w >> shift) & 255u], wt);
+    }
+    __syncthreads();
+    const unsigned long long own = s.hist[tid];
+    unsigned long long v = own;                  // -> weight of the digits >= tid
+    for (int o = 1; o < 256; o <<= 1) {
+      s.scan[tid] = v;
+      __syncthreads();
+      if (tid + o < 256) v += s.scan[tid + o];
+      __syncthreads();
+    }
+    if (v - own < target && target <= v) { s.sel = (uint32_t)tid; s.tgt = target - (v - own); s.own = own; }
+    __syncthreads();
+    prefix |= s.sel << shift;
+    pmask |= 255u << shift;
+    target = s.tgt;
+    own_sel = s.own;
+    __syncthreads();
+  }
+  *rem = target;
+  *at = own_sel;
+  return prefix;
+}
+
+__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* sh) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  unsigned long long t = 0ull;
+  for (int w = 0; w < NTHREADS / 64; ++w) t += sh[w];
+  return t;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* keys = reinterpret_cast<uint32_t*>(smem);          // [V] when STAGED (no dynamic LDS otherwise)
+  __shared__ uint32_t ban[VMAX / 32];
+  __shared__ SelScratch sel;
+  __shared__ float rm[NTHREADS / 64], rs[NTHREADS / 64], wv[NTHREADS / 64];
+  __shared__ int wi[NTHREADS / 64];
+  __shared__ unsigned long long r64[NTHREADS / 64];
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const int V = a.V;
+  const int nw = (V + 31) / 32;
+  for (int w = tid; w < nw; w += NTHREADS) ban[w] = 0u;
+  __syncthreads();
+  for (int b = tid; b < a.nbanned; b += NTHREADS) {
+    const int id = a.banned[b];
+    if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+  }
+  __syncthreads();
+  const int f = a.flags != nullptr ? a.flags[row] : 0;
+  const float* x = a.logits + (int64_t)row * a.ldl;
+  const int sep = a.sep;
+  auto make_key = [&](int j, float xv) -> uint32_t {
+    const bool out = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == sep) || ((f & 2) && j != sep) || !(xv > -INFINITY);
+    return out ? 0u : ord_key(xv);
+  };
+  auto key_at = [&](int j) -> uint32_t { return STAGED ? keys[j] : make_key(j, x[j]); };
+
+  // pass A: the row's log-sum-exp (lm_topk's online form, the same order of operations), the keys, their count and maximum
+  float m = -INFINITY, s = 0.f;
+  uint32_t kmax = 0u;
+  unsigned long long cnt = 0ull;
+  for (int j = tid; j < V; j += NTHREADS) {
+    const float xv = x[j];
+    if (xv > -INFINITY) {
+      if (xv > m) {
+        s = s * expf(m - xv) + 1.f;
+        m = xv;
+      } else {
+        s += expf(xv - m);
+      }
+    }
+    const uint32_t k = make_key(j, xv);
+    if (STAGED) keys[j] = k;
+    kmax = max(kmax, k);
+    cnt += k != 0u;
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    const float M = fmaxf(m, m2);
+    s = (M == -INFINITY) ? 0.f : s * expf(m - M) + s2 * expf(m2 - M);
+    m = M;
+    kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
+  }
+  if (lane == 0) { rm[wave] = m; rs[wave] = s; wi[wave] = (int)kmax; }
+  __syncthreads();
+  float M = rm[0];
+  kmax = (uint32_t)wi[0];
+  for (int w = 1; w < NTHREADS / 64; ++w) {
+    M = fmaxf(M, rm[w]);
+    kmax = max(kmax, (uint32_t)wi[w]);
+  }
+  float tot = 0.f;
+  for (int w = 0; w < NTHREADS / 64; ++w)
+    if (rm[w] > -INFINITY) tot += rs[w] * expf(rm[w] - M);
+  const float lse = M + logf(tot);
+  cnt = block_sum_u64(cnt, r64);                 // (its barriers also order the key stores before the passes below)
+  if (tid == 0 && a.lse != nullptr) a.lse[row] = lse;
+  if (cnt == 0ull) {
+    if (tid == 0) {
+      a.token[row] = -1;
+      a.logp[row] = -INFINITY;
+      a.logq[row] = -INFINITY;
+    }
+    return;
+  }
+
+  // top-k: key T of rank top_k and, where the ids tied at T do not all fit, the last id that does
+  uint32_t T = 0u;
+  int idcut = -1;                                // kept by top-k: key > T, or key == T and id <= idcut
+  if (a.top_k > 0 && (unsigned long long)a.top_k < cnt) {
+    unsigned long long rem, at;
+    T = radix_select([&](int j, uint32_t& w, unsigned long long& wt) { w = key_at(j); wt = 1ull; return w != 0u; }, V, 24,
+                     (unsigned long long)a.top_k, sel, &rem, &at);
+    idcut = V;
+    if (rem < at) {
+      unsigned long long r2, a2;
+      idcut = 0xFFFF - (int)radix_select([&](int j, uint32_t& w, unsigned long long& wt) {
+                                           w = 0xFFFFu - (uint32_t)j; wt = 1ull; return key_at(j) == T; },
+                                         V, 8, rem, sel, &r2, &a2);
+    }
+  }
+  auto kept_k = [&](int j, uint32_t k) -> bool { return k > T || (k == T && j <= idcut); };
+
+  // temperature: every y is taken relative to the row's largest eligible logit (always kept), y_i - y_max = (x_i - x_max) / t:
+  // argmax (y + g), q and logq do not change, and the rounding no longer grows with an offset of the whole row
+  const float xmax = key_val(kmax), temp = a.temperature;
+  auto rel = [&](uint32_t k) -> float { return (key_val(k) - xmax) / temp; };
+  auto fixed = [&](float d) -> unsigned long long { return (unsigned long long)(expf(d) * FIX_ONE); };
+
+  // nucleus: the largest key TH whose mass from the top reaches top_p of the kept mass
+  uint32_t TH = 0u;
+  if (a.top_p < 1.0f && cnt > 1ull) {
+    unsigned long long z = 0ull;
+    for (int j = tid; j < V; j += NTHREADS) {
+      const uint32_t k = key_at(j);
+      if (kept_k(j, k)) z += fixed(rel(k));
+    }
+    z = block_sum_u64(z, r64);
+    const double want = ceil((double)a.top_p * (double)z);
+    const unsigned long long target = want < 1.0 ? 1ull : (unsigned long long)want;
+    unsigned long long rem, at;
+    TH = radix_select([&](int j, uint32_t& w, unsigned long long& wt) {
+                        w = key_at(j);
+                        const bool on = kept_k(j, w);
+                        wt = on ? fixed(rel(w)) : 0ull;
+                        return on; },
+                      V, 24, target, sel, &rem, &at);
+  }
+
+  // draw: argmax of y + Gumbel noise over the kept ids (ties to the smaller id), and the kept mass
+  const uint32_t sk = mix32(a.key ^ ((uint32_t)a.stream[row] * 0x9E3779B1u + 0x7F4A7C15u));
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  unsigned long long zf = 0ull;
+  for (int j = tid; j < V; j += NTHREADS) {
+    const uint32_t k = key_at(j);
+    if (!kept_k(j, k) || k < TH) continue;
+    const float d = rel(k);
+    zf += fixed(d);
+    const uint32_t h = mix32(sk + (uint32_t)j * 0x85EBCA77u);
+    const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;      // 2^-23: exact, inside (0, 1)
+    const float v = d - logf(-logf(u));
+    if (better(v, j, bv, bi)) { bv = v; bi = j; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(bv, o, 64);
+    const int i2 = __shfl_xor(bi, o, 64);
+    if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+  }
+  if (lane == 0) { wv[wave] = bv; wi[wave] = bi; }
+  zf = block_sum_u64(zf, r64);                   // (its barriers publish wv / wi)
+  if (tid == 0) {
+    bv = wv[0];
+    bi = wi[0];
+    for (int w = 1; w < NTHREADS / 64; ++w)
+      if (better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+    if (bi < 0 || bi >= V) {                     // cannot happen (the top-ranked id is always kept); never index with it
+      a.token[row] = -1;
+      a.logp[row] = -INFINITY;
+      a.logq[row] = -INFINITY;
+    } else {
+      const float xt = x[bi];
+      a.token[row] = bi;
+      a.logp[row] = xt - lse;
+      a.logq[row] = (xt - xmax) / temp - logf((float)((double)zf * 9.094947017729282e-13));   // 2^-40
+    }
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -356,6 +602,37 @@ extern "C" int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32
   p.logits = logits; p.banned = banned; p.flags = flags; p.vals = vals; p.ids = ids; p.lse = lse;
   p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.K = K;
   hipLaunchKernelGGL(lm_topk_kernel, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+extern "C" int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                               const int32_t* flags, int32_t sep, float temperature, int32_t top_k, float top_p, uint32_t key,
+                               const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse, void* stream) {
+  if (logits == nullptr || stream_ids == nullptr || token == nullptr || logp == nullptr || logq == nullptr ||
+      (nbanned > 0 && banned == nullptr))
+    return UNIMM_E_ARG;
+  if (!(temperature > 0.f) || !(temperature < INFINITY) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0) return UNIMM_E_ARG;
+  if (rows < 0 || V < 1 || V > VMAX || ldl < V || nbanned < 0) return UNIMM_E_SHAPE;
+  if (rows == 0) return UNIMM_OK;
+  SampleParams p;
+  p.logits = logits; p.banned = banned; p.flags = flags; p.stream = stream_ids;
+  p.token = token; p.logp = logp; p.logq = logq; p.lse = lse;
+  p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = top_k;
+  p.temperature = temperature; p.top_p = top_p; p.key = key;
+  if (V <= STAGE_MAX) {
+    static bool done = false;
+    if (!done) {
+      if (hipFuncSetAttribute((const void*)lm_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              STAGE_MAX * (int)sizeof(uint32_t)) != hipSuccess)
+        return UNIMM_E_HIP;
+      done = true;
+    }
+    hipLaunchKernelGGL(lm_sample_kernel<true>, dim3((unsigned)rows), dim3(NTHREADS), (size_t)V * sizeof(uint32_t),
+                       (hipStream_t)stream, p);
+  } else {
+    hipLaunchKernelGGL(lm_sample_kernel<false>, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  }
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }

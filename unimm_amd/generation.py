@@ -45,15 +45,29 @@ text-attends-regions half of a connection layer, the MLM head on the copy rows, 
 `unimm_kv_cache_update` (append + reorder of the private caches of all text layers) between steps.  Beam selection runs as
 torch ops on the [G, beams * beams] candidates; the only device->host synchronisation of a step is the "all dialogs
 stopped" flag.  Inference only, bf16 engine with the connection layers.
+
+Sampling (`samples` > 0, `sample_search`): `samples` independent hypothesis slots per dialog, each DRAWING token k from its copy
+row's distribution after the same step rules (banned ids, [SEP] banned below min_answer_len and forced at the dialog's limit),
+then top-k, temperature and nucleus filtering -- `unimm_lm_sample`, whose header comment fixes the order.  The model part of the
+step is the beam search's; a slot never changes parent, so its private caches only grow: the new K | V row of every text layer is
+appended in place.  A slot is finished when it draws [SEP]; the loop ends when every slot is (one synchronisation per step) or
+after max_answer_len + 1 steps.  Draw j of dialog g at step k uses key = dropout.make_key(seed, k, SAMPLE_SITE) and stream
+sample_streams[g] * samples + j, and depends on nothing else but the row's logits: a caller that passes its own dialog ids as
+`sample_streams` gets the same draws for a dialog wherever it stands in the batch (up to the batch dependence of the logits
+themselves).  Every token comes with log p under the unmodified distribution (step_logp, summed in logp: equal to
+`sequence_log_likelihood` of the completed sequence, as for beams) and log q under the one sampled from (step_logq).  Samples are
+returned in draw order, not sorted.
 """
 from __future__ import annotations
 
 import math
+import zlib
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
+from . import dropout as DR
 from . import lib as L
 from . import params as PM
 from .inputs import DialogMaskSpec
@@ -61,7 +75,9 @@ from .inputs import DialogMaskSpec
 SEP, MASK = 102, 103
 BF16, F32 = torch.bfloat16, torch.float32
 MAX_BEAMS = 16
-SEP_BANNED, SEP_FORCED = 1, 2                  # per-row flags of unimm_lm_topk
+MAX_SAMPLES = 16                               # unimm_attn_decode takes 2 * slots <= 32 query rows per dialog
+SEP_BANNED, SEP_FORCED = 1, 2                  # per-row flags of unimm_lm_topk / unimm_lm_sample
+SAMPLE_SITE = zlib.crc32(b"generate.sample") & 0xFFFFFFFF   # the engine's dropout sites are crc32 of their parameter names
 
 
 @dataclass
@@ -71,6 +87,7 @@ class GeneratedAnswers:
     scores: torch.Tensor    # fp32 [G, beams]: logp / lengths ** length_penalty
     logp: torch.Tensor      # fp32 [G, beams]: summed log p
     step_logp: torch.Tensor  # fp32 [G, beams, max_answer_len + 1]: the log p of each token (an extension: per-step checks)
+    step_logq: torch.Tensor | None = None   # sampling only: the log q of each token under the distribution it was drawn from
 
 
 def answer_limits(context_len, T, max_answer_len):
@@ -187,12 +204,62 @@ def beam_search(step, G, beams, limits, max_answer_len, min_answer_len=1, length
                             step_logp=fin_lp[:, :beams].gather(1, order[:, :, None].expand(-1, -1, W)))
 
 
+def check_sampling(samples, beams, temperature, top_k, top_p):
+    """The refused sampling requests (ValueError)."""
+    if not 1 <= int(samples) <= MAX_SAMPLES:
+        raise ValueError(f"generate_answers: samples must be in [0, {MAX_SAMPLES}], got {samples}")
+    if int(beams) != 1:
+        raise ValueError(f"generate_answers: samples > 0 draws independent answers and needs beams = 1, got beams = {beams}")
+    if not (temperature > 0 and math.isfinite(temperature)):
+        raise ValueError(f"generate_answers: temperature must be positive and finite, got {temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"generate_answers: top_k must be an integer >= 0 (0 = off), got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"generate_answers: top_p must be in (0, 1] (1 = off), got {top_p}")
+
+
+def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
+    """Draw `samples` answers per dialog.  step(k, token, flags) -> (token int [G*samples], logp fp32, logq fp32): the draw of every
+    slot at step k with its two log-probabilities, where slot s = g * samples + j continues itself with answer token k-1 =
+    token[s] (k = 0: every slot of a dialog starts from the dialog's root; `token` is ignored).  flags as in beam_search
+    (step_flags).  A slot is finished when it draws [SEP]: at its dialog's limit at the latest, which forces it.  Finished slots
+    keep running through `step`; what they draw is dropped.  -> GeneratedAnswers with the samples in draw order j."""
+    S, W = G * samples, max_answer_len + 1
+    dev = torch.device(device)
+    limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev)
+    toks = torch.zeros((S, W), dtype=torch.int64, device=dev)
+    lp = torch.zeros((S, W), dtype=F32, device=dev)
+    lq = torch.zeros((S, W), dtype=F32, device=dev)
+    lengths = torch.zeros(S, dtype=torch.int64, device=dev)
+    done = torch.zeros(S, dtype=torch.bool, device=dev)
+    token = torch.zeros(S, dtype=torch.int64, device=dev)
+    for k in range(W):
+        tok, p, q = step(k, token, step_flags(k, limits, samples, min_answer_len).to(dev))
+        tok = tok.to(dev, torch.int64)
+        live = ~done
+        toks[:, k] = torch.where(live, tok, 0)
+        lp[:, k] = torch.where(live, p.to(dev, F32), 0.0)
+        lq[:, k] = torch.where(live, q.to(dev, F32), 0.0)
+        fin = live & (tok == SEP)
+        lengths = torch.where(fin, k + 1, lengths)
+        done = done | fin
+        token = tok.clamp_min(0)
+        if bool(done.all()):                                                  # the step's one device -> host synchronisation
+            break
+    logp = lp.sum(1)
+    scores = logp / lengths.clamp_min(1).to(F32) ** float(length_penalty)
+    shape = (G, samples)
+    return GeneratedAnswers(tokens=toks.view(*shape, W), lengths=lengths.view(shape), scores=scores.view(shape),
+                            logp=logp.view(shape), step_logp=lp.view(*shape, W), step_logq=lq.view(*shape, W))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the engine's step function
 # ---------------------------------------------------------------------------------------------------------------------------
 def generate_answers(model, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
-                     length_penalty=0.0, banned_tokens=(0, 101, 103)):
+                     length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                     sample_streams=None):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("generate_answers runs on the bf16 engine")
@@ -204,6 +271,16 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     if c_h.shape[0] != G:
         raise ValueError(f"generate_answers: {c_h.shape[0]} context lengths for {G} dialogs")
     limits = check_request(c_h, T, beams, max_answer_len, min_answer_len)
+    sampling = None
+    if samples:
+        check_sampling(samples, beams, temperature, top_k, top_p)
+        streams = np.arange(G) if sample_streams is None else np.asarray(
+            sample_streams.cpu() if torch.is_tensor(sample_streams) else sample_streams).astype(np.int64).reshape(-1)
+        if streams.shape[0] != G:
+            raise ValueError(f"generate_answers: {streams.shape[0]} sample streams for {G} dialogs")
+        streams = (streams[:, None] * int(samples) + np.arange(int(samples))[None]).reshape(-1)
+        sampling = dict(samples=int(samples), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed),
+                        streams=(streams & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
     eng = model._engine
     eng.ensure(model._device())
     inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
@@ -211,10 +288,13 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     inp = {k: v for k, v in inp.items() if v is not None}
     eng.stage_host_inputs(inp, pack=("attention_mask", "co_attention_mask"))   # the [G, R] image key mask stays a tensor
     return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
-                               tuple(int(t) for t in banned_tokens))
+                               tuple(int(t) for t in banned_tokens), sampling)
 
 
-def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens):
+def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None):
+    """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples."""
+    if sampling is not None:
+        beams = sampling["samples"]
     from .scoring import _forward_shared
     cfg = eng.cfg
     dev = eng.arena.device
@@ -299,16 +379,8 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
                    0, nwv, NO, qvar=(q_off, q_len), kvar=(k_off, k_len))
         return eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)[:2]
 
-    def step(k, parent, token, flags):
-        if k == 0:                                         # copy row 0 is the prefill's decoded row
-            L.lm_topk(pre["logits"], G, V, banned, flags[::beams].contiguous(), SEP, beams, vals[:G], tops[:G])
-            return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
-        if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
-            cur = st["cur"]
-            L.kv_cache_update(priv[cur], priv[1 - cur], stash[0][:, H:], parent.to(torch.int32), plen[cur], plen[1 - cur],
-                              nt, S, pcap, 2 * H, M * 3 * H, 2)
-            st["cur"] = 1 - cur
-        # new rows: (answer row k-1, copy row k) per slot
+    def model_rows(k, token):
+        """The model part of step k >= 1: the new rows (answer row k-1, copy row k) of every slot -> fp32 logits of the copy rows."""
         ids32 = torch.stack([token, torch.full_like(token, MASK)], 1).reshape(M).to(torch.int32)
         pos32 = torch.stack([slot_pos + (k - 1), slot_pos + k], 1).reshape(M).to(torch.int32)
         typ32 = slot_seg.repeat_interleave(2).to(torch.int32)
@@ -320,8 +392,40 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
                 xt32, xt = conn_block(f"c{i}", xt32, xt)
         xs = torch.empty((S, H), dtype=BF16, device=dev)
         L.gather_rows(xt, copy_rows, xs, S, H)
-        logits = eng.decode_rows(xs, S)
+        return eng.decode_rows(xs, S)
+
+    def step(k, parent, token, flags):
+        if k == 0:                                         # copy row 0 is the prefill's decoded row
+            L.lm_topk(pre["logits"], G, V, banned, flags[::beams].contiguous(), SEP, beams, vals[:G], tops[:G])
+            return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
+        if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
+            cur = st["cur"]
+            L.kv_cache_update(priv[cur], priv[1 - cur], stash[0][:, H:], parent.to(torch.int32), plen[cur], plen[1 - cur],
+                              nt, S, pcap, 2 * H, M * 3 * H, 2)
+            st["cur"] = 1 - cur
+        logits = model_rows(k, token)
         L.lm_topk(logits, S, V, banned, flags, SEP, beams, vals, tops)
         return vals, tops
 
-    return beam_search(step, G, beams, limits, max_answer_len, min_answer_len, length_penalty, device=dev)
+    if sampling is None:
+        return beam_search(step, G, beams, limits, max_answer_len, min_answer_len, length_penalty, device=dev)
+
+    streams = torch.from_numpy(sampling["streams"]).to(dev)
+    stok = torch.empty(S, dtype=torch.int32, device=dev)
+    slp = torch.empty(S, dtype=F32, device=dev)
+    slq = torch.empty(S, dtype=F32, device=dev)
+
+    def draw(k, logits, flags):
+        L.lm_sample(logits, S, V, banned, flags, SEP, sampling["temperature"], sampling["top_k"], sampling["top_p"],
+                    DR.make_key(sampling["seed"], k, SAMPLE_SITE), streams, stok, slp, slq)
+        return stok, slp, slq
+
+    def sample_step(k, token, flags):
+        if k == 0:                                         # every slot of a dialog draws from the prefill's copy row 0
+            return draw(k, pre["logits"][:, :V].repeat_interleave(beams, 0), flags)
+        if k >= 2:                                         # a slot keeps its own cache: append its answer row k-2 in place
+            priv[0][:, :, k - 2] = stash[:, 0::2, H:]
+            plen[0].add_(1)
+        return draw(k, model_rows(k, token), flags)
+
+    return sample_search(sample_step, G, beams, limits, max_answer_len, min_answer_len, length_penalty, device=dev)

@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -77,6 +77,7 @@ def lib():
     L.unimm_attn_decode.argtypes = [VP, VP]
     L.unimm_kv_cache_update.argtypes = [VP, VP]
     L.unimm_lm_topk.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, I32, VP, VP, VP, VP]
+    L.unimm_lm_sample.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, F32, I32, F32, U32, VP, VP, VP, VP, VP, VP]
     L.unimm_gemm_tn_grouped.argtypes = [VP, I32, VP]
     L.unimm_gemm_tn_grouped_ws.argtypes = [VP, I32, I32, VP, I64, VP]
     L.unimm_colpartials_finish_grouped.argtypes = [VP, I32, VP]
@@ -100,8 +101,8 @@ SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "uni
            "unimm_x3_split", "unimm_x3_split_wt", "unimm_x3_layernorm_bwd_partials", "unimm_embed_bwd_f32", "unimm_x3_lm_loss_bwd",
            "unimm_x3_kl_loss_bwd", "unimm_x3_rows_add", "unimm_x3_attn_fwd", "unimm_x3_attn_bwd", "unimm_x3_attn_set_impl", "unimm_x3_layernorm_fwd", "unimm_prof_tag", "unimm_prof_tagged",
            "unimm_sum_dropout", "unimm_sum_dropout_bwd", "unimm_mse_loss_fwd", "unimm_mse_loss_bwd", "unimm_host_mask_pack", "unimm_host_memcpy",
-           # answer generation (csrc/generate.hip, ABI 19)
-           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk"]
+           # answer generation (csrc/generate.hip, ABI 19; sampling ABI 20)
+           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk", "unimm_lm_sample"]
 
 
 def _check(rc, what):
@@ -376,6 +377,16 @@ def lm_topk(logits, rows, V, banned, flags, sep, K, vals, ids, lse=None):
     nb = 0 if banned is None else banned.numel()
     _check(lib().unimm_lm_topk(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, K,
                                vals.data_ptr(), ids.data_ptr(), _P(lse), _stream()), "unimm_lm_topk")
+
+
+def lm_sample(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, key, streams, token, logp, logq, lse=None):
+    """One draw per row of fp32 logits [rows, >= V] after temperature / top-k / nucleus filtering (unimm_lm_sample): token int32
+    [rows], logp (unmodified distribution) and logq (the one sampled from) fp32 [rows]; streams int32 [rows], key a 32-bit word."""
+    _dev(logits, banned, flags, streams, token, logp, logq, lse)
+    nb = 0 if banned is None else banned.numel()
+    _check(lib().unimm_lm_sample(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, temperature, top_k,
+                                 top_p, key & 0xFFFFFFFF, _P(streams), _P(token), _P(logp), _P(logq), _P(lse), _stream()),
+           "unimm_lm_sample")
 
 
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):
