@@ -105,6 +105,13 @@ typedef struct {
   void* splitk_ws;
   int64_t splitk_ws_bytes;
   int32_t splitk;
+  /* UNIMM_EPI_BIAS_DROP_RESID on a SUBSET of rows (each int32 [M] or NULL = the identity; UNIMM_E_ARG with another epilogue).
+   * drop_rows: output row m draws the dropout mask of row drop_rows[m], i.e. the mask the same launch over all rows gives
+   * that row.  aux_rows: the residual operand and, where given, its LayerNorm statistics (aux, aux_mean, aux_rstd) are read
+   * at row aux_rows[m] -- the rows of a gathered block read their residual straight from the full-row stream.  Every entry
+   * must name a valid row, those of surplus (capacity) rows included; an entry may repeat. */
+  const int32_t* drop_rows;
+  const int32_t* aux_rows;
 } unimm_gemm_nt_args;
 
 int unimm_gemm_nt(const unimm_gemm_nt_args* args, void* stream);
@@ -303,18 +310,21 @@ int64_t unimm_colpartials_bytes(int32_t H);
 int unimm_layernorm_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                         void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dbias, float* partials,
                         int32_t M, int32_t H, uint32_t drop_key, uint32_t drop_thr, float drop_scale,
-                        uint32_t odrop_key, uint32_t odrop_thr, float odrop_scale, const uint32_t* drop_salt, void* stream);
+                        uint32_t odrop_key, uint32_t odrop_thr, float odrop_scale, const uint32_t* drop_salt,
+                        const int32_t* drop_rows, void* stream);
 /* The same row kernel without the reduction of its column partials: `partials` (unimm_colpartials_bytes(H), private to
  * this call until it is reduced) holds [blocks][3][H] = per-block sums for dgamma, dbeta, dbias; *blocks_out (host)
  * receives the block count.  unimm_colpartials_finish_grouped then adds the column sums of up to many pending calls
  * into their destinations in one launch (dst[q] == NULL skips quantity q): the engine reduces a block's LayerNorm
  * partials once at the end of the block instead of between two dependent kernels each time.  m_dev (or NULL): device word with
- * the rows actually present (M = capacity); rows at or past it are neither read nor written and add nothing to the partials. */
+ * the rows actually present (M = capacity); rows at or past it are neither read nor written and add nothing to the partials.
+ * drop_rows (both entry points; int32 [M] or NULL = the identity): row m draws both dropout masks (drop_*, odrop_*) as row
+ * drop_rows[m] -- the rows of a gathered block keep the masks of the rows they came from (unimm_gemm_nt_args.drop_rows). */
 int unimm_layernorm_bwd_partials(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                                  void* dx, void* dx_drop, float* partials, int32_t M, int32_t H, uint32_t drop_key,
                                  uint32_t drop_thr, float drop_scale, uint32_t odrop_key, uint32_t odrop_thr,
                                  float odrop_scale, int32_t* blocks_out, const int32_t* m_dev, const uint32_t* drop_salt,
-                                 void* stream);
+                                 const int32_t* drop_rows, void* stream);
 #define UNIMM_FINISH_MAX 8
 typedef struct {
   const float* partials;

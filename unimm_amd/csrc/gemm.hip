@@ -759,6 +759,8 @@ extern "C" int unimm_gemm_nt(const unimm_gemm_nt_args* a, void* stream) {
   const int n_ln = (a->aux_mean != nullptr) + (a->aux_rstd != nullptr) + (a->aux_gamma != nullptr) + (a->aux_beta != nullptr);
   if (n_ln != 0 && (n_ln != 4 || a->epilogue != UNIMM_EPI_BIAS_DROP_RESID)) return UNIMM_E_ARG;
   p.aux_mean = a->aux_mean; p.aux_rstd = a->aux_rstd; p.aux_gamma = a->aux_gamma; p.aux_beta = a->aux_beta;
+  if ((a->drop_rows != nullptr || a->aux_rows != nullptr) && a->epilogue != UNIMM_EPI_BIAS_DROP_RESID) return UNIMM_E_ARG;
+  p.drop_rows = a->drop_rows; p.aux_rows = a->aux_rows;
   NtTune tune;
   if (!nt_tune_decode(a->tile, tune)) return UNIMM_E_ARG;
   p.gn = tune.gn > 0 ? tune.gn : 4;   // 4 tile columns per group: +1 % at 240 sequences, +5-8 % at 30 over 6 (A/B, two-stream schedule)

@@ -33,6 +33,9 @@ struct GemmNtParams {
   int gn;            // n-tiles per column group of the tile order (see tile_of)
   DropoutArg drop;
   const float* aux_mean; const float* aux_rstd; const float* aux_gamma; const float* aux_beta;  // DROP_RESID: aux = LayerNorm(aux)
+  // DROP_RESID on a row subset (both optional, [M] each): output row m draws the dropout mask of row drop_rows[m] and reads its
+  // residual (aux, aux_mean, aux_rstd) at row aux_rows[m]
+  const int32_t* drop_rows; const int32_t* aux_rows;
   // split-K (ring-loop tiles only; see nt_split_join): ksplit workgroups share one output tile, each reduces a slice of K,
   // partial tiles meet in `slabs` and the last arriver (ticket in `counters`) runs the epilogue.  ksplit <= 1: off.
   int ksplit; float* slabs; int* counters;
@@ -241,7 +244,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 
 // Shared epilogue of the NT kernels (inlined): bias / activation / residual / dropout on the wave's
 // [16*MT rows][64 columns] accumulator tile, stored row-contiguously.
-template <class C, int EPI, bool OUT_F32>
+template <class C, int EPI, bool OUT_F32, bool RMAP = false>
 __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[4][C::MT], char* smem, int m0, int n0,
                                             int wm, int wn, int wave, int lane) {
   constexpr int MT = C::MT;
@@ -291,6 +294,27 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[
   const int pf_a = full_ ? colA : 0, pf_b = full_ ? colB : 4;
   f32x4 pf0[2][PFN], pf1[2][PFN];
   float pfmu[2][PFN], pfrs[2][PFN];
+  // Row maps (RMAP: DROP_RESID on a row subset; kernels of their own, launched only when a map is given -- inside the one
+  // kernel the map's registers cost the persistent 192x256 three-slot form its last VGPRs and it spilled).  The residual's
+  // ADDRESS then depends on a loaded index: the entries of a batch are requested one batch before the operand loads that use
+  // them (nxa / nxd; the first before the barrier below) and arrive with the drain at the start of the batch in between, so
+  // the FAST walk waits no more often than without a map.
+  static_assert(!RMAP || AUX32, "row maps: the dropout + residual epilogue only");
+  int pfdr[2][PFN], nxa[PFN], nxd[PFN];
+  auto rows_prefetch = [&](int batch) {              // map entries of walk iterations [batch * PF, (batch + 1) * PF)
+    if constexpr (AUX32) {
+      if (batch * PF < NWALK) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+          const int g = batch * PF + k;
+          int m = m0 + wm * 16 * MT + (g / NIT) * 16 * C::JP + (g % NIT) * 8 + (lane >> 3);
+          m = m < p.M ? m : p.M - 1;
+          nxa[k] = p.aux_rows != nullptr ? p.aux_rows[m] : m;
+          nxd[k] = p.drop_rows != nullptr ? p.drop_rows[m] : m;
+        }
+      }
+    }
+  };
   auto aux_prefetch = [&](int batch, auto sure) {    // requests walk iterations [batch * PF, (batch + 1) * PF)
     if constexpr (PF > 0) {
       if (batch * PF < NWALK && (decltype(sure)::value || pf_on)) {
@@ -301,6 +325,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[
           int m = m0 + wm * 16 * MT + (g / NIT) * 16 * C::JP + row;
           m = m < p.M ? m : p.M - 1;
           if constexpr (AUX32) {
+            if constexpr (RMAP) { m = nxa[k]; pfdr[batch & 1][k] = nxd[k]; }
             const float* ap = reinterpret_cast<const float*>(p.aux) + (size_t)m * p.ldaux;
             pf0[batch & 1][k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ap + pf_a));
             pf1[batch & 1][k] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(ap + pf_b));
@@ -310,9 +335,11 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[
             pf0[batch & 1][k] = __builtin_bit_cast(f32x4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ap)));
           }
         }
+        if constexpr (RMAP) rows_prefetch(batch + 1);
       }
     }
   };
+  if constexpr (RMAP) rows_prefetch(0);
   aux_prefetch(0, std::false_type{});
   __builtin_amdgcn_s_barrier();                      // all waves finished reading the ring
   float b[8];
@@ -438,7 +465,16 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[
       if constexpr (EPI == UNIMM_EPI_BIAS_DROP_RESID || EPI == UNIMM_EPI_DGELU || EPI == UNIMM_EPI_ADD || EPI == UNIMM_EPI_MUL) {
         float a[8];
         if constexpr (EPI == UNIMM_EPI_BIAS_DROP_RESID) {   // fp32 residual stream
-          const float* ap = reinterpret_cast<const float*>(p.aux) + (size_t)m * p.ldaux;
+          int am = m, dm = m;                               // the rows the residual is read at / the mask is drawn for
+          if constexpr (RMAP) {
+            if constexpr (FAST) {
+              dm = pfdr[(gw / PFN) & 1][gw % PFN];          // (the residual itself was prefetched from its mapped row)
+            } else {
+              if (p.aux_rows != nullptr) am = p.aux_rows[m];
+              if (p.drop_rows != nullptr) dm = p.drop_rows[m];
+            }
+          }
+          const float* ap = reinterpret_cast<const float*>(p.aux) + (size_t)am * p.ldaux;
           if (vec_aux) {
             f32x4 r0, r1;
             if (PF > 0) { r0 = pfa0; r1 = pfa1; }
@@ -454,14 +490,14 @@ __device__ __forceinline__ void nt_epilogue(const GemmNtParams& p, f32x4 (&acc)[
           }
           if (aux_ln) {
             const bool pfd = PF > 0 && (FAST || pf_on);
-            const float mu = pfd ? pfamu : p.aux_mean[m], rs = pfd ? pfars : p.aux_rstd[m];
+            const float mu = pfd ? pfamu : p.aux_mean[am], rs = pfd ? pfars : p.aux_rstd[am];
 #pragma unroll
             for (int e = 0; e < 8; ++e) a[e] = (a[e] - mu) * rs * lg[e] + lb[e];
           }
           if (p.drop.thr != 0u) {
             const uint32_t kb = (SPLITCOL && FAST)
-                ? (drop_bits4(p.drop, (uint32_t)m, (uint32_t)p.N, (uint32_t)colA) | (drop_bits4(p.drop, (uint32_t)m, (uint32_t)p.N, (uint32_t)colB) << 4))
-                : drop_bits8(p.drop, (uint32_t)m, (uint32_t)p.N, (uint32_t)n);
+                ? (drop_bits4(p.drop, (uint32_t)dm, (uint32_t)p.N, (uint32_t)colA) | (drop_bits4(p.drop, (uint32_t)dm, (uint32_t)p.N, (uint32_t)colB) << 4))
+                : drop_bits8(p.drop, (uint32_t)dm, (uint32_t)p.N, (uint32_t)n);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = ((kb >> e) & 1u) ? v[e] * p.drop.scale : 0.f;
           }
@@ -792,7 +828,7 @@ __device__ __forceinline__ bool nt_split_join(const GemmNtParams& p, f32x4 (&acc
 }
 
 // One output tile (logical tile id `lid`, already XCD-remapped): ring-staged main loop + epilogue.
-template <class C, int EPI, bool OUT_F32>
+template <class C, int EPI, bool OUT_F32, bool RMAP = false>
 __device__ __forceinline__ void nt_tile(const GemmNtParams& p, char* smem, int lid) {
   constexpr int BM = C::BM, BN = C::BN, BK = C::BK, S = C::STAGES, G = C::G, MT = C::MT;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -824,7 +860,7 @@ __device__ __forceinline__ void nt_tile(const GemmNtParams& p, char* smem, int l
   }
   if constexpr (C::PP) {
     nt_mainloop_pp<C>(p, smem, m0, n0, acc);
-    nt_epilogue<C, EPI, OUT_F32>(p, acc, smem, m0, n0, wm, wn, wave, lane);
+    nt_epilogue<C, EPI, OUT_F32, RMAP>(p, acc, smem, m0, n0, wm, wn, wave, lane);
     return;
   }
   int nk = p.K / BK, kb = 0;                 // this workgroup reduces K-steps [kb, kb + nk)
@@ -944,14 +980,14 @@ __device__ __forceinline__ void nt_tile(const GemmNtParams& p, char* smem, int l
   if (p.ksplit > 1) {
     if (!nt_split_join<C>(p, acc, smem, lid, split)) return;
   }
-  nt_epilogue<C, EPI, OUT_F32>(p, acc, smem, m0, n0, wm, wn, wave, lane);
+  nt_epilogue<C, EPI, OUT_F32, RMAP>(p, acc, smem, m0, n0, wm, wn, wave, lane);
 }
 
-template <class C, int EPI, bool OUT_F32>
+template <class C, int EPI, bool OUT_F32, bool RMAP = false>
 __global__ __launch_bounds__(C::THREADS, C::MIN_WAVES) void gemm_nt_kernel(GemmNtParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if constexpr (EPI == UNIMM_EPI_BIAS_DROP_RESID) drop_resolve(p.drop);
-  nt_tile<C, EPI, OUT_F32>(p, smem, xcd_remap(blockIdx.x, gridDim.x));
+  nt_tile<C, EPI, OUT_F32, RMAP>(p, smem, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // Persistent form: one workgroup per CU slot walks tiles blockIdx, blockIdx + grid, ...  A tile's epilogue
@@ -981,6 +1017,11 @@ template <class C> constexpr int nt_tile_code() {
 }
 
 template <class C, int EPI, bool F32> constexpr auto pick_nt_kernel() { return &gemm_nt_kernel<C, EPI, F32>; }
+// the kernel of a launch with row maps (DROP_RESID, whose output is fp32): one workgroup per tile
+template <class C, int EPI> constexpr auto pick_nt_rmap_kernel() {
+  if constexpr (EPI == UNIMM_EPI_BIAS_DROP_RESID) return &gemm_nt_kernel<C, EPI, true, true>;
+  else return &gemm_nt_kernel<C, EPI, true>;
+}
 
 template <class C, int EPI>
 int launch_nt_cfg(const GemmNtParams& p_in, bool out_f32, int want_persist, hipStream_t s, const NtSplit& sk = NtSplit{0, nullptr, 0}) {
@@ -1007,11 +1048,13 @@ int launch_nt_cfg(const GemmNtParams& p_in, bool out_f32, int want_persist, hipS
       want_persist = 0;
     }
   }
-  auto k32 = pick_nt_kernel<C, EPI, true>();
+  const bool rmap = EPI == UNIMM_EPI_BIAS_DROP_RESID && out_f32 && (p.drop_rows != nullptr || p.aux_rows != nullptr);
+  if (rmap) want_persist = 0;
+  auto k32 = rmap ? pick_nt_rmap_kernel<C, EPI>() : pick_nt_kernel<C, EPI, true>();
   auto k16 = pick_nt_kernel<C, EPI, false>();
   if (C::LDS > 64 * 1024) {
-    static bool done32 = false, done16 = false;
-    bool& done = out_f32 ? done32 : done16;
+    static bool done32 = false, done16 = false, done_rmap = false;
+    bool& done = rmap ? done_rmap : (out_f32 ? done32 : done16);
     if (!done) {
       const void* fn = out_f32 ? (const void*)k32 : (const void*)k16;
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess) return UNIMM_E_HIP;

@@ -321,7 +321,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
                                                             const float* __restrict__ gamma, bf16_t* __restrict__ dx,
                                                             bf16_t* __restrict__ dx_drop, float* __restrict__ partials,
                                                             int M, int H, DropoutArg drop, DropoutArg out_drop,
-                                                            const int32_t* __restrict__ m_dev) {
+                                                            const int32_t* __restrict__ m_dev,
+                                                            const int32_t* __restrict__ drop_rows) {
   __shared__ float red[4 * 1024];  // [wave][col], reused for each of the three quantities
   drop_resolve(drop);
   drop_resolve(out_drop);
@@ -342,6 +343,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
   u32x4 pdy[MAXC];
   f32x4 pxa[MAXC], pxb[MAXC];
   float pmean = 0.f, prstd = 0.f;
+  int pdrow = 0;                   // the row whose dropout masks this row draws (drop_rows: rows of a gathered block)
 #define UNIMM_LNB_PREFETCH(r_)                                                                                 \
   {                                                                                                            \
     _Pragma("unroll") for (int i = 0; i < MAXC; ++i) {                                                         \
@@ -353,6 +355,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
       }                                                                                                        \
     }                                                                                                          \
     pmean = mean_i[r_]; prstd = rstd_i[r_];                                                                    \
+    pdrow = drop_rows != nullptr ? drop_rows[r_] : (r_);                                                       \
   }
   if (wave < M) UNIMM_LNB_PREFETCH(wave)
   for (int row = wave; row < M; row += nwaves) {
@@ -373,12 +376,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
       }
     }
     const float mean = pmean, rstd = prstd;
+    const uint32_t drow = (uint32_t)pdrow;
     if (row + nwaves < M) UNIMM_LNB_PREFETCH(row + nwaves)
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
       // forward applied dropout AFTER this LayerNorm (embeddings)
-      const uint32_t kbo = out_drop.thr != 0u ? drop_bits8(out_drop, (uint32_t)row, (uint32_t)H, (uint32_t)((lane + 64 * i) * 8)) : 0u;
+      const uint32_t kbo = out_drop.thr != 0u ? drop_bits8(out_drop, drow, (uint32_t)H, (uint32_t)((lane + 64 * i) * 8)) : 0u;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float d = dyv.v[i][j];
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
     Row8 dd;
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
-      const uint32_t kb = drop.thr != 0u ? drop_bits8(drop, (uint32_t)row, (uint32_t)H, (uint32_t)((lane + 64 * i) * 8)) : 0u;
+      const uint32_t kb = drop.thr != 0u ? drop_bits8(drop, drow, (uint32_t)H, (uint32_t)((lane + 64 * i) * 8)) : 0u;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = rstd * (dyv.v[i][j] - s1 - xv.v[i][j] * s2);
@@ -925,7 +929,7 @@ extern "C" int unimm_layernorm_bwd(const void* dy, const float* x, const float* 
                                    void* dx, void* dx_drop, float* dgamma, float* dbeta, float* dbias, float* partials,
                                    int32_t M, int32_t H, uint32_t drop_key, uint32_t drop_thr, float drop_scale,
                                    uint32_t odrop_key, uint32_t odrop_thr, float odrop_scale, const uint32_t* drop_salt,
-                                   void* stream) {
+                                   const int32_t* drop_rows, void* stream) {
   if (!dy || !x || !mean || !rstd || !gamma || !dx || !partials) return UNIMM_E_ARG;
   if (M <= 0 || H <= 0 || H > MAXC * 512 || (H % 8)) return UNIMM_E_SHAPE;
   int blocks = (M + 3) / 4;
@@ -933,7 +937,7 @@ extern "C" int unimm_layernorm_bwd(const void* dy, const float* x, const float* 
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)dy, x, mean, rstd,
                      gamma, (bf16_t*)dx, (bf16_t*)dx_drop, partials, M, H, mk_drop(drop_key, drop_thr, drop_scale, drop_salt),
-                     mk_drop(odrop_key, odrop_thr, odrop_scale, drop_salt), (const int32_t*)nullptr);
+                     mk_drop(odrop_key, odrop_thr, odrop_scale, drop_salt), (const int32_t*)nullptr, drop_rows);
   UNIMM_CHECK_LAUNCH();
   hipLaunchKernelGGL(colpartials_finish_kernel, dim3((H + 63) / 64, 3), dim3(1024), 0, s, partials, blocks, 3, H, dgamma,
                      dbeta, dbias, (float*)nullptr);
@@ -945,14 +949,14 @@ extern "C" int unimm_layernorm_bwd_partials(const void* dy, const float* x, cons
                                             const float* gamma, void* dx, void* dx_drop, float* partials, int32_t M, int32_t H,
                                             uint32_t drop_key, uint32_t drop_thr, float drop_scale, uint32_t odrop_key,
                                             uint32_t odrop_thr, float odrop_scale, int32_t* blocks_out, const int32_t* m_dev,
-                                            const uint32_t* drop_salt, void* stream) {
+                                            const uint32_t* drop_salt, const int32_t* drop_rows, void* stream) {
   if (!dy || !x || !mean || !rstd || !gamma || !dx || !partials || !blocks_out) return UNIMM_E_ARG;
   if (M <= 0 || H <= 0 || H > MAXC * 512 || (H % 8)) return UNIMM_E_SHAPE;
   int blocks = (M + 3) / 4;
   blocks = blocks > RED_BLOCKS ? RED_BLOCKS : blocks;
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, x, mean, rstd,
                      gamma, (bf16_t*)dx, (bf16_t*)dx_drop, partials, M, H, mk_drop(drop_key, drop_thr, drop_scale, drop_salt),
-                     mk_drop(odrop_key, odrop_thr, odrop_scale, drop_salt), m_dev);
+                     mk_drop(odrop_key, odrop_thr, odrop_scale, drop_salt), m_dev, drop_rows);
   UNIMM_CHECK_LAUNCH();
   *blocks_out = blocks;
   return UNIMM_OK;

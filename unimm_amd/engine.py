@@ -15,6 +15,7 @@ compute step is a C-ABI call and raises if the library is missing."""
 from __future__ import annotations
 
 import math
+import os
 import zlib
 from contextlib import contextmanager
 from typing import Dict, List, Optional
@@ -84,7 +85,7 @@ class Engine:
         self.unpad = True                # run the text stream on valid rows only (see the plan step of _forward)
         self._wq = []                    # queued weight-gradient problems (text side) waiting for their grouped launch
         # Schedule options are plain attributes (set them on `model.engine` before the first step; bench.py has flags for
-        # the ones that are measured: --single-stream).  No environment switches.
+        # the ones that are measured: --single-stream).  One environment switch: UNIMM_PRUNE_LAST_TEXT (see below).
         self.lazy_ln = True              # residual epilogues evaluate the previous LayerNorm instead of reading its fp32 output
         # The attention launches take their (sequence, head) items longest sequence first (unimm_attn_args.order, written by the
         # step's plan): the tail of a launch is then its shortest items.  5,691 / 5,732 -> 5,793 / 5,818 sequences/s at 240
@@ -153,13 +154,22 @@ class Engine:
         self._reported = set()
         self.host_staging = True         # CPU tensors handed to forward() go through a pinned staging ring + copy stream (stage_host_inputs)
         self._stager = None
+        # The last text layer feeds nothing but the MLM head (on the labelled rows) and the text pooler (on the first-token
+        # rows).  In a training step whose caller wants no sequence output, the row-wise half of that layer -- everything after
+        # the attention (`_post_attn`) -- and the heads therefore run on those rows alone, B first-token rows followed by the
+        # plan's labelled rows (~17 % of the rows at 240 sequences); the rows keep the dropout masks of the rows they came from
+        # (unimm_gemm_nt_args.drop_rows).  See `_prune_rows`.  UNIMM_PRUNE_LAST_TEXT=0 (read here, for A/B runs of bench.py)
+        # or `prune_last_text = False` runs the layer on all rows.
+        self.prune_last_text = os.environ.get("UNIMM_PRUNE_LAST_TEXT", "1") != "0"
+        self._seq_wanted = True          # the running forward's caller reads the text stream's sequence output (see forward)
 
     def schedule_key(self):
         """Every schedule attribute that is frozen into a captured launch sequence (unimm_amd/graphs.py keys its entries on
         it: changing one after a capture re-captures instead of replaying the old schedule beside an eager new one)."""
         return (self.dual_stream, self.unpad, self.lazy_ln, self.gemm_tile, self.wgrad_group_rounds, self.wgrad_stream, self.splitk,
                 self.attn_longest_first, self.wgrad_overwrite, tuple(sorted(self.tile_table.items())), self.image_tile,
-                self.small_rows, self.image_head_side, self.skinny_dx_rows, self.wgrad_ws_bytes, self.text_priority)
+                self.small_rows, self.image_head_side, self.skinny_dx_rows, self.wgrad_ws_bytes, self.text_priority,
+                self.prune_last_text)
 
     def register_arena_user(self, obj):
         import weakref
@@ -351,7 +361,10 @@ class Engine:
             return DR.drop_arg(p, DR.site_key(self.seed, _site(name))) + (self.salt_word,)
         return DR.drop_arg(p, DR.make_key(self.seed, self.step, _site(name)))
 
-    def _linear(self, x, lin, epi=L.EPI_BIAS, aux=None, want_u=False, drop=None, out_f32=False, ldo=None, M=None, out=None):
+    def _linear(self, x, lin, epi=L.EPI_BIAS, aux=None, want_u=False, drop=None, out_f32=False, ldo=None, M=None, out=None,
+                drop_rows=None, aux_rows=None):
+        """drop_rows / aux_rows (EPI_BIAS_DROP_RESID): x holds a subset of rows; row m draws the dropout mask of row drop_rows[m]
+        and reads its residual `aux` at row aux_rows[m]."""
         M = x.shape[0] if M is None else M
         ldo = ldo or lin.N
         if out is None:                              # or a caller's [M, ldo] buffer (answer generation's per-layer K / V stash)
@@ -363,10 +376,10 @@ class Engine:
         sk = self._splitk(M, lin.N, lin.K)
         if sk is not None:
             L.gemm_nt(x, lin.w, out, bias=lin.bias, epilogue=epi, aux=aux, out2=u, drop=drop, M=M, N=lin.N, K=lin.K, aux_ln=aux_ln,
-                      tile=sk[0], splitk=sk[1], splitk_ws=sk[2])
+                      tile=sk[0], splitk=sk[1], splitk_ws=sk[2], drop_rows=drop_rows, aux_rows=aux_rows)
         else:
             L.gemm_nt(x, lin.w, out, bias=lin.bias, epilogue=epi, aux=aux, out2=u, drop=drop, M=M, N=lin.N, K=lin.K, aux_ln=aux_ln,
-                      tile=self._tile(M, lin.N, lin.K))
+                      tile=self._tile(M, lin.N, lin.K), drop_rows=drop_rows, aux_rows=aux_rows)
         return (out, u) if want_u else out
 
     def _tile(self, M, N, K=None):
@@ -440,16 +453,19 @@ class Engine:
         dx = torch.empty((M, K), dtype=F32, device=dy.device)
         return L.linear_f32(dy, w32, dx, M, K, N, (dy.stride(0), 1), (w32.stride(0), 1))
 
-    def _wgrad(self, dy, x, gw, M, N, K, dbias=None, m_dev=None, sole=False):
+    def _wgrad(self, dy, x, gw, M, N, K, dbias=None, m_dev=None, sole=False, rule_M=None):
         """dW += dy^T x (+ bias gradient).  Nothing downstream in the backward chain reads a weight gradient,
         so the call is only queued; `_flush_wgrad` hands the list of SEVERAL encoder blocks to one grouped launch
         (`_flush_due` says when).  dy / x stay referenced by the queue until then.
         sole: this call is the ONLY contribution to gw in a backward pass (every encoder nn.Linear; not the tied decoder /
         word-embedding matrix, not the three split-operand products of the fp32x3 mode).  When the gradient arena is also known
         to be zero (`arena.fresh`: zeroed since the last backward) the kernel then writes the tile with plain stores instead of
-        256 KiB of memory-side atomics per workgroup (unimm_gemm_tn_args.overwrite)."""
+        256 KiB of memory-side atomics per workgroup (unimm_gemm_tn_args.overwrite).
+        rule_M: the row count the flush rule (`_flush_due`) counts this problem with, when it is not M: a block that runs on a
+        subset of the step's rows (`_prune_rows`) keeps the step's row count there, so that grouped launches and bucket
+        hand-overs fall where they always fell -- the subset's size differs between the ranks of a data-parallel step."""
         ow = bool(sole and self._bwd_fresh and self.wgrad_overwrite)
-        (self._wq_img if self._on_side else self._wq).append((dy, x, gw, M, N, K, dbias, m_dev, ow))
+        (self._wq_img if self._on_side else self._wq).append((dy, x, gw, M, N, K, dbias, m_dev, ow, rule_M))
         self._nq[1 if self._on_side else 0] += 1
         if self.prof_conn is not None:            # FLOPs of the weight gradients queued from inside / outside a connection layer
             MM = dy.shape[0] if M is None else M
@@ -477,8 +493,10 @@ class Engine:
     def _big_tiles(queue):
         """256x256 output tiles of the queue's problems that take the big tile (csrc/gemm.hip: tn_is_big)."""
         t = 0
-        for dy, x, gw, M, N, K, *_ in queue:
+        for dy, x, gw, M, N, K, *rest in queue:
             M = dy.shape[0] if M is None else M
+            if len(rest) > 3 and rest[3] is not None:
+                M = rest[3]                       # (see _wgrad: rule_M)
             N = dy.shape[1] if N is None else N
             K = x.shape[1] if K is None else K
             t += BP.big_tiles_of(M, N, K)
@@ -542,13 +560,15 @@ class Engine:
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
 
-    def _linear_bwd(self, dy, x, lin, epi=L.EPI_BIAS, aux=None, need_dx=True, bias_grad=True, M=None, N=None, xk=None, m_dev=None):
+    def _linear_bwd(self, dy, x, lin, epi=L.EPI_BIAS, aux=None, need_dx=True, bias_grad=True, M=None, N=None, xk=None, m_dev=None,
+                    rule_M=None):
         """dW += dy^T x ; db += colsum(dy) ; returns dx = epi(dy @ W).  m_dev: device word with the real row count when
         dy / x hold a capacity of rows (the surplus rows must not enter the reduction over rows)."""
         M = dy.shape[0] if M is None else M
         N = lin.N if N is None else N
         self._wgrad(dy, x, lin.gw, M, N, lin.K if xk is None else xk,
-                    dbias=lin.gb if (bias_grad and lin.gb is not None) else None, m_dev=m_dev, sole=lin is not self.lin.get("dec"))
+                    dbias=lin.gb if (bias_grad and lin.gb is not None) else None, m_dev=m_dev, sole=lin is not self.lin.get("dec"),
+                    rule_M=rule_M)
         if not need_dx:
             return None
         dx = torch.empty((M, lin.K), dtype=BF16, device=dy.device)
@@ -702,7 +722,8 @@ class Engine:
         for t in reads:
             self._touch(t, main)
 
-    def _layernorm_bwd(self, dy, x, mean, rstd, key, dbias=None, drop=L.NO_DROP, out_drop=L.NO_DROP, defer=True, m_dev=None):
+    def _layernorm_bwd(self, dy, x, mean, rstd, key, dbias=None, drop=L.NO_DROP, out_drop=L.NO_DROP, defer=True, m_dev=None,
+                       drop_rows=None):
         """Row kernel now; the column sums (dgamma, dbeta, dbias) of all the calls of a block are reduced by one grouped
         launch at the end of the block (`_flush_wgrad`), where nothing waits for them.  defer=False: reduce right away."""
         gmm, _, gg, gb = self.ln[key]
@@ -711,10 +732,12 @@ class Engine:
         dxd = torch.empty((M, H), dtype=BF16, device=x.device) if drop[1] != 0 else None
         if not defer:
             scratch = (self.part_side if self._on_side else self.part)[H]
-            L.layernorm_bwd(dy, x, mean, rstd, gmm, dx, dxd, gg, gb, dbias, scratch, M, H, drop=drop, out_drop=out_drop)
+            L.layernorm_bwd(dy, x, mean, rstd, gmm, dx, dxd, gg, gb, dbias, scratch, M, H, drop=drop, out_drop=out_drop,
+                            drop_rows=drop_rows)
             return dx, (dxd if dxd is not None else dx)
         part = torch.empty(self.part[H].numel(), dtype=F32, device=x.device)      # private until the grouped reduction
-        blocks = L.layernorm_bwd_partials(dy, x, mean, rstd, gmm, dx, dxd, part, M, H, drop=drop, out_drop=out_drop, m_dev=m_dev)
+        blocks = L.layernorm_bwd_partials(dy, x, mean, rstd, gmm, dx, dxd, part, M, H, drop=drop, out_drop=out_drop, m_dev=m_dev,
+                                          drop_rows=drop_rows)
         (self._fq_img if self._on_side else self._fq).append((part, blocks, H, [gg, gb, dbias]))
         return dx, (dxd if dxd is not None else dx)
 
@@ -827,35 +850,43 @@ class Engine:
     def _proj_bwd(self, dqkv, x, lin, add, m_dev=None):
         return self._linear_bwd(dqkv, x, lin, L.EPI_ADD, aux=add, m_dev=m_dev)
 
-    def _post_attn(self, ctx, res32, proj, ff1, ff2, ln_mid, ln_out, d_proj, d_ffn, save, m_dev=None):
+    def _post_attn(self, ctx, res32, proj, ff1, ff2, ln_mid, ln_out, d_proj, d_ffn, save, m_dev=None, rows=None):
         """What follows the attention in every encoder block: BertSelfOutput or one side of BertBiOutput
         (models/vilbert_dialog.py:744-754), then BertIntermediate, then BertOutput.
         ctx: the attention context; res32: the fp32 residual stream entering the block (possibly a `_LazyLN`); proj, ff1,
         ff2: the three linears; ln_mid, ln_out: keys of `self.ln`; d_proj, d_ffn: the dropout triples of the two residual
         joins; m_dev: device word with the valid rows, when the row dimension is a capacity.
+        rows (int32, one per row of ctx): ctx holds a SUBSET of the block's rows, row m being row rows[m] of res32's stream:
+        the residual is read there and both joins draw that row's dropout mask, so every row comes out as the block over all
+        rows computes it; bwd then maps the subset's dy to the subset's (dctx, dres).
         -> (y32, y, bwd): the fp32 residual stream leaving the block and its bf16 copy; bwd (None unless save) maps dy to
         (dctx, dres), dres being the gradient w.r.t. the first pre-LayerNorm sum: the caller adds it in the epilogue of
         its QKV input-gradient GEMM."""
-        pre1 = self._linear(ctx, proj, L.EPI_BIAS_DROP_RESID, aux=res32, drop=d_proj, out_f32=True)
+        pre1 = self._linear(ctx, proj, L.EPI_BIAS_DROP_RESID, aux=res32, drop=d_proj, out_f32=True, drop_rows=rows, aux_rows=rows)
         x1_32, x1, m1, r1 = self._layernorm(pre1, ln_mid, save, lazy=True)
         # training keeps GELU'(u) (not u): the backward epilogue is then a plain multiply
         h, u = self._linear(x1, ff1, L.EPI_BIAS_GELU_DG, want_u=True) if save else (self._linear(x1, ff1, L.EPI_BIAS_GELU), None)
-        pre2 = self._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_ffn, out_f32=True)
+        pre2 = self._linear(h, ff2, L.EPI_BIAS_DROP_RESID, aux=x1_32, drop=d_ffn, out_f32=True, drop_rows=rows)
         x2_32, x2, m2, r2 = self._layernorm(pre2, ln_out, save, lazy=True)
         if not save:
             return x2_32, x2, None
 
+        rm = self._step_rows if rows is not None else None       # the flush rule keeps counting the step's rows (_wgrad)
+
         def bwd(dx2):
-            dpre2, dpre2d = self._layernorm_bwd(dx2, pre2, m2, r2, ln_out, dbias=ff2.gb, drop=d_ffn, m_dev=m_dev)
-            du = self._linear_bwd(dpre2d, h, ff2, L.EPI_MUL, aux=u, bias_grad=False, m_dev=m_dev)
-            dx1 = self._linear_bwd(du, x1, ff1, L.EPI_ADD, aux=dpre2, m_dev=m_dev)
-            dpre1, dpre1d = self._layernorm_bwd(dx1, pre1, m1, r1, ln_mid, dbias=proj.gb, drop=d_proj, m_dev=m_dev)
-            return self._linear_bwd(dpre1d, ctx, proj, bias_grad=False, m_dev=m_dev), dpre1
+            dpre2, dpre2d = self._layernorm_bwd(dx2, pre2, m2, r2, ln_out, dbias=ff2.gb, drop=d_ffn, m_dev=m_dev, drop_rows=rows)
+            du = self._linear_bwd(dpre2d, h, ff2, L.EPI_MUL, aux=u, bias_grad=False, m_dev=m_dev, rule_M=rm)
+            dx1 = self._linear_bwd(du, x1, ff1, L.EPI_ADD, aux=dpre2, m_dev=m_dev, rule_M=rm)
+            dpre1, dpre1d = self._layernorm_bwd(dx1, pre1, m1, r1, ln_mid, dbias=proj.gb, drop=d_proj, m_dev=m_dev, drop_rows=rows)
+            return self._linear_bwd(dpre1d, ctx, proj, bias_grad=False, m_dev=m_dev, rule_M=rm), dpre1
         return x2_32, x2, bwd
 
-    def _self_block(self, key, x32, x, mask, B, T, heads, pname, p_attn, p_hid, st, var=None):
+    def _self_block(self, key, x32, x, mask, B, T, heads, pname, p_attn, p_hid, st, var=None, prune=None):
         """BertLayer / BertImageLayer (models/vilbert_dialog.py:385-483, :514-612).
-        (x32, x): fp32 residual stream and its copy as a GEMM operand (bf16, or the split operand of the fp32x3 mode)."""
+        (x32, x): fp32 residual stream and its copy as a GEMM operand (bf16, or the split operand of the fp32x3 mode).
+        prune (`_prune_rows`): the block's output is read on those rows only -- projection and attention run on all rows (every
+        query attends every key), everything after them on the listed rows; the block then returns, and its backward takes,
+        tensors of prune["Mc"] rows."""
         train, tape = st["train"], st["tape"]
         save = tape is not None
         qkv_l, so, ff1, ff2 = (self.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
@@ -868,16 +899,67 @@ class Engine:
         d_so = self._drop(pname + "so", p_hid, train)
         d_out = self._drop(pname + "out", p_hid, train)
         md = var[2] if var is not None else None      # device word: valid rows, when the row dimension is a capacity
-        x2_32, x2, post_bwd = self._post_attn(ctx_op, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
+        if prune is None:
+            x2_32, x2, post_bwd = self._post_attn(ctx_op, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save, m_dev=md)
+        else:
+            # (all Mc rows are gathered: the entries past the device count name a valid row, so no operand row is undefined)
+            ctx_c = torch.empty((prune["Mc"], ctx_op.shape[1]), dtype=ctx_op.dtype, device=ctx_op.device)
+            L.gather_rows(ctx_op, prune["rows"], ctx_c, prune["Mc"], ctx_op.shape[1])
+            x2_32, x2, post_bwd = self._post_attn(ctx_c, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", d_so, d_out, save,
+                                                  m_dev=prune["m_dev"], rows=prune["rows"])
         if save:
             def bwd(dx2):
                 dctx, dpre1 = post_bwd(dx2)
+                if prune is not None:
+                    dctx, dpre1 = self._unprune(dctx, prune, x.shape[0]), self._unprune(dpre1, prune, x.shape[0])
                 dqkv = self._qkv_grad(qkv)
                 self._attn_bwd(q, k, v, ctx, dctx, lse, mask, dqkv[:, :Hd], dqkv[:, Hd:2 * Hd], dqkv[:, 2 * Hd:3 * Hd], 3 * Hd,
                                B, heads, T, T, D, d_attn, qvar=var, kvar=var)
                 return self._proj_bwd(dqkv, x, qkv_l, dpre1, m_dev=md)
             tape.append((key, bwd))
         return x2_32, x2
+
+    # The last text layer on the rows the losses read.
+    prune_supported = True               # (`_post_attn` takes a row list: the bf16 engine)
+
+    def _prune_rows(self, sched, save, lm_rows, sel, dyn, var, B, T, dev):
+        """-> None, or what `_self_block(prune=...)` and the heads need to run the last text layer's row-wise half on the rows
+        the training losses read.  Only in a step that saves for backward, decodes the labelled rows, whose caller reads no
+        sequence output or attention probabilities, and whose last text-side block is a trained text layer; every other path
+        runs as it always did.
+        rows: the B first-token rows, then the plan's labelled rows in plan order (Mc = B + sel["n"] of them, a capacity; the
+        device word m_dev holds B + the real count; the plan gives the surplus entries a valid row).  A first token that carries
+        a label is listed twice and computed twice.  In the backward pass its two gradients -- the MLM head's and the pooler's
+        -- meet in the labelled copy (cls_dst: where the pooler's input gradient of each sequence is added), as they meet in
+        the one row of the all-rows step: the row's gradient is rounded to bf16 once, in the same order, and everything
+        upstream of the layer sees the bits it always saw; the first-token copy then carries a zero gradient."""
+        if not (self.prune_last_text and self.prune_supported and save and not self._seq_wanted and self.attn_sink is None):
+            return None
+        if lm_rows != "labelled" or sel is None or sel["n"] <= 0:
+            return None
+        text_side = [(k, i) for k, i in sched if k == "t" or (k == "c" and self.cfg.with_coattention)]
+        if not text_side or text_side[-1][0] != "t" or text_side[-1][1] < self.cfg.fixed_t_layer:
+            return None
+        cls_idx = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
+        n = sel["n"]
+        first = torch.arange(B, dtype=torch.int32, device=dev)
+        # the labelled copy of each first token, if it has one (entries past the device count are fillers, not labelled rows)
+        live = torch.arange(n, dtype=torch.int32, device=dev) < dyn["n_lm"]
+        match = (sel["idx"][None, :] == cls_idx[:, None]) & live[None, :]
+        cls_dst = torch.where(match.any(1), match.to(torch.int32).argmax(1).to(torch.int32) + B, first)
+        return dict(layer=text_side[-1][1], B=B, n=n, Mc=B + n, cls_idx=cls_idx, lm_idx=sel["idx"], n_lm_dev=dyn["n_lm"],
+                    rows=torch.cat((cls_idx, sel["idx"])), m_dev=dyn["n_lm"] + B, first=first, cls_dst=cls_dst,
+                    lm_dst=torch.arange(B, B + n, dtype=torch.int32, device=dev))
+
+    def _unprune(self, g, prune, M):
+        """Gradient rows of the pruned layer (bf16 [Mc, W]) -> all M rows, zero elsewhere.  In a fixed order: the labelled rows
+        are written (each names its own row), then the first-token rows are added (zero where the labelled copy took the
+        first token's gradient: `_prune_rows`)."""
+        B, W = prune["B"], g.shape[1]
+        full = torch.zeros((M, W), dtype=g.dtype, device=g.device)
+        L.gather_rows(g[B:], prune["lm_idx"], full, prune["n"], W, scatter=True, n_dev=prune["n_lm_dev"])
+        L.rows_add_f32(full, prune["cls_idx"], g[:B].float(), B, W)
+        return full
 
     def _conn_block(self, key, i, xv32, xv, xt32, xt, B, R, T, vmask, comask, st, var=None):
         """BertConnectionLayer (models/vilbert_dialog.py:655-783)."""
@@ -1055,8 +1137,14 @@ class Engine:
             header = L.plan_lengths(tmask, comask, R, lab32, w32, nw_dev, B, T, image_label=il32)
         return header, lab32, w32, nw_dev, il32
 
-    def forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
-        return self._on_text_stream(self._forward, inp, train, save, lm_rows, want_pred_v)
+    def forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool, want_seq: bool = True):
+        """want_seq=False: the caller reads neither out["seq_out_t"] nor out["seq32_t"]; a training step may then run its last
+        text layer on the rows the losses read (`_prune_rows`) and return those rows only (out["pruned"])."""
+        self._seq_wanted = want_seq
+        try:
+            return self._on_text_stream(self._forward, inp, train, save, lm_rows, want_pred_v)
+        finally:
+            self._seq_wanted = True
 
     def forward_with_attention(self, inp, train, lm_rows, want_pred_v):
         """Inference forward that also returns the attention probabilities of every layer as the reference's encoder
@@ -1266,6 +1354,7 @@ class Engine:
         # layers are enqueued first so that both queues are fed; the tape keeps each stream's order for backward.
         sched = PM.encoder_schedule(cfg)
         st_frozen = dict(train=train, tape=None)
+        pruned = self._prune_rows(sched, save, lm_rows, sel, dyn, var, B, T, dev)
         pos = 0
         while pos < len(sched):
             seg = []
@@ -1288,7 +1377,8 @@ class Engine:
                 if kind == "t":
                     fz = i < cfg.fixed_t_layer
                     xt32, xt = self._self_block(f"t{i}", xt32, xt, tmask, B, T, cfg.num_attention_heads, f"bert.encoder.layer.{i}.",
-                                                cfg.attention_probs_dropout_prob, cfg.hidden_dropout_prob, st_frozen if fz else st, var=var)
+                                                cfg.attention_probs_dropout_prob, cfg.hidden_dropout_prob, st_frozen if fz else st, var=var,
+                                                prune=pruned if (pruned is not None and i == pruned["layer"]) else None)
                     if save and not fz:
                         tape[-1] = ("t", tape[-1][0], tape[-1][1])
             if pos < len(sched):
@@ -1315,11 +1405,15 @@ class Engine:
 
         xt32, xv32 = self._dense32(xt32), self._dense32(xv32)      # the final residual stream is an output
         out = dict(seq_out_t=seq_t, seq_out_v=seq_v, seq32_t=xt32, seq32_v=xv32, B=B, T=T, R=R, plan=plan, Mt=Mt,
-                   nsp_weight_host=st_nspw, n_img=n_img, img_label32=il32, dyn=dyn, img=img)
+                   nsp_weight_host=st_nspw, n_img=n_img, img_label32=il32, dyn=dyn, img=img, pruned=pruned)
+        # (pruned: the text stream's outputs above hold rows `pruned["rows"]` only: first tokens, then the labelled rows)
         if pred_v_out is not None:
             out["pred_v"] = pred_v_out
         # ---- poolers + NSP (models/vilbert_dialog.py:946-967, 1064-1070) -------------------------
-        cls_idx_t = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
+        if pruned is not None:
+            cls_idx_t = pruned["first"]
+        else:
+            cls_idx_t = var[0] if var is not None else torch.arange(0, B * T, T, dtype=torch.int32, device=dev)
         cls_idx_v = torch.arange(0, B * R, R, dtype=torch.int32, device=dev)
         heads = self._pooled_heads(xt32, xv32, cls_idx_t, cls_idx_v, B, train)
         out["nsp"] = heads["nsp_pad"][:, :2]
@@ -1332,8 +1426,11 @@ class Engine:
             n = sel["n"]                                          # rows chosen by the plan kernels at the start of forward (a capacity)
             if n > 0:
                 W = seq_t.shape[1]                                # the operand's own width: split rows move as 3 H 16-bit elements
-                xs = torch.empty((n, W), dtype=BF16, device=dev)
-                L.gather_rows(seq_t, sel["idx"], xs, n, W, n_dev=dyn["n_lm"])
+                if pruned is not None:
+                    xs = seq_t[B:]                                # the last layer ran on these rows: they are in place
+                else:
+                    xs = torch.empty((n, W), dtype=BF16, device=dev)
+                    L.gather_rows(seq_t, sel["idx"], xs, n, W, n_dev=dyn["n_lm"])
                 lm = self._lm_head(xs, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"])
                 lm.update(idx=sel["idx"], pos_idx=sel["pos"], n=n, n_dev=dyn["n_lm"], inv_dev=dyn["inv_lm"])
             out["lm"] = lm
@@ -1347,6 +1444,9 @@ class Engine:
     @staticmethod
     def padded(out, x):
         """[rows computed, H] -> the reference's [B*T, H] layout (rows that were never computed are zero)."""
+        if out.get("pruned") is not None:
+            raise RuntimeError("this step ran its last text layer on the loss rows only (Engine.forward(want_seq=False)): "
+                               "it has no sequence output")
         plan = out.get("plan")
         if plan is None:
             return x
@@ -1496,7 +1596,8 @@ class Engine:
                                "`model.engine.arena.fresh` (INTEGRATION.md, 'Gradient arena')")
         self._step_rows = out["Mt"]              # the tile rule follows THIS step's rows (another forward may have run since)
 
-        dseq_t = torch.zeros((out["Mt"], cfg.hidden_size), dtype=self.grad_dtype, device=dev)
+        pruned = out.get("pruned")                # the text stream ends on the loss rows: first tokens, then the labelled rows
+        dseq_t = torch.zeros((out["Mt"] if pruned is None else pruned["Mc"], cfg.hidden_size), dtype=self.grad_dtype, device=dev)
         # ---- image head: on the image stream, beside the MLM head's backward -------------------------
         img = out["img"]
         gimg = self._gvec(g_img)
@@ -1512,7 +1613,7 @@ class Engine:
             dxs = self._transform_head_bwd(self._lm_loss_grad(lm, g_lm), lm, lm["xs"], self.lin["lmtr"], "lmtr", self.lin["dec"],
                                            M=n, N=cfg.vocab_size, m_dev=nd)
             src, w = _rows16(dxs)
-            L.gather_rows(src, lm["idx"], _rows16(dseq_t)[0], n, w, scatter=True, n_dev=nd)
+            L.gather_rows(src, lm["idx"] if pruned is None else pruned["lm_dst"], _rows16(dseq_t)[0], n, w, scatter=True, n_dev=nd)
         # ---- NSP + poolers ------------------------------------------------------------------------
         nlab, w0, w1 = out["nsp_state"]
         dnsp = torch.empty((B, 2), dtype=F32, device=dev)
@@ -1526,7 +1627,7 @@ class Engine:
                           fusion_sum=cfg.fusion_method == "sum")
         # pooler input gradients land on the first-token rows
         dcls_t = self._linear32_bwd(dpt, bw["cls_t"], "tpool")
-        self._rows_add(dseq_t, bw["cls_idx_t"], dcls_t, B)
+        self._rows_add(dseq_t, bw["cls_idx_t"] if pruned is None else pruned["cls_dst"], dcls_t, B)
         dcls_v = self._linear32_bwd(dpv, bw["cls_v"], "vpool")
         self._to_img(dcls_v)                     # the image pooler's input gradient joins the image head's on the image stream
         with self._img_if(self.image_head_side):

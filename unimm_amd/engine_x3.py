@@ -301,6 +301,7 @@ class EngineX3(Engine):
     # the step: the base engine's `_forward` / `_backward`, with fp32 gradient streams and split loss gradients
     # ------------------------------------------------------------------------------------------
     grad_dtype = F32
+    prune_supported = False              # every block runs on all rows (this `_post_attn` takes no row list)
 
     def _forward(self, inp: dict, train: bool, save: bool, lm_rows: str, want_pred_v: bool):
         cfg = self.cfg

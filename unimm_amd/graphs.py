@@ -322,7 +322,9 @@ class StepGraphs:
             torch.cuda.synchronize()
             ent.gF = _new_graph()
             with _quiet_collector(), torch.cuda.graph(ent.gF, pool=ent.pool, stream=ent.stream, capture_error_mode="thread_local"):
-                ent.out = eng.forward(ent.sin, train=opts["train"], save=True, lm_rows="labelled", want_pred_v=True)
+                # (eligible(): no sequence output -> the last text layer may run on the loss rows; their capacity, B + the
+                #  labelled-row bucket, is part of the signature)
+                ent.out = eng.forward(ent.sin, train=opts["train"], save=True, lm_rows="labelled", want_pred_v=True, want_seq=False)
                 ent.losses = eng.losses(ent.out, ent.sin)
                 ent.nsp = ent.out["nsp"]
                 ls = ent.losses

@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -33,7 +33,8 @@ class GemmNtArgs(C.Structure):
                 ("drop_key", C.c_uint32), ("drop_thr", C.c_uint32), ("drop_scale", C.c_float),
                 ("aux_mean", C.c_void_p), ("aux_rstd", C.c_void_p), ("aux_gamma", C.c_void_p), ("aux_beta", C.c_void_p),
                 ("tile", C.c_int32), ("drop_salt", C.c_void_p),
-                ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64), ("splitk", C.c_int32)]
+                ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64), ("splitk", C.c_int32),
+                ("drop_rows", C.c_void_p), ("aux_rows", C.c_void_p)]
 
 
 class GemmTnArgs(C.Structure):
@@ -83,8 +84,8 @@ def lib():
     L.unimm_colpartials_finish_grouped.argtypes = [VP, I32, VP]
     L.unimm_layernorm_fwd.argtypes = [VP] * 7 + [I32, I32, F32, U32, U32, F32, VP, VP]
     L.unimm_x3_layernorm_fwd.argtypes = [VP] * 7 + [I32, I32, F32, U32, U32, F32, VP, VP]
-    L.unimm_layernorm_bwd_partials.argtypes = [VP] * 8 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP, VP, VP]
-    L.unimm_layernorm_bwd.argtypes = [VP] * 11 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP]
+    L.unimm_layernorm_bwd_partials.argtypes = [VP] * 8 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP, VP, VP, VP]
+    L.unimm_layernorm_bwd.argtypes = [VP] * 11 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP, VP]
     _lib = L
     return L
 
@@ -167,11 +168,12 @@ def _dev(*ts):
 
 
 def gemm_nt(x, w, out, bias=None, epilogue=EPI_BIAS, aux=None, out2=None, drop=None, M=None, N=None, K=None, aux_ln=None, tile=0,
-            splitk=0, splitk_ws=None):
+            splitk=0, splitk_ws=None, drop_rows=None, aux_rows=None):
     """out[M,N] = epi(x[M,K] @ w[N,K]^T).  x/w bf16 2-D (row stride = stride(0)); out bf16 or fp32.
     aux_ln = (mean[M], rstd[M], gamma[N], beta[N]): the DROP_RESID residual is LayerNorm(aux) computed on the fly.
-    tile: per-call tuning code (include/unimm_hip.h: unimm_gemm_nt_args.tile); 0 = automatic."""
-    _dev(x, w, out, bias, aux, out2)
+    tile: per-call tuning code (include/unimm_hip.h: unimm_gemm_nt_args.tile); 0 = automatic.
+    drop_rows / aux_rows (int32 [M], DROP_RESID): the rows whose dropout mask output row m draws / whose residual it reads."""
+    _dev(x, w, out, bias, aux, out2, drop_rows, aux_rows)
     st = getattr(_tls, "nt", None)
     if st is None:
         a = GemmNtArgs()
@@ -202,6 +204,8 @@ def gemm_nt(x, w, out, bias=None, epilogue=EPI_BIAS, aux=None, out2=None, drop=N
         a.aux_mean, a.aux_rstd, a.aux_gamma, a.aux_beta = (t.data_ptr() for t in aux_ln)
     else:
         a.aux_mean = a.aux_rstd = a.aux_gamma = a.aux_beta = None
+    a.drop_rows = drop_rows.data_ptr() if drop_rows is not None else None
+    a.aux_rows = aux_rows.data_ptr() if aux_rows is not None else None
     rc = fn(addr, _stream())
     if rc != 0:
         _check(rc, "unimm_gemm_nt")
@@ -478,16 +482,17 @@ class FinishDesc(C.Structure):
                 ("pad_", C.c_int32)]
 
 
-def layernorm_bwd_partials(dy, x, mean, rstd, gamma, dx, dx_drop, partials, M, H, drop=None, out_drop=None, m_dev=None):
+def layernorm_bwd_partials(dy, x, mean, rstd, gamma, dx, dx_drop, partials, M, H, drop=None, out_drop=None, m_dev=None,
+                           drop_rows=None):
     """LayerNorm backward row kernel only; returns the number of partial blocks (see unimm_layernorm_bwd_partials)."""
     drop = drop or NO_DROP
     out_drop = out_drop or NO_DROP
-    _dev(dy, x, mean, rstd, gamma, dx, dx_drop, partials)
+    _dev(dy, x, mean, rstd, gamma, dx, dx_drop, partials, drop_rows)
     blocks = C.c_int32(0)
     rc = lib().unimm_layernorm_bwd_partials(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
                                             dx.data_ptr(), _P(dx_drop), partials.data_ptr(), M, H, drop[0], drop[1], drop[2],
                                             out_drop[0], out_drop[1], out_drop[2], C.addressof(blocks), _P(m_dev),
-                                            _salt(drop, out_drop), _stream())
+                                            _salt(drop, out_drop), _P(drop_rows), _stream())
     if rc != 0:
         _check(rc, "unimm_layernorm_bwd_partials")
     return blocks.value
@@ -515,11 +520,12 @@ def layernorm_fwd(x, gamma, beta, y32, y16, mean, rstd, M, H, eps=1e-12, drop=NO
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, dbias, partials, M, H, drop=NO_DROP,
-                  out_drop=NO_DROP):
-    _dev(dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, dbias, partials)
+                  out_drop=NO_DROP, drop_rows=None):
+    _dev(dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, dbias, partials, drop_rows)
     _check(lib().unimm_layernorm_bwd(_P(dy), _P(x), _P(mean), _P(rstd), _P(gamma), _P(dx), _P(dx_drop),
                                      _P(dgamma), _P(dbeta), _P(dbias), _P(partials), M, H, drop[0], drop[1], drop[2],
-                                     out_drop[0], out_drop[1], out_drop[2], _salt(drop, out_drop), _stream()), "unimm_layernorm_bwd")
+                                     out_drop[0], out_drop[1], out_drop[2], _salt(drop, out_drop), _P(drop_rows), _stream()),
+           "unimm_layernorm_bwd")
 
 
 class EmbedArgs(C.Structure):

@@ -99,7 +99,8 @@ class _HotPath(torch.autograd.Function):
                 ctx.graph_token = res[4].out.pop("_token", None)   # alive until backward ran: the entry is not replayed meanwhile
                 engine.last_seq_t = (None, None)
                 return res[0], res[1], res[2], res[3]
-        out = engine.forward(inp, train=opts["train"], save=True, lm_rows="labelled", want_pred_v=True)
+        out = engine.forward(inp, train=opts["train"], save=True, lm_rows="labelled", want_pred_v=True,
+                             want_seq=bool(opts["want_seq"]))
         losses = engine.losses(out, inp)
         ctx.engine, ctx.out = engine, out
         engine.last_seq_t = (engine.padded(out, out["seq32_t"]) if opts["want_seq"] else None,
@@ -284,7 +285,7 @@ class BertForMultiModalPreTraining(nn.Module):
                 lm_loss, img_loss, nsp_loss, nsp = eng.graphs.outputs(ent)
             else:
                 inp.pop("_plan_header", None)
-                out = eng.forward(inp, train=self.training, save=True, lm_rows="labelled", want_pred_v=True)
+                out = eng.forward(inp, train=self.training, save=True, lm_rows="labelled", want_pred_v=True, want_seq=False)
                 ls = eng.losses(out, inp)
                 lm_loss, img_loss, nsp_loss, nsp = ls["lm_loss"], ls["img_loss"], ls["nsp_loss"], out["nsp"].clone()
                 eng.backward(out, g_lm.reshape(lm_loss.shape), g_img.reshape(img_loss.shape), g_nsp.reshape(nsp_loss.shape), None)
