@@ -90,3 +90,58 @@ def test_flush_rule():
     assert BP.big_tiles_of(31162, 3072, 768) == 36 and BP.big_tiles_of(8880, 1024, 5) == 0 and BP.big_tiles_of(600, 768, 768) == 0
     assert BP.flush_due(40, 0, 4) and BP.flush_due(3, 1024, 4) and not BP.flush_due(3, 564, 4)
     assert BP.flush_due(3, 1020, 4) and BP.flush_due(3, 480, 2) and not BP.flush_due(3, 456, 2)
+
+
+def test_the_eight_rank_plan_is_pinned_in_full():
+    """Every hand-over and every grouped launch of the 8-rank share, as recorded before the planner and the engine were moved
+    onto one `Ledger`."""
+    calls, launches = BP.hand_overs(_cfg(), wgrad_group_rounds=2, **SHARE8)
+    assert launches == [(1, 2, 44), (0, 2, 0), (1, 20, 480), (0, 20, 564), (1, 20, 480), (0, 20, 576), (1, 10, 224), (0, 20, 552), (0, 12, 324)]
+    assert calls == [("heads", False), ("v5", True), ("t11", True), ("c5", True), ("v4", True), ("t10", True), ("c4", True), ("v3", True),
+                     ("t9", False), ("c3", True), ("v2", True), ("t8", True), ("c2", True), ("v1", True), ("t7", True), ("c1", False),
+                     ("v0", False), ("t6", True), ("c0", True), ("image_embeddings", True), ("t5", True), ("t4", True), ("t3", False),
+                     ("t2", True), ("t1", True), ("t0", True), ("text_embeddings", False)]
+
+
+def test_ledger_launches_a_side_that_holds_only_column_sums():
+    """What the engine does and the planner's events never produce: LayerNorm column sums queued without a weight gradient."""
+    led = BP.Ledger(log=[])
+    led.queue(0, 4096, 768, 768)
+    led.colsum(1)
+    assert led.mark("a", 2, on_side=True) == ([], [])                  # not due, not forced: the sums wait
+    assert led.mark("b", 2, on_side=True, force_img=True) == ([1], []) # forced: launched, though no problem is queued
+    assert led.sums == [False, False] and led.launched == [0, 0] and led.queued == [1, 0] and led.log == []
+    assert led.flush(2, force=False, force_img=True) == []             # nothing left there
+    led.colsum(0)
+    assert led.mark("c", 2, force=True) == ([0], [("a", True), ("b", True), ("c", False)])
+    assert led.launched == led.queued == [1, 0] and led.log == [(0, 1, 9)] and led.pending == []
+
+
+def test_ledger_mark_from_the_image_side_leaves_the_text_side_alone():
+    led = BP.Ledger()
+    for _ in range(40):                                                 # a full descriptor table: due on both sides
+        led.queue(0, 4096, 768, 768)
+        led.queue(1, 4096, 1024, 1024)
+    assert led.mark("v", 2, on_side=True, force=True, force_img=True) == ([1], [])
+    assert led.launched == [0, 40] and led.tiles == [360, 0] and led.pending == [("v", 40, 40)]
+    assert led.mark("t", 2) == ([0], [("v", True), ("t", False)])      # the text side hands both over, oldest first
+    assert led.launched == [40, 40] and led.pending == []
+
+
+def test_ledger_direct_flush_and_hookless_passes():
+    led = BP.Ledger(log=[])
+    led.queue(0, 40, 768, 768)
+    led.queue(1, 37, 1024, 1024)
+    led.colsum(0)
+    assert led.flush(4) == [1, 0]                                       # outside a pass: everything, the image side first
+    assert led.launched == led.queued == [1, 1] and led.tiles == [0, 0] and led.sums == [False, False]
+    assert led.flush(4) == [] and led.log == [(1, 1, 0), (0, 1, 0)]
+    for _ in range(3):                                                  # nobody takes buckets: nothing is kept pending
+        led.begin()
+        assert led.reported == set()
+        led.queue(0, 4096, 768, 768)
+        assert led.mark("heads", 4, force=True, hand_over=False) == ([0], [])
+        led.queue(1, 4096, 1024, 1024)
+        assert led.mark("v0", 4, on_side=True, hand_over=False) == ([], [])
+        assert led.mark("text_embeddings", 4, force=True, hand_over=False) == ([1], [])
+        assert led.pending == [] and led.reported == {"heads", "v0", "text_embeddings"} and led.launched == led.queued

@@ -154,7 +154,7 @@ def test_two_engine_ranks_of_the_fp32_accuracy_engine(tmp_path, golden_dir):
 def test_exchange_plan_matches_the_engine(rounds):
     """`unimm_amd.bucket_plan` (host arithmetic; tests/test_bucket_plan_cpu.py checks the N = 8 plan with it) against the
     hand-overs a REAL backward produces at the full config on the 8-GPU share of the headline batch: the same buckets in the
-    same order with the same `more` flags, for both grouping depths."""
+    same order with the same `more` flags, and the same grouped launches (queue, problems, big tiles), for both grouping depths."""
     from unimm_amd import BertConfig, BertForMultiModalPreTraining, bucket_plan as BP, synth
     cfg = BertConfig.from_json_file(os.path.join(ROOT, "unimm_amd", "config", "bert_base_6layer_6conect.json"))
     torch.manual_seed(0)
@@ -164,6 +164,7 @@ def test_exchange_plan_matches_the_engine(rounds):
     eng.wgrad_group_rounds = rounds
     calls = []
     eng.grad_bucket_hook = lambda group, more=False: calls.append((group, bool(more)))
+    eng._ledger.log = []                  # the engine's own record of its grouped launches
     b = synth.make_batch(n_seq=30, T=256, R=37, cfg=cfg, seed=3, device="cuda")
     kw = dict(token_type_ids=b["token_type_ids"], position_ids=b["token_position_ids"], attention_mask=b["attention_mask"],
               image_attention_mask=b["image_attention_mask"], co_attention_mask=b["co_attention_mask"],
@@ -176,13 +177,16 @@ def test_exchange_plan_matches_the_engine(rounds):
     torch.cuda.synchronize()
     want, launches = BP.hand_overs(cfg, B, sum(hdr[:B]), sum(hdr[B:2 * B]), wgrad_group_rounds=rounds)
     assert calls == want, (calls, want)
+    assert eng._ledger.log == launches, (eng._ledger.log, launches)
     assert sorted(g for g, _ in calls) == sorted(g for g, _, _ in eng.arena.buckets)
     assert BP.arena_ranges(cfg) == list(eng.arena.buckets)
     # one stream: the image side's problems join the text queue; the plan follows
     calls.clear()
+    eng._ledger.log.clear()
     eng.dual_stream = False
     lm, img, nsp_l, _, _, _ = model(b["input_ids"], b["image_feat"], b["image_loc"], _want_lm_scores=False, **kw)
     (lm + img + nsp_l).sum().backward()
     torch.cuda.synchronize()
-    want1, _ = BP.hand_overs(cfg, B, sum(hdr[:B]), sum(hdr[B:2 * B]), wgrad_group_rounds=rounds, dual_stream=False)
+    want1, launches1 = BP.hand_overs(cfg, B, sum(hdr[:B]), sum(hdr[B:2 * B]), wgrad_group_rounds=rounds, dual_stream=False)
     assert calls == want1, (calls, want1)
+    assert eng._ledger.log == launches1, (eng._ledger.log, launches1)

@@ -2,11 +2,11 @@
 
 Under data parallelism (`parallel.DataParallelRCCL`, the replacement of utils/data_parallel.py:91-132) the engine hands a
 gradient bucket to the wrapper once every weight-gradient launch that covers it has been enqueued, and the engine launches
-weight gradients GROUPED over several encoder blocks (`Engine._flush_due`).  Which buckets travel together, in how many
-collectives and of what size is therefore a function of the config, the step's row counts and `wgrad_group_rounds` alone.
-This module restates that function without a device: `Engine` takes its flush rule from here (so the two cannot drift),
-`tests/test_bucket_plan_cpu.py` checks the N = 8 plan of the full config on the CPU, and `tests/test_gpu_dp2.py` holds the
-plan against the hand-overs a real backward produces.
+weight gradients GROUPED over several encoder blocks.  Which buckets travel together, in how many collectives and of what
+size is therefore a function of the config, the step's row counts and `wgrad_group_rounds` alone.  That rule is written ONCE,
+in `Ledger`, and has two drivers: `Engine` (`_wgrad`, `_bucket_done`), which launches what the ledger names and hands over
+what it says, and `hand_overs`, which feeds it the backward pass as a list of events, without a device.  `tests/test_bucket_plan_cpu.py`
+checks both on the CPU; `tests/test_gpu_dp2.py` holds the plan against the hand-overs and launches of a real backward.
 
 Covers the default encoder options (every layer trained, connection layers on: what bert_base_6layer_6conect.json and every script of
 the reference use); under `fixed_t_layer` / `with_coattention=False` the engine reports the buckets of skipped blocks at the end of backward.
@@ -40,6 +40,56 @@ def flush_due(n_problems: int, tiles: int, rounds: int) -> bool:
         return True
     waste = (-tiles) % CHIP_SLOTS
     return tiles >= max(2, rounds // 2) * CHIP_SLOTS - 32 and waste <= CHIP_SLOTS // 8
+
+
+class Ledger:
+    """The books of a backward pass's weight-gradient queues, per side (0 = text queue, 1 = image queue).  Host arithmetic
+    only: the driver keeps the operands and does the launches."""
+
+    def __init__(self, log=None):
+        self.queued, self.launched = [0, 0], [0, 0]   # weight-gradient problems ever queued / ever launched
+        self.tiles = [0, 0]           # big tiles of the problems now queued
+        self.sums = [False, False]    # a column-sum reduction waits for the side's next launch
+        self.pending = []             # buckets whose weight gradients are still queued: (group, queued[0], queued[1]) at their mark
+        self.reported = set()         # groups marked in this pass
+        self.log = log                # list, or None: (side, n_problems, big_tiles) of every launch with problems
+
+    def begin(self):
+        self.reported = set()
+
+    def queue(self, side, M, N, K):
+        self.queued[side] += 1
+        self.tiles[side] += big_tiles_of(M, N, K)
+
+    def colsum(self, side):
+        self.sums[side] = True
+
+    def _take(self, side, force, rounds):
+        n = self.queued[side] - self.launched[side]
+        if not (n or self.sums[side]) or not (force or flush_due(n, self.tiles[side], rounds)):
+            return False
+        if n and self.log is not None:
+            self.log.append((side, n, self.tiles[side]))
+        self.launched[side], self.tiles[side], self.sums[side] = self.queued[side], 0, False
+        return True
+
+    def flush(self, rounds, on_side=False, force=True, force_img=False):
+        """-> the sides to launch now, in launch order: the image side first, the text side only from the text side.  A side
+        goes out when it is due (`flush_due`) or forced; the defaults flush everything, for callers outside a backward."""
+        sides = [1] if self._take(1, force or force_img, rounds) else []
+        return (sides + [0]) if not on_side and self._take(0, force, rounds) else sides
+
+    def mark(self, group, rounds, on_side=False, force=False, force_img=False, hand_over=True):
+        """`group`'s backward is enqueued -> (sides to launch now, [(group, more), ...] buckets to hand over after them):
+        whatever is complete, oldest first, and only from the text side -- a bucket whose launches are out is not held back by
+        an older one that waits for the other side's queue.  hand_over=False (nobody takes buckets): nothing is kept pending."""
+        self.reported.add(group)
+        if hand_over:
+            self.pending.append((group, self.queued[0], self.queued[1]))
+        sides = self.flush(rounds, on_side, force, force_img)
+        ready = [] if on_side else [p for p in self.pending if self.launched[0] >= p[1] and self.launched[1] >= p[2]]
+        self.pending = [p for p in self.pending if p not in ready]
+        return sides, [(g, j + 1 < len(ready)) for j, (g, _, _) in enumerate(ready)]
 
 
 def arena_ranges(cfg) -> List[Tuple[str, int, int]]:
@@ -121,38 +171,14 @@ def backward_events(cfg, n_seq: int, text_rows: int, lm_rows: int, regions: int 
 def hand_overs(cfg, n_seq, text_rows, lm_rows, regions=37, wgrad_group_rounds=2, dual_stream=True, image_head_side=True):
     """-> ([(group, more), ...] in the order `Engine._bucket_done` calls the data-parallel hook,
            [number of weight-gradient problems per grouped launch, per queue: (side, n_problems, big_tiles), ...])."""
-    q = [[], []]
-    nq, nf = [0, 0], [0, 0]
-    pending, calls, launches = [], [], []
-
-    def flush(side):
-        if q[side]:
-            launches.append((side, len(q[side]), sum(big_tiles_of(*p) for p in q[side])))
-        q[side] = []
-        nf[side] = nq[side]
-
-    def due(side):
-        return flush_due(len(q[side]), sum(big_tiles_of(*p) for p in q[side]), wgrad_group_rounds)
-
+    led, calls = Ledger(log=[]), []
     for e in backward_events(cfg, n_seq, text_rows, lm_rows, regions, dual_stream, image_head_side):
         if e[0] == "w":
-            _, side, M, N, K = e
-            q[side].append((M, N, K))
-            nq[side] += 1
-            continue
-        _, group, on_side, force, force_img = e
-        pending.append((group, nq[0], nq[1]))
-        if q[1] and (force or force_img or due(1)):   # Engine._flush_wgrad: the image queue first ...
-            flush(1)
-        if not on_side and (force or due(0)):         # ... the text queue only from the text side
-            flush(0)
-        if on_side:
-            continue
-        ready = [p for p in pending if nf[0] >= p[1] and nf[1] >= p[2]]   # Engine._bucket_done: whatever is complete, oldest first
-        pending = [p for p in pending if p not in ready]
-        calls += [(g, j + 1 < len(ready)) for j, (g, _, _) in enumerate(ready)]
-    assert not pending, pending
-    return calls, launches
+            led.queue(*e[1:])
+        else:
+            calls += led.mark(e[1], wgrad_group_rounds, *e[2:])[1]      # ("b", group, on_side, force, force_img)
+    assert not led.pending, led.pending
+    return calls, led.log
 
 
 def collectives(cfg, calls):

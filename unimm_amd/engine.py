@@ -17,6 +17,7 @@ from __future__ import annotations
 import math
 import os
 import zlib
+from collections import namedtuple
 from contextlib import contextmanager
 from typing import Dict, List, Optional
 
@@ -59,6 +60,10 @@ class _LazyLN:
         self.x, self.mean, self.rstd, self.gamma, self.beta = x, mean, rstd, gamma, beta
 
 
+# One queued weight gradient dw[N,K] += dy[:M,:N]^T x[:M,:K], in the field order `lib.gemm_tn_grouped` takes
+_WGrad = namedtuple("_WGrad", "dy x dw M N K dbias m_dev overwrite", defaults=(None, None, False))
+
+
 class _Lin:
     """One (possibly fused) linear: bf16 weight [N,K], transposed bf16 copy [K,Npad], fp32 bias + grads."""
     __slots__ = ("w", "wt", "bias", "gw", "gb", "N", "K", "gbs")
@@ -83,7 +88,10 @@ class Engine:
         self._anchor = None
         self.last_seq_t = None
         self.unpad = True                # run the text stream on valid rows only (see the plan step of _forward)
-        self._wq = []                    # queued weight-gradient problems (text side) waiting for their grouped launch
+        # Weight gradients wait for a grouped launch, per side (0 = text, 1 = image: inside `_img()`).  The ledger, shared with
+        # the exchange planner, decides when a side is launched and which gradient buckets that completes; the operands wait here.
+        self._ledger = BP.Ledger()
+        self._wq, self._fq = [[], []], [[], []]   # queued _WGrad problems / column-partials reductions of LayerNorm backward calls
         # Schedule options are plain attributes (set them on `model.engine` before the first step; bench.py has flags for
         # the ones that are measured: --single-stream).  One environment switch: UNIMM_PRUNE_LAST_TEXT (see below).
         self.lazy_ln = True              # residual epilogues evaluate the previous LayerNorm instead of reading its fp32 output
@@ -109,8 +117,6 @@ class Engine:
         self.text_priority = False       # text side on an internal high-priority stream (measured -0.6 %: off)
         self._tstream = None
         self._on_side = False            # inside `_img()`: launches (and queued weight gradients) belong to the image side
-        self._wq_img = []
-        self._fq, self._fq_img = [], []  # pending column-partials reductions of LayerNorm backward calls, per stream
         self.last_plan = None
         self._arena_users = []           # weakrefs of objects that cache `self.arena` (FusedAdamW, DataParallelRCCL)
         # Partial-tile workspaces of the weight-gradient launches, one per launch stream (text / image / optional side).
@@ -122,7 +128,7 @@ class Engine:
         self._wgrad_ws = {}
         self._plist = []
         self.gemm_tile = 0               # tuning code handed to every encoder GEMM (unimm_gemm_nt_args.tile; 0 = automatic)
-        # Weight-gradient launches cover SEVERAL encoder blocks (see `_flush_due`): a launch is due once its 256x256 tiles
+        # Weight-gradient launches cover SEVERAL encoder blocks (see `_flush_wgrad`): a launch is due once its 256x256 tiles
         # fill about `wgrad_group_rounds` rounds of the chip; a data-parallel wrapper may lower it (smaller, earlier buckets).
         self.wgrad_group_rounds = 4
         # Row-count capacities.  Launch arguments hold CAPACITIES (the step's valid text rows / decoded rows rounded up to
@@ -148,10 +154,6 @@ class Engine:
         self.splitk = True
         self.splitk_ws_bytes = 48 << 20
         self._splitk_ws = {}
-        self._pending = []               # gradient buckets whose weight gradients are still queued: (group, #text, #image queued)
-        self._nq = [0, 0]                # weight-gradient problems ever queued (text side, image side) ...
-        self._nf = [0, 0]                # ... and launched
-        self._reported = set()
         self.host_staging = True         # CPU tensors handed to forward() go through a pinned staging ring + copy stream (stage_host_inputs)
         self._stager = None
         # The last text layer feeds nothing but the MLM head (on the labelled rows) and the text pooler (on the first-token
@@ -456,22 +458,23 @@ class Engine:
     def _wgrad(self, dy, x, gw, M, N, K, dbias=None, m_dev=None, sole=False, rule_M=None):
         """dW += dy^T x (+ bias gradient).  Nothing downstream in the backward chain reads a weight gradient,
         so the call is only queued; `_flush_wgrad` hands the list of SEVERAL encoder blocks to one grouped launch
-        (`_flush_due` says when).  dy / x stay referenced by the queue until then.
+        (the ledger says when).  dy / x stay referenced by the queue until then.
         sole: this call is the ONLY contribution to gw in a backward pass (every encoder nn.Linear; not the tied decoder /
         word-embedding matrix, not the three split-operand products of the fp32x3 mode).  When the gradient arena is also known
         to be zero (`arena.fresh`: zeroed since the last backward) the kernel then writes the tile with plain stores instead of
         256 KiB of memory-side atomics per workgroup (unimm_gemm_tn_args.overwrite).
-        rule_M: the row count the flush rule (`_flush_due`) counts this problem with, when it is not M: a block that runs on a
+        rule_M: the row count the flush rule counts this problem with, when it is not M: a block that runs on a
         subset of the step's rows (`_prune_rows`) keeps the step's row count there, so that grouped launches and bucket
         hand-overs fall where they always fell -- the subset's size differs between the ranks of a data-parallel step."""
-        ow = bool(sole and self._bwd_fresh and self.wgrad_overwrite)
-        (self._wq_img if self._on_side else self._wq).append((dy, x, gw, M, N, K, dbias, m_dev, ow, rule_M))
-        self._nq[1 if self._on_side else 0] += 1
+        self._wq[self._on_side].append(_WGrad(dy, x, gw, M, N, K, dbias, m_dev, bool(sole and self._bwd_fresh and self.wgrad_overwrite)))
+        self._ledger.queue(int(self._on_side), M if rule_M is None else rule_M, N, K)
         if self.prof_conn is not None:            # FLOPs of the weight gradients queued from inside / outside a connection layer
-            MM = dy.shape[0] if M is None else M
-            NN = dy.shape[1] if N is None else N
-            KK = x.shape[1] if K is None else K
-            self.prof_conn["tn_conn" if self.prof_conn["in"] else "tn_other"] += 2.0 * MM * NN * KK
+            self.prof_conn["tn_conn" if self.prof_conn["in"] else "tn_other"] += 2.0 * M * N * K
+
+    def _colsum(self, part, blocks, H, dsts):
+        """Queue the reduction of a LayerNorm backward's column partials into `dsts` for the side's next grouped launch."""
+        self._fq[self._on_side].append((part, blocks, H, dsts))
+        self._ledger.colsum(int(self._on_side))
 
     @contextmanager
     def _conn_tag(self):
@@ -489,29 +492,6 @@ class Engine:
             self.prof_conn["in"] = False
             L.prof_tag(0)
 
-    @staticmethod
-    def _big_tiles(queue):
-        """256x256 output tiles of the queue's problems that take the big tile (csrc/gemm.hip: tn_is_big)."""
-        t = 0
-        for dy, x, gw, M, N, K, *rest in queue:
-            M = dy.shape[0] if M is None else M
-            if len(rest) > 3 and rest[3] is not None:
-                M = rest[3]                       # (see _wgrad: rule_M)
-            N = dy.shape[1] if N is None else N
-            K = x.shape[1] if K is None else K
-            t += BP.big_tiles_of(M, N, K)
-        return t
-
-    def _flush_due(self, queue):
-        """Weight-gradient launches are grouped over blocks.  One block's 4-5 gradients are ~110 tiles: less than half a
-        round of the 256 CUs, so the launcher had to split the reduction 7 ways and every one of the 756 workgroups ended
-        by adding its 256 KiB partial tile with fp32 atomics (51 us per workgroup at the per-CU atomic rate against
-        118 us of main loop; 8x the algorithmic write traffic).  Nothing waits for a weight gradient, so the queue
-        simply keeps growing until its tiles fill whole rounds WITHOUT a split: each tile is then reduced by one
-        workgroup over all rows and written once (round 3: 484 -> 394 us per text block at 7 blocks per launch).
-        The rule itself is host arithmetic shared with the exchange planner: `bucket_plan.flush_due`."""
-        return BP.flush_due(len(queue), self._big_tiles(queue), self.wgrad_group_rounds)
-
     def _ws(self, which):
         """Zero-initialised workspace of the weight-gradient launches of one stream (0 bytes = fp32-atomic path)."""
         if self.wgrad_ws_bytes <= 0:
@@ -521,27 +501,27 @@ class Engine:
             t = self._wgrad_ws[which] = torch.zeros(self.wgrad_ws_bytes, dtype=torch.uint8, device=self.arena.flat.device)
         return t
 
-    def _flush_wgrad(self, force=False, force_img=False):
-        """Launch the queues that are due (all of them with force=True; force_img: the image side's whatever its size)."""
+    def _flush_wgrad(self, force=False, force_img=False, sides=None):
+        """Launch the sides the ledger names: `sides` as `_bucket_done` got them from its mark, else the ledger's direct flush
+        (all of them with force=True; force_img: the image side's whatever its size) for callers outside a backward.
+        Why launches are grouped over blocks: DESIGN.md, "Weight-gradient launches are grouped over blocks"."""
+        for side in self._ledger.flush(self.wgrad_group_rounds, self._on_side, force, force_img) if sides is None else sides:
+            self._launch_wgrad(side)
+
+    def _launch_wgrad(self, side):
+        probs, sums = self._wq[side], self._fq[side]
+        self._wq[side], self._fq[side] = [], []
         shared = self._dual()                     # the launches of this backward share the chip with the other stream's
-        if (self._wq_img or self._fq_img) and (force or force_img or self._flush_due(self._wq_img)):
+        if side:
             with self._img():                     # image-side problems: operands were produced on that stream
-                L.gemm_tn_grouped(self._wq_img, shared=shared, ws=self._ws("img"))
-                L.colpartials_finish_grouped(self._fq_img)
-            self._wq_img, self._fq_img = [], []
-            self._nf[1] = self._nq[1]
-        if self._on_side:
-            return                                # the text side's queues are flushed from the text side
-        if not (force or self._flush_due(self._wq)):
+                L.gemm_tn_grouped(probs, shared=shared, ws=self._ws("img"))
+                L.colpartials_finish_grouped(sums)
             return
-        L.colpartials_finish_grouped(self._fq)
-        self._fq = []
-        self._nf[0] = self._nq[0]
-        if not self._wq:
+        L.colpartials_finish_grouped(sums)
+        if not probs:
             return
         if not self.wgrad_stream:
-            L.gemm_tn_grouped(self._wq, shared=shared, ws=self._ws("txt"))
-            self._wq = []
+            L.gemm_tn_grouped(probs, shared=shared, ws=self._ws("txt"))
             return
         # side stream: the grouped launch ends with a partial last round and a memory-side atomic drain during
         # which most CUs idle; the next block's input-gradient GEMMs can fill them
@@ -550,11 +530,10 @@ class Engine:
             self._side = torch.cuda.Stream(device=self.arena.flat.device)
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side), L.stream_scope(self._side):
-            L.gemm_tn_grouped(self._wq, shared=shared, ws=self._ws("side"))
-        for dy, x, *_ in self._wq:              # keep the caching allocator from recycling them early
-            dy.record_stream(self._side)
-            x.record_stream(self._side)
-        self._wq = []
+            L.gemm_tn_grouped(probs, shared=shared, ws=self._ws("side"))
+        for p in probs:                           # keep the caching allocator from recycling them early
+            p.dy.record_stream(self._side)
+            p.x.record_stream(self._side)
 
     def _join_wgrad(self):
         if self._side is not None:
@@ -738,7 +717,7 @@ class Engine:
         part = torch.empty(self.part[H].numel(), dtype=F32, device=x.device)      # private until the grouped reduction
         blocks = L.layernorm_bwd_partials(dy, x, mean, rstd, gmm, dx, dxd, part, M, H, drop=drop, out_drop=out_drop, m_dev=m_dev,
                                           drop_rows=drop_rows)
-        (self._fq_img if self._on_side else self._fq).append((part, blocks, H, [gg, gb, dbias]))
+        self._colsum(part, blocks, H, [gg, gb, dbias])
         return dx, (dxd if dxd is not None else dx)
 
     # ------------------------------------------------------------------------------------------
@@ -1589,7 +1568,7 @@ class Engine:
         B, R = out["B"], out["R"]
         self.arena.attach_grads()
         self._bwd_fresh = bool(self.arena.fresh)   # gradients known to be zero: sole contributors may write instead of add (_wgrad)
-        self._reported = set()                     # gradient buckets reported done in this pass (_bucket_done)
+        self._ledger.begin()                       # no gradient bucket reported done in this pass yet (_bucket_done)
         if self._bwd_fresh and self.debug_fresh and bool(self.arena.grad_flat.any()):
             raise RuntimeError("the gradient arena is marked fresh (zeroed since the last backward) but holds non-zero values: "
                                "something wrote into .grad / grad_flat between zero_grad() and backward() without clearing "
@@ -1692,29 +1671,21 @@ class Engine:
         # blocks without a backward step (frozen layers, connection layers under with_coattention = False) still own a gradient
         # bucket: report them, so that a data-parallel wrapper sees every bucket once per step (their gradients are zero / None)
         for g, _, _ in self.arena.buckets:
-            if g not in self._reported and g != "text_embeddings":
+            if g not in self._ledger.reported and g != "text_embeddings":
                 self._bucket_done(g)
 
     def _bucket_done(self, group, force_img=False):
-        """A block's backward is enqueued.  Its weight gradients may stay queued for a later grouped launch (`_flush_due`);
-        the data-parallel hook of a bucket fires once the launches that cover it are enqueued.  Buckets are handed over as
-        they complete, not in the order they were finished: a bucket whose launches are out is not held back by an older one
-        that still waits for the other stream's queue (bucket_plan.py restates this rule on the host)."""
+        """A block's backward is enqueued: mark it in the ledger, launch the sides the ledger names and call the data-parallel
+        hook with the buckets it hands over.  A block's weight gradients may stay queued for a later grouped launch; its bucket
+        is handed over once the launches that cover it are enqueued (`bucket_plan.Ledger.mark`, which the planner drives too)."""
         last = group == "text_embeddings"
         force = last or group == "heads"          # the decoder's gradient has its own row count: a launch of its own
-        self._reported.add(group)
-        if self.grad_bucket_hook is not None:
-            self._pending.append((group, self._nq[0], self._nq[1]))
-        self._flush_wgrad(force=force, force_img=force_img)
-        if self.grad_bucket_hook is not None:
-            ready = [] if self._on_side else [p for p in self._pending if self._nf[0] >= p[1] and self._nf[1] >= p[2]]
-            if ready:
-                self._join_wgrad()                # the exchange reads them
-                self._to_txt()                    # ... including the ones the image side produced for these buckets
-                self._pending = [p for p in self._pending if p not in ready]
-                for j, (g, _, _) in enumerate(ready):
-                    self.grad_bucket_hook(g, j + 1 < len(ready))    # more: the next bucket follows at once (adjacent slices travel together)
-            assert not (last and self._pending), self._pending
-        elif last:                                # last bucket: everything joined before the caller continues
-            self._join_wgrad()
-            self._to_txt()                        # ... including the image side's last grouped launch
+        hook = self.grad_bucket_hook
+        sides, ready = self._ledger.mark(group, self.wgrad_group_rounds, self._on_side, force, force_img, hand_over=hook is not None)
+        self._flush_wgrad(sides=sides)
+        if ready or (last and hook is None):      # before the exchange reads them, or (last bucket) before the caller continues:
+            self._join_wgrad()                    # every grouped launch so far joined into this stream ...
+            self._to_txt()                        # ... including the ones the image side produced
+        for g, more in ready:
+            hook(g, more)                         # more: the next bucket follows at once (adjacent slices travel together)
+        assert not (last and self._ledger.pending), self._ledger.pending

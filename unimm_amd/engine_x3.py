@@ -180,10 +180,9 @@ class EngineX3(Engine):
         dxd3 = torch.empty((M, 3 * H), dtype=BF16, device=x.device) if want3 else None
         part = torch.empty(self.part[H].numel(), dtype=F32, device=x.device)
         blocks = L.x3_layernorm_bwd_partials(dy, x, mean, rstd, gmm, dx32, dxd3, part, M, H, drop=drop, out_drop=out_drop, m_dev=m_dev)
-        fq = self._fq_img if self._on_side else self._fq
-        fq.append((part, blocks, H, [gg, gb, dbias]))
+        self._colsum(part, blocks, H, [gg, gb, dbias])
         if dbias2 is not None:
-            fq.append((part, blocks, H, [None, None, dbias2]))
+            self._colsum(part, blocks, H, [None, None, dbias2])
         return dx32, dxd3
 
     def _attn(self, q, k, v, mask, B, H, Tq, Tk, D, drop, save, qvar=None, kvar=None, tag=None):
