@@ -442,6 +442,28 @@ int unimm_lm_loss_fwd(const float* logits, const int32_t* labels, const int32_t*
 int unimm_lm_loss_bwd(const float* logits, const int32_t* labels, const int32_t* weights, const float* lse,
                       const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld,
                       int32_t ldd, const int32_t* n_dev, const float* inv_dev, void* stream);
+/* Policy-gradient objective on decoded rows of SAMPLED answers (csrc/policy.hip, ABI 22; an extension: self-critical /
+ * importance-weighted fine-tuning on a sequence-level reward).  logits, labels, lse, rownll, n / n_dev / inv_dev, ld / ldd and
+ * the zero-filled columns >= V are those of unimm_lm_loss_*; V <= 65536.  The row's advantage A and behaviour log-probability
+ * b are read by the kernel: A = adv[pos[row]], b = blogp[pos[row]] (pos = the row's flat position b * T + t; pos == NULL:
+ * adv[row], blogp[row]); adv / blogp hold n_adv floats and a position outside [0, n_adv) makes the row an ignored one.
+ * With logp = z_y - lse and H = -sum_i p_i log p_i:
+ *   mode 0 (LOGP):   surr = A logp                                         (blogp is not read and may be NULL)
+ *   mode 1 (RATIO):  r = exp(logp - b), surr = min(r A, clamp(r, 1 - clip_eps, 1 + clip_eps) A)   (clip_eps = +inf: unclipped)
+ *   rowloss = -surr - beta H;  A == 0 gives surr = 0 whatever logp is;  ent = H is written for every row
+ *   label < 0:  rowloss = rownll = 0 and an all-zero gradient row (also with beta != 0)
+ * H comes out of the log-sum-exp pass (H = lse - sum_i e^(z_i - m) z_i / sum_i e^(z_i - m)): each logit is read once per
+ * direction; a -inf logit has p = 0 and contributes 0 to H and to its gradient.
+ *   dlogits[row, i] = g inv ( c (p_i - [i == y]) + beta p_i (log p_i + H) ),  c = A (LOGP);  c = A r (RATIO), or 0 where the
+ *   clipped branch is the strict minimum (A > 0 and r > 1 + clip_eps, or A < 0 and r < 1 - clip_eps).
+ * With beta = 0 and mode 0 both directions equal unimm_lm_loss_* with weight w = A bit for bit (A a positive integer). */
+int unimm_pg_loss_fwd(const float* logits, const int32_t* labels, const int32_t* pos, const float* adv, const float* blogp,
+                      int32_t n_adv, int32_t mode, float clip_eps, float beta, float* rowloss, float* rownll, float* lse,
+                      float* ent, int32_t n, int32_t V, int32_t ld, const int32_t* n_dev, void* stream);
+int unimm_pg_loss_bwd(const float* logits, const int32_t* labels, const int32_t* pos, const float* adv, const float* blogp,
+                      int32_t n_adv, int32_t mode, float clip_eps, float beta, const float* lse, const float* ent,
+                      const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
+                      const int32_t* n_dev, const float* inv_dev, void* stream);
 /* Masked-region KL (models/vilbert_dialog.py:1569-1574): rowloss = [label==1] * sum_j t_j (log t_j - logp_j) */
 int unimm_kl_loss_fwd(const float* pred, const float* target, const int32_t* label, float* rowloss, float* lse,
                       int32_t rows, int32_t C, int32_t ld, void* stream);

@@ -1,0 +1,158 @@
+"""The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
+
+    python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8]
+
+Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
+[rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
+(lm, pg, lm, pg, ...), each timing `launches` forward + backward pairs between two device events after a warm-up.  Per pair
+the tool prints both times and their ratio, then the medians and the run-to-run spread of the likelihood pair (max - min over
+its repeats, relative): a ratio further from 1 than that spread is a real difference.  Three objectives: "logp" with beta = 0
+(the kernel the bit-equality test compares), "logp" with the entropy bonus, "ratio" clipped with the entropy bonus.  Both pairs
+read each logit once per direction (2 x rows x 30522 x 4 bytes) and write rows x 30528 bf16 gradients; the achieved bytes/s
+are printed from that count.
+
+Step: one trainer.self_critical_step at G dialogs x N samples (baseline "mean": no greedy pass), split by host clocks around
+device synchronisations into sampling (generate_answers), assembly (the reward, self_critical_advantage,
+sampled_training_batch and spread: host only, each call clocked) and the train step (forward_backward + optimizer.step);
+`other_ms` is what remains of the step's wall time (mode switches, the scheduler, building the constant inputs)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CFG_PATH = os.path.join(ROOT, "unimm_amd", "config", "bert_base_6layer_6conect.json")
+V, LD = 30522, 30528
+
+
+def event_ms(fn, n):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def kernels(rows, pairs, launches):
+    from unimm_amd import lib as L
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn((rows, LD), generator=g) * 3).cuda()
+    labels = torch.randint(0, V, (rows,), generator=g).to(torch.int32).cuda()
+    weights = torch.ones(rows, dtype=torch.int32, device="cuda")
+    adv = torch.randn(rows, generator=g).cuda()
+    blogp = (-8.0 + torch.randn(rows, generator=g)).cuda()
+    f = lambda: torch.empty(rows, device="cuda")
+    rowloss, rownll, lse, ent = f(), f(), f(), f()
+    dlog = torch.empty((rows, LD), dtype=torch.bfloat16, device="cuda")
+    gvec = torch.ones(1, device="cuda")
+    inv = 1.0 / rows
+
+    def lm():
+        L.lm_loss_fwd(logits, labels, weights, rowloss, rownll, lse, rows, V)
+        L.lm_loss_bwd(logits, labels, weights, lse, gvec, inv, dlog, rows, V)
+
+    def pg(mode, eps, beta):
+        def run():
+            L.pg_loss_fwd(logits, labels, None, adv, blogp, mode, eps, beta, rowloss, rownll, lse, ent, rows, V)
+            L.pg_loss_bwd(logits, labels, None, adv, blogp, mode, eps, beta, lse, ent, gvec, inv, dlog, rows, V)
+        return run
+
+    nbytes = 2 * rows * V * 4 + rows * LD * 2
+    out = {}
+    for name, fn in (("logp", pg(L.PG_LOGP, float("inf"), 0.0)), ("logp_entropy", pg(L.PG_LOGP, float("inf"), 0.01)),
+                     ("ratio_clip_entropy", pg(L.PG_RATIO, 0.2, 0.01))):
+        t_lm, t_pg = [], []
+        for _ in range(pairs):
+            t_lm.append(event_ms(lm, launches))
+            t_pg.append(event_ms(fn, launches))
+        m_lm, m_pg = statistics.median(t_lm), statistics.median(t_pg)
+        spread = (max(t_lm) - min(t_lm)) / m_lm
+        print(f"{name}: lm fwd+bwd {m_lm * 1e3:.1f} us, pg fwd+bwd {m_pg * 1e3:.1f} us, ratio {m_pg / m_lm:.3f} "
+              f"(pairs {[round(p / q, 3) for p, q in zip(t_pg, t_lm)]}; lm spread {spread:.3f}); "
+              f"{nbytes / m_lm / 1e9:.2f} / {nbytes / m_pg / 1e9:.2f} TB/s")
+        out[name] = dict(lm_us=round(m_lm * 1e3, 1), pg_us=round(m_pg * 1e3, 1), ratio=round(m_pg / m_lm, 4),
+                         lm_spread=round(spread, 4), lm_TBps=round(nbytes / m_lm / 1e9, 3), pg_TBps=round(nbytes / m_pg / 1e9, 3))
+    return out
+
+
+def step(G, N):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_generate import dialogs
+    from oracle import vilbert_ref as RF
+    from unimm_amd import VisualDialogEncoder, policy, trainer
+    from unimm_amd.optim import FusedAdamW, WarmupLinearScheduleNonZero, default_language_weights, reference_param_groups
+    enc = VisualDialogEncoder(CFG_PATH)
+    enc.bert_pretrained.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    enc = enc.cuda()
+    groups = reference_param_groups(enc, lr=1e-5, image_lr=1e-5, language_weights=default_language_weights(enc))
+    opt = FusedAdamW(groups, enc.bert_pretrained.engine, lr=1e-5)
+    sch = WarmupLinearScheduleNonZero(opt, warmup_steps=2, t_total=100, min_lr=1e-6)
+    d, c = dialogs(G, seed=3)
+    batch = dict(tokens=d["input_ids"], segments=d["token_type_ids"], positions=d["position_ids"], context_len=c,
+                 image_feat=d["image_feat"], image_loc=d["image_loc"], image_mask=d["image_attention_mask"])
+    marks = {}
+    real_gen, real_fb = enc.generate_answers, enc.forward_backward
+
+    def clocked(name, fn):
+        def run(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn(*a, **kw)
+            torch.cuda.synchronize()
+            marks[name] = marks.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+            return r
+        return run
+
+    enc.generate_answers, enc.forward_backward = clocked("sampling", real_gen), clocked("train", real_fb)
+    opt.step = clocked("train", opt.step)
+    for name in ("sampled_training_batch", "spread", "self_critical_advantage"):       # the names the step calls
+        setattr(trainer, name, clocked("assembly", getattr(policy, name)))
+    reward = clocked("assembly", lambda tokens, lengths: -lengths.float())
+    rows = []
+    for it in range(1, 5):                                   # the first iterations warm every shape up
+        marks.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = trainer.self_critical_step(enc, opt, sch, batch, dict(batch_multiply=1), it, reward, samples=N, baseline="mean",
+                                         objective=policy.PolicyObjective(entropy_coef=0.01), temperature=0.8, top_k=50, top_p=0.9)
+        torch.cuda.synchronize()
+        total = (time.perf_counter() - t0) * 1e3
+        rows.append(dict(total_ms=round(total, 2), sampling_ms=round(marks["sampling"], 2), assembly_ms=round(marks["assembly"], 2),
+                         train_ms=round(marks["train"], 2),
+                         other_ms=round(total - marks["sampling"] - marks["assembly"] - marks["train"], 2), loss=out[0]))
+        print(f"self_critical_step {it} (G = {G}, N = {N}): {rows[-1]}")
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=5016)
+    ap.add_argument("--pairs", type=int, default=7)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--G", type=int, default=8)
+    ap.add_argument("--N", type=int, default=8)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_policy.py measures on the GPU: no device found")
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    result = dict(rows=a.rows, kernels=kernels(a.rows, a.pairs, a.launches))
+    if not a.no_step:
+        result["step"] = step(a.G, a.N)
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -21,7 +21,9 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// log-sum-exp of one fp32 row (16-byte loads when `vec`), block-wide
+// log-sum-exp of one fp32 row (16-byte loads when `vec`), block-wide.  csrc/policy.hip's row_lse_ent performs these operations on
+// m and s one for one (plus a third running sum): the policy step with integer advantages equals the weighted-likelihood step
+// bit for bit (tests/test_gpu_policy_model.py), so a change of the order of operations here is made there as well.
 __device__ __forceinline__ float row_lse(const float* __restrict__ z, int V, bool vec, float* red) {
   float m = -INFINITY, s = 0.f;
   if (vec) {

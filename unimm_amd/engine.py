@@ -87,6 +87,7 @@ class Engine:
         self.grad_bucket_hook = None     # set by the data-parallel wrapper: f(group_name, more_follow_at_once)
         self._anchor = None
         self.last_seq_t = None
+        self.last_lm_entropy = None      # fp32 [1]: mean entropy of the rows the last policy-gradient step trained (`_losses`)
         self.unpad = True                # run the text stream on valid rows only (see the plan step of _forward)
         # Weight gradients wait for a grouped launch, per side (0 = text, 1 = image: inside `_img()`).  The ledger, shared with
         # the exchange planner, decides when a side is launched and which gradient buckets that completes; the operands wait here.
@@ -1410,7 +1411,8 @@ class Engine:
                 else:
                     xs = torch.empty((n, W), dtype=BF16, device=dev)
                     L.gather_rows(seq_t, sel["idx"], xs, n, W, n_dev=dyn["n_lm"])
-                lm = self._lm_head(xs, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"])
+                lm = self._lm_head(xs, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"],
+                                   policy=self._policy_inputs(inp, sel["pos"], dev))
                 lm.update(idx=sel["idx"], pos_idx=sel["pos"], n=n, n_dev=dyn["n_lm"], inv_dev=dyn["inv_lm"])
             out["lm"] = lm
         elif lm_rows == "all":
@@ -1448,13 +1450,31 @@ class Engine:
         _, hn, mean, rstd = self._layernorm(t, ln_key, save, want32=False)
         return t, u, hn, mean, rstd, self._linear(hn, dec, out_f32=True, ldo=ldo)
 
-    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None):
+    def _policy_inputs(self, inp, pos, dev):
+        """`lm_advantage` given (unimm_amd/policy.py): what the policy-gradient row kernels read -- the decoded rows' flat
+        positions, fp32 [B * T] advantages and behaviour log-probabilities on the device, the objective.  None otherwise."""
+        adv = inp.get("lm_advantage")
+        if adv is None:
+            return None
+        obj = inp["lm_objective"]
+        flat = lambda t: t.to(dev, dtype=F32, non_blocking=True).contiguous().reshape(-1)
+        blogp = inp.get("lm_behaviour_logp")
+        return dict(pos=pos, adv=flat(adv), blogp=flat(blogp) if obj.mode == "ratio" else None,
+                    mode=L.PG_RATIO if obj.mode == "ratio" else L.PG_LOGP, eps=float(obj.clip_eps), beta=float(obj.entropy_coef))
+
+    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None, policy=None):
         V = self.cfg.vocab_size
         t1, u, hn, mean, rstd, logits = self._transform_head(xs, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(V, 64), save)
         rowloss, rownll, lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
-        L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
+        ent = None
+        if policy is not None:                 # the advantage-weighted objective on sampled answers, entropy kept with lse
+            ent = torch.empty(n, dtype=F32, device=xs.device)
+            L.pg_loss_fwd(logits, lab_sel, policy["pos"], policy["adv"], policy["blogp"], policy["mode"], policy["eps"],
+                          policy["beta"], rowloss, rownll, lse, ent, n, V, n_dev=n_dev)
+        else:
+            L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
         return dict(xs=xs, t1=t1, u=u, hn=hn, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll,
-                    lse=lse, labels=lab_sel, weights=w_sel)
+                    lse=lse, labels=lab_sel, weights=w_sel, policy=policy, ent=ent)
 
     def decode_rows(self, x, n):
         """MLM transform + decoder for n rows of the GEMM operand x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
@@ -1475,6 +1495,12 @@ class Engine:
     def _lm_loss_grad(self, lm, g_lm):
         n, V = lm["n"], self.cfg.vocab_size          # n is a capacity: the real count lives on the device (n_dev)
         dlog = torch.empty((n, _rup(V, 64)), dtype=BF16, device=self.arena.device)
+        pg = lm.get("policy")
+        if pg is not None:
+            L.pg_loss_bwd(lm["logits"], lm["labels"], pg["pos"], pg["adv"], pg["blogp"], pg["mode"], pg["eps"], pg["beta"],
+                          lm["lse"], lm["ent"], self._gvec(g_lm), 1.0 / n, dlog, n, V, n_dev=lm.get("n_dev"),
+                          inv_dev=lm.get("inv_dev"))
+            return dlog
         L.lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], self._gvec(g_lm), 1.0 / n, dlog, n, V,
                       n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
         return dlog
@@ -1521,6 +1547,10 @@ class Engine:
             lm_loss.fill_(float("nan"))        # 0 / 0 in the reference when nothing is labelled
         else:
             L.reduce_sum(lm["rowloss"], lm["n"], lm_loss, 1.0 / lm["n"], n_dev=lm.get("n_dev"), scale_dev=lm.get("inv_dev"))
+            if lm.get("ent") is not None:      # the policy-gradient step reports the mean entropy of the rows it trained
+                self.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
+                L.reduce_sum(lm["ent"], lm["n"], self.last_lm_entropy, 1.0 / lm["n"], n_dev=lm.get("n_dev"),
+                             scale_dev=lm.get("inv_dev"))
         res["lm_loss"] = lm_loss
         # image KL
         img = out["img"]

@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -103,7 +103,9 @@ SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "uni
            "unimm_x3_kl_loss_bwd", "unimm_x3_rows_add", "unimm_x3_attn_fwd", "unimm_x3_attn_bwd", "unimm_x3_attn_set_impl", "unimm_x3_layernorm_fwd", "unimm_prof_tag", "unimm_prof_tagged",
            "unimm_sum_dropout", "unimm_sum_dropout_bwd", "unimm_mse_loss_fwd", "unimm_mse_loss_bwd", "unimm_host_mask_pack", "unimm_host_memcpy",
            # answer generation (csrc/generate.hip, ABI 19; sampling ABI 20)
-           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk", "unimm_lm_sample"]
+           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk", "unimm_lm_sample",
+           # policy-gradient objective on sampled answers (csrc/policy.hip, ABI 22)
+           "unimm_pg_loss_fwd", "unimm_pg_loss_bwd"]
 
 
 def _check(rc, what):
@@ -705,6 +707,27 @@ def lm_loss_bwd(logits, labels, weights, lse, g, inv_denom, dlogits, n, V, n_dev
     _check(lib().unimm_lm_loss_bwd(_ptr(logits), _ptr(labels), _ptr(weights), _ptr(lse), _ptr(g), C.c_float(inv_denom),
                                    _ptr(dlogits), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)),
                                    C.c_int32(dlogits.stride(0)), _ptr(n_dev), _ptr(inv_dev), _stream()), "unimm_lm_loss_bwd")
+
+
+PG_LOGP, PG_RATIO = 0, 1
+
+
+def pg_loss_fwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, rowloss, rownll, lse, ent, n, V, n_dev=None):
+    """Policy-gradient rows (include/unimm_hip.h: unimm_pg_loss_fwd).  adv / blogp: fp32, indexed by pos[row] (pos None: by row)."""
+    _dev(logits, labels, pos, adv, blogp, rowloss, rownll, lse, ent, n_dev)
+    _check(lib().unimm_pg_loss_fwd(_ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), C.c_int32(adv.numel()),
+                                   C.c_int32(mode), C.c_float(clip_eps), C.c_float(beta), _ptr(rowloss), _ptr(rownll), _ptr(lse),
+                                   _ptr(ent), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)), _ptr(n_dev), _stream()),
+           "unimm_pg_loss_fwd")
+
+
+def pg_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, ent, g, inv_denom, dlogits, n, V, n_dev=None,
+                inv_dev=None):
+    _dev(logits, labels, pos, adv, blogp, lse, ent, g, dlogits, n_dev, inv_dev)
+    _check(lib().unimm_pg_loss_bwd(_ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), C.c_int32(adv.numel()),
+                                   C.c_int32(mode), C.c_float(clip_eps), C.c_float(beta), _ptr(lse), _ptr(ent), _ptr(g),
+                                   C.c_float(inv_denom), _ptr(dlogits), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)),
+                                   C.c_int32(dlogits.stride(0)), _ptr(n_dev), _ptr(inv_dev), _stream()), "unimm_pg_loss_bwd")
 
 
 def kl_loss_fwd(pred, target, label, rowloss, lse, rows, Cn):

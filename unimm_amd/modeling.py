@@ -15,6 +15,7 @@ from torch import nn
 from . import params as PM
 from .config import BertConfig
 from .engine import Engine
+from .policy import check_policy_inputs
 
 logger = logging.getLogger(__name__)
 
@@ -184,7 +185,8 @@ class BertForMultiModalPreTraining(nn.Module):
                 position_ids=None, attention_mask=None, image_attention_mask=None, co_attention_mask=None,
                 masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None,
                 output_all_attention_masks=False, nsp_weight=None, lm_weight=None,
-                _want_lm_scores=True, _want_pred_v=True, image_index=None):
+                _want_lm_scores=True, _want_pred_v=True, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
+                lm_objective=None):
         """Same contract as models/vilbert_dialog.py:1519-1626.  `sep_indices` / `sep_len` are accepted and
         ignored exactly as the reference's embeddings do (:326-356).  Train branch (labels, NSP label and
         image target all given) -> (lm_loss[1], img_loss[1], nsp_loss[1], seq_out_t, pred_t, nsp[B,2]);
@@ -193,7 +195,12 @@ class BertForMultiModalPreTraining(nn.Module):
         skips materialising the dense [B,T,vocab] logits; the loss only ever needs the labelled rows.
         Extensions (unimm_amd/inputs.py): `attention_mask` may be a `DialogMaskSpec`
         (then `co_attention_mask` must be None) and `image_feat` / `image_loc` / `image_target` may hold one
-        entry per IMAGE with `image_index` [B] mapping sequences to them."""
+        entry per IMAGE with `image_index` [B] mapping sequences to them.  `lm_advantage` (fp32 [B, T], with
+        `lm_behaviour_logp` and `lm_objective`: unimm_amd/policy.py) makes lm_loss the policy-gradient objective on the
+        labelled rows instead of the weighted likelihood; bf16 engine, train branch."""
+        train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
+        lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
+                                           self.compute_dtype, train_branch)
         eng = self._engine
         dev = self._device()
         eng.ensure(dev)
@@ -201,11 +208,11 @@ class BertForMultiModalPreTraining(nn.Module):
                    position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
-                   lm_weight=lm_weight, image_index=image_index)
+                   lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
         eng.stage_host_inputs(inp)             # the reference's callers pass CPU tensors (train.py:113-161): pinned ring + copy stream
         B, T = input_ids.shape
         H, V = self.config.hidden_size, self.config.vocab_size
-        train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         if self.training:
             eng.step += 1
         if train_branch:
@@ -239,7 +246,8 @@ class BertForMultiModalPreTraining(nn.Module):
     def forward_backward(self, input_ids, image_feat, image_loc, loss_weights, sep_indices=None, sep_len=None, token_type_ids=None,
                          position_ids=None, attention_mask=None, image_attention_mask=None, co_attention_mask=None,
                          masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None, nsp_weight=None,
-                         lm_weight=None, image_index=None, plan_header=None):
+                         lm_weight=None, image_index=None, plan_header=None, lm_advantage=None, lm_behaviour_logp=None,
+                         lm_objective=None):
         """The training step's forward AND backward in one call (an extension; the reference writes
         `loss = c_lm * lm.mean() + c_nsp * nsp.mean() + c_img * img.mean(); loss.backward()`, train.py:164-168, :315).
         loss_weights = (c_lm, c_nsp, c_img).  With the weights known up front the backward does not wait for the host to see
@@ -247,7 +255,10 @@ class BertForMultiModalPreTraining(nn.Module):
         (a hand-over to the autograd thread and ~8 one-element launches between the halves: 0.2-0.4 ms during which a
         30-sequence step's GPU idles).  Parameter gradients accumulate into `.grad` exactly as with `loss.backward()`.
         -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits).  plan_header: `engine.count_rows(...)` of this batch if the caller
-        has it already (a prefetcher: the step then starts without its host sync)."""
+        has it already (a prefetcher: the step then starts without its host sync).  lm_advantage / lm_behaviour_logp /
+        lm_objective: as in `forward` (the policy-gradient step always runs eagerly)."""
+        lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
+                                           self.compute_dtype)
         if masked_lm_labels is None or next_sentence_label is None or image_target is None:
             raise ValueError("forward_backward needs the training inputs (masked_lm_labels, next_sentence_label, image_target)")
         eng = self._engine
@@ -257,7 +268,8 @@ class BertForMultiModalPreTraining(nn.Module):
                    position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
-                   lm_weight=lm_weight, image_index=image_index)
+                   lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
         eng.stage_host_inputs(inp)
         if plan_header is not None:
             inp["_plan_header"] = plan_header
@@ -363,13 +375,15 @@ class VisualDialogEncoder(nn.Module):
                 token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
                 head_mask=None, random_round_indices=None, output_nsp_scores=False, output_lm_scores=False,
                 image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
-                nsp_weight=None, lm_weight=None, image_index=None):
+                nsp_weight=None, lm_weight=None, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
+                lm_objective=None):
         masked_lm_loss = masked_img_loss = nsp_loss = None
         kw = dict(sep_indices=sep_indices, sep_len=sep_len, token_type_ids=token_type_ids,
                   position_ids=token_position_ids, attention_mask=attention_mask, masked_lm_labels=masked_lm_labels,
                   next_sentence_label=next_sentence_label, image_attention_mask=image_attention_mask,
                   co_attention_mask=co_attention_mask, image_label=image_label, image_target=image_target,
-                  nsp_weight=nsp_weight, lm_weight=lm_weight, _want_lm_scores=output_lm_scores, image_index=image_index)
+                  nsp_weight=nsp_weight, lm_weight=lm_weight, _want_lm_scores=output_lm_scores, image_index=image_index,
+                  lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
         if next_sentence_label is not None and masked_lm_labels is not None and image_target is not None:
             masked_lm_loss, masked_img_loss, nsp_loss, _, prediction_scores_t, seq_relationship_score = \
                 self.bert_pretrained(input_ids, image_feat, image_loc, **kw)
@@ -397,7 +411,8 @@ class VisualDialogEncoder(nn.Module):
     def forward_backward(self, input_ids, image_feat, image_loc, loss_weights, sep_indices=None, sep_len=None, token_type_ids=None,
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
                          image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
-                         nsp_weight=None, lm_weight=None, image_index=None, plan_header=None):
+                         nsp_weight=None, lm_weight=None, image_index=None, plan_header=None, lm_advantage=None,
+                         lm_behaviour_logp=None, lm_objective=None):
         """forward + `(c_lm * lm + c_nsp * nsp + c_img * img).backward()` in one call, loss_weights = (c_lm, c_nsp, c_img)
         (BertForMultiModalPreTraining.forward_backward).  -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits)."""
         return self.bert_pretrained.forward_backward(
@@ -405,4 +420,4 @@ class VisualDialogEncoder(nn.Module):
             position_ids=token_position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
             co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label, image_target=image_target,
             next_sentence_label=next_sentence_label, nsp_weight=nsp_weight, lm_weight=lm_weight, image_index=image_index,
-            plan_header=plan_header)
+            plan_header=plan_header, lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)

@@ -1,0 +1,171 @@
+"""Policy-gradient fine-tuning of the answer generator on a sequence-level reward (an extension; the reference trains the
+generative head by likelihood only).
+
+`generate_answers(samples=N)` draws N answers per dialog and returns, per token, log p under the model (step_logp) and log q
+under the distribution it was drawn from (step_logq).  A host-side reward (NDCG of the answer, an answer-quality metric, a
+preference score) turns into a per-sequence advantage, and the LM head's objective on the [MASK]-copy rows of the sampled
+sequences becomes (csrc/policy.hip, include/unimm_hip.h: unimm_pg_loss_fwd / _bwd)
+
+    mode "logp"    -A log p_y                                              REINFORCE / self-critical
+    mode "ratio"   -min(r A, clamp(r, 1 - clip_eps, 1 + clip_eps) A)       r = p_y / q_y; clip_eps = inf: importance-weighted
+    both           -entropy_coef H(p)                                      entropy bonus of the row's distribution
+
+summed over the labelled rows and divided by their number, exactly where the weighted likelihood sits otherwise: the row-sparse
+decoder, the transform head's backward, the weight-gradient ledger and the data-parallel buckets are the training step's.
+
+This module is host-side: the objective's description, the refusals, the assembly of the training batch from the sampled
+answers (the layout `utils/data_utils.py:139-288` gives a generative sequence; `oracle/masks.py::encode_gen` restates it) and the
+advantage arithmetic.  The data is small and on the host anyway, where the reward is computed.  `trainer.self_critical_step`
+is the loop body."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from .inputs import DialogMaskSpec
+
+SEP, MASK = 102, 103
+
+
+@dataclass(frozen=True)
+class PolicyObjective:
+    """mode: "logp" | "ratio"; clip_eps: the ratio's clipping range (inf = none); entropy_coef: weight of the entropy bonus."""
+    mode: str = "logp"
+    clip_eps: float = math.inf
+    entropy_coef: float = 0.0
+
+    def __post_init__(self):
+        if self.mode not in ("logp", "ratio"):
+            raise ValueError(f"PolicyObjective: mode must be 'logp' or 'ratio', got {self.mode!r}")
+        if not float(self.clip_eps) >= 0.0:
+            raise ValueError(f"PolicyObjective: clip_eps must be >= 0 (inf = no clipping), got {self.clip_eps}")
+        if not math.isfinite(float(self.entropy_coef)):
+            raise ValueError(f"PolicyObjective: entropy_coef must be finite, got {self.entropy_coef}")
+
+
+def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, compute_dtype, train_branch=True):
+    """The refused combinations of the policy-gradient arguments of `forward` / `forward_backward` (ValueError, before
+    anything touches the device) -> the objective in force (None without `lm_advantage`).  train_branch: whether the call
+    computes the losses (labels, NSP label and image target all given)."""
+    if lm_advantage is None:
+        if lm_behaviour_logp is not None or lm_objective is not None:
+            raise ValueError("lm_behaviour_logp / lm_objective describe the policy-gradient objective: pass lm_advantage "
+                             "(fp32 [B, T]) with them, or drop them for the likelihood objective")
+        return None
+    if lm_weight is not None:
+        raise ValueError("lm_weight (the integer likelihood / unlikelihood weights) and lm_advantage (the policy-gradient "
+                         "objective) are two objectives for the same rows: pass one of them")
+    if compute_dtype != "bf16":
+        raise ValueError(f"the policy-gradient objective runs on the bf16 engine only: build the model with "
+                         f"compute_dtype='bf16' (got {compute_dtype!r})")
+    obj = PolicyObjective() if lm_objective is None else lm_objective
+    if not isinstance(obj, PolicyObjective):
+        raise ValueError(f"lm_objective must be a policy.PolicyObjective, got {type(lm_objective).__name__}")
+    if obj.mode == "ratio" and lm_behaviour_logp is None:
+        raise ValueError("PolicyObjective(mode='ratio') weighs each token by p / q: pass lm_behaviour_logp (fp32 [B, T], the "
+                         "step_logq of generate_answers spread over the copy rows), or use mode='logp'")
+    B, T = (int(x) for x in shape)
+    for name, t in (("lm_advantage", lm_advantage), ("lm_behaviour_logp", lm_behaviour_logp)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (B, T)):
+            got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+            raise ValueError(f"{name} must be a tensor of shape [B, T] = {(B, T)} like input_ids (one value per token, read on "
+                             f"the labelled rows), got {got}: build it with policy.spread")
+    if not train_branch:
+        raise ValueError("lm_advantage weighs the LM loss of the train branch: pass masked_lm_labels, next_sentence_label and "
+                         "image_target with it (this call computes no loss and would ignore it)")
+    return obj
+
+
+@dataclass
+class SampledBatch:
+    """The sampled answers of G dialogs as K <= G * N generative training sequences of T tokens (hypotheses of length 0 dropped)."""
+    input_ids: torch.Tensor          # int64 [K, T]: context, answer tokens + [SEP], the [MASK] copy block
+    token_type_ids: torch.Tensor     # int64 [K, T]
+    position_ids: torch.Tensor       # int64 [K, T]
+    masked_lm_labels: torch.Tensor   # int64 [K, T]: -1 except on the copy rows (the answer's tokens + [SEP])
+    attention_mask: DialogMaskSpec   # mode 1, length c + n, answer n
+    image_index: torch.Tensor        # int64 [K]: the sequence's dialog (= its image)
+    copy_rows: torch.Tensor          # bool [K, T]
+    kept: torch.Tensor               # int64 [K]: g * N + j of every sequence
+    shape: tuple                     # (G, N)
+
+
+def sampled_training_batch(input_ids, token_type_ids, position_ids, context_len, answers, T):
+    """G dialog contexts (the first context_len[g] tokens of input_ids / token_type_ids / position_ids, as `generate_answers`
+    took them) + a GeneratedAnswers with N hypotheses each -> SampledBatch.  Answer token k and its [MASK] copy get position id
+    position_ids[g, c-1] + 1 + k and segment token_type_ids[g, c-1] ^ 1 (generation.answer_ids)."""
+    ids, tt, pp = (np.asarray(t.cpu() if torch.is_tensor(t) else t).astype(np.int64) for t in (input_ids, token_type_ids, position_ids))
+    c_all = np.asarray(context_len.cpu() if torch.is_tensor(context_len) else context_len).astype(np.int64).reshape(-1)
+    tokens = answers.tokens.cpu().numpy().astype(np.int64)
+    lengths = answers.lengths.cpu().numpy().astype(np.int64)
+    G, N = lengths.shape
+    if ids.shape[0] != G or c_all.shape[0] != G:
+        raise ValueError(f"sampled_training_batch: {ids.shape[0]} contexts / {c_all.shape[0]} context lengths for the answers of {G} dialogs")
+    kept = [(g, j) for g in range(G) for j in range(N) if lengths[g, j] > 0]
+    K = len(kept)
+    out_ids, out_tt, out_pp = (np.zeros((K, T), np.int64) for _ in range(3))
+    labels = np.full((K, T), -1, np.int64)
+    copy = np.zeros((K, T), bool)
+    L, n_all = np.zeros(K, np.int64), np.zeros(K, np.int64)
+    for k, (g, j) in enumerate(kept):
+        c, n = int(c_all[g]), int(lengths[g, j])
+        if c + 2 * n > T:
+            raise ValueError(f"sampled_training_batch: dialog {g} (context {c}) with an answer of {n} tokens needs {c + 2 * n} "
+                             f"positions, more than T = {T}: generate with the same T")
+        ans = tokens[g, j, :n]
+        out_ids[k, :c], out_tt[k, :c], out_pp[k, :c] = ids[g, :c], tt[g, :c], pp[g, :c]
+        out_ids[k, c:c + n], out_ids[k, c + n:c + 2 * n] = ans, MASK
+        out_tt[k, c:c + 2 * n] = tt[g, c - 1] ^ 1
+        out_pp[k, c:c + n] = out_pp[k, c + n:c + 2 * n] = pp[g, c - 1] + 1 + np.arange(n)
+        labels[k, c + n:c + 2 * n] = ans
+        copy[k, c + n:c + 2 * n] = True
+        L[k], n_all[k] = c + n, n
+    T_ = torch.from_numpy
+    flat = np.array([g * N + j for g, j in kept], np.int64)
+    return SampledBatch(input_ids=T_(out_ids), token_type_ids=T_(out_tt), position_ids=T_(out_pp), masked_lm_labels=T_(labels),
+                        attention_mask=DialogMaskSpec(np.ones(K), L, n_all), image_index=T_(flat // max(N, 1)),
+                        copy_rows=T_(copy), kept=T_(flat), shape=(G, N))
+
+
+def spread(values, batch: SampledBatch):
+    """values [G, N] (one per sequence) or [G, N, W] (one per answer token: step_logq / step_logp) -> fp32 [K, T] with the
+    value(s) on the sequence's copy rows and zero elsewhere."""
+    v = torch.as_tensor(values).detach().to("cpu", torch.float32)
+    G, N = batch.shape
+    if tuple(v.shape[:2]) != (G, N) or v.dim() not in (2, 3):
+        raise ValueError(f"spread: values must be [G, N] or [G, N, W] with (G, N) = {(G, N)}, got {tuple(v.shape)}")
+    per_sequence = v.dim() == 2
+    v = v.reshape(G * N, -1)[batch.kept]                       # [K, 1 | W]
+    n = batch.copy_rows.sum(1)
+    out = torch.zeros(batch.copy_rows.shape, dtype=torch.float32)
+    if per_sequence:
+        out[batch.copy_rows] = v[:, 0].repeat_interleave(n)
+    else:
+        if int(n.max()) > v.shape[1]:
+            raise ValueError(f"spread: {v.shape[1]} values per answer, but an answer has {int(n.max())} tokens")
+        out[batch.copy_rows] = v[torch.arange(v.shape[1])[None, :] < n[:, None]]
+    return out
+
+
+def self_critical_advantage(rewards, baseline):
+    """rewards [G, N] -> advantages [G, N] (fp32, host).  baseline: a [G] tensor (the reward of the dialog's greedy answer:
+    self-critical sequence training), "mean" (for sample j the mean reward of the dialog's OTHER samples; N >= 2) or None."""
+    r = torch.as_tensor(rewards).detach().to("cpu", torch.float32)
+    if r.dim() != 2:
+        raise ValueError(f"self_critical_advantage: rewards must be [G, N], got {tuple(r.shape)}")
+    if baseline is None:
+        return r.clone()
+    if isinstance(baseline, str):
+        if baseline != "mean":
+            raise ValueError(f"self_critical_advantage: baseline must be a [G] tensor, 'mean' or None, got {baseline!r}")
+        N = r.shape[1]
+        if N < 2:
+            raise ValueError("self_critical_advantage: baseline='mean' is the mean of the other samples and needs N >= 2")
+        return r - (r.sum(1, keepdim=True) - r) / (N - 1)
+    b = torch.as_tensor(baseline).detach().to("cpu", torch.float32).reshape(-1)
+    if b.shape[0] != r.shape[0]:
+        raise ValueError(f"self_critical_advantage: {b.shape[0]} baselines for {r.shape[0]} dialogs")
+    return r - b[:, None]

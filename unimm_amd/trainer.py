@@ -13,6 +13,8 @@ dataloader and the checkpoint file, without the data plane.
 * `dense_finetune_step` - one iteration of dense_annotation_finetuning.py:146-301 (row F4): one annotated
                        round of one image against its 100 options (ground truth first, the rest permuted),
                        NeuralNDCG^T + LM + weighted NSP objective, scheduler stepped before the optimizer.
+* `self_critical_step` - one iteration of policy-gradient fine-tuning of the answer generator on a host-side
+                       reward (an extension, unimm_amd/policy.py): sample answers, score them, train on the advantage.
 * `visdial_evaluate`  - the validation pass of train.py:180-290 (chunked NSP scoring -> SparseGTMetrics + NDCG).
 * `generative_evaluate` - the validation pass of val_lm.py:38-150 (candidates ranked by sequence log-likelihood)."""
 from __future__ import annotations
@@ -23,6 +25,7 @@ from typing import Optional
 import torch
 
 from . import harness, metrics, ranking
+from .policy import PolicyObjective, sampled_training_batch, self_critical_advantage, spread
 
 
 def expand_image_fields(batch: dict) -> dict:
@@ -98,6 +101,70 @@ def dense_finetune_step(dialog_encoder, optimizer, scheduler, batch, params, ite
         optimizer.step()
         optimizer.zero_grad()
     return float(loss.detach()) / bm, {k: v.detach() for k, v in parts.items()}
+
+
+def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
+                       objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None):
+    """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
+    `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
+    [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
+    The model draws `samples` answers per dialog in eval mode (and, for baseline="greedy", its greedy answer);
+    `reward_fn(tokens [G, N, W], lengths [G, N]) -> rewards [G, N]` scores them on the host; the advantage (reward minus the
+    greedy reward, minus the mean of the dialog's other samples for "mean", or the reward itself for None) weighs the
+    `objective` on every token of its answer; mode "ratio" corrects for temperature / top-k / nucleus sampling with the
+    tokens' step_logq.  The train-mode step is `forward_backward` on the LM term alone, with the `batch_multiply` /
+    `no_sync` / `sync_gradients` cadence of `train_step`.  seed: of the draws (default iter_id).
+    -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
+    distributions; NaN when the step decoded no row)."""
+    bm = int(params.get("batch_multiply", 1))
+    boundary = iter_id % bm == 0
+    model = _unwrap(dialog_encoder)
+    T = batch["tokens"].shape[1]
+    gen_args = (batch["tokens"], batch["image_feat"], batch["image_loc"], batch["context_len"])
+    gen_kw = dict(token_type_ids=batch["segments"], position_ids=batch["positions"], image_attention_mask=batch.get("image_mask"),
+                  max_answer_len=max_answer_len)
+    dialog_encoder.eval()
+    answers = model.generate_answers(*gen_args, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p,
+                                     seed=iter_id if seed is None else seed, **gen_kw)
+    rewards = torch.as_tensor(reward_fn(answers.tokens.cpu(), answers.lengths.cpu())).to("cpu", torch.float32)
+    if isinstance(baseline, str) and baseline == "greedy":
+        greedy = model.generate_answers(*gen_args, beams=1, **gen_kw)
+        base = torch.as_tensor(reward_fn(greedy.tokens.cpu(), greedy.lengths.cpu())).to("cpu", torch.float32).reshape(-1)
+    else:
+        base = baseline
+    advantage = self_critical_advantage(rewards, base)
+    sb = sampled_training_batch(batch["tokens"], batch["segments"], batch["positions"], batch["context_len"], answers, T)
+    K, (G, R) = sb.input_ids.shape[0], batch["image_feat"].shape[:2]
+    if K == 0:
+        raise ValueError("self_critical_step: every sampled answer has length 0, there is nothing to train on")
+    # the step trains the LM term only (loss_weights (1, 0, 0)); the NSP and region terms still run and must stay finite:
+    # label 0 everywhere, one labelled region per sequence against a uniform target distribution
+    engine = (model.bert_pretrained if hasattr(model, "bert_pretrained") else model).engine
+    image_label = torch.zeros((K, R), dtype=torch.int64)
+    image_label[:, 0] = 1
+    C = engine.cfg.v_target_size
+    dialog_encoder.train()
+    engine.last_lm_entropy = None               # set by this step's losses (never a value an earlier step left behind)
+    sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
+    with sync_ctx:
+        _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
+            sb.input_ids, batch["image_feat"], batch["image_loc"], (1.0 / bm, 0.0, 0.0), token_type_ids=sb.token_type_ids,
+            token_position_ids=sb.position_ids, attention_mask=sb.attention_mask, masked_lm_labels=sb.masked_lm_labels,
+            next_sentence_label=torch.zeros(K, dtype=torch.int64),
+            image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
+            image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+            lm_advantage=spread(advantage, sb), lm_objective=objective,
+            lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None)
+    entropy = engine.last_lm_entropy
+    if boundary:
+        if hasattr(dialog_encoder, "sync_gradients"):
+            dialog_encoder.sync_gradients()
+        optimizer.step()
+        optimizer.zero_grad()
+    scheduler.step()
+    trained = rewards.reshape(-1)[sb.kept], advantage.reshape(-1)[sb.kept]      # hypotheses of length 0 took no part
+    return (float(lm_loss), float(trained[0].mean()), float((trained[0] - trained[1]).mean()),
+            float(entropy) if entropy is not None else float("nan"))
 
 
 def eval_chunk_size(n_gpus: int) -> int:
