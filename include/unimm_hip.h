@@ -192,7 +192,8 @@ typedef struct {
    * else private row j - ks_len[b]; the sequence has k_len[b] + ks_len[b] <= 256 keys and the mask words index key positions.
    * The position count is clamped to Tk, ks_len[b] < 0 is taken as 0, and nothing outside the two row ranges is read.
    * ks_off and ks_len come together or not at all; a segment without k_off / k_len, with ks_ins < 0 or with drop_thr != 0 is
-   * UNIMM_E_ARG before any launch.  Both backward entry points have no such fields and never take a segment.
+   * UNIMM_E_ARG before any launch.  unimm_attn_bwd and unimm_x3_attn_bwd have no such fields and never take a segment: the training
+   * pair of the spliced launch is unimm_attn_spliced_fwd / unimm_attn_spliced_bwd below.
    * Generative scoring (val_lm.py:52-121): the 100 candidate answers of a dialog round attend the round's context rows,
    * which are computed once (utils/data_utils.py:199-210: context rows never see the answer).  ABI 16. */
   const int32_t* ks_off; const int32_t* ks_len;
@@ -233,6 +234,50 @@ typedef struct {
 } unimm_attn_bwd_args;
 
 int unimm_attn_bwd(const unimm_attn_bwd_args* args, void* stream);
+
+/* Training pair of the spliced launch (ABI 23): sequences whose private query rows attend their own rows and a SHARED key/value
+ * segment (ks_off / ks_len / ks_ins above) -- N sampled answers of one dialog over the dialog's context rows, which are projected
+ * once (unimm_amd/engine.py, the shared-context training step).
+ * unimm_attn_spliced_fwd: unimm_attn_fwd's launch (same struct, same key-position rule, same kernels: with dropout off the two
+ * are bit-identical) with lse required and attention dropout allowed; the dropout counter of (b, h, query q, key POSITION j) is
+ * ((b*H+h)*Tq+q)*Tk+j as everywhere.
+ * Limits of both: D = 64; Tq <= 32 (at most 32 private rows per sequence); Tk <= 256 and k_len[b] + ks_len[b] <= 256; q_off .. k_len,
+ * ks_off and ks_len given; ks_ins >= 0.  Anything else: UNIMM_E_ARG (alignment: UNIMM_E_ALIGN, the rules above), before any launch.
+ *
+ * unimm_attn_spliced_bwd: the fields of unimm_attn_bwd_args, the segment, and the GROUPS of sequences that name the same segment:
+ * g_seq (int32 [B], device) lists the launch's sequences group by group, g_first (int32 [G+1]) is where each group starts in it.
+ * Members of a group need not be adjacent in the batch.  The group's segment is that of its first member with ks_len > 0; a member
+ * with ks_len <= 0 attends its private rows only and adds nothing to the segment's rows.
+ *   dq          rows of each sequence's private queries
+ *   dk / dv     rows of each sequence's private keys, written once;
+ *               rows of each group's segment: the sum over the group's sequences, accumulated in fp32 and rounded to bf16 ONCE.
+ *               accumulate != 0: that one rounding is of (what the rows hold + the sum) -- the S x S self-attention backward
+ *               (unimm_attn_bwd over the segments) writes its dk / dv into the same rows first.
+ * P is recomputed from Q, K and lse, the dropout mask from the key, delta = rowsum(dO o out) of the GIVEN out inside the kernel:
+ * `delta` and `order` are not read (a workgroup is one (group, head): list the largest groups first).  One workgroup walks its group's
+ * sequences in list order and holds the segment's dK / dV in registers: no atomics, no scratch, the same bits on every launch.
+ * A segment no listed sequence names gets nothing written. */
+int unimm_attn_spliced_fwd(const unimm_attn_args* args, void* stream);
+typedef struct {
+  const void* q; const void* k; const void* v; const void* out; const void* dout; /* bf16 */
+  const float* lse; float* delta;
+  void* dq; void* dk; void* dv; /* bf16 */
+  const uint32_t* mask;
+  const int32_t* q_off; const int32_t* q_len; const int32_t* k_off; const int32_t* k_len;
+  int32_t B, H, Tq, Tk, D;
+  int32_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
+  int32_t mask_q_stride, mask_b_stride;
+  float scale;
+  uint32_t drop_key, drop_thr; float drop_scale;
+  const uint32_t* drop_salt;
+  const int32_t* order;
+  const int32_t* ks_off; const int32_t* ks_len;
+  int32_t ks_ins;
+  const int32_t* g_first; const int32_t* g_seq;
+  int32_t G;
+  int32_t accumulate;
+} unimm_attn_spliced_bwd_args;
+int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Row kernels (HBM-bound).
@@ -353,6 +398,16 @@ int unimm_embed_fwd(const unimm_embed_args* args, float* y32, void* y16, void* s
  * position / extension-type gradient tables; dtype [2, H], dgamma, dbeta accumulated via partials. */
 int unimm_embed_bwd(const unimm_embed_args* args, const void* dy, float* dword, float* dpos, float* dtype,
                     float* dext, float* dgamma, float* dbeta, float* partials, void* stream);
+/* The same without the atomics (ABI 23): the gradient of every embedded row is STORED in drow (fp32 [M, H]) and no table is
+ * touched; dtype, dgamma, dbeta as above.  unimm_rows_scatter_sum_f32 then adds the rows into a table in a fixed order:
+ * dst[keys[j]] += src[order[j]] over the list positions j of one key, one writer per destination row, the addends in a fixed order
+ * (eight interleaved partial sums in list order, then added in order) -- keys int32 [M] ascending (negative or >= n_dst: skipped)
+ * and order int32 [M] as a stable sort of the rows' table indices gives them; H <= 1024 (UNIMM_E_SHAPE).  The
+ * embedding gradient of the shared-context training step: a step repeats bit for bit. */
+int unimm_embed_bwd_rows(const unimm_embed_args* args, const void* dy, float* drow, float* dtype, float* dgamma, float* dbeta,
+                         float* partials, void* stream);
+int unimm_rows_scatter_sum_f32(const float* src, const int32_t* keys, const int32_t* order, int32_t M, int32_t H, float* dst,
+                               int32_t n_dst, void* stream);
 
 /* db[N] += column sums of dy (bf16 [M, N], row stride ld): bias gradients. */
 int unimm_colsum(const void* dy, float* db, int32_t M, int32_t N, int32_t ld, void* stream);
@@ -370,6 +425,13 @@ int unimm_transpose_bf16(const void* src, void* dst, int32_t R, int32_t C, int32
  * slabs + s * stride.  n a multiple of 8, stride of 4, 16-byte aligned pointers.  The fixed-order reduction of the
  * per-chunk partial sums of the split decoder input gradient (see unimm_transpose_bf16). */
 int unimm_sum_slabs_bf16(const float* slabs, int32_t count, int64_t stride, void* out, int64_t n, void* stream);
+/* Segmented sum of row BLOCKS (ABI 23): src holds n_items blocks of R rows x W bf16 (row stride lds), block g of dst (R rows, row
+ * stride ldd) = the sum of the blocks items[first[g]] .. items[first[g + 1] - 1], added in fp32 in list order, rounded once; first
+ * int32 [G + 1], items int32 (device).  W, lds, ldd multiples of 8, 16-byte aligned pointers.  The region gradients of the
+ * shared-context training step: every text block of a group attends the group's regions, the text-attends-regions backward
+ * writes one copy of dK / dV per block and this adds a group's copies up -- the same bits on every run. */
+int unimm_segment_rows_sum_bf16(const void* src, int32_t lds, const int32_t* first, const int32_t* items, int32_t n_items,
+                                int32_t G, void* dst, int32_t ldd, int32_t R, int32_t W, void* stream);
 /* The same for `count` matrices in one launch.  `table` is a DEVICE array; entry i owns blocks
  * [tile0_i, tile0_{i+1}) with ceil(C/32) * ceil(ldd/32) blocks each (tile0 ascending, tile0_0 = 0);
  * total_tiles = their sum.  Used after the optimizer step to rebuild every transposed weight copy. */

@@ -1,6 +1,6 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
-    python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8]
+    python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
 [rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
@@ -14,7 +14,13 @@ are printed from that count.
 Step: one trainer.self_critical_step at G dialogs x N samples (baseline "mean": no greedy pass), split by host clocks around
 device synchronisations into sampling (generate_answers), assembly (the reward, self_critical_advantage,
 sampled_training_batch and spread: host only, each call clocked) and the train step (forward_backward + optimizer.step);
-`other_ms` is what remains of the step's wall time (mode switches, the scheduler, building the constant inputs)."""
+`other_ms` is what remains of the step's wall time (mode switches, the scheduler, building the constant inputs).
+
+--shared (instead of the above): the train-mode step of one sampled batch of G dialogs x N answers in its two forms --
+`forward_backward` on G x N full sequences (replicated) and `forward_backward(shared_context=<dialog of each sequence>)`, which
+computes each dialog's context and image once -- as alternating pairs in one process after a warm-up: wall time per step between
+device synchronisations (medians, every pair's ratio, the replicated step's run-to-run spread), the device kernels each form
+launches per step with the mean duration of its text self-attention backward kernel (torch.profiler), and the packed row counts."""
 from __future__ import annotations
 
 import argparse
@@ -136,6 +142,86 @@ def step(G, N):
     return rows
 
 
+def shared(G, N, pairs):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_generate import dialogs
+    from oracle import vilbert_ref as RF
+    from unimm_amd import VisualDialogEncoder, policy
+    enc = VisualDialogEncoder(CFG_PATH)
+    enc.bert_pretrained.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    enc = enc.cuda()
+    eng = enc.bert_pretrained.engine
+    d, c = dialogs(G, seed=3)
+    T, R, C = d["input_ids"].shape[1], d["image_feat"].shape[1], eng.cfg.v_target_size
+    enc.eval()
+    # (answers of at most 14 tokens: 1 + 2 (14 + 1) = 31 private rows, the shared step's one query tile)
+    ans = enc.generate_answers(d["input_ids"], d["image_feat"], d["image_loc"], c, token_type_ids=d["token_type_ids"],
+                               position_ids=d["position_ids"], image_attention_mask=d["image_attention_mask"],
+                               samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1, max_answer_len=14)
+    sb = policy.sampled_training_batch(d["input_ids"], d["token_type_ids"], d["position_ids"], c, ans, T)
+    K = sb.input_ids.shape[0]
+    adv = policy.self_critical_advantage(-ans.lengths.cpu().float(), "mean" if N > 1 else None)
+    label = torch.zeros((K, R), dtype=torch.int64)
+    label[:, 0] = 1
+    kw = dict(token_type_ids=sb.token_type_ids, token_position_ids=sb.position_ids, attention_mask=sb.attention_mask,
+              masked_lm_labels=sb.masked_lm_labels, next_sentence_label=torch.zeros(K, dtype=torch.int64),
+              image_attention_mask=d["image_attention_mask"][sb.image_index.to(d["image_attention_mask"].device)],
+              image_label=label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+              lm_advantage=policy.spread(adv, sb), lm_objective=policy.PolicyObjective(entropy_coef=0.01))
+    enc.train()
+
+    def one(share):
+        eng.arena.zero_grads()
+        return enc.forward_backward(sb.input_ids, d["image_feat"], d["image_loc"], (1.0, 0.0, 0.0),
+                                    **kw, **(dict(shared_context=sb.image_index) if share else {}))[1]
+
+    def wall_ms(share, n=3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            one(share)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    def launches(share):
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                one(share)
+                torch.cuda.synchronize()
+            ev = [e for e in prof.events() if str(e.device_type).endswith("CUDA")]
+            attn = {}                                          # the text self-attention backward kernels: launches, mean us
+            for e in ev:
+                for key in ("attn_spliced_bwd", "attn_bwd_fused"):
+                    if key in e.name:
+                        t = getattr(e, "device_time", None)
+                        a = attn.setdefault(key, [0, 0.0])
+                        a[0] += 1
+                        a[1] += float(t if t is not None else e.cuda_time)
+            return dict(launches=len(ev), **{k: dict(launches=v[0], mean_us=round(v[1] / v[0], 1)) for k, v in attn.items()})
+        except Exception as e:                                 # the counts are a report, not a result
+            return f"unavailable ({type(e).__name__}: {e})"
+
+    losses = {s_: float(one(s_)) for s_ in (False, True)}
+    for s_ in (False, True):                                   # warm every shape up
+        wall_ms(s_, 2)
+    t_rep, t_sh = [], []
+    for _ in range(pairs):
+        t_rep.append(wall_ms(False))
+        t_sh.append(wall_ms(True))
+    m_rep, m_sh = statistics.median(t_rep), statistics.median(t_sh)
+    n_ans = sb.attention_mask.answer.astype(np.int64)
+    ctx = (sb.attention_mask.length.astype(np.int64) - n_ans)
+    first = np.unique(sb.image_index.numpy(), return_index=True)[1]
+    res = dict(G=G, N=N, sequences=K, replicated_ms=round(m_rep, 3), shared_ms=round(m_sh, 3), ratio=round(m_sh / m_rep, 4),
+               pair_ratios=[round(a / b, 3) for a, b in zip(t_sh, t_rep)], replicated_spread=round((max(t_rep) - min(t_rep)) / m_rep, 4),
+               text_rows_replicated=int((ctx + 2 * n_ans).sum()), text_rows_shared=int((ctx[first] - 1).sum() + (1 + 2 * n_ans).sum()),
+               region_rows_replicated=K * R, region_rows_shared=len(first) * R,
+               launches_replicated=launches(False), launches_shared=launches(True), loss_replicated=losses[False], loss_shared=losses[True])
+    print(f"shared-context step (G = {G}, N = {N}): {res}")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=5016)
@@ -144,10 +230,14 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--G", type=int, default=8)
     ap.add_argument("--N", type=int, default=8)
+    ap.add_argument("--shared", action="store_true", help="time the shared-context train step beside the replicated one")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
     torch.set_num_threads(min(16, torch.get_num_threads()))
+    if a.shared:
+        print(json.dumps(dict(shared=shared(a.G, a.N, a.pairs))))
+        return
     result = dict(rows=a.rows, kernels=kernels(a.rows, a.pairs, a.launches))
     if not a.no_step:
         result["step"] = step(a.G, a.N)

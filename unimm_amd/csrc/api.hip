@@ -1,5 +1,5 @@
 // ABI identification.
 #include "common.h"
 
-extern "C" int unimm_version(void) { return 22; }
+extern "C" int unimm_version(void) { return 23; }
 extern "C" const char* unimm_arch(void) { return "gfx950"; }

@@ -1442,6 +1442,297 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fewk128_kernel(AttnBwdParams 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward of the SPLICED text self-attention (unimm_attn_spliced_fwd: the private query rows of a sequence attend their own
+// rows and their group's shared key/value segment, D = 64, at most 32 private rows, at most 256 key positions).
+// The orientation of attn_bwd_fused_kernel, one workgroup per (group, head): wave w holds tile w of the SHARED segment (32 keys on
+// the lanes: K / V images in LDS, the fp32 dK / dV accumulators in registers for the whole walk) and wave 7 the current sequence's
+// <= 32 PRIVATE keys (when the segment has an eighth tile, both: its shared accumulators are parked in LDS meanwhile).  The workgroup walks the group's sequences: a sequence's Q / dO rows,
+// -lse, delta and the mask words of every key tile (re-aligned from key POSITIONS to the tile's keys) are staged in LDS, every
+// wave forms S, dP, P, dS of its tile against the one query tile, adds into its dK / dV and leaves dS^T in its LDS tile; two
+// waves then form dQ^T over all key tiles, in tile order.  The private wave stores its dK / dV per sequence; the shared tiles are
+// rounded to bf16 ONCE, after the walk (with `accumulate`, together with what the rows already hold).  No atomics, no scratch:
+// the result does not depend on how workgroups are scheduled.
+// LDS: Q / dO images 8 KiB + words 1.4 KiB + dS tiles 18 KiB + K images 40 KiB + V images 36 KiB + parking 16 KiB = 119 KiB.
+// ------------------------------------------------------------------------------------------------
+struct AttnSplBwdParams {
+  AttnBwdParams b;
+  const int* ks_off; const int* ks_len; int ks_ins;
+  const int* g_first; const int* g_seq; int G;
+  int accumulate;
+};
+
+// 32 mask bits of one row from key position pos0 on (words past the row's nw words read as 0)
+__device__ __forceinline__ uint32_t mask_bits_at(const uint32_t* mr, int nw, int pos0) {
+  const int w = pos0 >> 5, sh = pos0 & 31;
+  const uint32_t lo = w < nw ? mr[w] : 0u, hi = w + 1 < nw ? mr[w + 1] : 0u;
+  return sh == 0 ? lo : (lo >> sh) | (hi << (32 - sh));
+}
+
+// bwd_score_tile for a tile whose lane holds the key at POSITION kpos (any parity: every lane hashes its own words);
+// lin0 = linear hash stage of (query 0, kpos), halfm = words per query row * M1, fsh = 16 (kpos & 1)
+__device__ __forceinline__ void spl_score_tile(const DropoutArg& drop, uint32_t lin0, uint32_t halfm, uint32_t fsh, uint32_t thr16,
+                                               float dsc, float c1, bool dropping, const f32x16& sacc, const f32x16& dpacc,
+                                               const float* lse_s, const float* del_s, const uint32_t* mrow, int r, int h,
+                                               float (&pd)[16], float (&ds)[16]) {
+  constexpr float MOFF = -10000.0f * LOG2E;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    const int qb = 8 * g4 + 4 * h;        // 4 consecutive queries for registers 4*g4 .. 4*g4+3
+    const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_s + qb);
+    const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_s + qb);
+    const u32x4 w4 = *reinterpret_cast<const u32x4*>(mrow + qb);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = 4 * g4 + i;
+      const uint32_t mb = (uint32_t)__builtin_amdgcn_sbfe((int)w4[i], (uint32_t)r, 1) & __builtin_bit_cast(uint32_t, MOFF);
+      float tk = dsc;
+      if (dropping) {
+        const uint32_t w = drop_fin(drop, lin0 + (uint32_t)(qb + i) * halfm);
+        tk = __builtin_amdgcn_ubfe(w, fsh, 16) >= thr16 ? dsc : 0.0f;
+      }
+      const float pe = __builtin_amdgcn_exp2f(sacc[e] * c1 + (l4[i] + __uint_as_float(mb)));
+      pd[e] = pe * tk;
+      ds[e] = pe * (dpacc[e] * tk - d4[i]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(512, 2) void attn_spliced_bwd_kernel(AttnSplBwdParams sp) {
+  constexpr int D = 64, NT = 9, PT = 8, PW = 7, IMG = 32 * 2 * D;   // PT: the private tile, PW: its wave; IMG: bytes of a 32-row image
+  AttnBwdParams& p = sp.b;
+  drop_resolve(p.drop);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* qimg = smem;
+  char* doimg = smem + IMG;
+  float* lse_s = reinterpret_cast<float*>(smem + 2 * IMG);
+  float* del_s = lse_s + 32;
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + 32);     // [key tile][query] INVERTED mask words of the tile's keys
+  char* scr = reinterpret_cast<char*>(mw_s + NT * 32);          // [key tile][32 keys][32 queries] bf16 dS^T
+  char* kimg = scr + NT * 2048;                                 // [8 shared tiles + 2 private (alternating)][32 keys][D] bf16
+  char* vimg = kimg + (NT + 1) * IMG;                           // [key tile][32 keys][D] bf16
+  float* park = reinterpret_cast<float*>(vimg + NT * IMG);      // [64 registers][64 lanes]: see `both` below
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = blockIdx.x / p.H, head = blockIdx.x % p.H;
+  const int r = lane & 31, h = lane >> 5;
+  const int nw = (p.Tk + 31) >> 5;
+
+  int m0 = sp.g_first[g], m1 = sp.g_first[g + 1];
+  m0 = m0 < 0 ? 0 : m0;
+  m1 = m1 > p.B ? p.B : m1;
+  // the group's segment: that of its first member that names one
+  int slen = 0;
+  size_t soff = 0;
+  for (int m = m0; m < m1 && slen == 0; ++m) {
+    const int b = sp.g_seq[m];
+    if (b < 0 || b >= p.B) continue;
+    const int l = sp.ks_len[b];
+    if (l > 0) { slen = l < 256 ? l : 256; soff = (size_t)sp.ks_off[b]; }
+  }
+  const int nst = (slen + 31) >> 5;                             // shared key tiles
+  const bool is_priv = wave == PW;
+  // A segment of more than 224 rows has a tile for the private wave too.  That wave then runs both passes per sequence, and its
+  // shared accumulators wait in LDS while the registers serve the private tile.
+  const bool both = is_priv && nst > PW;
+
+  // The wave's 32 keys (rows first .. first + n - 1 of k / v) as LDS images: K / V row fragments for S and dP, K^T for dQ.  Rows past
+  // n are zero, so what those lanes compute never reaches dQ.  (A wave reads its own images without a barrier: its LDS accesses
+  // execute in order.)
+  auto load_keys = [&](size_t first, int n, char* kt, char* vt) {
+    const bool ok = r < n;
+    const size_t row = first + (ok ? r : n - 1);
+    const bf16_t* kg = p.k + row * p.ldk + head * D;
+    const bf16_t* vg = p.v + row * p.ldv + head * D;
+#pragma unroll
+    for (int ks = 0; ks < D / 16; ++ks) {
+      u32x4 kv = *reinterpret_cast<const u32x4*>(kg + 16 * ks + 8 * h);
+      u32x4 vv = *reinterpret_cast<const u32x4*>(vg + 16 * ks + 8 * h);
+      if (!ok) { kv = u32x4{0u, 0u, 0u, 0u}; vv = kv; }
+      *reinterpret_cast<u32x4*>(kt + r * (2 * D) + (((2 * ks + h) ^ swz<D>(r)) << 4)) = kv;
+      *reinterpret_cast<u32x4*>(vt + r * (2 * D) + (((2 * ks + h) ^ swz<D>(r)) << 4)) = vv;
+    }
+  };
+  const bool shared_on = wave < nst;
+  const int sn = slen - 32 * wave < 32 ? slen - 32 * wave : 32;   // (shared waves) keys of the wave's tile
+  if (shared_on) load_keys(soff + 32 * wave, sn, kimg + wave * IMG, vimg + wave * IMG);
+
+  f32x16 dk[D / 32], dv[D / 32];
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
+  const uint32_t halfw = ((uint32_t)p.Tk + 1u) >> 1, halfm = halfw * DROP_M1;
+  const float c1 = p.scale * LOG2E;
+  const bool dropping = p.drop.thr != 0u;
+  const uint32_t thr16 = dropping ? (p.drop.thr >> 16) : 0u;
+  const float dsc = dropping ? p.drop.scale : 1.0f;
+  int pbuf = 0;                                                 // which private K image this sequence uses
+
+#pragma unroll 1
+  for (int m = m0; m < m1; ++m) {
+    const int b = sp.g_seq[m];
+    if (b < 0 || b >= p.B) continue;
+    int ql = p.q_len[b], kl = p.k_len[b];
+    ql = ql < 32 ? ql : 32; ql = ql < p.Tq ? ql : p.Tq;
+    kl = kl < 0 ? 0 : (kl < 32 ? kl : 32);
+    const bool has_s = sp.ks_len[b] > 0 && slen > 0;
+    const int Ts = has_s ? slen : 0;
+    if (ql <= 0 || kl + Ts <= 0) continue;                       // (workgroup-uniform)
+    const int ins = sp.ks_ins < kl ? sp.ks_ins : kl;             // private rows ahead of the segment
+    const size_t qbase = (size_t)p.q_off[b], kbase = (size_t)p.k_off[b];
+    const int nsh = has_s ? nst : 0;
+    const bool s_on = wave < nsh, p_on = is_priv && kl > 0;
+    pbuf ^= 1;
+
+    // ---- stage the sequence's query tile
+    stage_head<D>(p.q + qbase * p.ldq + head * D, p.ldq, ql, 32, qimg, tid, blockDim.x);
+    stage_head<D>(p.dout + qbase * p.lddo + head * D, p.lddo, ql, 32, doimg, tid, blockDim.x);
+    if (tid >= 256) {                                            // delta = rowsum(dO o O): 8 lanes share a row
+      const int i = tid - 256, row = i >> 3, c = i & 7;
+      float part = 0.f;
+      if (row < ql) {
+        const u32x4 a = *reinterpret_cast<const u32x4*>(p.dout + (qbase + row) * p.lddo + head * D + 8 * c);
+        const u32x4 o = *reinterpret_cast<const u32x4*>(p.o + (qbase + row) * p.ldo + head * D + 8 * c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          part = fmaf(__uint_as_float(a[e] << 16), __uint_as_float(o[e] << 16), part);
+          part = fmaf(__uint_as_float(a[e] & 0xffff0000u), __uint_as_float(o[e] & 0xffff0000u), part);
+        }
+      }
+#pragma unroll
+      for (int o = 1; o < 8; o <<= 1) part += __shfl_xor(part, o, 64);
+      if (c == 0) del_s[row] = part;
+      if (i < 32) lse_s[i] = i < ql ? -p.lse[((size_t)b * p.H + head) * p.Tq + i] * LOG2E : -INFINITY;
+    }
+    if (tid < NT * 32) {                                         // mask words of (tile, query), in the tile's key order
+      const int t = tid >> 5, qi = tid & 31;
+      const int qc = qi < ql ? qi : ql - 1;
+      const uint32_t* mr = p.mask + (size_t)b * p.mask_b_stride + (size_t)qc * p.mask_q_stride;
+      uint32_t bits, pad;
+      if (t < PT) {                                              // shared keys 32 t ..: positions ins + 32 t ..
+        bits = mask_bits_at(mr, nw, ins + 32 * t);
+        const int n = Ts - 32 * t;
+        pad = n >= 32 ? 0u : (n <= 0 ? ~0u : ~0u << n);
+      } else {                                                   // private key i: position i below ins, else i + Ts
+        const uint32_t lo = mask_bits_at(mr, nw, 0), hi = mask_bits_at(mr, nw, ins + Ts);
+        bits = ins >= 32 ? lo : ((lo & ((1u << ins) - 1u)) | (hi << ins));
+        pad = kl >= 32 ? 0u : ~0u << kl;
+      }
+      mw_s[t * 32 + qi] = ~bits | pad;
+    }
+    if (p_on) load_keys(kbase, kl, kimg + (PT + pbuf) * IMG, vimg + PT * IMG);
+    stage_wait();
+    __syncthreads();
+
+    // S, dP, P, dS of key tile t (its key on the lane, at position kpos) against the query tile; dS^T to the tile's LDS image
+    // (row = key, 4 consecutive queries per store: what dQ is formed from), dV and dK into the wave's accumulators
+    auto tile_pass = [&](int t, const char* kt, int kpos) {
+      const char* vt = vimg + t * IMG;
+      char* ws = scr + t * 2048;
+      const uint32_t lin0 = drop_lin(p.drop, ((uint32_t)b * p.H + head) * (uint32_t)p.Tq * halfw + ((uint32_t)kpos >> 1));
+      f32x16 sacc = {}, dpacc = {};
+#pragma unroll
+      for (int ks = 0; ks < D / 16; ++ks) {
+        const bf16x8 qf = read_row_frag<D>(qimg, r, 2 * ks + h);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, read_row_frag<D>(kt, r, 2 * ks + h), sacc, 0, 0, 0);
+        const bf16x8 df = read_row_frag<D>(doimg, r, 2 * ks + h);
+        dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, read_row_frag<D>(vt, r, 2 * ks + h), dpacc, 0, 0, 0);
+      }
+      float pd[16], ds[16];
+      spl_score_tile(p.drop, lin0, halfm, ((uint32_t)kpos & 1u) << 4, thr16, dsc, c1, dropping, sacc, dpacc, lse_s, del_s,
+                     mw_s + t * 32, r, h, pd, ds);
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+        *reinterpret_cast<u32x2*>(ws + r * 64 + (((2 * g4 + h) ^ tile64_swz(r)) << 3)) =
+            u32x2{pack2bf(ds[4 * g4], ds[4 * g4 + 1]), pack2bf(ds[4 * g4 + 2], ds[4 * g4 + 3])};
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+        const bf16x8 pf = pack8(pd + 8 * ss);
+        const bf16x8 dsf = pack8(ds + 8 * ss);
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt) {
+          const bf16x8 dotf = read_tr_frag<D>(doimg, 16 * ss, 32 * dt, lane);
+          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf, pf, dv[dt], 0, 0, 0);
+          const bf16x8 qtf = read_tr_frag<D>(qimg, 16 * ss, 32 * dt, lane);
+          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf, dsf, dk[dt], 0, 0, 0);
+        }
+      }
+    };
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {                       // (one copy of the code: the two passes inlined do not fit the registers)
+      const bool priv = pass == 1;
+      if (priv ? !p_on : !s_on) continue;                        // (wave-uniform: the lane swap of the stores needs every lane)
+      if (priv) {
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            if (both) { park[(32 * dt + e) * 64 + lane] = dk[dt][e]; park[(32 * dt + 16 + e) * 64 + lane] = dv[dt][e]; }
+            dk[dt][e] = 0.f; dv[dt][e] = 0.f;
+          }
+      }
+      const int t = priv ? PT : wave;
+      tile_pass(t, kimg + (priv ? PT + pbuf : wave) * IMG, priv ? (r < ins ? r : r + Ts) : ins + 32 * wave + r);
+      if (priv) {
+        const bool ok = r < kl;
+        store_acc_row<D>(p.dk + (kbase + (ok ? r : 0)) * p.lddk + head * D, dk, p.scale, h, ok);
+        store_acc_row<D>(p.dv + (kbase + (ok ? r : 0)) * p.lddv + head * D, dv, 1.0f, h, ok);
+        if (both) {
+#pragma unroll
+          for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { dk[dt][e] = park[(32 * dt + e) * 64 + lane]; dv[dt][e] = park[(32 * dt + 16 + e) * 64 + lane]; }
+        }
+      }
+    }
+    __syncthreads();                                             // every tile's dS^T is in LDS
+    // ---- dQ^T, output-stationary: wave 5 + dt owns the 32-wide slice dt of D over every key tile, in tile order (the K^T
+    // fragments are transposed reads of the tiles' K images).  The other waves go on to stage the next sequence: nothing read
+    // here is rewritten before the next staging barrier, the private K image alternates.
+    if (wave == 5 || wave == 6) {
+      const int dt = wave - 5;
+      f32x16 dq1[1] = {f32x16{}};
+      const int ntile = nsh + (kl > 0 ? 1 : 0);
+      for (int i = 0; i < ntile; ++i) {
+        const int t = i < nsh ? i : PT;
+        const char* ki = kimg + (t == PT ? PT + pbuf : t) * IMG;
+#pragma unroll
+        for (int ss = 0; ss < 2; ++ss) {
+          const bf16x8 ktf = read_tr_frag<D>(ki, 16 * ss, 32 * dt, lane);
+          const bf16x8 dstf = read_tr_tile64s(scr + t * 2048, 16 * ss, lane);
+          dq1[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf, dstf, dq1[0], 0, 0, 0);
+        }
+      }
+      const bool ok = r < ql;
+      store_acc_row<32>(p.dq + (qbase + (ok ? r : 0)) * p.lddq + head * D + 32 * dt, dq1, p.scale, h, ok);
+    }
+  }
+
+  if (shared_on) {                                               // the segment's rows: one rounding of the fp32 sums
+    const bool ok = r < sn;
+    bf16_t* dkg = p.dk + (soff + 32 * wave + (ok ? r : 0)) * p.lddk + head * D;
+    bf16_t* dvg = p.dv + (soff + 32 * wave + (ok ? r : 0)) * p.lddv + head * D;
+    if (!sp.accumulate) {
+      store_acc_row<D>(dkg, dk, p.scale, h, ok);
+      store_acc_row<D>(dvg, dv, 1.0f, h, ok);
+    } else if (ok) {                                             // ... together with what the rows hold
+#pragma unroll
+      for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const int d0 = 32 * dt + 8 * gg + 4 * h;               // registers 4 gg .. 4 gg + 3 = columns d0 .. d0 + 3
+          u32x2* pk = reinterpret_cast<u32x2*>(dkg + d0);
+          u32x2* pv = reinterpret_cast<u32x2*>(dvg + d0);
+          const u32x2 hk = *pk, hv = *pv;
+          *pk = u32x2{pack2bf(fmaf(dk[dt][4 * gg], p.scale, __uint_as_float(hk[0] << 16)),
+                              fmaf(dk[dt][4 * gg + 1], p.scale, __uint_as_float(hk[0] & 0xffff0000u))),
+                      pack2bf(fmaf(dk[dt][4 * gg + 2], p.scale, __uint_as_float(hk[1] << 16)),
+                              fmaf(dk[dt][4 * gg + 3], p.scale, __uint_as_float(hk[1] & 0xffff0000u)))};
+          *pv = u32x2{pack2bf(dv[dt][4 * gg] + __uint_as_float(hv[0] << 16), dv[dt][4 * gg + 1] + __uint_as_float(hv[0] & 0xffff0000u)),
+                      pack2bf(dv[dt][4 * gg + 2] + __uint_as_float(hv[1] << 16), dv[dt][4 * gg + 3] + __uint_as_float(hv[1] & 0xffff0000u))};
+        }
+    }
+  }
+}
+
 // Workgroups per (sequence, head).  Default: one workgroup (up to 8 waves) per item.  Two 4-wave
 // workgroups per item fit two to a CU and overlap each other's staging, but both stage the full K/V
 // (or Q/dO) images: measured 589 vs 545 us for the text fwd+bwd trio, so it stays a tuning knob.
@@ -1640,7 +1931,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, float* __
 
 }  // namespace
 
-extern "C" int unimm_attn_fwd(const unimm_attn_args* a, void* stream) {
+// unimm_attn_fwd, and (train_seg) unimm_attn_spliced_fwd: the same launch with dropout allowed beside a shared segment
+static int attn_fwd_entry(const unimm_attn_args* a, void* stream, bool train_seg) {
   if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->mask) return UNIMM_E_ARG;
   if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->Tk <= 0 || a->Tq > 256 || a->Tk > 256) return UNIMM_E_SHAPE;
   if (a->D != 64 && a->D != 128) return UNIMM_E_SHAPE;
@@ -1653,7 +1945,7 @@ extern "C" int unimm_attn_fwd(const unimm_attn_args* a, void* stream) {
   if ((p.q_off == nullptr) != (p.q_len == nullptr) || (p.k_off == nullptr) != (p.k_len == nullptr)) return UNIMM_E_ARG;
   p.ks_off = a->ks_off; p.ks_len = a->ks_len; p.ks_ins = a->ks_ins;
   if ((p.ks_off == nullptr) != (p.ks_len == nullptr)) return UNIMM_E_ARG;
-  if (p.ks_off != nullptr && (p.k_off == nullptr || a->ks_ins < 0 || a->drop_thr != 0u)) return UNIMM_E_ARG;   // variable-length keys, inference
+  if (p.ks_off != nullptr && (p.k_off == nullptr || a->ks_ins < 0 || (a->drop_thr != 0u && !train_seg))) return UNIMM_E_ARG;   // variable-length keys, inference
   if (p.ks_off == nullptr) p.ks_ins = 0;
   p.order = a->order;
   p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
@@ -1666,6 +1958,15 @@ extern "C" int unimm_attn_fwd(const unimm_attn_args* a, void* stream) {
   if (a->D == 64) return small_k ? launch_fwd<64, 2>(p, s) : launch_fwd<64, 8>(p, s);
   if (UNIMM_ATTN_FEWQ_FWD && !small_k && a->Tq <= 64 && p.ks_off == nullptr) return launch_fwd_fewq128(p, s);   // few queries, many keys
   return small_k ? launch_fwd<128, 2>(p, s) : launch_fwd<128, 8>(p, s);
+}
+
+extern "C" int unimm_attn_fwd(const unimm_attn_args* a, void* stream) { return attn_fwd_entry(a, stream, false); }
+
+extern "C" int unimm_attn_spliced_fwd(const unimm_attn_args* a, void* stream) {
+  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->mask || !a->lse) return UNIMM_E_ARG;
+  if (!a->q_off || !a->q_len || !a->k_off || !a->k_len || !a->ks_off || !a->ks_len || a->ks_ins < 0) return UNIMM_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > 32 || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
+  return attn_fwd_entry(a, stream, true);
 }
 
 extern "C" int unimm_attn_probs(const unimm_attn_args* a, float* probs, void* stream) {
@@ -1736,4 +2037,40 @@ extern "C" int unimm_attn_bwd(const unimm_attn_bwd_args* a, void* stream) {
   if (rc != UNIMM_OK) return rc;
   if (a->D == 64) return small_q ? launch_bwd_dkv<64, 2>(p, s) : launch_bwd_dkv<64, 8>(p, s);
   return small_q ? launch_bwd_dkv<128, 2>(p, s) : launch_bwd_dkv<128, 8>(p, s);
+}
+
+extern "C" int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* a, void* stream) {
+  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->dout || !a->lse || !a->dq || !a->dk || !a->dv || !a->mask)
+    return UNIMM_E_ARG;
+  if (!a->q_off || !a->q_len || !a->k_off || !a->k_len || !a->ks_off || !a->ks_len || a->ks_ins < 0) return UNIMM_E_ARG;
+  if (!a->g_first || !a->g_seq || a->G <= 0) return UNIMM_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > 32 || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
+  if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8) || (a->lddo % 8) || (a->lddq % 8) || (a->lddk % 8) ||
+      (a->lddv % 8))
+    return UNIMM_E_ALIGN;
+  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out | (uintptr_t)a->dout | (uintptr_t)a->dq |
+       (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
+    return UNIMM_E_ALIGN;
+  AttnSplBwdParams sp;
+  AttnBwdParams& p = sp.b;
+  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v; p.o = (const bf16_t*)a->out;
+  p.dout = (const bf16_t*)a->dout; p.lse = a->lse; p.delta = nullptr;
+  p.dq = (bf16_t*)a->dq; p.dk = (bf16_t*)a->dk; p.dv = (bf16_t*)a->dv; p.mask = a->mask;
+  p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
+  p.order = nullptr;
+  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
+  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.lddo = a->lddo;
+  p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
+  p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride;
+  p.parts = 1;
+  p.scale = a->scale;
+  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt;
+  sp.ks_off = a->ks_off; sp.ks_len = a->ks_len; sp.ks_ins = a->ks_ins;
+  sp.g_first = a->g_first; sp.g_seq = a->g_seq; sp.G = a->G;
+  sp.accumulate = a->accumulate;
+  constexpr size_t lds = 2 * 4096 + 2 * 32 * sizeof(float) + 9 * 32 * sizeof(uint32_t) + 9 * 2048 + (size_t)(10 + 9) * 4096 + 64 * 64 * sizeof(float);
+  if (set_lds(attn_spliced_bwd_kernel, lds) != UNIMM_OK) return UNIMM_E_HIP;
+  hipLaunchKernelGGL(attn_spliced_bwd_kernel, dim3(a->G * a->H), dim3(512), lds, (hipStream_t)stream, sp);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
 }

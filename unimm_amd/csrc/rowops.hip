@@ -569,7 +569,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbArgs a, float* __rest
 template <typename DY>      // bf16_t (the bf16 path) or float (the fp32x3 mode's gradient stream)
 __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbArgs a, const DY* __restrict__ dy, float* __restrict__ dword,
                                                         float* __restrict__ dpos, float* __restrict__ dext,
-                                                        float* __restrict__ partials) {
+                                                        float* __restrict__ partials, float* __restrict__ drow = nullptr) {
+  // drow (fp32 [M, H], or NULL): the rows' gradients are STORED there instead of being scattered with atomics; the caller adds
+  // them into the tables in an order of its own (rows_scatter_sum_f32_kernel: the same bits on every run)
   __shared__ float red[4 * 1024];
   drop_resolve(a.drop);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -628,6 +630,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(EmbArgs a, const DY* __r
     }
     // one atomic wave-instruction = 256 contiguous bytes of one row (full-rate shape; a lane-strided
     // shape runs ~8x slower, MI355X_MICROARCH.md "Global float atomics")
+    if (drow != nullptr) {
+      for (int col = lane; col < a.H; col += 64) drow[(size_t)row * a.H + col] = mine[col];
+      continue;
+    }
     for (int col = lane; col < a.H; col += 64) {
       const float v = mine[col];
       atomicAdd(wrow + col, v);
@@ -770,6 +776,66 @@ __global__ __launch_bounds__(256) void sum_slabs_bf16_kernel(const float* __rest
     }
     u32x4 o = {pack2bf(a0[0], a0[1]), pack2bf(a0[2], a0[3]), pack2bf(a1[0], a1[1]), pack2bf(a1[2], a1[3])};
     *reinterpret_cast<u32x4*>(out + 8 * i) = o;
+  }
+}
+
+// dst block g (R rows of W bf16) = sum over the items first[g] .. first[g + 1] - 1 of `items` of their R-row blocks of src, added in
+// fp32 in list order and rounded once.  One workgroup per (group, row), a thread per 8 columns.
+__global__ __launch_bounds__(256) void segment_rows_sum_bf16_kernel(const bf16_t* __restrict__ src, int lds, const int* __restrict__ first,
+                                                                    const int* __restrict__ items, int n_items, bf16_t* __restrict__ dst,
+                                                                    int ldd, int R, int W8) {
+  const int g = blockIdx.x / R, r = blockIdx.x % R;
+  int m0 = first[g], m1 = first[g + 1];
+  m0 = m0 < 0 ? 0 : m0;
+  m1 = m1 > n_items ? n_items : m1;
+  for (int c = threadIdx.x; c < W8; c += 256) {
+    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int m = m0; m < m1; ++m) {
+      const int it = items[m];
+      if (it < 0 || it >= n_items) continue;
+      const u32x4 v = *reinterpret_cast<const u32x4*>(src + ((size_t)it * R + r) * lds + 8 * c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { a[2 * e] += __uint_as_float(v[e] << 16); a[2 * e + 1] += __uint_as_float(v[e] & 0xffff0000u); }
+    }
+    *reinterpret_cast<u32x4*>(dst + ((size_t)g * R + r) * ldd + 8 * c) =
+        u32x4{pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(a[4], a[5]), pack2bf(a[6], a[7])};
+  }
+}
+
+// dst[key] += the sum of the rows of src that carry that key: keys (sorted, ascending) and order (the row of src at each list
+// position) come from a stable sort; one workgroup per list position, the one at the start of a key's run does the run.  Its
+// eight 128-thread parts add the run's rows j = start + part, + 8, ... in list order, the eight partial sums are then added in
+// part order: one writer per destination row and a fixed order of addends, no atomics, the same bits on every run.  H <= 1024.
+__global__ __launch_bounds__(1024) void rows_scatter_sum_f32_kernel(const float* __restrict__ src, const int* __restrict__ keys,
+                                                                    const int* __restrict__ order, int M, int H,
+                                                                    float* __restrict__ dst, int n_dst) {
+  __shared__ float part[8][1024];
+  const int m = blockIdx.x;
+  const int k = keys[m];
+  if (k < 0 || k >= n_dst || (m > 0 && keys[m - 1] == k)) return;      // (workgroup-uniform)
+  int lo = m + 1, hi = M;                                              // end of the run: the keys ascend
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] == k) lo = mid + 1; else hi = mid;
+  }
+  const int end = lo, sub = threadIdx.x >> 7, lane = threadIdx.x & 127;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int j = m + sub; j < end; j += 8) {
+    const int r = order[j];
+    if (r < 0 || r >= M) continue;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (lane + 128 * i < H) acc[i] += src[(size_t)r * H + lane + 128 * i];
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if (lane + 128 * i < H) part[sub][lane + 128 * i] = acc[i];
+  __syncthreads();
+  for (int col = threadIdx.x; col < H; col += 1024) {
+    float t = part[0][col];
+#pragma unroll
+    for (int s2 = 1; s2 < 8; ++s2) t += part[s2][col];
+    dst[(size_t)k * H + col] += t;
   }
 }
 
@@ -1002,7 +1068,20 @@ extern "C" int unimm_embed_fwd(const unimm_embed_args* a, float* y32, void* y, v
 
 namespace {
 int embed_bwd_any(const unimm_embed_args* a, const void* dy, bool dy_f32, float* dword, float* dpos, float* dtype,
-                  float* dext, float* dgamma, float* dbeta, float* partials, void* stream);
+                  float* dext, float* dgamma, float* dbeta, float* partials, void* stream, float* drow = nullptr);
+}
+extern "C" int unimm_embed_bwd_rows(const unimm_embed_args* a, const void* dy, float* drow, float* dtype, float* dgamma, float* dbeta,
+                                    float* partials, void* stream) {
+  if (!drow) return UNIMM_E_ARG;
+  return embed_bwd_any(a, dy, false, drow, drow, dtype, drow, dgamma, dbeta, partials, stream, drow);   // (no table is touched)
+}
+extern "C" int unimm_rows_scatter_sum_f32(const float* src, const int32_t* keys, const int32_t* order, int32_t M, int32_t H,
+                                          float* dst, int32_t n_dst, void* stream) {
+  if (!src || !keys || !order || !dst || M <= 0 || H <= 0 || n_dst <= 0) return UNIMM_E_ARG;
+  if (H > 1024) return UNIMM_E_SHAPE;
+  hipLaunchKernelGGL(rows_scatter_sum_f32_kernel, dim3(M), dim3(1024), 0, (hipStream_t)stream, src, keys, order, M, H, dst, n_dst);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
 }
 extern "C" int unimm_embed_bwd(const unimm_embed_args* a, const void* dy, float* dword, float* dpos, float* dtype,
                                float* dext, float* dgamma, float* dbeta, float* partials, void* stream) {
@@ -1014,7 +1093,7 @@ extern "C" int unimm_embed_bwd_f32(const unimm_embed_args* a, const float* dy, f
 }
 namespace {
 int embed_bwd_any(const unimm_embed_args* a, const void* dy, bool dy_f32, float* dword, float* dpos, float* dtype,
-                  float* dext, float* dgamma, float* dbeta, float* partials, void* stream) {
+                  float* dext, float* dgamma, float* dbeta, float* partials, void* stream, float* drow) {
   if (!a || !dy || !dword || !dpos || !dtype || !dext || !dgamma || !dbeta || !partials) return UNIMM_E_ARG;
   if (a->M <= 0 || a->H <= 0 || a->H > MAXC * 512 || (a->H % 8) || a->type_vocab != 2) return UNIMM_E_SHAPE;
   EmbArgs e;
@@ -1028,7 +1107,7 @@ int embed_bwd_any(const unimm_embed_args* a, const void* dy, bool dy_f32, float*
   blocks = blocks > RED_BLOCKS ? RED_BLOCKS : blocks;
   hipStream_t s = (hipStream_t)stream;
   if (dy_f32) hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(blocks), dim3(256), 0, s, e, (const float*)dy, dword, dpos, dext, partials);
-  else hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, e, (const bf16_t*)dy, dword, dpos, dext, partials);
+  else hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, e, (const bf16_t*)dy, dword, dpos, dext, partials, drow);
   UNIMM_CHECK_LAUNCH();
   hipLaunchKernelGGL(colpartials_finish_kernel, dim3((a->H + 63) / 64, 4), dim3(1024), 0, s, partials, blocks, 4, a->H,
                      dgamma, dbeta, dtype, dtype + a->H);
@@ -1109,6 +1188,16 @@ extern "C" int unimm_sum_slabs_bf16(const float* slabs, int32_t count, int64_t s
   blocks = blocks > 2048 ? 2048 : blocks;
   hipLaunchKernelGGL(sum_slabs_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, slabs, count,
                      (size_t)stride, (bf16_t*)out, (size_t)(n / 8));
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+extern "C" int unimm_segment_rows_sum_bf16(const void* src, int32_t lds, const int32_t* first, const int32_t* items, int32_t n_items,
+                                           int32_t G, void* dst, int32_t ldd, int32_t R, int32_t W, void* stream) {
+  if (!src || !first || !items || !dst || n_items <= 0 || G <= 0 || R <= 0 || W <= 0 || lds < W || ldd < W) return UNIMM_E_ARG;
+  if ((W % 8) || (lds % 8) || (ldd % 8) || (((uintptr_t)src | (uintptr_t)dst) & 15)) return UNIMM_E_ALIGN;
+  hipLaunchKernelGGL(segment_rows_sum_bf16_kernel, dim3((unsigned)(G * R)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, lds,
+                     first, items, n_items, (bf16_t*)dst, ldd, R, W / 8);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }

@@ -754,16 +754,27 @@ class Engine:
     # disjoint row ranges of ONE context buffer (the S rows, then the P rows with the group's rows spliced into their keys)
     # and embeds rows chosen by its own plan:
     #   _ctx_rows(rows, width, device)   an uninitialised context buffer
-    #   _attn_rows(q, k, v, ctx, mask, ..., kshared)   one launch into it, no dropout, no lse
+    #   _attn_rows(q, k, v, ctx, mask, ..., kshared)   one launch into it; no dropout and no lse unless the pass trains
+    #                                    (drop / lse given: the bf16 engine's shared-context training step)
     #   _ctx_operand(ctx)                what `_post_attn` takes, once every row is written
     #   _embed_image / _embed_text       the step's embeddings, without dropout and without a backward
     def _ctx_rows(self, rows, width, device):
         return torch.empty((rows, width), dtype=BF16, device=device)
 
-    def _attn_rows(self, q, k, v, ctx, mask, B, H, Tq, Tk, D, qvar=None, kvar=None, kshared=None):
+    def _attn_rows(self, q, k, v, ctx, mask, B, H, Tq, Tk, D, qvar=None, kvar=None, kshared=None, drop=L.NO_DROP, lse=None):
         words, mq, mb = mask
-        L.attn_fwd(q, k, v, ctx, None, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, L.NO_DROP, qvar=qvar, kvar=kvar,
+        if kshared is not None and lse is not None:          # the spliced launch in its training form
+            L.attn_spliced_fwd(q, k, v, ctx, lse, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar, kvar, kshared)
+            return
+        L.attn_fwd(q, k, v, ctx, lse, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar=qvar, kvar=kvar,
                    kshared=kshared)
+
+    def _attn_spliced_bwd(self, q, k, v, ctx, dctx, lse, mask, dq, dk, dv, B, H, Tq, Tk, D, drop, qvar, kvar, kshared, groups):
+        """Backward of the spliced `_attn_rows` launch; the groups' shared rows of dk / dv already hold the S x S launch's
+        gradient and get the groups' sums on top, in one rounding."""
+        words, mq, mb = mask
+        L.attn_spliced_bwd(q, k, v, ctx, dctx, lse, dq, dk, dv, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar, kvar,
+                           kshared, groups, accumulate=True)
 
     def _ctx_operand(self, ctx):
         return ctx
@@ -815,6 +826,31 @@ class Engine:
             kernel(*emb, dxt, A.grad(e + "word_embeddings.weight"), A.grad(e + "position_embeddings.weight"),
                    A.grad(e + "token_type_embeddings.weight"), A.grad(e + "token_type_embeddings_extension.weight"), ggm, gbt,
                    self.part[H], M, H, self.cfg.type_vocab_size, drop=drop, m_dev=m_dev, rows=rows)
+        return bwd
+
+    def _embed_text_bwd_ordered(self, ids32, pos32, typ32, M, rows, drop):
+        """`_embed_text_bwd` without floating-point atomics (the shared-context training step, bf16): the rows' gradients are
+        stored, then added into the word / position / extension-type tables run by run of a stable sort of their table indices
+        -- a fixed order of addends, one writer per table row.  The tied decoder's weight gradient is joined first: it adds
+        into the same word rows."""
+        A, e, H, tv = self.arena, "bert.embeddings.", self.cfg.hidden_size, self.cfg.type_vocab_size
+        emb = self._embed_text_args(ids32, pos32, typ32)
+        _, _, ggm, gbt = self.ln["emb_t"]
+        src = rows if rows is not None else torch.arange(M, device=ids32.device)
+        tt = typ32[src]
+        lists = []
+        for key, name in ((ids32[src], "word_embeddings"), (pos32[src], "position_embeddings"),
+                          (torch.where(tt >= tv, tt - tv, torch.full_like(tt, -1)), "token_type_embeddings_extension")):
+            ks, order = torch.sort(key.to(torch.int32), stable=True)
+            lists.append((ks.contiguous(), order.to(torch.int32), name))
+
+        def bwd(dxt):
+            drow = torch.empty((M, H), dtype=F32, device=dxt.device)
+            L.embed_bwd_rows(*emb, dxt, drow, A.grad(e + "token_type_embeddings.weight"), ggm, gbt, self.part[H], M, H, tv,
+                             drop=drop, rows=rows)
+            self._join_wgrad()
+            for ks, order, name in lists:
+                L.rows_scatter_sum_f32(drow, ks, order, A.grad(e + name + ".weight"))
         return bwd
 
     def _qkv_grad(self, qkv):
@@ -1150,6 +1186,13 @@ class Engine:
 
     def backward(self, out, g_lm, g_img, g_nsp, g_nsp_scores=None):
         return self._on_text_stream(self._backward, out, g_lm, g_img, g_nsp, g_nsp_scores)
+
+    def forward_backward_shared(self, inp: dict, groups, g_lm, train: bool):
+        """The LM term's forward and backward over sequences that share their dialog context and image group by group
+        (unimm_amd/scoring.py, `train_shared`) -> the LM loss, fp32 [1] (NaN, and nothing added to the gradients, when a
+        sequence's context does not match its group's)."""
+        from .scoring import train_shared
+        return self._on_text_stream(train_shared, self, inp, groups, g_lm, train)
 
     def losses(self, out, inp):
         return self._on_text_stream(self._losses, out, inp)

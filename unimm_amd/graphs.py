@@ -194,6 +194,8 @@ class StepGraphs:
         eng = self.eng
         if opts.get("want_seq") or eng.text_priority or eng.cfg.predict_feature:      # (the MSE branch's divisor is a launch argument)
             return False
+        if inp.get("shared_context") is not None:    # the shared-context step (unimm_amd/scoring.py) packs its own rows: eager
+            return False
         if inp.get("lm_advantage") is not None:      # the policy-gradient step (unimm_amd/policy.py) has no replayed form: its
             return False                             # advantages are not among the staged inputs; the eager step runs
         for k in _TENSOR_KEYS:

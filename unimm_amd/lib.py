@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -71,6 +71,8 @@ def lib():
     L.unimm_gemm_nt.argtypes = [VP, VP]
     L.unimm_attn_fwd.argtypes = [VP, VP]
     L.unimm_attn_bwd.argtypes = [VP, VP]
+    L.unimm_attn_spliced_fwd.argtypes = [VP, VP]
+    L.unimm_attn_spliced_bwd.argtypes = [VP, VP]
     L.unimm_x3_split.argtypes = [VP, VP]
     L.unimm_x3_attn_fwd.argtypes = [VP, VP, VP]
     L.unimm_x3_attn_bwd.argtypes = [VP, VP, VP]
@@ -105,7 +107,10 @@ SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "uni
            # answer generation (csrc/generate.hip, ABI 19; sampling ABI 20)
            "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk", "unimm_lm_sample",
            # policy-gradient objective on sampled answers (csrc/policy.hip, ABI 22)
-           "unimm_pg_loss_fwd", "unimm_pg_loss_bwd"]
+           "unimm_pg_loss_fwd", "unimm_pg_loss_bwd",
+           # training pair of the spliced attention launch (csrc/attention.hip, ABI 23)
+           "unimm_attn_spliced_fwd", "unimm_attn_spliced_bwd", "unimm_segment_rows_sum_bf16",
+           "unimm_embed_bwd_rows", "unimm_rows_scatter_sum_f32"]
 
 
 def _check(rc, what):
@@ -283,6 +288,11 @@ class AttnBwdArgs(C.Structure):
                 ("order", C.c_void_p)]
 
 
+class AttnSplicedBwdArgs(C.Structure):
+    _fields_ = AttnBwdArgs._fields_ + [("ks_off", C.c_void_p), ("ks_len", C.c_void_p), ("ks_ins", C.c_int32),
+                                       ("g_first", C.c_void_p), ("g_seq", C.c_void_p), ("G", C.c_int32), ("accumulate", C.c_int32)]
+
+
 def _item_order(qvar, kvar):
     """The item order of an attention launch (unimm_attn_args.order): element 3 of a variable-length descriptor, if it has one."""
     for v in (qvar, kvar):
@@ -328,6 +338,57 @@ def attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mas
     rc = fn(addr, _stream())
     if rc != 0:
         _check(rc, "unimm_attn_fwd")
+
+
+def group_lists(gid, G=None):
+    """Host lists that name the groups of a spliced backward launch (unimm_attn_spliced_bwd_args.g_first / g_seq): gid = one group
+    index in 0 .. G - 1 per sequence -> (g_first int32 [G + 1], g_seq int32 [B]): the sequences group by group, each group's members
+    in batch order."""
+    import numpy as np
+    gid = np.asarray(gid, dtype=np.int64).reshape(-1)
+    G = int(gid.max()) + 1 if G is None else int(G)
+    if gid.size == 0 or gid.min() < 0 or gid.max() >= G:
+        raise ValueError("group_lists: one group index in [0, G) per sequence")
+    g_seq = np.argsort(gid, kind="stable").astype(np.int32)
+    g_first = np.concatenate([[0], np.cumsum(np.bincount(gid, minlength=G))]).astype(np.int32)
+    return g_first, g_seq
+
+
+def attn_spliced_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar, kshared):
+    """attn_fwd with a shared key/value segment in its training form (unimm_attn_spliced_fwd): lse is written, dropout allowed."""
+    _dev(q, k, v, out, lse, mask)
+    a = AttnArgs()
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
+    a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
+    _check(lib().unimm_attn_spliced_fwd(C.byref(a), _stream()), "unimm_attn_spliced_fwd")
+
+
+def spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar,
+                     kshared, groups, accumulate=False):
+    """The argument struct of `attn_spliced_bwd` (groups = (g_first int32 [G + 1], g_seq int32 [B]) device tensors)."""
+    a = AttnSplicedBwdArgs()
+    _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
+    a.order = None                                  # a workgroup is a (group, head): the sequence order does not apply
+    a.out, a.dout, a.lse, a.delta = out.data_ptr(), dout.data_ptr(), _P(lse), None
+    a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    a.ldo, a.lddo = out.stride(0), dout.stride(0)
+    a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
+    a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
+    a.g_first, a.g_seq = _P(groups[0]), _P(groups[1])
+    a.G = (groups[0].numel() - 1) if groups[0] is not None else 0
+    a.accumulate = 1 if accumulate else 0
+    return a
+
+
+def attn_spliced_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar,
+                     kshared, groups, accumulate=False):
+    """Backward of `attn_spliced_fwd` (unimm_attn_spliced_bwd): dq of the private queries, dk / dv of the private keys and -- summed
+    over each group's sequences in fp32, rounded once; accumulate: on top of what the rows hold -- of the groups' shared rows."""
+    _dev(q, k, v, out, dout, lse, dq, dk, dv, mask, *groups)
+    a = spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar,
+                         kvar, kshared, groups, accumulate)
+    _check(lib().unimm_attn_spliced_bwd(C.byref(a), _stream()), "unimm_attn_spliced_bwd")
 
 
 class AttnDecodeArgs(C.Structure):
@@ -568,6 +629,23 @@ def embed_bwd(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, dword, dpo
                                  _ptr(dbeta), _ptr(partials), _stream()), "unimm_embed_bwd")
 
 
+def embed_bwd_rows(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, drow, dtype, dgamma, dbeta, partials, M, H,
+                   type_vocab=2, eps=1e-12, drop=NO_DROP, rows=None):
+    """embed_bwd without atomics: the rows' gradients are stored in drow (fp32 [M, H]); `rows_scatter_sum_f32` adds them up."""
+    a = _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_vocab, eps, drop, None, rows)
+    _dev(dy, drow, dtype, dgamma, dbeta, partials)
+    _check(lib().unimm_embed_bwd_rows(C.byref(a), _ptr(dy), _ptr(drow), _ptr(dtype), _ptr(dgamma), _ptr(dbeta), _ptr(partials),
+                                      _stream()), "unimm_embed_bwd_rows")
+
+
+def rows_scatter_sum_f32(src, keys, order, dst):
+    """dst[keys[j]] += src[order[j]] over each key's run, in a fixed order (keys ascending int32 [M], negative = skipped): one writer
+    per destination row, no atomics (unimm_rows_scatter_sum_f32).  src fp32 [M, H], dst fp32 [n, H], both contiguous."""
+    _dev(src, keys, order, dst)
+    _check(lib().unimm_rows_scatter_sum_f32(_ptr(src), _ptr(keys), _ptr(order), C.c_int32(src.shape[0]), C.c_int32(src.shape[1]),
+                                            _ptr(dst), C.c_int32(dst.shape[0]), _stream()), "unimm_rows_scatter_sum_f32")
+
+
 def colsum(dy, db, M, N):
     _dev(dy, db)
     _check(lib().unimm_colsum(_ptr(dy), _ptr(db), C.c_int32(M), C.c_int32(N), C.c_int32(dy.stride(0)), _stream()),
@@ -645,6 +723,15 @@ def sum_slabs_bf16(slabs, out, n):
     _dev(slabs, out)
     _check(lib().unimm_sum_slabs_bf16(_ptr(slabs), C.c_int32(slabs.shape[0]), C.c_int64(slabs.stride(0)), _ptr(out),
                                       C.c_int64(n), _stream()), "unimm_sum_slabs_bf16")
+
+
+def segment_rows_sum_bf16(src, first, items, dst, R, W):
+    """dst block g (R rows x W, 2-D bf16 view) = sum of src's R-row blocks items[first[g] : first[g + 1]], fp32 in list order,
+    rounded once (unimm_segment_rows_sum_bf16); first int32 [G + 1], items int32 device tensors."""
+    _dev(src, first, items, dst)
+    _check(lib().unimm_segment_rows_sum_bf16(_ptr(src), C.c_int32(src.stride(0)), _ptr(first), _ptr(items), C.c_int32(items.numel()),
+                                             C.c_int32(first.numel() - 1), _ptr(dst), C.c_int32(dst.stride(0)), C.c_int32(R),
+                                             C.c_int32(W), _stream()), "unimm_segment_rows_sum_bf16")
 
 
 class TransposeDesc(C.Structure):

@@ -247,7 +247,7 @@ class BertForMultiModalPreTraining(nn.Module):
                          position_ids=None, attention_mask=None, image_attention_mask=None, co_attention_mask=None,
                          masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None, nsp_weight=None,
                          lm_weight=None, image_index=None, plan_header=None, lm_advantage=None, lm_behaviour_logp=None,
-                         lm_objective=None):
+                         lm_objective=None, shared_context=None):
         """The training step's forward AND backward in one call (an extension; the reference writes
         `loss = c_lm * lm.mean() + c_nsp * nsp.mean() + c_img * img.mean(); loss.backward()`, train.py:164-168, :315).
         loss_weights = (c_lm, c_nsp, c_img).  With the weights known up front the backward does not wait for the host to see
@@ -256,14 +256,41 @@ class BertForMultiModalPreTraining(nn.Module):
         30-sequence step's GPU idles).  Parameter gradients accumulate into `.grad` exactly as with `loss.backward()`.
         -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits).  plan_header: `engine.count_rows(...)` of this batch if the caller
         has it already (a prefetcher: the step then starts without its host sync).  lm_advantage / lm_behaviour_logp /
-        lm_objective: as in `forward` (the policy-gradient step always runs eagerly)."""
+        lm_objective: as in `forward` (the policy-gradient step always runs eagerly).
+        shared_context (an extension): one group id per sequence, as in `sequence_log_likelihood` -- the sequences of a group
+        share image and dialog context and differ only in the answer (the N sampled answers of a dialog, unimm_amd/policy.py).
+        The context rows and the image stream then run ONCE per group, forward and backward (unimm_amd/scoring.py); only the LM
+        term is trained: loss_weights must be (c, 0, 0), attention_mask a generative-mode DialogMaskSpec, the engine bf16 with
+        its connection layers and no frozen layers (ValueError otherwise).  The image and NSP losses come back as zeros and
+        nsp_logits as None; when a sequence's context does not match its group's, the loss is NaN and the call adds nothing to
+        the gradients.  Always eager."""
         lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
                                            self.compute_dtype)
-        if masked_lm_labels is None or next_sentence_label is None or image_target is None:
+        if shared_context is not None:
+            from .scoring import check_shared_training
+            check_shared_training(self.config, self.compute_dtype, loss_weights, attention_mask, shared_context, input_ids.shape[1],
+                                  image_feat.shape[1])
+            if masked_lm_labels is None:
+                raise ValueError("forward_backward(shared_context=...) needs masked_lm_labels (the copy rows)")
+        elif masked_lm_labels is None or next_sentence_label is None or image_target is None:
             raise ValueError("forward_backward needs the training inputs (masked_lm_labels, next_sentence_label, image_target)")
         eng = self._engine
         dev = self._device()
         eng.ensure(dev)
+        if shared_context is not None:
+            inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
+                       position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
+                       masked_lm_labels=masked_lm_labels, lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
+                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+            eng.stage_host_inputs(inp, pack=())      # (the [B, R] image key mask stays a tensor: the pass indexes it by group)
+            if self.training:
+                eng.step += 1
+            with torch.no_grad():
+                g_lm = torch.full((1,), float(loss_weights[0]), dtype=torch.float32, device=dev)
+                lm_loss = eng.forward_backward_shared(inp, shared_context, g_lm, self.training)
+                eng.last_seq_t = None
+                zero = torch.zeros(1, dtype=torch.float32, device=dev)
+                return (g_lm * lm_loss).reshape(()), lm_loss, zero, zero.clone(), None
         inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
                    position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
@@ -412,12 +439,13 @@ class VisualDialogEncoder(nn.Module):
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
                          image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
                          nsp_weight=None, lm_weight=None, image_index=None, plan_header=None, lm_advantage=None,
-                         lm_behaviour_logp=None, lm_objective=None):
+                         lm_behaviour_logp=None, lm_objective=None, shared_context=None):
         """forward + `(c_lm * lm + c_nsp * nsp + c_img * img).backward()` in one call, loss_weights = (c_lm, c_nsp, c_img)
-        (BertForMultiModalPreTraining.forward_backward).  -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits)."""
+        (BertForMultiModalPreTraining.forward_backward, shared_context included).  -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits)."""
         return self.bert_pretrained.forward_backward(
             input_ids, image_feat, image_loc, loss_weights, sep_indices=sep_indices, sep_len=sep_len, token_type_ids=token_type_ids,
             position_ids=token_position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
             co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label, image_target=image_target,
             next_sentence_label=next_sentence_label, nsp_weight=nsp_weight, lm_weight=lm_weight, image_index=image_index,
-            plan_header=plan_header, lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+            plan_header=plan_header, lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective,
+            shared_context=shared_context)

@@ -25,7 +25,19 @@ only the rows that do depend on the candidate -- row 0, the answer rows and the 
     regions attend text     regions_g x S_g                          (co-attention mask = the context = all of S_g)
     text attends regions    (S_g | P_b) x regions_g(b)               one launch over groups + sequences
 
-Inference only (no tape, no dropout), on either engine: the pass is written once against the engine's operand hooks
+TRAINING (`train_shared`, bf16 engine): the same pass with a tape and every dropout site -- N sampled answers of a dialog
+(unimm_amd/policy.py) are N sequences of one group, so the context and the image are computed ONCE, forward and backward.  The
+blocks below take `st` (train / tape) as `Engine._self_block` / `_conn_block` do and push `(kind, key, fn)` entries that
+`Engine._backward_encoder` consumes.  In the backward pass the gradients of the rows a group shares ADD over its sequences:
+  text self-attention     the S x S launch's backward (unimm_attn_bwd) writes dQ / dK / dV of the S rows; the spliced launch's
+                          backward (unimm_attn_spliced_bwd) then writes the P rows and adds each group's fp32 sums onto the S
+                          rows' dK / dV, rounding once
+  text attends regions    every text block gets its own copy of its group's region K / V rows, unimm_attn_bwd writes one dK / dV
+                          copy per block, unimm_segment_rows_sum_bf16 adds a group's copies in list order
+  regions attend text     touches S rows only: today's kernel
+Only the LM term on the copy rows is trained (either objective `_lm_head` has); poolers, NSP and image head take no part.
+
+Inference (no tape, no dropout) runs on either engine: the pass is written once against the engine's operand hooks
 (unimm_amd/engine.py: `_proj`, `_post_attn`, `_self_block`, `_lm_head`, `_pooled_heads`, and the inference hooks `_ctx_rows` /
 `_attn_rows` / `_ctx_operand` / `_embed_image` / `_embed_text`), so on the bf16 engine the rows are bf16 tensors and
 on the fp32x3 engine fp32 rows with their split operands (the spliced launch is then unimm_x3_attn_fwd's).  Results equal the
@@ -123,8 +135,13 @@ def forward_shared(eng, inp: dict, groups, want_nsp=True, cache=None):
     return eng._on_text_stream(_forward_shared, eng, inp, groups, want_nsp, cache)
 
 
-def _forward_shared(eng, inp, groups, want_nsp, cache=None):
+def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
+    """st (train / tape, as in `Engine._self_block`): None = inference; with a tape the pass saves for backward, draws every
+    dropout mask and returns the LM head's state and the embeddings' backward passes in out['lm'] / out['bwd']."""
     cfg = eng.cfg
+    st = dict(train=False, tape=None) if st is None else st
+    train, tape = st["train"], st["tape"]
+    save = tape is not None
     dev = eng.arena.device
     if cache is not None and getattr(eng, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("the key/value caches of the shared pass are answer generation's, which runs on the bf16 engine")
@@ -218,7 +235,6 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
             raise ValueError(f"image_feat has {feat.shape[0]} rows for {B} sequences and no image_index was given")
         img_rows = rep
 
-    st = dict(train=False, tape=None)
     NO = L.NO_DROP
     # ---- image embedding, one per group (image stream) -----------------------------------------------------------------
     F = cfg.v_feature_size
@@ -232,7 +248,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     with eng._img():
         featd = feat_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, F)
         locd = loc_d.index_select(0, img_rows).to(F32).contiguous().view(G * R, 5)
-        xv32, xv, _ = eng._embed_image(featd, locd, G * R, NO, False)
+        xv32, xv, bwd_embv = eng._embed_image(featd, locd, G * R, eng._drop("emb_v", cfg.hidden_dropout_prob, train), save)
     if im is None:
         im = torch.ones((B, R), dtype=torch.uint8, device=dev)
     imd = im.to(dev, non_blocking=True)
@@ -249,7 +265,10 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     ids32 = eng._i32(ids.reshape(-1), dev)
     typ32 = eng._i32(tt.reshape(-1), dev) if tt is not None else torch.zeros(B * T, dtype=torch.int32, device=dev)
     pos32 = eng._i32(pp.reshape(-1), dev) if pp is not None else torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-    xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, rows, NO, False, None)
+    d_embt = eng._drop("emb_t", cfg.hidden_dropout_prob, train)
+    xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, rows, d_embt, False, None)
+    # (the step's embedding backward scatters with fp32 atomics; this one adds in a fixed order: the step repeats bit for bit)
+    bwd_embt = eng._embed_text_bwd_ordered(ids32, pos32, typ32, M, rows, d_embt) if save else None
 
     heads, D = cfg.num_attention_heads, H // cfg.num_attention_heads
     nh, Db = cfg.bi_num_attention_heads, Hb // cfg.bi_num_attention_heads
@@ -260,24 +279,66 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     it_klen = torch.full_like(it_koff, R)
     it_vwords = vmask[0].view(G, nwv)[it_img.long()].contiguous()                                  # [G + B, nwv]
 
+    if save:
+        # the groups of the spliced backward launch, and of the region sums: item g (the group's S block) then G + b of its members
+        g_first, g_seq = L.group_lists(plan.gid, G)
+        groups_dev = (_i32(g_first, dev), _i32(g_seq, dev))
+        it_first = _i32(g_first + np.arange(G + 1), dev)
+        it_seq = _i32(np.concatenate([np.concatenate([[g], G + g_seq[g_first[g]:g_first[g + 1]]]) for g in range(G)]), dev)
+        rep_rows = (it_img.long()[:, None] * R + torch.arange(R, device=dev)[None, :]).reshape(-1).to(torch.int32)
+        rep_koff = torch.arange(G + B, dtype=torch.int32, device=dev) * R
+
+    def train_kw(drop, lse):
+        """what a training pass adds to an `_attn_rows` launch (inference passes nothing: both engines take the call)"""
+        return dict(drop=drop, lse=lse) if save else {}
+
     # (x32, x) below: an fp32 residual stream and its copy as the engine's GEMM operand, as in `Engine._self_block`
-    def text_block(key, x32, x):
-        """BertLayer (models/vilbert_dialog.py:385-483) on the packed rows, inference."""
+    def text_block(key, i, x32, x):
+        """BertLayer (models/vilbert_dialog.py:385-483) on the packed rows."""
+        pn = f"bert.encoder.layer.{i}."
         qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
         qkv = eng._proj(x, qkv_l)
         if cache is not None:
             cache[key] = qkv
         q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
         ctx = eng._ctx_rows(M, H, dev)
-        eng._attn_rows(q, k, v, ctx, (ones_t, 0, nw), G, heads, T, T, D, qvar=(s_off, s_len), kvar=(s_off, s_len))
-        eng._attn_rows(q, k, v, ctx, (pwords, nw, 32 * nw), B, heads, 32, T, D, qvar=(p_off, p_len, None, p_ord),
-                       kvar=(p_off, p_len), kshared=(ks_off, ks_len, 1))
-        return eng._post_attn(eng._ctx_operand(ctx), x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
+        # (two launches, two dropout sites: their counters both start at item 0)
+        da_s = eng._drop(pn + "attn", cfg.attention_probs_dropout_prob, train)
+        da_p = eng._drop(pn + "attn.private", cfg.attention_probs_dropout_prob, train)
+        lse_s = torch.empty((G, heads, T), dtype=F32, device=dev) if save else None
+        lse_p = torch.empty((B, heads, 32), dtype=F32, device=dev) if save else None
+        s_var, p_var, p_mask, p_ks = (s_off, s_len), (p_off, p_len), (pwords, nw, 32 * nw), (ks_off, ks_len, 1)
+        eng._attn_rows(q, k, v, ctx, (ones_t, 0, nw), G, heads, T, T, D, qvar=s_var, kvar=s_var, **train_kw(da_s, lse_s))
+        eng._attn_rows(q, k, v, ctx, p_mask, B, heads, 32, T, D, qvar=(p_off, p_len, None, p_ord), kvar=p_var, kshared=p_ks,
+                       **train_kw(da_p, lse_p))
+        x2_32, x2, post_bwd = eng._post_attn(eng._ctx_operand(ctx), x32, so, ff1, ff2, key + ".ln1", key + ".ln2",
+                                             eng._drop(pn + "so", cfg.hidden_dropout_prob, train),
+                                             eng._drop(pn + "out", cfg.hidden_dropout_prob, train), save)
+        if save:
+            def bwd(dx2):
+                dctx, dpre1 = post_bwd(dx2)
+                dqkv = eng._qkv_grad(qkv)                          # every row is written: S rows by the first launch, P rows by the second
+                dq, dk, dv = dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:3 * H]
+                eng._attn_bwd(q, k, v, ctx, dctx, lse_s, (ones_t, 0, nw), dq, dk, dv, 3 * H, G, heads, T, T, D, da_s, qvar=s_var, kvar=s_var)
+                eng._attn_spliced_bwd(q, k, v, ctx, dctx, lse_p, p_mask, dq, dk, dv, B, heads, 32, T, D, da_p, p_var, p_var, p_ks, groups_dev)
+                return eng._proj_bwd(dqkv, x, qkv_l, dpre1)
+            tape.append(("t", key, bwd))
+        return x2_32, x2
 
-    def conn_block(key, xv32, xv, xt32, xt):
-        """BertConnectionLayer (models/vilbert_dialog.py:655-783), inference: the image half once per group."""
+    def conn_block(key, i, xv32, xv, xt32, xt):
+        """BertConnectionLayer (models/vilbert_dialog.py:655-783): the image half once per group."""
+        pn = f"bert.encoder.c_layer.{i}."
         lq1, lq2, d1, d2 = (eng.lin[key + s] for s in (".qkv1", ".qkv2", ".d1", ".d2"))
         vff1, vff2, tff1, tff2 = (eng.lin[key + s] for s in (".vff1", ".vff2", ".tff1", ".tff2"))
+        da1 = eng._drop(pn + "attn1", cfg.v_attention_probs_dropout_prob, train)
+        da2 = eng._drop(pn + "attn2", cfg.attention_probs_dropout_prob, train)
+        db1 = eng._drop(pn + "bo1", cfg.v_hidden_dropout_prob, train)
+        db2 = eng._drop(pn + "bo2", cfg.hidden_dropout_prob, train)
+        dvo = eng._drop(pn + "vout", cfg.v_hidden_dropout_prob, train)
+        dto = eng._drop(pn + "tout", cfg.hidden_dropout_prob, train)
+        lse_v = torch.empty((G, nh, R), dtype=F32, device=dev) if save else None
+        lse_t = torch.empty((G + B, nh, T), dtype=F32, device=dev) if save else None
+        co_mask, v_mask, t_var, s_var = (ones_t, 0, nw), (it_vwords, 0, nwv), (it_off, it_len), (s_off, s_len)
         with eng._img():
             qkv1 = eng._proj(xv, lq1)
         qkv2 = eng._proj(xt, lq2)
@@ -290,12 +351,38 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
         with eng._img():
             ctx_v = eng._ctx_rows(G * R, Hb, dev)
             # regions attend text (:701-721): the co-attention mask is 1 on the context [1, c) = all of S_g
-            eng._attn_rows(q1, k2, v2, ctx_v, (ones_t, 0, nw), G, nh, R, T, Db, kvar=(s_off, s_len))
-            ov32, ov, _ = eng._post_attn(eng._ctx_operand(ctx_v), xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", NO, NO, False)
+            eng._attn_rows(q1, k2, v2, ctx_v, co_mask, G, nh, R, T, Db, kvar=s_var, **train_kw(da2, lse_v))
+            ov32, ov, bwd_v = eng._post_attn(eng._ctx_operand(ctx_v), xv32, d1, vff1, vff2, key + ".lnb1", key + ".lnv", db1, dvo, save)
         ctx_t = eng._ctx_rows(M, Hb, dev)
         # text attends regions (:681-698): every packed text block against its group's regions
-        eng._attn_rows(q2, k1, v1, ctx_t, (it_vwords, 0, nwv), G + B, nh, T, R, Db, qvar=(it_off, it_len), kvar=(it_koff, it_klen))
-        ot32, ot, _ = eng._post_attn(eng._ctx_operand(ctx_t), xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)
+        eng._attn_rows(q2, k1, v1, ctx_t, v_mask, G + B, nh, T, R, Db, qvar=t_var, kvar=(it_koff, it_klen), **train_kw(da1, lse_t))
+        ot32, ot, bwd_t = eng._post_attn(eng._ctx_operand(ctx_t), xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", db2, dto, save)
+        if save:
+            def bwd(dov, dot):
+                with eng._img():
+                    dqkv1 = eng._qkv_grad(qkv1)
+                dqkv2 = torch.zeros_like(qkv2)                     # (no region attends a P row: its K2 / V2 gradient is zero)
+                eng._to_txt(dqkv1)
+                eng._to_img(dqkv2)
+                with eng._img():
+                    dctx_v, dprev = bwd_v(dov)
+                    eng._attn_bwd(q1, k2, v2, ctx_v, dctx_v, lse_v, co_mask, dqkv1[:, :Hb], dqkv2[:, Hb:2 * Hb], dqkv2[:, 2 * Hb:3 * Hb],
+                                  3 * Hb, G, nh, R, T, Db, da2, kvar=s_var)
+                dctx_t, dpret = bwd_t(dot)
+                # one copy of its group's region K / V per text block, one dK / dV copy back, then the groups' sums in list order
+                rep1 = torch.empty(((G + B) * R, 3 * Hb), dtype=BF16, device=dev)
+                L.gather_rows(qkv1, rep_rows, rep1, (G + B) * R, 3 * Hb)
+                dkv = torch.empty(((G + B) * R, 2 * Hb), dtype=BF16, device=dev)
+                eng._attn_bwd(q2, rep1[:, Hb:2 * Hb], rep1[:, 2 * Hb:], ctx_t, dctx_t, lse_t, v_mask, dqkv2[:, :Hb], dkv[:, :Hb], dkv[:, Hb:],
+                              2 * Hb, G + B, nh, T, R, Db, da1, qvar=t_var, kvar=(rep_koff, it_klen))
+                L.segment_rows_sum_bf16(dkv, it_first, it_seq, dqkv1[:, Hb:], R, 2 * Hb)
+                eng._to_img()                                      # dK1 / dV1 written by the text side
+                eng._to_txt()                                      # dK2 / dV2 written by the image side
+                with eng._img():
+                    dxv = eng._proj_bwd(dqkv1, xv, lq1, dprev)
+                dxt = eng._proj_bwd(dqkv2, xt, lq2, dpret)
+                return dxv, dxt
+            tape.append(("c", key, bwd))
         return ov32, ov, ot32, ot
 
     # ---- encoder (schedule of models/vilbert_dialog.py:842-929) ---------------------------------------------------------
@@ -304,10 +391,13 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
             with eng._img():
                 xv32, xv = eng._self_block(f"v{i}", xv32, xv, vmask, G, R, cfg.v_num_attention_heads, f"bert.encoder.v_layer.{i}.",
                                            cfg.v_attention_probs_dropout_prob, cfg.v_hidden_dropout_prob, st)
+            if save:
+                tape[-1] = ("v", tape[-1][0], tape[-1][1])
         elif kind == "t":
-            xt32, xt = text_block(f"t{i}", xt32, xt)
+            xt32, xt = text_block(f"t{i}", i, xt32, xt)
         else:
-            xv32, xv, xt32, xt = conn_block(f"c{i}", xv32, xv, xt32, xt)
+            with eng._conn_tag():
+                xv32, xv, xt32, xt = conn_block(f"c{i}", i, xv32, xv, xt32, xt)
     eng._to_txt(xv32, xv)
 
     out = dict(plan=plan, ok=same)
@@ -322,10 +412,17 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None):
     lm_idx = _i32(plan.lm_idx, dev)
     lm_pos = _i64(plan.lm_pos, dev)
     lab_sel = lab_d.reshape(-1)[lm_pos].to(torch.int32)
-    w_sel = torch.ones(n, dtype=torch.int32, device=dev)
+    lmw = inp.get("lm_weight") if save else None
+    w_sel = (torch.ones(n, dtype=torch.int32, device=dev) if lmw is None else
+             lmw.to(dev, non_blocking=True).reshape(-1)[lm_pos].to(torch.int32))
     xs = torch.empty((n, xt.shape[1]), dtype=BF16, device=dev)             # rows of the GEMM operand: H, or the split's 3 H, bf16 words
     L.gather_rows(xt, lm_idx, xs, n, xt.shape[1])
-    lm = eng._lm_head(xs, n, lab_sel, w_sel, False)
+    if save:
+        lm = eng._lm_head(xs, n, lab_sel, w_sel, True, policy=eng._policy_inputs(inp, lm_pos.to(torch.int32), dev))
+        lm.update(n=n, idx=lm_idx)
+        out["lm"], out["bwd"] = lm, dict(tape=tape, embt=bwd_embt, embv=bwd_embv)
+    else:
+        lm = eng._lm_head(xs, n, lab_sel, w_sel, False)
     out["rownll"] = lm["rownll"]
     if cache is not None:
         out["logits"] = lm["logits"]
@@ -354,3 +451,56 @@ def sequence_log_likelihood_shared(model, input_ids, image_feat, image_loc, mask
         scores = scores / cnt
     scores = torch.where(out["ok"], scores, torch.full_like(scores, float("nan")))
     return scores, out.get("nsp")
+
+
+def check_shared_training(cfg, compute_dtype, loss_weights, attention_mask, groups, T, R):
+    """What `forward_backward(shared_context=...)` refuses, on the host, before anything reaches the device."""
+    c_lm, c_nsp, c_img = (float(c) for c in loss_weights)
+    if c_nsp != 0.0 or c_img != 0.0:
+        raise ValueError(f"shared_context trains the LM term only: loss_weights must be (c, 0, 0), got {tuple(loss_weights)}")
+    if compute_dtype != "bf16":
+        raise ValueError(f"the shared-context training step runs on the bf16 engine only (compute_dtype={compute_dtype!r})")
+    if not cfg.with_coattention or cfg.fixed_t_layer or cfg.fixed_v_layer:
+        raise ValueError("the shared-context training step needs the connection layers (with_coattention) and no frozen layers "
+                         "(fixed_t_layer = fixed_v_layer = 0)")
+    spec = attention_mask
+    if not isinstance(spec, DialogMaskSpec) or len(spec) == 0 or int(spec.mode.min()) != 1:
+        raise ValueError("shared_context: attention_mask must be a generative-mode DialogMaskSpec (one descriptor per sequence)")
+    n = spec.answer.astype(np.int64)
+    length = spec.length.astype(np.int64) + n
+    return SharedContextPlan(groups.cpu().numpy() if torch.is_tensor(groups) else groups, length - 2 * n, n, length, T, R)
+
+
+def train_shared(eng, inp, groups, g_lm, train):
+    """Forward and backward of the LM term on the shared schedule -> the LM loss (fp32 [1]).  `ok` -- every sequence's context,
+    image and labels are its group's -- stays on the device: it multiplies the loss gradient (a mismatch adds nothing to the
+    gradient arena) and turns the returned loss into NaN."""
+    dev = eng.arena.device
+    cfg = eng.cfg
+    out = _forward_shared(eng, inp, groups, False, None, dict(train=train, tape=[]))
+    lm, plan = out["lm"], out["plan"]
+    n = lm["n"]
+    ok = out["ok"].all().to(F32).reshape(1)
+    lm_loss = torch.empty(1, dtype=F32, device=dev)
+    L.reduce_sum(lm["rowloss"], n, lm_loss, 1.0 / n)
+    if lm.get("ent") is not None:                                  # the policy-gradient step reports the mean entropy of its rows
+        eng.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
+        L.reduce_sum(lm["ent"], n, eng.last_lm_entropy, 1.0 / n)
+    # ---- backward: the MLM head, then the tape (Engine._backward without poolers, NSP and image head)
+    eng.arena.attach_grads()
+    eng._bwd_fresh = bool(eng.arena.fresh)
+    eng._ledger.begin()
+    eng._step_rows = plan.M
+    dxs = eng._transform_head_bwd(eng._lm_loss_grad(lm, g_lm.reshape(1) * ok), lm, lm["xs"], eng.lin["lmtr"], "lmtr", eng.lin["dec"],
+                                  M=n, N=cfg.vocab_size)
+    gt = torch.zeros((plan.M, cfg.hidden_size), dtype=eng.grad_dtype, device=dev)
+    L.gather_rows(dxs, lm["idx"], gt, n, dxs.shape[1], scatter=True)
+    gv = torch.zeros((plan.G * plan.R, cfg.v_hidden_size), dtype=eng.grad_dtype, device=dev)
+    eng._bucket_done("heads")
+    eng._to_img(gv)
+    eng._backward_encoder(out["bwd"], list(reversed(out["bwd"]["tape"])), gt, gv)
+    eng._to_txt()
+    eng._bucket_done("text_embeddings")
+    eng.arena.fresh = False
+    eng._bwd_fresh = False
+    return torch.where(ok > 0, lm_loss, torch.full_like(lm_loss, float("nan")))

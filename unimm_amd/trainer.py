@@ -104,7 +104,8 @@ def dense_finetune_step(dialog_encoder, optimizer, scheduler, batch, params, ite
 
 
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
-                       objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None):
+                       objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
+                       shared_context=False):
     """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
@@ -114,6 +115,9 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     `objective` on every token of its answer; mode "ratio" corrects for temperature / top-k / nucleus sampling with the
     tokens' step_logq.  The train-mode step is `forward_backward` on the LM term alone, with the `batch_multiply` /
     `no_sync` / `sync_gradients` cadence of `train_step`.  seed: of the draws (default iter_id).
+    shared_context: the train-mode step computes each dialog's context and image once for its N answers, forward and backward
+    (`forward_backward(shared_context=sb.image_index)`): the same gradient up to summation order, less work.  An answer then
+    has at most 14 tokens (max_answer_len <= 14: 1 + 2 (n + 1) private rows fit one 32-row tile; ValueError otherwise).
     -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
     distributions; NaN when the step decoded no row)."""
     bm = int(params.get("batch_multiply", 1))
@@ -154,7 +158,8 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
             image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
             image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
             lm_advantage=spread(advantage, sb), lm_objective=objective,
-            lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None)
+            lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None,
+            **(dict(shared_context=sb.image_index) if shared_context else {}))
     entropy = engine.last_lm_entropy
     if boundary:
         if hasattr(dialog_encoder, "sync_gradients"):
