@@ -18,6 +18,10 @@
 // reverse sweep needs: with the clamp inactive v_t = 1 / (P^T u_{t-1}) and u_t = 1 / (P v_t), so
 //     dP += -(ubar u_t^2) v_t^T - u_{t-1} (vbar v_t^2)^T        (two rank-1 updates, in registers)
 // and the adjoints move through the same two mat-vecs.  The softmax / |s_j - s_k| backward follows.
+// dP itself can leave the fp32 range although P o dP does not (where the clamp was active u and v grow by 1e8 a sweep:
+// u = 1e15, v = 5e29 and dP = 2.5e43 on a 12-option slate at tau = 0.02), so the registers hold dP_ij 2^-(eu_i + ev_j) with
+// eu, ev the binary exponents of the final u, v.  Every scaling is a power of two, so below the overflow the rounding of
+// each operation, and with it the result, is bit for bit that of the unscaled accumulation.
 #include "common.h"
 
 namespace {
@@ -41,6 +45,7 @@ struct Lds {
   float u[NMAX], v[NMAX], ub[NMAX], vb[NMAX], x[NMAX], y[NMAX], w[NMAX], z[NMAX];
   float part[2 * NMAX];
   float red[8];
+  int eu[NMAX], ev[NMAX];                       // binary exponents of the final u, v (reverse sweep)
 };
 
 // out_j = sum_i in_i M[i][j]      (in must be 0 on rows >= n)
@@ -150,7 +155,8 @@ __global__ __launch_bounds__(NTHREADS) void neural_ndcg_kernel(NdcgParams P) {
       if (row_ok && L.ok[lane] != 0.f) l0 = (sl * L.s[lane] - L.a[lane]) * P.inv_tau;
       if (row_ok && L.ok[lane + 64] != 0.f) l1 = (sl * L.s[lane + 64] - L.a[lane + 64]) * P.inv_tau;
       const float mx = wave_max(fmaxf(l0, l1));
-      const float e0 = (l0 == -INFINITY) ? 0.f : __expf(l0 - mx), e1 = (l1 == -INFINITY) ? 0.f : __expf(l1 - mx);
+      // expf, not __expf: at small tau the logits are in the hundreds and the fast form's argument rounding costs 1e-5
+      const float e0 = (l0 == -INFINITY) ? 0.f : expf(l0 - mx), e1 = (l1 == -INFINITY) ? 0.f : expf(l1 - mx);
       const float sum = wave_sum(e0 + e1);
       const float inv = row_ok ? 1.f / sum : 0.f;
       L.M[i * LD + lane] = e0 * inv;
@@ -213,10 +219,22 @@ __global__ __launch_bounds__(NTHREADS) void neural_ndcg_kernel(NdcgParams P) {
   if (tid == 0) { P.ndcg[slate] = ndcg; P.alive[slate] = 1.f; P.iters[slate] = T; }
 
   // ---- reverse sweep -------------------------------------------------------------------------------------
-  if (tid < NMAX) L.vb[tid] = L.gp[tid] * L.x[tid];
+  if (tid < NMAX) {
+    L.vb[tid] = L.gp[tid] * L.x[tid];
+    int eu = 0, ev = 0;
+    const float uf = L.u[tid], vf = L.v[tid];
+    if (uf > 0.f && uf < INFINITY) frexpf(uf, &eu);
+    if (vf > 0.f && vf < INFINITY) frexpf(vf, &ev);
+    L.eu[tid] = eu; L.ev[tid] = ev;
+  }
   __syncthreads();
   matvec(L, L.x, L.z, n);
-  if (tid < NMAX) L.ub[tid] = L.dsc[tid] * L.x[tid];
+  if (tid < NMAX) {
+    L.ub[tid] = L.dsc[tid] * L.x[tid];
+    L.w[tid] = ldexpf(L.w[tid], -L.eu[tid]);                           // first term of dP, scaled: (d_i u_i) (v_j g_j)
+    L.z[tid] = ldexpf(L.z[tid], -L.ev[tid]);
+  }
+  __syncthreads();
   const int ti = tid >> 4, tj = tid & 15;          // this thread's 8x8 entries of dP: rows ti+16a, columns tj+16b
   float acc[8][8];
 #pragma unroll
@@ -225,32 +243,37 @@ __global__ __launch_bounds__(NTHREADS) void neural_ndcg_kernel(NdcgParams P) {
     for (int b = 0; b < 8; ++b) acc[a][b] = L.w[ti + 16 * a] * L.z[tj + 16 * b];
   __syncthreads();
 
+  // from here L.gp holds the scaled copy of the adjoint in L.x (L.gp is not read again)
   for (int t = T - 1; t >= 0; --t) {
     // u_t = u_{t-1} / max(u_{t-1} (P v_t), eps)
     if (tid < NMAX) {
       const float ut = L.uh[t * NMAX + tid], ub = L.ub[tid];
-      L.x[tid] = (ut > 0.f) ? -ub * ut * ut : 0.f;                    // adjoint of q = P v_t
+      const float xq = (ut > 0.f) ? -ub * ut * ut : 0.f;              // adjoint of q = P v_t
+      L.x[tid] = xq;
+      L.gp[tid] = ldexpf(xq, -L.eu[tid]);
       L.ub[tid] = (ut < 0.f) ? ub / SK_EPS : 0.f;                     // what reaches u_{t-1} directly
-      L.z[tid] = fabsf(L.vh[t * NMAX + tid]);
+      L.z[tid] = ldexpf(fabsf(L.vh[t * NMAX + tid]), -L.ev[tid]);
     }
     __syncthreads();
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-      for (int b = 0; b < 8; ++b) acc[a][b] = fmaf(L.x[ti + 16 * a], L.z[tj + 16 * b], acc[a][b]);
+      for (int b = 0; b < 8; ++b) acc[a][b] = fmaf(L.gp[ti + 16 * a], L.z[tj + 16 * b], acc[a][b]);
     matvec_t(L, L.y, L.x, n);
     // v_t = v_{t-1} / max(v_{t-1} (P^T u_{t-1}), eps)
     if (tid < NMAX) {
       const float vt = L.vh[t * NMAX + tid], vb = L.vb[tid] + L.y[tid];
-      L.x[tid] = (vt > 0.f) ? -vb * vt * vt : 0.f;                    // adjoint of p = P^T u_{t-1}
+      const float xp = (vt > 0.f) ? -vb * vt * vt : 0.f;              // adjoint of p = P^T u_{t-1}
+      L.x[tid] = xp;
+      L.gp[tid] = ldexpf(xp, -L.ev[tid]);
       L.vb[tid] = (vt < 0.f) ? vb / SK_EPS : 0.f;
-      L.w[tid] = (t > 0) ? fabsf(L.uh[(t - 1) * NMAX + tid]) : L.ok[tid];
+      L.w[tid] = ldexpf((t > 0) ? fabsf(L.uh[(t - 1) * NMAX + tid]) : L.ok[tid], -L.eu[tid]);
     }
     __syncthreads();
 #pragma unroll
     for (int a = 0; a < 8; ++a)
 #pragma unroll
-      for (int b = 0; b < 8; ++b) acc[a][b] = fmaf(L.w[ti + 16 * a], L.x[tj + 16 * b], acc[a][b]);
+      for (int b = 0; b < 8; ++b) acc[a][b] = fmaf(L.w[ti + 16 * a], L.gp[tj + 16 * b], acc[a][b]);
     matvec(L, L.y, L.x, n);
     if (tid < NMAX) L.ub[tid] += L.y[tid];
     __syncthreads();
@@ -260,13 +283,18 @@ __global__ __launch_bounds__(NTHREADS) void neural_ndcg_kernel(NdcgParams P) {
 #pragma unroll
   for (int a = 0; a < 8; ++a) {
     const int i = ti + 16 * a;
-    float pr[8], dot = 0.f;
+    float pr[8], dot = 0.f;                                          // dot = (sum_j dP_ij P_ij) 2^-eu_i
+    const int eui = L.eu[i];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) { pr[b] = L.M[i * LD + tj + 16 * b]; dot = fmaf(acc[a][b], pr[b], dot); }
+    for (int b = 0; b < 8; ++b) {
+      pr[b] = L.M[i * LD + tj + 16 * b];
+      dot = fmaf(acc[a][b], ldexpf(pr[b], L.ev[tj + 16 * b]), dot);
+    }
     dot += __shfl_xor(dot, 1, 64); dot += __shfl_xor(dot, 2, 64);
     dot += __shfl_xor(dot, 4, 64); dot += __shfl_xor(dot, 8, 64);   // the 16 lanes that share row i
 #pragma unroll
-    for (int b = 0; b < 8; ++b) L.M[i * LD + tj + 16 * b] = pr[b] * (acc[a][b] - dot) * P.inv_tau;
+    for (int b = 0; b < 8; ++b)
+      L.M[i * LD + tj + 16 * b] = ldexpf(pr[b], eui) * (ldexpf(acc[a][b], L.ev[tj + 16 * b]) - dot) * P.inv_tau;
   }
   __syncthreads();
   matvec_t(L, L.x, L.slope, n);                    // d/ds_j through the slope term
