@@ -790,6 +790,23 @@ int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int32_t ldl, c
                     const int32_t* flags, int32_t sep, float temperature, int32_t top_k, float top_p, uint32_t key,
                     const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse, void* stream);
 
+/* The same with PER-ROW decoding parameters (ABI 24): temperature fp32 [rows], top_k int32 [rows] and top_p fp32 [rows] are
+ * device arrays, everything else is unimm_lm_sample's (the same kernel template; both the LDS-staged and the re-read path).
+ * Row r is processed exactly as unimm_lm_sample processes it when launched with (temperature[r], top_k[r], top_p[r]): steps 1-6,
+ * logp, logq and lse are bit-identical, and a row depends on its own logits, flags, stream id and parameters alone -- not on
+ * its position, on the other rows or on their parameters.  So one launch can mix decoding rules, and:
+ *  - a row with top_k = 1 is GREEDY: token = the first id of the rank order of step 2 (the id unimm_lm_topk reports first),
+ *    logp = the value unimm_lm_topk reports for it, logq = 0 exactly, whatever its temperature, top_p and stream id are;
+ *  - the host cannot see the values, so the kernel refuses them per row: a row whose temperature is not positive and finite,
+ *    whose top_p is outside (0, 1] or whose top_k < 0 returns token = -1, logp = logq = -inf (lse is still written, and
+ *    nothing is read out of bounds); the other rows of the launch are not affected.
+ * Any of the three arrays NULL returns UNIMM_E_ARG before any launch (as do the NULL cases of unimm_lm_sample); rows = 0
+ * returns UNIMM_OK without a launch and leaves the outputs untouched. */
+int unimm_lm_sample_rows(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                         const int32_t* flags, int32_t sep, const float* temperature, const int32_t* top_k, const float* top_p,
+                         uint32_t key, const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse,
+                         void* stream);
+
 /* Launch profiler for bench.py's `roofline` block: HIP events around every GEMM launch on its own
  * stream while enabled.  Variant index: 0..11 = unimm_gemm_nt (epilogue * 2 + out_f32), 12 = unimm_gemm_tn.
  * unimm_prof_collect synchronises the events and returns per-variant summed milliseconds, algorithmic

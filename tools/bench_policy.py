@@ -1,6 +1,7 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
     python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared]
+                                 [--baseline mean|greedy] [--rollout separate|fused ...]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
 [rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
@@ -15,6 +16,11 @@ Step: one trainer.self_critical_step at G dialogs x N samples (baseline "mean": 
 device synchronisations into sampling (generate_answers), assembly (the reward, self_critical_advantage,
 sampled_training_batch and spread: host only, each call clocked) and the train step (forward_backward + optimizer.step);
 `other_ms` is what remains of the step's wall time (mode switches, the scheduler, building the constant inputs).
+--baseline greedy times the self-critical baseline proper: with --rollout separate the greedy answer is a generate_answers call
+of its own (both calls count as sampling), with --rollout fused it is one more slot of the sampling call.  `--rollout separate
+fused` times both in one process as alternating pairs (separate, fused, separate, fused, ...; --pairs of them after a warm-up of
+each, both steps of a pair with the same seed) and prints the medians of sampling_ms and total_ms, each form's min-to-max spread
+over the pairs, the ratios, and whether fused is faster than separate by more than separate's own spread.
 
 --shared (instead of the above): the train-mode step of one sampled batch of G dialogs x N answers in its two forms --
 `forward_backward` on G x N full sequences (replicated) and `forward_backward(shared_context=<dialog of each sequence>)`, which
@@ -93,7 +99,7 @@ def kernels(rows, pairs, launches):
     return out
 
 
-def step(G, N):
+def step(G, N, baseline="mean", rollouts=("separate",), pairs=7):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from bench_generate import dialogs
     from oracle import vilbert_ref as RF
@@ -118,6 +124,9 @@ def step(G, N):
             r = fn(*a, **kw)
             torch.cuda.synchronize()
             marks[name] = marks.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
+            if name == "sampling":                           # decode steps walked: the longest answer of every call
+                marks["decode_steps"] = marks.get("decode_steps", 0) + max(
+                    int(x.lengths.max()) for x in (r, getattr(r, "greedy", None)) if x is not None)
             return r
         return run
 
@@ -126,20 +135,46 @@ def step(G, N):
     for name in ("sampled_training_batch", "spread", "self_critical_advantage"):       # the names the step calls
         setattr(trainer, name, clocked("assembly", getattr(policy, name)))
     reward = clocked("assembly", lambda tokens, lengths: -lengths.float())
-    rows = []
-    for it in range(1, 5):                                   # the first iterations warm every shape up
+    def one(it, rollout, seed=None):
         marks.clear()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = trainer.self_critical_step(enc, opt, sch, batch, dict(batch_multiply=1), it, reward, samples=N, baseline="mean",
-                                         objective=policy.PolicyObjective(entropy_coef=0.01), temperature=0.8, top_k=50, top_p=0.9)
+        out = trainer.self_critical_step(enc, opt, sch, batch, dict(batch_multiply=1), it, reward, samples=N, baseline=baseline,
+                                         objective=policy.PolicyObjective(entropy_coef=0.01), temperature=0.8, top_k=50, top_p=0.9,
+                                         seed=seed, **(dict(rollout=rollout) if rollout != "separate" else {}))
         torch.cuda.synchronize()
         total = (time.perf_counter() - t0) * 1e3
-        rows.append(dict(total_ms=round(total, 2), sampling_ms=round(marks["sampling"], 2), assembly_ms=round(marks["assembly"], 2),
-                         train_ms=round(marks["train"], 2),
-                         other_ms=round(total - marks["sampling"] - marks["assembly"] - marks["train"], 2), loss=out[0]))
-        print(f"self_critical_step {it} (G = {G}, N = {N}): {rows[-1]}")
-    return rows
+        row = dict(total_ms=round(total, 2), sampling_ms=round(marks["sampling"], 2), assembly_ms=round(marks["assembly"], 2),
+                   train_ms=round(marks["train"], 2),
+                   other_ms=round(total - marks["sampling"] - marks["assembly"] - marks["train"], 2), loss=out[0])
+        if baseline != "mean" or rollout != "separate":
+            row.update(baseline=baseline, rollout=rollout, decode_steps=marks["decode_steps"])
+        print(f"self_critical_step {it} (G = {G}, N = {N}): {row}")
+        return row
+
+    if len(rollouts) == 1:
+        return [one(it, rollouts[0]) for it in range(1, 5)]   # the first iterations warm every shape up
+    it = 0
+    for _ in range(2):                                       # warm every shape of both forms up
+        for r in rollouts:
+            it += 1
+            one(it, r, seed=0)
+    rows = {r: [] for r in rollouts}
+    for pair in range(1, pairs + 1):
+        for r in rollouts:
+            it += 1
+            rows[r].append(one(it, r, seed=pair))
+    res = dict(G=G, N=N, baseline=baseline, pairs=pairs)
+    for key in ("sampling_ms", "total_ms"):
+        med = {r: statistics.median(x[key] for x in rows[r]) for r in rollouts}
+        spread = {r: round(max(x[key] for x in rows[r]) - min(x[key] for x in rows[r]), 2) for r in rollouts}
+        a, b = rollouts
+        res[key] = dict(median=med, spread=spread, ratio=round(med[b] / med[a], 4),
+                        pair_ratios=[round(y[key] / x[key], 3) for x, y in zip(rows[a], rows[b])],
+                        second_faster_by_more_than_first_spread=bool(med[a] - med[b] > spread[a]))
+    res["decode_steps"] = {r: [x["decode_steps"] for x in rows[r]] for r in rollouts}
+    print(f"rollouts {rollouts}: {res}")
+    return dict(summary=res, rows=rows)
 
 
 def shared(G, N, pairs):
@@ -231,6 +266,9 @@ def main():
     ap.add_argument("--G", type=int, default=8)
     ap.add_argument("--N", type=int, default=8)
     ap.add_argument("--shared", action="store_true", help="time the shared-context train step beside the replicated one")
+    ap.add_argument("--baseline", choices=("mean", "greedy"), default="mean", help="the step's baseline (greedy: with the greedy pass)")
+    ap.add_argument("--rollout", choices=("separate", "fused"), nargs="+", default=["separate"],
+                    help="how the greedy baseline is decoded; both values: alternating pairs in one process")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
@@ -240,7 +278,11 @@ def main():
         return
     result = dict(rows=a.rows, kernels=kernels(a.rows, a.pairs, a.launches))
     if not a.no_step:
-        result["step"] = step(a.G, a.N)
+        if len(a.rollout) > 2 or len(set(a.rollout)) != len(a.rollout):
+            raise SystemExit("--rollout takes separate, fused, or both once each")
+        if "fused" in a.rollout and a.baseline != "greedy":
+            raise SystemExit("--rollout fused needs --baseline greedy")
+        result["step"] = step(a.G, a.N, a.baseline, tuple(a.rollout), a.pairs)
     print(json.dumps(result))
 
 

@@ -1,5 +1,5 @@
 // ABI identification.
 #include "common.h"
 
-extern "C" int unimm_version(void) { return 23; }
+extern "C" int unimm_version(void) { return 24; }
 extern "C" const char* unimm_arch(void) { return "gfx950"; }

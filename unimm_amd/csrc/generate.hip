@@ -1,6 +1,7 @@
 // Answer generation kernels (include/unimm_hip.h, ABI 19-20): text self-attention of the decode rows against a shared context
 // cache plus per-hypothesis private caches, the per-step private-cache append + reorder, log-softmax + top-K of the
-// decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20).
+// decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20; with per-row
+// parameters unimm_lm_sample_rows, ABI 24: the same kernel template).
 // unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
 #include <math.h>
 
@@ -306,6 +307,8 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
 // id asc" and every selection below is an exact radix select on integers.  V <= STAGE_MAX: the keys are staged in LDS once and
 // every later pass reads LDS; larger V: the passes recompute the key from the (L2-resident) row.  Masses are summed as
 // 2^-40 fixed point in 64-bit integers: an integer sum does not depend on the order of the atomics, so a launch is reproducible.
+// PER_ROW (unimm_lm_sample_rows): temperature / top_k / top_p come from device arrays indexed by the row, and values the scalar
+// entry point refuses on the host make the row return the `nothing eligible` result; nothing else differs.
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int STAGE_MAX = 36864;               // 144 KiB of keys + 12.3 KiB of static LDS <= 160 KiB
 constexpr float FIX_ONE = 1099511627776.f;     // 2^40
@@ -317,6 +320,7 @@ struct SampleParams {
   int rows, V, ldl, nbanned, sep, top_k;
   float temperature, top_p;
   uint32_t key;
+  const float* temp_rows; const int32_t* topk_rows; const float* topp_rows;   // PER_ROW: [rows] each, instead of the scalars
 };
 
 struct SelScratch {
@@ -382,7 +386,7 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
   return t;
 }
 
-template <bool STAGED>
+template <bool STAGED, bool PER_ROW>
 __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint32_t* keys = reinterpret_cast<uint32_t*>(smem);          // [V] when STAGED (no dynamic LDS otherwise)
@@ -404,6 +408,11 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   const int f = a.flags != nullptr ? a.flags[row] : 0;
   const float* x = a.logits + (int64_t)row * a.ldl;
   const int sep = a.sep;
+  // PER_ROW (unimm_lm_sample_rows): the row's own decoding parameters; the arithmetic below is the scalar kernel's
+  const float temp = PER_ROW ? a.temp_rows[row] : a.temperature;
+  const int top_k = PER_ROW ? a.topk_rows[row] : a.top_k;
+  const float top_p = PER_ROW ? a.topp_rows[row] : a.top_p;
+  const bool bad = PER_ROW && (!(temp > 0.f) || !(temp < INFINITY) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0);
   auto make_key = [&](int j, float xv) -> uint32_t {
     const bool out = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == sep) || ((f & 2) && j != sep) || !(xv > -INFINITY);
     return out ? 0u : ord_key(xv);
@@ -452,7 +461,7 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   const float lse = M + logf(tot);
   cnt = block_sum_u64(cnt, r64);                 // (its barriers also order the key stores before the passes below)
   if (tid == 0 && a.lse != nullptr) a.lse[row] = lse;
-  if (cnt == 0ull) {
+  if (cnt == 0ull || bad) {                      // nothing eligible, or (PER_ROW) parameters the host could not refuse
     if (tid == 0) {
       a.token[row] = -1;
       a.logp[row] = -INFINITY;
@@ -464,10 +473,10 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   // top-k: key T of rank top_k and, where the ids tied at T do not all fit, the last id that does
   uint32_t T = 0u;
   int idcut = -1;                                // kept by top-k: key > T, or key == T and id <= idcut
-  if (a.top_k > 0 && (unsigned long long)a.top_k < cnt) {
+  if (top_k > 0 && (unsigned long long)top_k < cnt) {
     unsigned long long rem, at;
     T = radix_select([&](int j, uint32_t& w, unsigned long long& wt) { w = key_at(j); wt = 1ull; return w != 0u; }, V, 24,
-                     (unsigned long long)a.top_k, sel, &rem, &at);
+                     (unsigned long long)top_k, sel, &rem, &at);
     idcut = V;
     if (rem < at) {
       unsigned long long r2, a2;
@@ -480,20 +489,20 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
 
   // temperature: every y is taken relative to the row's largest eligible logit (always kept), y_i - y_max = (x_i - x_max) / t:
   // argmax (y + g), q and logq do not change, and the rounding no longer grows with an offset of the whole row
-  const float xmax = key_val(kmax), temp = a.temperature;
+  const float xmax = key_val(kmax);
   auto rel = [&](uint32_t k) -> float { return (key_val(k) - xmax) / temp; };
   auto fixed = [&](float d) -> unsigned long long { return (unsigned long long)(expf(d) * FIX_ONE); };
 
   // nucleus: the largest key TH whose mass from the top reaches top_p of the kept mass
   uint32_t TH = 0u;
-  if (a.top_p < 1.0f && cnt > 1ull) {
+  if (top_p < 1.0f && cnt > 1ull) {
     unsigned long long z = 0ull;
     for (int j = tid; j < V; j += NTHREADS) {
       const uint32_t k = key_at(j);
       if (kept_k(j, k)) z += fixed(rel(k));
     }
     z = block_sum_u64(z, r64);
-    const double want = ceil((double)a.top_p * (double)z);
+    const double want = ceil((double)top_p * (double)z);
     const unsigned long long target = want < 1.0 ? 1ull : (unsigned long long)want;
     unsigned long long rem, at;
     TH = radix_select([&](int j, uint32_t& w, unsigned long long& wt) {
@@ -606,6 +615,29 @@ extern "C" int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32
   return UNIMM_OK;
 }
 
+namespace {
+
+template <bool PER_ROW>
+int launch_lm_sample(const SampleParams& p, hipStream_t stream) {
+  if (p.V <= STAGE_MAX) {
+    static bool done = false;                    // one per instantiation
+    if (!done) {
+      if (hipFuncSetAttribute((const void*)lm_sample_kernel<true, PER_ROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              STAGE_MAX * (int)sizeof(uint32_t)) != hipSuccess)
+        return UNIMM_E_HIP;
+      done = true;
+    }
+    hipLaunchKernelGGL((lm_sample_kernel<true, PER_ROW>), dim3((unsigned)p.rows), dim3(NTHREADS), (size_t)p.V * sizeof(uint32_t),
+                       stream, p);
+  } else {
+    hipLaunchKernelGGL((lm_sample_kernel<false, PER_ROW>), dim3((unsigned)p.rows), dim3(NTHREADS), 0, stream, p);
+  }
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+}  // namespace
+
 extern "C" int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
                                const int32_t* flags, int32_t sep, float temperature, int32_t top_k, float top_p, uint32_t key,
                                const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse, void* stream) {
@@ -620,19 +652,24 @@ extern "C" int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int
   p.token = token; p.logp = logp; p.logq = logq; p.lse = lse;
   p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = top_k;
   p.temperature = temperature; p.top_p = top_p; p.key = key;
-  if (V <= STAGE_MAX) {
-    static bool done = false;
-    if (!done) {
-      if (hipFuncSetAttribute((const void*)lm_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              STAGE_MAX * (int)sizeof(uint32_t)) != hipSuccess)
-        return UNIMM_E_HIP;
-      done = true;
-    }
-    hipLaunchKernelGGL(lm_sample_kernel<true>, dim3((unsigned)rows), dim3(NTHREADS), (size_t)V * sizeof(uint32_t),
-                       (hipStream_t)stream, p);
-  } else {
-    hipLaunchKernelGGL(lm_sample_kernel<false>, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
-  }
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
+  p.temp_rows = nullptr; p.topk_rows = nullptr; p.topp_rows = nullptr;
+  return launch_lm_sample<false>(p, (hipStream_t)stream);
+}
+
+extern "C" int unimm_lm_sample_rows(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned,
+                                    int32_t nbanned, const int32_t* flags, int32_t sep, const float* temperature,
+                                    const int32_t* top_k, const float* top_p, uint32_t key, const int32_t* stream_ids,
+                                    int32_t* token, float* logp, float* logq, float* lse, void* stream) {
+  if (logits == nullptr || stream_ids == nullptr || token == nullptr || logp == nullptr || logq == nullptr ||
+      (nbanned > 0 && banned == nullptr) || temperature == nullptr || top_k == nullptr || top_p == nullptr)
+    return UNIMM_E_ARG;
+  if (rows < 0 || V < 1 || V > VMAX || ldl < V || nbanned < 0) return UNIMM_E_SHAPE;
+  if (rows == 0) return UNIMM_OK;
+  SampleParams p;
+  p.logits = logits; p.banned = banned; p.flags = flags; p.stream = stream_ids;
+  p.token = token; p.logp = logp; p.logq = logq; p.lse = lse;
+  p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = 0;
+  p.temperature = 1.f; p.top_p = 1.f; p.key = key;
+  p.temp_rows = temperature; p.topk_rows = top_k; p.topp_rows = top_p;
+  return launch_lm_sample<true>(p, (hipStream_t)stream);
 }

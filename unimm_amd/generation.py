@@ -57,6 +57,16 @@ sample_streams[g] * samples + j, and depends on nothing else but the row's logit
 themselves).  Every token comes with log p under the unmodified distribution (step_logp, summed in logp: equal to
 `sequence_log_likelihood` of the completed sequence, as for beams) and log q under the one sampled from (step_logq).  Samples are
 returned in draw order, not sorted.
+
+Per-draw decoding parameters and the greedy slot (one rollout for self-critical training).  `temperature`, `top_k` and `top_p` each
+take a scalar or a sequence of `samples` values, value j for draw j of every dialog.  `greedy=True` adds one more slot per dialog
+to the SAME prefill and decode steps: dialog g then owns slots g * (N + 1) + j, j < N the samples and j = N a slot that decodes
+greedily (top_k = 1, temperature 1, top_p 1: its one kept id is the first of the rank order, the token beams = 1 takes, with
+log q = 0).  The samples keep their streams sample_streams[g] * N + j, keys and step rules, so they are the draws of the call
+without the greedy slot (up to the batch dependence of the logits); the greedy answer comes back in `GeneratedAnswers.greedy`,
+shaped like a beams = 1 result.  With per-draw parameters or a greedy slot the draw is `unimm_lm_sample_rows` (the same kernel
+with per-row parameters, ABI 24); a call that uses neither launches `unimm_lm_sample` as before.  The loop ends when every slot,
+the greedy one included, has finished.
 """
 from __future__ import annotations
 
@@ -88,6 +98,7 @@ class GeneratedAnswers:
     logp: torch.Tensor      # fp32 [G, beams]: summed log p
     step_logp: torch.Tensor  # fp32 [G, beams, max_answer_len + 1]: the log p of each token (an extension: per-step checks)
     step_logq: torch.Tensor | None = None   # sampling only: the log q of each token under the distribution it was drawn from
+    greedy: "GeneratedAnswers | None" = None   # samples with greedy=True: the greedy answers, shaped like a beams = 1 result
 
 
 def answer_limits(context_len, T, max_answer_len):
@@ -204,26 +215,62 @@ def beam_search(step, G, beams, limits, max_answer_len, min_answer_len=1, length
                             step_logp=fin_lp[:, :beams].gather(1, order[:, :, None].expand(-1, -1, W)))
 
 
-def check_sampling(samples, beams, temperature, top_k, top_p):
-    """The refused sampling requests (ValueError)."""
+def _per_draw(value, samples, name):
+    """A scalar, or a sequence of `samples` values (value j for draw j) -> (list of `samples` values, was it a sequence)."""
+    if torch.is_tensor(value):
+        value = value.tolist()
+    if isinstance(value, (list, tuple, np.ndarray)):
+        vals = [v.item() if isinstance(v, np.generic) else v for v in value]
+        if len(vals) != int(samples):
+            raise ValueError(f"generate_answers: {len(vals)} {name} values for {samples} samples (a scalar, or one value per draw)")
+        return vals, True
+    return [value] * int(samples), False
+
+
+def check_sampling(samples, beams, temperature, top_k, top_p, greedy=False):
+    """The refused sampling requests (ValueError) -> (temperature fp32 [N], top_k int32 [N], top_p fp32 [N], per_draw): the
+    decoding parameters of draw j, and whether any of the three was given per draw."""
     if not 1 <= int(samples) <= MAX_SAMPLES:
         raise ValueError(f"generate_answers: samples must be in [0, {MAX_SAMPLES}], got {samples}")
     if int(beams) != 1:
         raise ValueError(f"generate_answers: samples > 0 draws independent answers and needs beams = 1, got beams = {beams}")
-    if not (temperature > 0 and math.isfinite(temperature)):
-        raise ValueError(f"generate_answers: temperature must be positive and finite, got {temperature}")
-    if int(top_k) != top_k or top_k < 0:
-        raise ValueError(f"generate_answers: top_k must be an integer >= 0 (0 = off), got {top_k}")
-    if not 0.0 < top_p <= 1.0:
-        raise ValueError(f"generate_answers: top_p must be in (0, 1] (1 = off), got {top_p}")
+    if greedy and int(samples) + 1 > MAX_SAMPLES:
+        raise ValueError(f"generate_answers: greedy=True adds a slot per dialog, and samples + 1 = {int(samples) + 1} slots exceed "
+                         f"{MAX_SAMPLES}: unimm_attn_decode takes 2 * slots <= 32 query rows per dialog")
+    (ts, st), (ks, sk), (ps, sp) = (_per_draw(v, samples, n) for v, n in ((temperature, "temperature"), (top_k, "top_k"),
+                                                                          (top_p, "top_p")))
+    for t, k, p in zip(ts, ks, ps):
+        if not (t > 0 and math.isfinite(t)):
+            raise ValueError(f"generate_answers: temperature must be positive and finite, got {t}")
+        if int(k) != k or k < 0:
+            raise ValueError(f"generate_answers: top_k must be an integer >= 0 (0 = off), got {k}")
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"generate_answers: top_p must be in (0, 1] (1 = off), got {p}")
+    return (np.asarray(ts, dtype=np.float32), np.asarray([int(k) for k in ks], dtype=np.int32), np.asarray(ps, dtype=np.float32),
+            st or sk or sp)
 
 
-def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
+def slot_parameters(G, temperature, top_k, top_p, greedy=False):
+    """Per-draw parameters (check_sampling) -> the same per hypothesis slot, (fp32, int32, fp32) [G * slots]: dialog g owns slots
+    g * slots + j, the draws in order and then, with `greedy`, the greedy slot (temperature 1, top_k 1, top_p 1)."""
+    extra = ((1.0,), (1,), (1.0,)) if greedy else ((), (), ())
+    return tuple(np.tile(np.concatenate([a, np.asarray(e, dtype=a.dtype)]), G) for a, e in zip((temperature, top_k, top_p), extra))
+
+
+def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu", greedy=False):
     """Draw `samples` answers per dialog.  step(k, token, flags) -> (token int [G*samples], logp fp32, logq fp32): the draw of every
     slot at step k with its two log-probabilities, where slot s = g * samples + j continues itself with answer token k-1 =
     token[s] (k = 0: every slot of a dialog starts from the dialog's root; `token` is ignored).  flags as in beam_search
     (step_flags).  A slot is finished when it draws [SEP]: at its dialog's limit at the latest, which forces it.  Finished slots
-    keep running through `step`; what they draw is dropped.  -> GeneratedAnswers with the samples in draw order j."""
+    keep running through `step`; what they draw is dropped.  -> GeneratedAnswers with the samples in draw order j.
+    greedy: every dialog has samples + 1 slots, s = g * (samples + 1) + j, and `step` decodes slot j = samples greedily (the first
+    token of the rank order, its log p, log q = 0).  The loop runs until that slot has finished too; its answer is returned in
+    `.greedy`, what beam_search(beams=1) returns: logp summed in step order, scores = logp / length ** length_penalty with the
+    divisor beam_search uses, step_logq None."""
+    if greedy and not samples:
+        raise ValueError("generate_answers: greedy=True adds a greedy slot to a sampling call and needs samples >= 1; for greedy "
+                         "decoding alone use beams=1")
+    N, samples = int(samples), int(samples) + bool(greedy)
     S, W = G * samples, max_answer_len + 1
     dev = torch.device(device)
     limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev)
@@ -233,6 +280,9 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
     lengths = torch.zeros(S, dtype=torch.int64, device=dev)
     done = torch.zeros(S, dtype=torch.bool, device=dev)
     token = torch.zeros(S, dtype=torch.int64, device=dev)
+    if greedy:                                                                # beam_search's arithmetic for the greedy slots
+        gcum = torch.zeros(G, dtype=F32, device=dev)
+        gscore = torch.full((G,), float("-inf"), dtype=F32, device=dev)
     for k in range(W):
         tok, p, q = step(k, token, step_flags(k, limits, samples, min_answer_len).to(dev))
         tok = tok.to(dev, torch.int64)
@@ -241,6 +291,9 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
         lp[:, k] = torch.where(live, p.to(dev, F32), 0.0)
         lq[:, k] = torch.where(live, q.to(dev, F32), 0.0)
         fin = live & (tok == SEP)
+        if greedy:
+            gcum = gcum + lp[:, k].view(G, samples)[:, N]
+            gscore = torch.where(fin.view(G, samples)[:, N], gcum / float((k + 1) ** length_penalty), gscore)
         lengths = torch.where(fin, k + 1, lengths)
         done = done | fin
         token = tok.clamp_min(0)
@@ -249,8 +302,18 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
     logp = lp.sum(1)
     scores = logp / lengths.clamp_min(1).to(F32) ** float(length_penalty)
     shape = (G, samples)
-    return GeneratedAnswers(tokens=toks.view(*shape, W), lengths=lengths.view(shape), scores=scores.view(shape),
-                            logp=logp.view(shape), step_logp=lp.view(*shape, W), step_logq=lq.view(*shape, W))
+    if not greedy:
+        return GeneratedAnswers(tokens=toks.view(*shape, W), lengths=lengths.view(shape), scores=scores.view(shape),
+                                logp=logp.view(shape), step_logp=lp.view(*shape, W), step_logq=lq.view(*shape, W))
+    # the draws as the call without the greedy slot returns them (contiguous [G, N, ...]), and the greedy slot on its own
+    toks, lp, lq = (a.view(*shape, W) for a in (toks, lp, lq))
+    lengths, scores, logp = (a.view(shape) for a in (lengths, scores, logp))
+    best = GeneratedAnswers(tokens=toks[:, N:].contiguous(), lengths=lengths[:, N:].contiguous(), scores=gscore.view(G, 1),
+                            logp=torch.where(lengths[:, N:] > 0, gcum.view(G, 1), float("-inf")),
+                            step_logp=lp[:, N:].contiguous())
+    return GeneratedAnswers(tokens=toks[:, :N].contiguous(), lengths=lengths[:, :N].contiguous(), scores=scores[:, :N].contiguous(),
+                            logp=logp[:, :N].contiguous(), step_logp=lp[:, :N].contiguous(), step_logq=lq[:, :N].contiguous(),
+                            greedy=best)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -259,7 +322,7 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
 def generate_answers(model, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                      length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                     sample_streams=None):
+                     sample_streams=None, greedy=False):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("generate_answers runs on the bf16 engine")
@@ -272,15 +335,24 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
         raise ValueError(f"generate_answers: {c_h.shape[0]} context lengths for {G} dialogs")
     limits = check_request(c_h, T, beams, max_answer_len, min_answer_len)
     sampling = None
+    if greedy and not samples:
+        raise ValueError("generate_answers: greedy=True adds a greedy slot to a sampling call and needs samples >= 1; for greedy "
+                         "decoding alone use beams=1")
     if samples:
-        check_sampling(samples, beams, temperature, top_k, top_p)
+        ts, ks, ps, per_draw = check_sampling(samples, beams, temperature, top_k, top_p, greedy)
         streams = np.arange(G) if sample_streams is None else np.asarray(
             sample_streams.cpu() if torch.is_tensor(sample_streams) else sample_streams).astype(np.int64).reshape(-1)
         if streams.shape[0] != G:
             raise ValueError(f"generate_answers: {streams.shape[0]} sample streams for {G} dialogs")
-        streams = (streams[:, None] * int(samples) + np.arange(int(samples))[None]).reshape(-1)
-        sampling = dict(samples=int(samples), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), seed=int(seed),
-                        streams=(streams & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
+        streams = streams[:, None] * int(samples) + np.arange(int(samples))[None]
+        if greedy:                                         # the greedy slot keeps one id: its stream decides nothing
+            streams = np.concatenate([streams, np.zeros((G, 1), dtype=np.int64)], 1)
+        sampling = dict(samples=int(samples), greedy=bool(greedy), seed=int(seed),
+                        streams=(streams.reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
+        if per_draw or greedy:                             # per-row parameters: unimm_lm_sample_rows
+            sampling["rows"] = slot_parameters(G, ts, ks, ps, greedy)
+        else:
+            sampling.update(temperature=float(ts[0]), top_k=int(ks[0]), top_p=float(ps[0]))
     eng = model._engine
     eng.ensure(model._device())
     inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
@@ -294,7 +366,7 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
 def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None):
     """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples."""
     if sampling is not None:
-        beams = sampling["samples"]
+        beams = sampling["samples"] + sampling["greedy"]
     from .scoring import _forward_shared
     cfg = eng.cfg
     dev = eng.arena.device
@@ -415,9 +487,15 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     slp = torch.empty(S, dtype=F32, device=dev)
     slq = torch.empty(S, dtype=F32, device=dev)
 
+    rows = [torch.from_numpy(a).to(dev) for a in sampling["rows"]] if "rows" in sampling else None
+
     def draw(k, logits, flags):
-        L.lm_sample(logits, S, V, banned, flags, SEP, sampling["temperature"], sampling["top_k"], sampling["top_p"],
-                    DR.make_key(sampling["seed"], k, SAMPLE_SITE), streams, stok, slp, slq)
+        key = DR.make_key(sampling["seed"], k, SAMPLE_SITE)
+        if rows is not None:
+            L.lm_sample_rows(logits, S, V, banned, flags, SEP, rows[0], rows[1], rows[2], key, streams, stok, slp, slq)
+        else:
+            L.lm_sample(logits, S, V, banned, flags, SEP, sampling["temperature"], sampling["top_k"], sampling["top_p"], key,
+                        streams, stok, slp, slq)
         return stok, slp, slq
 
     def sample_step(k, token, flags):
@@ -428,4 +506,5 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
             plen[0].add_(1)
         return draw(k, model_rows(k, token), flags)
 
-    return sample_search(sample_step, G, beams, limits, max_answer_len, min_answer_len, length_penalty, device=dev)
+    return sample_search(sample_step, G, sampling["samples"], limits, max_answer_len, min_answer_len, length_penalty, device=dev,
+                         greedy=sampling["greedy"])

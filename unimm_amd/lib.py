@@ -13,7 +13,7 @@ import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libunimm_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_DROP_RESID, EPI_BIAS_RELU, EPI_DGELU, EPI_ADD, EPI_MUL, EPI_BIAS_GELU_DG = range(8)
 
@@ -81,6 +81,7 @@ def lib():
     L.unimm_kv_cache_update.argtypes = [VP, VP]
     L.unimm_lm_topk.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, I32, VP, VP, VP, VP]
     L.unimm_lm_sample.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, F32, I32, F32, U32, VP, VP, VP, VP, VP, VP]
+    L.unimm_lm_sample_rows.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, VP, VP, VP, U32, VP, VP, VP, VP, VP, VP]
     L.unimm_gemm_tn_grouped.argtypes = [VP, I32, VP]
     L.unimm_gemm_tn_grouped_ws.argtypes = [VP, I32, I32, VP, I64, VP]
     L.unimm_colpartials_finish_grouped.argtypes = [VP, I32, VP]
@@ -110,7 +111,9 @@ SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "uni
            "unimm_pg_loss_fwd", "unimm_pg_loss_bwd",
            # training pair of the spliced attention launch (csrc/attention.hip, ABI 23)
            "unimm_attn_spliced_fwd", "unimm_attn_spliced_bwd", "unimm_segment_rows_sum_bf16",
-           "unimm_embed_bwd_rows", "unimm_rows_scatter_sum_f32"]
+           "unimm_embed_bwd_rows", "unimm_rows_scatter_sum_f32",
+           # sampling with per-row decoding parameters (csrc/generate.hip, ABI 24)
+           "unimm_lm_sample_rows"]
 
 
 def _check(rc, what):
@@ -454,6 +457,16 @@ def lm_sample(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, ke
     _check(lib().unimm_lm_sample(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, temperature, top_k,
                                  top_p, key & 0xFFFFFFFF, _P(streams), _P(token), _P(logp), _P(logq), _P(lse), _stream()),
            "unimm_lm_sample")
+
+
+def lm_sample_rows(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, key, streams, token, logp, logq, lse=None):
+    """lm_sample with per-row decoding parameters (unimm_lm_sample_rows): temperature fp32 [rows], top_k int32 [rows], top_p fp32
+    [rows] on the device.  A row with top_k = 1 is greedy (logq = 0); a row with invalid parameters returns token = -1."""
+    _dev(logits, banned, flags, temperature, top_k, top_p, streams, token, logp, logq, lse)
+    nb = 0 if banned is None else banned.numel()
+    _check(lib().unimm_lm_sample_rows(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, _P(temperature),
+                                      _P(top_k), _P(top_p), key & 0xFFFFFFFF, _P(streams), _P(token), _P(logp), _P(logq), _P(lse),
+                                      _stream()), "unimm_lm_sample_rows")
 
 
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):

@@ -105,7 +105,7 @@ def dense_finetune_step(dialog_encoder, optimizer, scheduler, batch, params, ite
 
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
                        objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
-                       shared_context=False):
+                       shared_context=False, rollout="separate"):
     """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
@@ -118,8 +118,18 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     shared_context: the train-mode step computes each dialog's context and image once for its N answers, forward and backward
     (`forward_backward(shared_context=sb.image_index)`): the same gradient up to summation order, less work.  An answer then
     has at most 14 tokens (max_answer_len <= 14: 1 + 2 (n + 1) private rows fit one 32-row tile; ValueError otherwise).
+    rollout: "separate" decodes the greedy baseline in a generate_answers call of its own (beams = 1); "fused" (baseline="greedy"
+    only, samples <= 15; ValueError otherwise) decodes it as one more slot of the sampling call, `generate_answers(samples=N,
+    greedy=True)`: one prefill and one walk over the decode steps for both.  Only the samples are trained on either way.
     -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
     distributions; NaN when the step decoded no row)."""
+    greedy_baseline = isinstance(baseline, str) and baseline == "greedy"
+    if rollout not in ("separate", "fused"):
+        raise ValueError(f"self_critical_step: rollout must be 'separate' or 'fused', got {rollout!r}")
+    if rollout == "fused" and not greedy_baseline:
+        raise ValueError(f"self_critical_step: rollout='fused' decodes the greedy baseline with the samples and needs "
+                         f"baseline='greedy', got baseline = {baseline!r}")
+    fused = rollout == "fused"
     bm = int(params.get("batch_multiply", 1))
     boundary = iter_id % bm == 0
     model = _unwrap(dialog_encoder)
@@ -129,10 +139,10 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
                   max_answer_len=max_answer_len)
     dialog_encoder.eval()
     answers = model.generate_answers(*gen_args, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p,
-                                     seed=iter_id if seed is None else seed, **gen_kw)
+                                     seed=iter_id if seed is None else seed, **(dict(greedy=True) if fused else {}), **gen_kw)
     rewards = torch.as_tensor(reward_fn(answers.tokens.cpu(), answers.lengths.cpu())).to("cpu", torch.float32)
-    if isinstance(baseline, str) and baseline == "greedy":
-        greedy = model.generate_answers(*gen_args, beams=1, **gen_kw)
+    if greedy_baseline:
+        greedy = answers.greedy if fused else model.generate_answers(*gen_args, beams=1, **gen_kw)
         base = torch.as_tensor(reward_fn(greedy.tokens.cpu(), greedy.lengths.cpu())).to("cpu", torch.float32).reshape(-1)
     else:
         base = baseline
