@@ -307,7 +307,8 @@ int unimm_mask_synth(const int32_t* mode, const int32_t* len, const int32_t* nan
 
 /* Plan of the unpadded schedule, on the device (replaces ~25 eager kernels over the dense masks and two of the three
  * device->host round trips of a step).  unimm_plan_lengths: header[b] = valid prefix length of sequence b (>= 1; a token
- * is valid when it attends something, is attended by a token or a region, or carries a label / weight), header[B+b] =
+ * is valid when it attends something, is attended by a token or a region, or carries a label / weight; a sequence with a
+ * valid token whose own row of a dense text mask is empty gets its full length T, as that token attends all T keys), header[B+b] =
  * rows the MLM head decodes (weight != 0 when weights are given, else label != -1), header[2B..2B+1] = bit patterns of
  * the two NSP class weights when nsp_weight != NULL, header[2B+2+b] = regions of sequence b with image_label == 1
  * (int32 [B, R] or NULL: the divisor of the masked-region loss); header has 3B+2 entries.  Masks are the packed words of
@@ -327,7 +328,10 @@ int unimm_plan_lengths(const uint32_t* text_words, int32_t t_q_stride, int32_t t
  * the masked-region loss}, dims_f = {1 / decoded rows, 1 / regions (inf when none, as the reference's division)}; it also
  * fills rows[real .. rows_cap) and the lm_* lists [real .. lm_cap) with safe values (index 0, label -1, weight 0) so that
  * row-independent kernels (GEMM, LayerNorm forward, gathers) may run over the whole capacity.  dims_i (>= 4 words) / dims_f
- * (>= 2) both or neither; capacities 0 = lists are exact.  A batch whose real counts EXCEED a capacity (a replayed step sized
+ * (>= 2) both or neither.  Capacities are REQUIRED: rows_cap is the length of rows whenever rows is given, lm_cap that of the lm_*
+ * lists whenever they are given, and a list with a capacity <= 0 is refused (UNIMM_E_ARG, nothing is launched); for an exact
+ * plan pass the header's own totals (capacities >= the counts; a capacity is ignored when its list is NULL).  With no decoded
+ * row dims_f[0] = 1.  A batch whose real counts EXCEED a capacity (a replayed step sized
  * from a stale header) never writes past the lists: indices and the counts in dims_i are clamped to the capacities,
  * dims_i[3] = 1 and both dims_f words are NaN (the step's losses come out NaN instead of memory being corrupted). */
 int unimm_plan_build(const int32_t* header, const int32_t* labels, const int32_t* weights, int32_t B, int32_t T,

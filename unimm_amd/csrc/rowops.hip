@@ -1135,6 +1135,8 @@ extern "C" int unimm_plan_build(const int32_t* header, const int32_t* labels, co
   if ((dims_i == nullptr) != (dims_f == nullptr)) return UNIMM_E_ARG;
   if (header == nullptr || off == nullptr || lens == nullptr) return UNIMM_E_ARG;
   if (lm_pos != nullptr && (lm_idx == nullptr || lm_label == nullptr || lm_weight == nullptr || labels == nullptr)) return UNIMM_E_ARG;
+  // a list that is given needs its capacity: the kernel bounds every index by it (a capacity <= 0 has no index inside it)
+  if ((rows != nullptr && rows_cap <= 0) || (lm_pos != nullptr && lm_cap <= 0)) return UNIMM_E_ARG;
   if (B <= 0 || T <= 0 || T > 256) return UNIMM_E_SHAPE;
   hipLaunchKernelGGL(plan_build_kernel, dim3(B + 1), dim3(256), 0, (hipStream_t)stream, header, labels, weights, B, T, off, lens,
                      rows, inv, lm_pos, lm_idx, lm_label, lm_weight, rows_cap, lm_cap, dims_i, dims_f, order);

@@ -34,11 +34,23 @@ struct SplitParams {
   long rows; int cols, cp, lda, ldb, ld32, op, wtype;
 };
 
+// GELU and GELU' of this mode.  The bf16 path's fast_erf (|abs err| <= 1.5e-7) is fp32-grade only where the result is of order 1:
+// on the negative side 1 + erf(x) cancels (at x = -3 the value is off by ~1000 units of 2^-24 |gelu(x)|), and GELU' =
+// Phi(b) + b phi(b) crosses zero at b = -0.7518, where even correctly rounded fp32 terms leave ~350 such units of a row's
+// resolution.  erfc has no cancellation; the derivative is formed in double and rounded once.
+__device__ __forceinline__ float gelu_x3(float x) { return 0.5f * x * erfcf(-0.70710678118654752f * x); }
+__device__ __forceinline__ float gelu_grad_x3(float b) {
+  const double t = (double)b;
+  const double cdf = 0.5 * erfc(-0.70710678118654752440 * t);
+  const double pdf = 0.39894228040143267794 * exp(-0.5 * t * t);
+  return (float)(cdf + t * pdf);
+}
+
 __device__ __forceinline__ float ew_op(int op, float a, float b) {
   switch (op) {
     case UNIMM_X3_ADD: return a + b;
-    case UNIMM_X3_GELU: return gelu_erf(a);
-    case UNIMM_X3_MUL_DGELU: return a * gelu_erf_grad(b);
+    case UNIMM_X3_GELU: return gelu_x3(a);
+    case UNIMM_X3_MUL_DGELU: return a * gelu_grad_x3(b);
     default: return a;
   }
 }
