@@ -3,7 +3,6 @@ marshalling of `lib.attn_spliced_bwd`, and what `forward_backward(shared_context
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -25,19 +24,9 @@ def test_group_lists():
             lib.group_lists(bad, G=3)
 
 
-def test_spliced_bwd_struct_matches_the_header():
-    """field order of the ctypes struct = field order of unimm_attn_spliced_bwd_args in include/unimm_hip.h"""
+def test_spliced_bwd_struct_begins_with_the_bwd_struct():
+    """`_attn_common` fills both through the same field names (the struct against the header: tests/test_abi.py)"""
     from unimm_amd import lib
-    hdr = open(os.path.join(ROOT, "include", "unimm_hip.h")).read()
-    body = re.search(r"typedef struct \{([^}]*)\} unimm_attn_spliced_bwd_args;", hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            head, *rest = decl.split(",")
-            names += [head.split()[-1].lstrip("*")] + [r.strip().lstrip("*") for r in rest]
-    assert names == [f[0] for f in lib.AttnSplicedBwdArgs._fields_]
     assert [f[0] for f in lib.AttnSplicedBwdArgs._fields_][:len(lib.AttnBwdArgs._fields_)] == [f[0] for f in lib.AttnBwdArgs._fields_]
 
 

@@ -15,6 +15,9 @@ y32 = torch.empty_like(x32)
 y16 = torch.empty_like(o)
 mean = torch.empty(256, device=dev)
 rstd = torch.empty(256, device=dev)
+idx = torch.arange(256, device=dev, dtype=torch.int32)
+one = torch.zeros(1, device=dev)
+db = torch.zeros(768, device=dev)
 
 
 def t(fn, n=2000):
@@ -37,6 +40,11 @@ print("gemm_nt                    %.2f us" % t(lambda: L.gemm_nt(x, w, o, bias=b
 with L.stream_scope(torch.cuda.current_stream()):
     print("gemm_nt (scoped stream)    %.2f us" % t(lambda: L.gemm_nt(x, w, o, bias=b)))
     print("layernorm_fwd (scoped)     %.2f us" % t(lambda: L.layernorm_fwd(x32, g, b, y32, y16, mean, rstd, 256, 768)))
+    # scalar and pointer arguments only, no argument struct: the cost of marshalling them one by one
+    print("colsum (scoped)            %.2f us" % t(lambda: L.colsum(y16, db, 256, 768)))
+    print("gather_rows (scoped)       %.2f us" % t(lambda: L.gather_rows(y16, idx, o, 256, 768)))
+    print("reduce_sum (scoped)        %.2f us" % t(lambda: L.reduce_sum(mean, 256, one, scale=0.5)))
+    print("mul_dropout (scoped)       %.2f us" % t(lambda: L.mul_dropout(x32, x32, y32, x32.numel(), drop=(7, 1 << 30, 4.0 / 3.0))))
 print("torch add_ (eager op)      %.2f us" % t(lambda: y32.add_(1.0)))
 ev = torch.cuda.Event()
 print("event record               %.2f us" % t(lambda: ev.record()))

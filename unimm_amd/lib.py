@@ -2,7 +2,9 @@
 
 There is no CPU fallback: if the library is missing or a kernel call fails, this raises.
 PyTorch is used only for device memory and streams; every compute call below goes straight to a
-hand-written HIP kernel on torch's current stream."""
+hand-written HIP kernel on torch's current stream.
+A new entry point goes in three places: its prototype in the header, its row in `SIGNATURES` (and, for a new argument struct, its
+class in `STRUCTS`) and its wrapper function; tests/test_abi.py fails until the first two agree."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,6 +24,98 @@ _ERR = {-1: "UNIMM_E_ARG", -2: "UNIMM_E_SHAPE", -3: "UNIMM_E_ALIGN", -4: "UNIMM_
 
 class UnimmHipError(RuntimeError):
     pass
+
+
+# Every entry point include/unimm_hip.h declares, in header order: name -> (result type, argument types).  A pointer of any kind is
+# VP; tests/test_abi.py compares each row with the header's prototype and the .so's exports with the keys.
+VP, I32, U32, F32, I64, _INT = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_int64, C.c_int
+_DROP = [U32, U32, F32]                                             # a dropout triple: key, threshold, scale
+_LM_ROWS = [VP, I32, I32, I32, VP, I32, VP, I32]                    # logits, rows, V, ldl, banned, nbanned, flags, sep
+SIGNATURES = {
+    "unimm_version": (_INT, []),
+    "unimm_arch": (C.c_char_p, []),
+    "unimm_gemm_nt": (_INT, [VP, VP]),
+    "unimm_gemm_tn": (_INT, [VP, VP]),
+    "unimm_gemm_tn_grouped": (_INT, [VP, I32, VP]),
+    "unimm_gemm_tn_grouped_ws": (_INT, [VP, I32, I32, VP, I64, VP]),
+    "unimm_attn_fwd": (_INT, [VP, VP]),
+    "unimm_attn_probs": (_INT, [VP, VP, VP]),
+    "unimm_attn_bwd": (_INT, [VP, VP]),
+    "unimm_attn_spliced_fwd": (_INT, [VP, VP]),
+    "unimm_attn_spliced_bwd": (_INT, [VP, VP]),
+    # row kernels
+    "unimm_mask_pack": (_INT, [VP, _INT, VP, I64, I32, VP]),
+    "unimm_host_mask_pack": (_INT, [VP, _INT, VP, I64, I32, I32]),
+    "unimm_host_memcpy": (_INT, [VP, VP, I64, I32]),
+    "unimm_mask_synth": (_INT, [VP] * 5 + [I32, I32, VP]),
+    "unimm_plan_lengths": (_INT, [VP, I32, I32, VP, I32, I32, I32, VP, VP, VP, VP, I32, I32, VP, VP]),
+    "unimm_plan_build": (_INT, [VP] * 3 + [I32, I32] + [VP] * 8 + [I32, I32] + [VP] * 4),
+    "unimm_layernorm_fwd": (_INT, [VP] * 7 + [I32, I32, F32] + _DROP + [VP, VP]),
+    "unimm_colpartials_bytes": (I64, [I32]),
+    "unimm_layernorm_bwd": (_INT, [VP] * 11 + [I32, I32] + _DROP + _DROP + [VP, VP, VP]),
+    "unimm_layernorm_bwd_partials": (_INT, [VP] * 8 + [I32, I32] + _DROP + _DROP + [VP] * 5),
+    "unimm_colpartials_finish_grouped": (_INT, [VP, I32, VP]),
+    "unimm_embed_fwd": (_INT, [VP] * 4),
+    "unimm_embed_bwd": (_INT, [VP] * 10),
+    "unimm_embed_bwd_rows": (_INT, [VP] * 8),
+    "unimm_rows_scatter_sum_f32": (_INT, [VP, VP, VP, I32, I32, VP, I32, VP]),
+    "unimm_colsum": (_INT, [VP, VP, I32, I32, I32, VP]),
+    "unimm_cast_f32_bf16": (_INT, [VP, VP, I64, VP]),
+    "unimm_transpose_cast": (_INT, [VP, VP, I32, I32, I32, VP]),
+    "unimm_transpose_bf16": (_INT, [VP, VP, I32, I32, I32, I32, VP]),
+    "unimm_sum_slabs_bf16": (_INT, [VP, I32, I64, VP, I64, VP]),
+    "unimm_segment_rows_sum_bf16": (_INT, [VP, I32, VP, VP, I32, I32, VP, I32, I32, I32, VP]),
+    "unimm_transpose_cast_grouped": (_INT, [VP, I32, I32, VP]),
+    "unimm_pack_image": (_INT, [VP, VP, VP, I32, I32, I32, VP]),
+    "unimm_mul_dropout": (_INT, [VP] * 3 + [I64] + _DROP + [VP, VP]),
+    "unimm_mul_dropout_bwd": (_INT, [VP] * 5 + [I64] + _DROP + [VP, VP]),
+    "unimm_sum_dropout": (_INT, [VP] * 3 + [I64] + _DROP + [VP, VP]),
+    "unimm_sum_dropout_bwd": (_INT, [VP] * 5 + [I64] + _DROP + [VP, VP]),
+    "unimm_linear_f32": (_INT, [VP, VP]),
+    "unimm_rows_add_f32": (_INT, [VP, VP, VP, I32, I32, VP]),
+    "unimm_gelu_bwd": (_INT, [VP, VP, VP, I64, VP]),
+    "unimm_gather_rows": (_INT, [VP, VP, VP, I32, I32, I32, VP, VP]),
+    # losses
+    "unimm_lm_loss_fwd": (_INT, [VP] * 6 + [I32] * 3 + [VP, VP]),
+    "unimm_lm_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP, VP]),
+    "unimm_pg_loss_fwd": (_INT, [VP] * 5 + [I32, I32, F32, F32] + [VP] * 4 + [I32] * 3 + [VP, VP]),
+    "unimm_pg_loss_bwd": (_INT, [VP] * 5 + [I32, I32, F32, F32, VP, VP, VP, F32, VP] + [I32] * 4 + [VP, VP, VP]),
+    "unimm_kl_loss_fwd": (_INT, [VP] * 5 + [I32] * 3 + [VP]),
+    "unimm_kl_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP]),
+    "unimm_mse_loss_fwd": (_INT, [VP] * 4 + [I32] * 3 + [VP]),
+    "unimm_mse_loss_bwd": (_INT, [VP] * 4 + [F32, VP] + [I32] * 5 + [VP]),
+    "unimm_nsp_loss_fwd": (_INT, [VP, VP, F32, F32, VP, I32, I32, VP]),
+    "unimm_nsp_loss_bwd": (_INT, [VP, VP, F32, F32, VP, VP, VP, I32, I32, I32, VP]),
+    "unimm_reduce_sum": (_INT, [VP, I64, VP, F32, VP, VP, VP]),
+    "unimm_segment_sum": (_INT, [VP, VP, VP, I64, F32, VP]),
+    "unimm_adamw_step": (_INT, [VP, VP]),
+    "unimm_neural_ndcg": (_INT, [VP, VP]),
+    # the fp32-accuracy mode (csrc/x3ops.hip)
+    "unimm_x3_split": (_INT, [VP, VP]),
+    "unimm_x3_split_wt": (_INT, [VP, VP, I32, I32, I32, I32, VP]),
+    "unimm_x3_layernorm_bwd_partials": (_INT, [VP] * 8 + [I32, I32] + _DROP + _DROP + [VP] * 4),
+    "unimm_x3_layernorm_fwd": (_INT, [VP] * 7 + [I32, I32, F32] + _DROP + [VP, VP]),
+    "unimm_embed_bwd_f32": (_INT, [VP] * 10),
+    "unimm_x3_lm_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP, VP]),
+    "unimm_x3_kl_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP]),
+    "unimm_x3_rows_add": (_INT, [VP, VP, VP, I32, I32, I32, VP]),
+    "unimm_x3_attn_fwd": (_INT, [VP, VP, VP]),
+    "unimm_x3_attn_bwd": (_INT, [VP, VP, VP]),
+    "unimm_x3_attn_set_impl": (_INT, [I32]),
+    # answer generation (csrc/generate.hip)
+    "unimm_attn_decode": (_INT, [VP, VP]),
+    "unimm_kv_cache_update": (_INT, [VP, VP]),
+    "unimm_lm_topk": (_INT, _LM_ROWS + [I32, VP, VP, VP, VP]),
+    "unimm_lm_sample": (_INT, _LM_ROWS + [F32, I32, F32, U32] + [VP] * 6),
+    "unimm_lm_sample_rows": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 6),
+    # launch profiler
+    "unimm_prof_enable": (_INT, [I32]),
+    "unimm_prof_collect": (_INT, [VP, VP, VP, I32]),
+    "unimm_prof_tag": (_INT, [I32]),
+    "unimm_prof_tagged": (_INT, [VP, VP, VP, VP, I32]),
+}
+SYMBOLS = list(SIGNATURES)
+_STREAMED = {name for name, (_, args) in SIGNATURES.items() if args and args[-1] is VP}    # the only trailing pointer: `void* stream`
 
 
 class GemmNtArgs(C.Structure):
@@ -57,63 +151,13 @@ def lib():
             f"{path} is missing: build it with `python -m unimm_amd.build` (hipcc, gfx950). "
             "unimm_amd has no CPU or PyTorch fallback for its kernels.")
     L = C.CDLL(path)
-    L.unimm_version.restype = C.c_int
-    L.unimm_arch.restype = C.c_char_p
     if L.unimm_version() != ABI_VERSION:
         raise UnimmHipError(f"libunimm_hip.so ABI {L.unimm_version()} != expected {ABI_VERSION}: rebuild")
-    for name in SYMBOLS:
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(L, name)
-        if name == "unimm_colpartials_bytes":
-            fn.restype = C.c_int64
-        elif name != "unimm_arch":
-            fn.restype = C.c_int
-    VP, I32, U32, F32, I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_float, C.c_int64
-    L.unimm_gemm_nt.argtypes = [VP, VP]
-    L.unimm_attn_fwd.argtypes = [VP, VP]
-    L.unimm_attn_bwd.argtypes = [VP, VP]
-    L.unimm_attn_spliced_fwd.argtypes = [VP, VP]
-    L.unimm_attn_spliced_bwd.argtypes = [VP, VP]
-    L.unimm_x3_split.argtypes = [VP, VP]
-    L.unimm_x3_attn_fwd.argtypes = [VP, VP, VP]
-    L.unimm_x3_attn_bwd.argtypes = [VP, VP, VP]
-    L.unimm_attn_probs.argtypes = [VP, VP, VP]
-    L.unimm_attn_decode.argtypes = [VP, VP]
-    L.unimm_kv_cache_update.argtypes = [VP, VP]
-    L.unimm_lm_topk.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, I32, VP, VP, VP, VP]
-    L.unimm_lm_sample.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, F32, I32, F32, U32, VP, VP, VP, VP, VP, VP]
-    L.unimm_lm_sample_rows.argtypes = [VP, I32, I32, I32, VP, I32, VP, I32, VP, VP, VP, U32, VP, VP, VP, VP, VP, VP]
-    L.unimm_gemm_tn_grouped.argtypes = [VP, I32, VP]
-    L.unimm_gemm_tn_grouped_ws.argtypes = [VP, I32, I32, VP, I64, VP]
-    L.unimm_colpartials_finish_grouped.argtypes = [VP, I32, VP]
-    L.unimm_layernorm_fwd.argtypes = [VP] * 7 + [I32, I32, F32, U32, U32, F32, VP, VP]
-    L.unimm_x3_layernorm_fwd.argtypes = [VP] * 7 + [I32, I32, F32, U32, U32, F32, VP, VP]
-    L.unimm_layernorm_bwd_partials.argtypes = [VP] * 8 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP, VP, VP, VP]
-    L.unimm_layernorm_bwd.argtypes = [VP] * 11 + [I32, I32, U32, U32, F32, U32, U32, F32, VP, VP, VP]
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-# every symbol include/unimm_hip.h declares (tests check the .so exports each of them)
-SYMBOLS = ["unimm_version", "unimm_arch", "unimm_gemm_nt", "unimm_gemm_tn", "unimm_gemm_tn_grouped", "unimm_attn_fwd", "unimm_attn_bwd",
-           "unimm_mask_pack", "unimm_layernorm_fwd", "unimm_colpartials_bytes", "unimm_layernorm_bwd",
-           "unimm_embed_fwd", "unimm_embed_bwd", "unimm_colsum", "unimm_cast_f32_bf16", "unimm_transpose_cast",
-           "unimm_pack_image", "unimm_mul_dropout", "unimm_mul_dropout_bwd", "unimm_lm_loss_fwd",
-           "unimm_lm_loss_bwd", "unimm_kl_loss_fwd", "unimm_kl_loss_bwd", "unimm_nsp_loss_fwd",
-           "unimm_nsp_loss_bwd", "unimm_reduce_sum", "unimm_segment_sum", "unimm_gelu_bwd", "unimm_gather_rows", "unimm_prof_enable", "unimm_prof_collect", "unimm_adamw_step", "unimm_transpose_cast_grouped", "unimm_mask_synth", "unimm_neural_ndcg", "unimm_plan_lengths", "unimm_plan_build", "unimm_layernorm_bwd_partials",
-           "unimm_colpartials_finish_grouped", "unimm_gemm_tn_grouped_ws", "unimm_linear_f32", "unimm_rows_add_f32", "unimm_transpose_bf16", "unimm_sum_slabs_bf16", "unimm_attn_probs",
-           # the fp32-accuracy mode (csrc/x3ops.hip)
-           "unimm_x3_split", "unimm_x3_split_wt", "unimm_x3_layernorm_bwd_partials", "unimm_embed_bwd_f32", "unimm_x3_lm_loss_bwd",
-           "unimm_x3_kl_loss_bwd", "unimm_x3_rows_add", "unimm_x3_attn_fwd", "unimm_x3_attn_bwd", "unimm_x3_attn_set_impl", "unimm_x3_layernorm_fwd", "unimm_prof_tag", "unimm_prof_tagged",
-           "unimm_sum_dropout", "unimm_sum_dropout_bwd", "unimm_mse_loss_fwd", "unimm_mse_loss_bwd", "unimm_host_mask_pack", "unimm_host_memcpy",
-           # answer generation (csrc/generate.hip, ABI 19; sampling ABI 20)
-           "unimm_attn_decode", "unimm_kv_cache_update", "unimm_lm_topk", "unimm_lm_sample",
-           # policy-gradient objective on sampled answers (csrc/policy.hip, ABI 22)
-           "unimm_pg_loss_fwd", "unimm_pg_loss_bwd",
-           # training pair of the spliced attention launch (csrc/attention.hip, ABI 23)
-           "unimm_attn_spliced_fwd", "unimm_attn_spliced_bwd", "unimm_segment_rows_sum_bf16",
-           "unimm_embed_bwd_rows", "unimm_rows_scatter_sum_f32",
-           # sampling with per-row decoding parameters (csrc/generate.hip, ABI 24)
-           "unimm_lm_sample_rows"]
 
 
 def _check(rc, what):
@@ -143,7 +187,7 @@ class stream_scope:
     backward with it: `torch.cuda.current_stream()` costs ~4 us and was asked ~240 times per step."""
 
     def __init__(self, stream):
-        self.ptr = C.c_void_p(stream.cuda_stream)
+        self.ptr = C.c_void_p(stream.cuda_stream)         # an object of its own: the engine tells scopes apart by its identity
 
     def __enter__(self):
         self.old, _tls.stream = getattr(_tls, "stream", None), self.ptr
@@ -154,12 +198,14 @@ class stream_scope:
         return False
 
 
+def _call(name, *args):
+    """One cold entry point by name, on the current stream where its prototype ends in one; a failure is raised under that name."""
+    fn = getattr(lib(), name)
+    _check(fn(*args, _stream()) if name in _STREAMED else fn(*args), name)
+
+
 def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _P(t):
-    """raw device address for an entry point with declared argtypes / a c_void_p struct field (None = NULL)"""
+    """raw address of a tensor's data (None = NULL): what a c_void_p argument or struct field takes"""
     return t.data_ptr() if t is not None else None
 
 
@@ -227,13 +273,12 @@ def gemm_tn(dy, x, dw, M=None, N=None, K=None, dbias=None, m_dev=None):
     m_dev: int32 device word with the rows actually present (M is then a capacity)."""
     _dev(dy, x, dw, dbias, m_dev)
     a = GemmTnArgs()
-    a.dy, a.x, a.dw, a.dbias = _ptr(dy), _ptr(x), _ptr(dw), _ptr(dbias)
-    a.m_dev = _P(m_dev)
+    a.dy, a.x, a.dw, a.dbias, a.m_dev = _ptr(dy), _ptr(x), _ptr(dw), _ptr(dbias), _ptr(m_dev)
     a.M = dy.shape[0] if M is None else M
     a.N = dy.shape[1] if N is None else N
     a.K = x.shape[1] if K is None else K
     a.lddy, a.ldx, a.lddw = dy.stride(0), x.stride(0), dw.stride(0)
-    _check(lib().unimm_gemm_tn(C.byref(a), _stream()), "unimm_gemm_tn")
+    _call("unimm_gemm_tn", C.byref(a))
     return dw
 
 
@@ -250,18 +295,17 @@ def gemm_tn_grouped(problems, shared=None, ws=None):
     arr = (GemmTnArgs * n)()
     for a, (dy, x, dw, M, N, K, dbias, *rest) in zip(arr, problems):
         _dev(dy, x, dw, dbias)
-        a.dy, a.x, a.dw, a.dbias = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), (dbias.data_ptr() if dbias is not None else None)
-        a.m_dev = rest[0].data_ptr() if rest and rest[0] is not None else None
+        a.dy, a.x, a.dw, a.dbias = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(dbias)
+        a.m_dev = _ptr(rest[0]) if rest else None
         a.overwrite = 1 if (len(rest) > 1 and rest[1]) else 0
         a.M = dy.shape[0] if M is None else M
         a.N = dy.shape[1] if N is None else N
         a.K = x.shape[1] if K is None else K
         a.lddy, a.ldx, a.lddw = dy.stride(0), x.stride(0), dw.stride(0)
     if shared is None and ws is None:
-        _check(lib().unimm_gemm_tn_grouped(C.addressof(arr), n, _stream()), "unimm_gemm_tn_grouped")
+        _call("unimm_gemm_tn_grouped", C.addressof(arr), n)
         return
-    _check(lib().unimm_gemm_tn_grouped_ws(C.addressof(arr), n, int(shared or 0), _P(ws),
-                                          ws.numel() if ws is not None else 0, _stream()), "unimm_gemm_tn_grouped_ws")
+    _call("unimm_gemm_tn_grouped_ws", C.addressof(arr), n, int(shared or 0), _ptr(ws), ws.numel() if ws is not None else 0)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -309,7 +353,7 @@ NO_DROP = (0, 0, 1.0)
 
 def _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar=None, kvar=None):
     """The fields `AttnArgs` and `AttnBwdArgs` share, for every attention wrapper (v = None: the launch reads no values)."""
-    a.q, a.k, a.v, a.mask = q.data_ptr(), k.data_ptr(), _P(v), mask.data_ptr()
+    a.q, a.k, a.v, a.mask = q.data_ptr(), k.data_ptr(), _ptr(v), mask.data_ptr()
     a.q_off, a.q_len = (qvar[0].data_ptr(), qvar[1].data_ptr()) if qvar is not None else (None, None)
     a.k_off, a.k_len = (kvar[0].data_ptr(), kvar[1].data_ptr()) if kvar is not None else (None, None)
     a.order = _item_order(qvar, kvar)
@@ -333,7 +377,7 @@ def attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mas
         st = _tls.af = (a, C.addressof(a), lib().unimm_attn_fwd)
     a, addr, fn = st
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
-    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
+    a.out, a.lse, a.ldo = out.data_ptr(), _ptr(lse), out.stride(0)
     if kshared is not None:
         a.ks_off, a.ks_len, a.ks_ins = kshared[0].data_ptr(), kshared[1].data_ptr(), int(kshared[2])
     else:
@@ -362,9 +406,9 @@ def attn_spliced_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_str
     _dev(q, k, v, out, lse, mask)
     a = AttnArgs()
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
-    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
-    a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
-    _check(lib().unimm_attn_spliced_fwd(C.byref(a), _stream()), "unimm_attn_spliced_fwd")
+    a.out, a.lse, a.ldo = out.data_ptr(), _ptr(lse), out.stride(0)
+    a.ks_off, a.ks_len, a.ks_ins = _ptr(kshared[0]), _ptr(kshared[1]), int(kshared[2])
+    _call("unimm_attn_spliced_fwd", C.byref(a))
 
 
 def spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar,
@@ -373,12 +417,12 @@ def spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D,
     a = AttnSplicedBwdArgs()
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
     a.order = None                                  # a workgroup is a (group, head): the sequence order does not apply
-    a.out, a.dout, a.lse, a.delta = out.data_ptr(), dout.data_ptr(), _P(lse), None
+    a.out, a.dout, a.lse, a.delta = out.data_ptr(), dout.data_ptr(), _ptr(lse), None
     a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
     a.ldo, a.lddo = out.stride(0), dout.stride(0)
     a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
-    a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
-    a.g_first, a.g_seq = _P(groups[0]), _P(groups[1])
+    a.ks_off, a.ks_len, a.ks_ins = _ptr(kshared[0]), _ptr(kshared[1]), int(kshared[2])
+    a.g_first, a.g_seq = _ptr(groups[0]), _ptr(groups[1])
     a.G = (groups[0].numel() - 1) if groups[0] is not None else 0
     a.accumulate = 1 if accumulate else 0
     return a
@@ -391,7 +435,7 @@ def attn_spliced_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D,
     _dev(q, k, v, out, dout, lse, dq, dk, dv, mask, *groups)
     a = spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar,
                          kvar, kshared, groups, accumulate)
-    _check(lib().unimm_attn_spliced_bwd(C.byref(a), _stream()), "unimm_attn_spliced_bwd")
+    _call("unimm_attn_spliced_bwd", C.byref(a))
 
 
 class AttnDecodeArgs(C.Structure):
@@ -417,7 +461,7 @@ def attn_decode(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, pl
     a = AttnDecodeArgs()
     a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     a.ctx_k, a.ctx_v, a.ctx_off, a.ctx_len = ctx_k.data_ptr(), ctx_v.data_ptr(), ctx_off.data_ptr(), ctx_len.data_ptr()
-    a.priv_k, a.priv_v, a.plen = _P(priv_k), _P(priv_v), plen.data_ptr()
+    a.priv_k, a.priv_v, a.plen = _ptr(priv_k), _ptr(priv_v), plen.data_ptr()
     a.G, a.beams, a.nr, a.H, a.D, a.pcap = G, beams, nr, H, D, pcap
     a.ldq, a.ldk, a.ldv, a.ldo, a.ldc = q.stride(0), k.stride(0), v.stride(0), out.stride(0), ctx_k.stride(0)
     if ctx_v.stride(0) != ctx_k.stride(0):
@@ -426,7 +470,7 @@ def attn_decode(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, pl
     if priv_v is not None and priv_v.stride(0) != a.ldp:
         raise UnimmHipError("attn_decode: priv_k and priv_v need one row stride")
     a.scale = scale
-    _check(lib().unimm_attn_decode(C.byref(a), _stream()), "unimm_attn_decode")
+    _call("unimm_attn_decode", C.byref(a))
 
 
 def kv_cache_update(src, dst, new_kv, parent, plen, plen_out, layers, slots, pcap, width, new_layer_stride, new_row_mul):
@@ -438,15 +482,15 @@ def kv_cache_update(src, dst, new_kv, parent, plen, plen_out, layers, slots, pca
     a.parent, a.plen, a.plen_out = parent.data_ptr(), plen.data_ptr(), plen_out.data_ptr()
     a.layers, a.slots, a.pcap, a.ldp, a.width = layers, slots, pcap, src.shape[-1], width
     a.new_layer_stride, a.ld_new, a.new_row_mul = new_layer_stride, new_kv.stride(0), new_row_mul
-    _check(lib().unimm_kv_cache_update(C.byref(a), _stream()), "unimm_kv_cache_update")
+    _call("unimm_kv_cache_update", C.byref(a))
 
 
 def lm_topk(logits, rows, V, banned, flags, sep, K, vals, ids, lse=None):
     """log-softmax + top-K of fp32 logits [rows, >= V] (unimm_lm_topk): vals fp32 [rows, K], ids int32 [rows, K]."""
     _dev(logits, banned, flags, vals, ids, lse)
     nb = 0 if banned is None else banned.numel()
-    _check(lib().unimm_lm_topk(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, K,
-                               vals.data_ptr(), ids.data_ptr(), _P(lse), _stream()), "unimm_lm_topk")
+    _call("unimm_lm_topk", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, K, vals.data_ptr(),
+          ids.data_ptr(), _ptr(lse))
 
 
 def lm_sample(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, key, streams, token, logp, logq, lse=None):
@@ -454,9 +498,8 @@ def lm_sample(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, ke
     [rows], logp (unmodified distribution) and logq (the one sampled from) fp32 [rows]; streams int32 [rows], key a 32-bit word."""
     _dev(logits, banned, flags, streams, token, logp, logq, lse)
     nb = 0 if banned is None else banned.numel()
-    _check(lib().unimm_lm_sample(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, temperature, top_k,
-                                 top_p, key & 0xFFFFFFFF, _P(streams), _P(token), _P(logp), _P(logq), _P(lse), _stream()),
-           "unimm_lm_sample")
+    _call("unimm_lm_sample", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, temperature, top_k,
+          top_p, key & 0xFFFFFFFF, _ptr(streams), _ptr(token), _ptr(logp), _ptr(logq), _ptr(lse))
 
 
 def lm_sample_rows(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, key, streams, token, logp, logq, lse=None):
@@ -464,9 +507,8 @@ def lm_sample_rows(logits, rows, V, banned, flags, sep, temperature, top_k, top_
     [rows] on the device.  A row with top_k = 1 is greedy (logq = 0); a row with invalid parameters returns token = -1."""
     _dev(logits, banned, flags, temperature, top_k, top_p, streams, token, logp, logq, lse)
     nb = 0 if banned is None else banned.numel()
-    _check(lib().unimm_lm_sample_rows(logits.data_ptr(), rows, V, logits.stride(0), _P(banned), nb, _P(flags), sep, _P(temperature),
-                                      _P(top_k), _P(top_p), key & 0xFFFFFFFF, _P(streams), _P(token), _P(logp), _P(logq), _P(lse),
-                                      _stream()), "unimm_lm_sample_rows")
+    _call("unimm_lm_sample_rows", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, _ptr(temperature),
+          _ptr(top_k), _ptr(top_p), key & 0xFFFFFFFF, _ptr(streams), _ptr(token), _ptr(logp), _ptr(logq), _ptr(lse))
 
 
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):
@@ -474,7 +516,7 @@ def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_
     _dev(q, k, probs, mask)
     a = AttnArgs()                  # out / lse / ldo / ks_* stay zero
     _attn_common(a, q, k, None, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop)
-    _check(lib().unimm_attn_probs(C.byref(a), _ptr(probs), _stream()), "unimm_attn_probs")
+    _call("unimm_attn_probs", C.byref(a), _ptr(probs))
 
 
 def attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride,
@@ -512,8 +554,7 @@ def mask_pack(mask, out=None):
     nw = (t + 31) // 32
     if out is None:
         out = torch.empty(mask.shape[:-1] + (nw,), dtype=torch.int32, device=mask.device)
-    _check(lib().unimm_mask_pack(_ptr(mask), _DT[mask.dtype], _ptr(out), C.c_int64(rows), C.c_int32(t), _stream()),
-           "unimm_mask_pack")
+    _call("unimm_mask_pack", _ptr(mask), _DT[mask.dtype], _ptr(out), rows, t)
     return out
 
 
@@ -532,8 +573,7 @@ def host_mask_pack(mask, out=None, threads=0):
         out = torch.empty(mask.shape[:-1] + (nw,), dtype=torch.int32)
     if out.is_cuda or out.dtype != torch.int32 or out.numel() != rows * nw or not out.is_contiguous():
         raise UnimmHipError("host_mask_pack: out must be a contiguous int32 CPU tensor of rows x ceil(T/32) words")
-    _check(lib().unimm_host_mask_pack(C.c_void_p(mask.data_ptr()), _DT[mask.dtype], C.c_void_p(out.data_ptr()), C.c_int64(rows),
-                                      C.c_int32(t), C.c_int32(threads)), "unimm_host_mask_pack")
+    _call("unimm_host_mask_pack", mask.data_ptr(), _DT[mask.dtype], out.data_ptr(), rows, t, threads)
     return out
 
 
@@ -544,13 +584,12 @@ def host_copy(dst, src, threads=0):
             or not src.is_contiguous() or src.numel() * src.element_size() < (8 << 20)):
         dst.copy_(src)
         return dst
-    _check(lib().unimm_host_memcpy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), C.c_int64(src.numel() * src.element_size()),
-                                   C.c_int32(threads)), "unimm_host_memcpy")
+    _call("unimm_host_memcpy", dst.data_ptr(), src.data_ptr(), src.numel() * src.element_size(), threads)
     return dst
 
 
 def colpartials_bytes(H):
-    return int(lib().unimm_colpartials_bytes(C.c_int32(H)))
+    return int(lib().unimm_colpartials_bytes(H))
 
 
 class FinishDesc(C.Structure):
@@ -565,12 +604,9 @@ def layernorm_bwd_partials(dy, x, mean, rstd, gamma, dx, dx_drop, partials, M, H
     out_drop = out_drop or NO_DROP
     _dev(dy, x, mean, rstd, gamma, dx, dx_drop, partials, drop_rows)
     blocks = C.c_int32(0)
-    rc = lib().unimm_layernorm_bwd_partials(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                            dx.data_ptr(), _P(dx_drop), partials.data_ptr(), M, H, drop[0], drop[1], drop[2],
-                                            out_drop[0], out_drop[1], out_drop[2], C.addressof(blocks), _P(m_dev),
-                                            _salt(drop, out_drop), _P(drop_rows), _stream())
-    if rc != 0:
-        _check(rc, "unimm_layernorm_bwd_partials")
+    _call("unimm_layernorm_bwd_partials", dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
+          dx.data_ptr(), _ptr(dx_drop), partials.data_ptr(), M, H, *drop[:3], *out_drop[:3], C.addressof(blocks), _ptr(m_dev),
+          _salt(drop, out_drop), _ptr(drop_rows))
     return blocks.value
 
 
@@ -583,25 +619,21 @@ def colpartials_finish_grouped(pending):
     for d, (part, blocks, H, dsts) in zip(arr, pending):
         d.partials, d.blocks, d.nq, d.H = part.data_ptr(), blocks, len(dsts), H
         for q, t in enumerate(dsts):
-            d.dst[q] = t.data_ptr() if t is not None else None
-    _check(lib().unimm_colpartials_finish_grouped(C.addressof(arr), n, _stream()), "unimm_colpartials_finish_grouped")
+            d.dst[q] = _ptr(t)
+    _call("unimm_colpartials_finish_grouped", C.addressof(arr), n)
 
 
 def layernorm_fwd(x, gamma, beta, y32, y16, mean, rstd, M, H, eps=1e-12, drop=NO_DROP):
     _dev(x, gamma, beta, y32, y16, mean, rstd)
-    rc = lib().unimm_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _P(y32), _P(y16), _P(mean), _P(rstd), M, H, eps,
-                                   drop[0], drop[1], drop[2], _salt(drop), _stream())
-    if rc != 0:
-        _check(rc, "unimm_layernorm_fwd")
+    _call("unimm_layernorm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(y32), _ptr(y16), _ptr(mean), _ptr(rstd), M, H,
+          eps, *drop[:3], _salt(drop))
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, dbias, partials, M, H, drop=NO_DROP,
                   out_drop=NO_DROP, drop_rows=None):
     _dev(dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, dbias, partials, drop_rows)
-    _check(lib().unimm_layernorm_bwd(_P(dy), _P(x), _P(mean), _P(rstd), _P(gamma), _P(dx), _P(dx_drop),
-                                     _P(dgamma), _P(dbeta), _P(dbias), _P(partials), M, H, drop[0], drop[1], drop[2],
-                                     out_drop[0], out_drop[1], out_drop[2], _salt(drop, out_drop), _P(drop_rows), _stream()),
-           "unimm_layernorm_bwd")
+    _call("unimm_layernorm_bwd", _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx), _ptr(dx_drop), _ptr(dgamma),
+          _ptr(dbeta), _ptr(dbias), _ptr(partials), M, H, *drop[:3], *out_drop[:3], _salt(drop, out_drop), _ptr(drop_rows))
 
 
 class EmbedArgs(C.Structure):
@@ -622,7 +654,7 @@ def _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_v
     a.M, a.H, a.type_vocab, a.eps = M, H, type_vocab, eps
     a.drop_key, a.drop_thr, a.drop_scale = drop[:3]
     a.drop_salt = _salt(drop)
-    a.m_dev, a.rows = _P(m_dev), _P(rows)
+    a.m_dev, a.rows = _ptr(m_dev), _ptr(rows)
     return a
 
 
@@ -631,15 +663,15 @@ def embed_fwd(ids, pos, typ, word, post, type_, ext, gamma, beta, y32, y16, M, H
     """rows (int64 [M]): row r embeds ids / pos / typ at index rows[r]; m_dev: int32 device word, rows actually present."""
     a = _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_vocab, eps, drop, m_dev, rows)
     _dev(y32, y16)
-    _check(lib().unimm_embed_fwd(C.byref(a), _ptr(y32), _ptr(y16), _stream()), "unimm_embed_fwd")
+    _call("unimm_embed_fwd", C.byref(a), _ptr(y32), _ptr(y16))
 
 
 def embed_bwd(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, dword, dpos, dtype, dext, dgamma, dbeta,
               partials, M, H, type_vocab=2, eps=1e-12, drop=NO_DROP, m_dev=None, rows=None):
     a = _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_vocab, eps, drop, m_dev, rows)
     _dev(dy, dword, dpos, dtype, dext, dgamma, dbeta, partials)
-    _check(lib().unimm_embed_bwd(C.byref(a), _ptr(dy), _ptr(dword), _ptr(dpos), _ptr(dtype), _ptr(dext), _ptr(dgamma),
-                                 _ptr(dbeta), _ptr(partials), _stream()), "unimm_embed_bwd")
+    _call("unimm_embed_bwd", C.byref(a), _ptr(dy), _ptr(dword), _ptr(dpos), _ptr(dtype), _ptr(dext), _ptr(dgamma), _ptr(dbeta),
+          _ptr(partials))
 
 
 def embed_bwd_rows(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, drow, dtype, dgamma, dbeta, partials, M, H,
@@ -647,28 +679,24 @@ def embed_bwd_rows(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, drow,
     """embed_bwd without atomics: the rows' gradients are stored in drow (fp32 [M, H]); `rows_scatter_sum_f32` adds them up."""
     a = _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_vocab, eps, drop, None, rows)
     _dev(dy, drow, dtype, dgamma, dbeta, partials)
-    _check(lib().unimm_embed_bwd_rows(C.byref(a), _ptr(dy), _ptr(drow), _ptr(dtype), _ptr(dgamma), _ptr(dbeta), _ptr(partials),
-                                      _stream()), "unimm_embed_bwd_rows")
+    _call("unimm_embed_bwd_rows", C.byref(a), _ptr(dy), _ptr(drow), _ptr(dtype), _ptr(dgamma), _ptr(dbeta), _ptr(partials))
 
 
 def rows_scatter_sum_f32(src, keys, order, dst):
     """dst[keys[j]] += src[order[j]] over each key's run, in a fixed order (keys ascending int32 [M], negative = skipped): one writer
     per destination row, no atomics (unimm_rows_scatter_sum_f32).  src fp32 [M, H], dst fp32 [n, H], both contiguous."""
     _dev(src, keys, order, dst)
-    _check(lib().unimm_rows_scatter_sum_f32(_ptr(src), _ptr(keys), _ptr(order), C.c_int32(src.shape[0]), C.c_int32(src.shape[1]),
-                                            _ptr(dst), C.c_int32(dst.shape[0]), _stream()), "unimm_rows_scatter_sum_f32")
+    _call("unimm_rows_scatter_sum_f32", _ptr(src), _ptr(keys), _ptr(order), src.shape[0], src.shape[1], _ptr(dst), dst.shape[0])
 
 
 def colsum(dy, db, M, N):
     _dev(dy, db)
-    _check(lib().unimm_colsum(_ptr(dy), _ptr(db), C.c_int32(M), C.c_int32(N), C.c_int32(dy.stride(0)), _stream()),
-           "unimm_colsum")
+    _call("unimm_colsum", _ptr(dy), _ptr(db), M, N, dy.stride(0))
 
 
 def cast_f32_bf16(src, dst, n=None):
     _dev(src, dst)
-    _check(lib().unimm_cast_f32_bf16(_ptr(src), _ptr(dst), C.c_int64(src.numel() if n is None else n), _stream()),
-           "unimm_cast_f32_bf16")
+    _call("unimm_cast_f32_bf16", _ptr(src), _ptr(dst), src.numel() if n is None else n)
 
 
 def mask_synth(mode, length, nans, T):
@@ -677,8 +705,7 @@ def mask_synth(mode, length, nans, T):
     B, nw = mode.numel(), (T + 31) // 32
     text = torch.empty((B, T, nw), dtype=torch.int32, device=mode.device)
     co = torch.empty((B, nw), dtype=torch.int32, device=mode.device)
-    _check(lib().unimm_mask_synth(_ptr(mode), _ptr(length), _ptr(nans), _ptr(text), _ptr(co), C.c_int32(B), C.c_int32(T),
-                                  _stream()), "unimm_mask_synth")
+    _call("unimm_mask_synth", _ptr(mode), _ptr(length), _ptr(nans), _ptr(text), _ptr(co), B, T)
     return text, co
 
 
@@ -690,10 +717,8 @@ def plan_lengths(text_mask, co_mask, R, labels, weights, nsp_weight, B, T, image
     ref = tw if tw is not None else (cw if cw is not None else labels)
     header = torch.zeros(3 * B + 2, dtype=torch.int32, device=ref.device)
     _dev(tw, cw, labels, weights, nsp_weight, image_label)
-    _check(lib().unimm_plan_lengths(_ptr(tw), C.c_int32(tq), C.c_int32(tb), _ptr(cw), C.c_int32(cq), C.c_int32(cb), C.c_int32(R),
-                                    _ptr(labels), _ptr(weights), _ptr(nsp_weight), _ptr(image_label), C.c_int32(B), C.c_int32(T),
-                                    _ptr(header),
-                                    _stream()), "unimm_plan_lengths")
+    _call("unimm_plan_lengths", _ptr(tw), tq, tb, _ptr(cw), cq, cb, R, _ptr(labels), _ptr(weights), _ptr(nsp_weight),
+          _ptr(image_label), B, T, _ptr(header))
     return header
 
 
@@ -711,40 +736,34 @@ def plan_build(header, labels, weights, B, T, Mv, n_lm, want_rows=True, dims=Non
     di, df = dims if dims is not None else (None, None)
     _dev(di, df)
     order = i32(B)                     # the sequences by length, longest first: the item order of the attention launches
-    _check(lib().unimm_plan_build(_ptr(header), _ptr(labels), _ptr(weights), C.c_int32(B), C.c_int32(T), _ptr(off), _ptr(lens),
-                                  _ptr(rows), _ptr(inv), *[_ptr(t) for t in lm], C.c_int32(Mv if want_rows else 0),
-                                  C.c_int32(n_lm if lm[0] is not None else 0), _ptr(di), _ptr(df), _ptr(order), _stream()),
-           "unimm_plan_build")
+    _call("unimm_plan_build", _ptr(header), _ptr(labels), _ptr(weights), B, T, _ptr(off), _ptr(lens), _ptr(rows), _ptr(inv),
+          *[_ptr(t) for t in lm], Mv if want_rows else 0, n_lm if lm[0] is not None else 0, _ptr(di), _ptr(df), _ptr(order))
     return dict(off=off, lens=lens, rows=rows, inv=inv, lm_pos=lm[0], lm_idx=lm[1], lm_label=lm[2], lm_weight=lm[3], order=order)
 
 
 def transpose_cast(src, dst, R, C_, ldd):
     _dev(src, dst)
-    _check(lib().unimm_transpose_cast(_ptr(src), _ptr(dst), C.c_int32(R), C.c_int32(C_), C.c_int32(ldd), _stream()),
-           "unimm_transpose_cast")
+    _call("unimm_transpose_cast", _ptr(src), _ptr(dst), R, C_, ldd)
 
 
 def transpose_bf16(src, dst, R, C_):
     """dst[c, r] = src[r, c] (bf16 [R, C] -> bf16 [C, ldd >= R], surplus columns zero)."""
     _dev(src, dst)
-    _check(lib().unimm_transpose_bf16(_ptr(src), _ptr(dst), C.c_int32(R), C.c_int32(C_), C.c_int32(src.stride(0)),
-                                      C.c_int32(dst.stride(0)), _stream()), "unimm_transpose_bf16")
+    _call("unimm_transpose_bf16", _ptr(src), _ptr(dst), R, C_, src.stride(0), dst.stride(0))
 
 
 def sum_slabs_bf16(slabs, out, n):
     """out[:n] (bf16) = slabs.sum(0) in slab order; slabs: fp32 [S, ...] contiguous, n a multiple of 8."""
     _dev(slabs, out)
-    _check(lib().unimm_sum_slabs_bf16(_ptr(slabs), C.c_int32(slabs.shape[0]), C.c_int64(slabs.stride(0)), _ptr(out),
-                                      C.c_int64(n), _stream()), "unimm_sum_slabs_bf16")
+    _call("unimm_sum_slabs_bf16", _ptr(slabs), slabs.shape[0], slabs.stride(0), _ptr(out), n)
 
 
 def segment_rows_sum_bf16(src, first, items, dst, R, W):
     """dst block g (R rows x W, 2-D bf16 view) = sum of src's R-row blocks items[first[g] : first[g + 1]], fp32 in list order,
     rounded once (unimm_segment_rows_sum_bf16); first int32 [G + 1], items int32 device tensors."""
     _dev(src, first, items, dst)
-    _check(lib().unimm_segment_rows_sum_bf16(_ptr(src), C.c_int32(src.stride(0)), _ptr(first), _ptr(items), C.c_int32(items.numel()),
-                                             C.c_int32(first.numel() - 1), _ptr(dst), C.c_int32(dst.stride(0)), C.c_int32(R),
-                                             C.c_int32(W), _stream()), "unimm_segment_rows_sum_bf16")
+    _call("unimm_segment_rows_sum_bf16", _ptr(src), src.stride(0), _ptr(first), _ptr(items), items.numel(), first.numel() - 1,
+          _ptr(dst), dst.stride(0), R, W)
 
 
 class TransposeDesc(C.Structure):
@@ -766,30 +785,24 @@ def transpose_table(entries, device):
 
 
 def transpose_cast_grouped(table, count, tiles):
-    _check(lib().unimm_transpose_cast_grouped(_ptr(table), C.c_int32(count), C.c_int32(tiles), _stream()),
-           "unimm_transpose_cast_grouped")
+    _call("unimm_transpose_cast_grouped", _ptr(table), count, tiles)
 
 
 def pack_image(feat, loc, out, rows, F, ld):
     _dev(feat, loc, out)
-    _check(lib().unimm_pack_image(_ptr(feat), _ptr(loc), _ptr(out), C.c_int32(rows), C.c_int32(F), C.c_int32(ld),
-                                  _stream()), "unimm_pack_image")
+    _call("unimm_pack_image", _ptr(feat), _ptr(loc), _ptr(out), rows, F, ld)
 
 
 def mul_dropout(a, b, out, n, drop=NO_DROP, fusion_sum=False):
     """out = dropout(a * b) (fusion_method 'mul') or dropout(a + b) ('sum')."""
     _dev(a, b, out)
-    fn = lib().unimm_sum_dropout if fusion_sum else lib().unimm_mul_dropout
-    _check(fn(_ptr(a), _ptr(b), _ptr(out), C.c_int64(n), C.c_uint32(drop[0]), C.c_uint32(drop[1]),
-                                   C.c_float(drop[2]), C.c_void_p(_salt(drop)), _stream()), "unimm_mul_dropout")
+    _call("unimm_sum_dropout" if fusion_sum else "unimm_mul_dropout", _ptr(a), _ptr(b), _ptr(out), n, *drop[:3], _salt(drop))
 
 
 def mul_dropout_bwd(a, b, dout, da, db, n, drop=NO_DROP, fusion_sum=False):
     _dev(a, b, dout, da, db)
-    fn = lib().unimm_sum_dropout_bwd if fusion_sum else lib().unimm_mul_dropout_bwd
-    _check(fn(_ptr(a), _ptr(b), _ptr(dout), _ptr(da), _ptr(db), C.c_int64(n),
-                                       C.c_uint32(drop[0]), C.c_uint32(drop[1]), C.c_float(drop[2]), C.c_void_p(_salt(drop)),
-                                       _stream()), "unimm_mul_dropout_bwd")
+    _call("unimm_sum_dropout_bwd" if fusion_sum else "unimm_mul_dropout_bwd", _ptr(a), _ptr(b), _ptr(dout), _ptr(da), _ptr(db), n,
+          *drop[:3], _salt(drop))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -797,16 +810,14 @@ def mul_dropout_bwd(a, b, dout, da, db, n, drop=NO_DROP, fusion_sum=False):
 # ---------------------------------------------------------------------------------------------
 def lm_loss_fwd(logits, labels, weights, rowloss, rownll, lse, n, V, n_dev=None):
     _dev(logits, labels, weights, rowloss, rownll, lse, n_dev)
-    _check(lib().unimm_lm_loss_fwd(_ptr(logits), _ptr(labels), _ptr(weights), _ptr(rowloss), _ptr(rownll), _ptr(lse),
-                                   C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)), _ptr(n_dev), _stream()),
-           "unimm_lm_loss_fwd")
+    _call("unimm_lm_loss_fwd", _ptr(logits), _ptr(labels), _ptr(weights), _ptr(rowloss), _ptr(rownll), _ptr(lse), n, V,
+          logits.stride(0), _ptr(n_dev))
 
 
 def lm_loss_bwd(logits, labels, weights, lse, g, inv_denom, dlogits, n, V, n_dev=None, inv_dev=None):
     _dev(logits, labels, weights, lse, g, dlogits, n_dev, inv_dev)
-    _check(lib().unimm_lm_loss_bwd(_ptr(logits), _ptr(labels), _ptr(weights), _ptr(lse), _ptr(g), C.c_float(inv_denom),
-                                   _ptr(dlogits), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)),
-                                   C.c_int32(dlogits.stride(0)), _ptr(n_dev), _ptr(inv_dev), _stream()), "unimm_lm_loss_bwd")
+    _call("unimm_lm_loss_bwd", _ptr(logits), _ptr(labels), _ptr(weights), _ptr(lse), _ptr(g), inv_denom, _ptr(dlogits), n, V,
+          logits.stride(0), dlogits.stride(0), _ptr(n_dev), _ptr(inv_dev))
 
 
 PG_LOGP, PG_RATIO = 0, 1
@@ -815,53 +826,44 @@ PG_LOGP, PG_RATIO = 0, 1
 def pg_loss_fwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, rowloss, rownll, lse, ent, n, V, n_dev=None):
     """Policy-gradient rows (include/unimm_hip.h: unimm_pg_loss_fwd).  adv / blogp: fp32, indexed by pos[row] (pos None: by row)."""
     _dev(logits, labels, pos, adv, blogp, rowloss, rownll, lse, ent, n_dev)
-    _check(lib().unimm_pg_loss_fwd(_ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), C.c_int32(adv.numel()),
-                                   C.c_int32(mode), C.c_float(clip_eps), C.c_float(beta), _ptr(rowloss), _ptr(rownll), _ptr(lse),
-                                   _ptr(ent), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)), _ptr(n_dev), _stream()),
-           "unimm_pg_loss_fwd")
+    _call("unimm_pg_loss_fwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta,
+          _ptr(rowloss), _ptr(rownll), _ptr(lse), _ptr(ent), n, V, logits.stride(0), _ptr(n_dev))
 
 
 def pg_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, ent, g, inv_denom, dlogits, n, V, n_dev=None,
                 inv_dev=None):
     _dev(logits, labels, pos, adv, blogp, lse, ent, g, dlogits, n_dev, inv_dev)
-    _check(lib().unimm_pg_loss_bwd(_ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), C.c_int32(adv.numel()),
-                                   C.c_int32(mode), C.c_float(clip_eps), C.c_float(beta), _ptr(lse), _ptr(ent), _ptr(g),
-                                   C.c_float(inv_denom), _ptr(dlogits), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)),
-                                   C.c_int32(dlogits.stride(0)), _ptr(n_dev), _ptr(inv_dev), _stream()), "unimm_pg_loss_bwd")
+    _call("unimm_pg_loss_bwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta, _ptr(lse),
+          _ptr(ent), _ptr(g), inv_denom, _ptr(dlogits), n, V, logits.stride(0), dlogits.stride(0), _ptr(n_dev), _ptr(inv_dev))
 
 
 def kl_loss_fwd(pred, target, label, rowloss, lse, rows, Cn):
     _dev(pred, target, label, rowloss, lse)
-    _check(lib().unimm_kl_loss_fwd(_ptr(pred), _ptr(target), _ptr(label), _ptr(rowloss), _ptr(lse), C.c_int32(rows),
-                                   C.c_int32(Cn), C.c_int32(pred.stride(0)), _stream()), "unimm_kl_loss_fwd")
+    _call("unimm_kl_loss_fwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(rowloss), _ptr(lse), rows, Cn, pred.stride(0))
 
 
 def kl_loss_bwd(pred, target, label, lse, g, inv_denom, dpred, rows, Cn, inv_dev=None):
     _dev(pred, target, label, lse, g, dpred, inv_dev)
-    _check(lib().unimm_kl_loss_bwd(_ptr(pred), _ptr(target), _ptr(label), _ptr(lse), _ptr(g), C.c_float(inv_denom),
-                                   _ptr(dpred), C.c_int32(rows), C.c_int32(Cn), C.c_int32(pred.stride(0)),
-                                   C.c_int32(dpred.stride(0)), _ptr(inv_dev), _stream()), "unimm_kl_loss_bwd")
+    _call("unimm_kl_loss_bwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(lse), _ptr(g), inv_denom, _ptr(dpred), rows, Cn,
+          pred.stride(0), dpred.stride(0), _ptr(inv_dev))
 
 
 def mse_loss_fwd(pred, target, label, rowloss, rows, Cn):
     _dev(pred, target, label, rowloss)
-    _check(lib().unimm_mse_loss_fwd(_ptr(pred), _ptr(target), _ptr(label), _ptr(rowloss), C.c_int32(rows), C.c_int32(Cn),
-                                    C.c_int32(pred.stride(0)), _stream()), "unimm_mse_loss_fwd")
+    _call("unimm_mse_loss_fwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(rowloss), rows, Cn, pred.stride(0))
 
 
 def mse_loss_bwd(pred, target, label, g, inv_denom, dpred, rows, Cn, split=False):
     """dpred: bf16 [rows, ldd], or (split=True) an x-type split operand [rows, 3 ldd]."""
     _dev(pred, target, label, g, dpred)
     ldd = dpred.shape[1] // 3 if split else dpred.stride(0)
-    _check(lib().unimm_mse_loss_bwd(_ptr(pred), _ptr(target), _ptr(label), _ptr(g), C.c_float(inv_denom), _ptr(dpred),
-                                    C.c_int32(rows), C.c_int32(Cn), C.c_int32(pred.stride(0)), C.c_int32(ldd),
-                                    C.c_int32(1 if split else 0), _stream()), "unimm_mse_loss_bwd")
+    _call("unimm_mse_loss_bwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(g), inv_denom, _ptr(dpred), rows, Cn, pred.stride(0), ldd,
+          1 if split else 0)
 
 
 def nsp_loss_fwd(logits, labels, w0, w1, loss, B):
     _dev(logits, labels, loss)
-    _check(lib().unimm_nsp_loss_fwd(_ptr(logits), _ptr(labels), C.c_float(w0), C.c_float(w1), _ptr(loss), C.c_int32(B),
-                                    C.c_int32(logits.stride(0)), _stream()), "unimm_nsp_loss_fwd")
+    _call("unimm_nsp_loss_fwd", _ptr(logits), _ptr(labels), w0, w1, _ptr(loss), B, logits.stride(0))
 
 
 def nsp_loss_bwd(logits, labels, w0, w1, g, dlogits, B, extra=None):
@@ -869,9 +871,8 @@ def nsp_loss_bwd(logits, labels, w0, w1, g, dlogits, B, extra=None):
     _dev(logits, labels, g, dlogits, extra)
     if dlogits.dtype != torch.float32 or (extra is not None and (extra.dtype != torch.float32 or not extra.is_contiguous())):
         raise UnimmHipError("nsp_loss_bwd: dlogits / extra must be fp32 (extra contiguous [B, 2])")
-    _check(lib().unimm_nsp_loss_bwd(_ptr(logits), _ptr(labels), C.c_float(w0), C.c_float(w1), _ptr(g), _ptr(extra), _ptr(dlogits),
-                                    C.c_int32(B), C.c_int32(logits.stride(0)), C.c_int32(dlogits.stride(0)), _stream()),
-           "unimm_nsp_loss_bwd")
+    _call("unimm_nsp_loss_bwd", _ptr(logits), _ptr(labels), w0, w1, _ptr(g), _ptr(extra), _ptr(dlogits), B, logits.stride(0),
+          dlogits.stride(0))
 
 
 class LinearF32Args(C.Structure):
@@ -889,41 +890,38 @@ def linear_f32(a, b, out, M, N, K, sa, sb, bias=None, relu=False, accumulate=Fal
         if t is not None and t.dtype != torch.float32:
             raise UnimmHipError("linear_f32: every operand is fp32")
     g = LinearF32Args()
-    g.a, g.b, g.bias, g.out, g.rowsum = a.data_ptr(), b.data_ptr(), _P(bias), out.data_ptr(), _P(rowsum)
+    g.a, g.b, g.bias, g.out, g.rowsum = a.data_ptr(), b.data_ptr(), _ptr(bias), out.data_ptr(), _ptr(rowsum)
     g.M, g.N, g.K = M, N, K
     g.sa_m, g.sa_k, g.sb_k, g.sb_n, g.ldo = sa[0], sa[1], sb[0], sb[1], out.stride(0)
     g.relu, g.accumulate = int(bool(relu)), int(bool(accumulate))
-    _check(lib().unimm_linear_f32(C.byref(g), _stream()), "unimm_linear_f32")
+    _call("unimm_linear_f32", C.byref(g))
     return out
 
 
 def rows_add_f32(dst, idx, src, n, H):
     """dst (bf16 [*, H] contiguous rows)[idx[r], :] += src (fp32 [n, H] contiguous)[r, :]"""
     _dev(dst, idx, src)
-    _check(lib().unimm_rows_add_f32(_ptr(dst), _ptr(idx), _ptr(src), C.c_int32(n), C.c_int32(H), _stream()), "unimm_rows_add_f32")
+    _call("unimm_rows_add_f32", _ptr(dst), _ptr(idx), _ptr(src), n, H)
 
 
 def reduce_sum(src, n, dst, scale=1.0, n_dev=None, scale_dev=None):
     _dev(src, dst, n_dev, scale_dev)
-    _check(lib().unimm_reduce_sum(_ptr(src), C.c_int64(n), _ptr(dst), C.c_float(scale), _ptr(n_dev), _ptr(scale_dev), _stream()),
-           "unimm_reduce_sum")
+    _call("unimm_reduce_sum", _ptr(src), n, _ptr(dst), scale, _ptr(n_dev), _ptr(scale_dev))
 
 
 def segment_sum(src, seg, dst, n, sign=1.0):
     _dev(src, seg, dst)
-    _check(lib().unimm_segment_sum(_ptr(src), _ptr(seg), _ptr(dst), C.c_int64(n), C.c_float(sign), _stream()),
-           "unimm_segment_sum")
+    _call("unimm_segment_sum", _ptr(src), _ptr(seg), _ptr(dst), n, sign)
 
 
 def gelu_bwd(dt, u, du, n):
     _dev(dt, u, du)
-    _check(lib().unimm_gelu_bwd(_ptr(dt), _ptr(u), _ptr(du), C.c_int64(n), _stream()), "unimm_gelu_bwd")
+    _call("unimm_gelu_bwd", _ptr(dt), _ptr(u), _ptr(du), n)
 
 
 def gather_rows(src, idx, dst, n, H, scatter=False, n_dev=None):
     _dev(src, idx, dst, n_dev)
-    _check(lib().unimm_gather_rows(_ptr(src), _ptr(idx), _ptr(dst), C.c_int32(n), C.c_int32(H),
-                                   C.c_int32(1 if scatter else 0), _ptr(n_dev), _stream()), "unimm_gather_rows")
+    _call("unimm_gather_rows", _ptr(src), _ptr(idx), _ptr(dst), n, H, 1 if scatter else 0, _ptr(n_dev))
 
 
 _EPI_NAMES = ["BIAS", "BIAS_GELU", "BIAS_DROP_RESID", "BIAS_RELU", "DGELU", "ADD", "MUL", "BIAS_GELU_DG"]
@@ -958,14 +956,13 @@ def adamw_step(p, g, m, v, group, lrs, wds, step, beta1=0.9, beta2=0.999, eps=1e
     if len(lrs) != len(wds) or not 1 <= len(lrs) <= ADAMW_MAX_GROUPS:
         raise UnimmHipError(f"adamw_step: 1..{ADAMW_MAX_GROUPS} (lr, weight_decay) groups, got {len(lrs)}")
     a = AdamWArgs()
-    a.p, a.g, a.m, a.v, a.w16, a.group = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), \
-        (w16.data_ptr() if w16 is not None else None), group.data_ptr()
+    a.p, a.g, a.m, a.v, a.w16, a.group = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(w16), group.data_ptr()
     a.n, a.n_groups, a.step = p.numel(), len(lrs), int(step)
     for i, (lr, wd) in enumerate(zip(lrs, wds)):
         a.lr[i], a.weight_decay[i] = float(lr), float(wd)
     a.beta1, a.beta2, a.eps, a.grad_scale = beta1, beta2, eps, grad_scale
     a.correct_bias, a.zero_grad = int(bool(correct_bias)), int(bool(zero_grad))
-    _check(lib().unimm_adamw_step(C.byref(a), _stream()), "unimm_adamw_step")
+    _call("unimm_adamw_step", C.byref(a))
 
 
 NDCG_MAX_OPTIONS, NDCG_MAX_ITER = 128, 64
@@ -996,33 +993,33 @@ def neural_ndcg(pred, truth, pad_label=-1.0, temperature=1.0, powered=True, k=No
     a.pred, a.truth, a.ndcg, a.alive, a.dpred, a.iters = (t.data_ptr() for t in (pred, truth, ndcg, alive, dpred, iters))
     a.slates, a.n, a.k, a.powered_relevancies, a.max_iter = S, n, (0 if k is None else int(k)), int(bool(powered)), int(max_iter)
     a.pad_label, a.temperature, a.tol = float(pad_label), float(temperature), float(tol)
-    _check(lib().unimm_neural_ndcg(C.byref(a), _stream()), "unimm_neural_ndcg")
+    _call("unimm_neural_ndcg", C.byref(a))
     return ndcg, alive, dpred, iters
 
 
 def prof_enable(on):
     """False / 0 = off, True / 1 = every GEMM launch, 2 = weight-gradient launches only."""
-    _check(lib().unimm_prof_enable(C.c_int32(int(on))), "unimm_prof_enable")
+    _call("unimm_prof_enable", int(on))
 
 
 def prof_collect():
     """-> {variant name: (total_ms, total_flops, launches)} for the launches since prof_enable(True)."""
     n = PROF_VARIANTS
     ms, fl, cnt = (C.c_double * n)(), (C.c_double * n)(), (C.c_int32 * n)()
-    _check(lib().unimm_prof_collect(ms, fl, cnt, C.c_int32(n)), "unimm_prof_collect")
+    _call("unimm_prof_collect", ms, fl, cnt, n)
     return {gemm_variant_name(i): (ms[i], fl[i], cnt[i]) for i in range(n) if cnt[i] > 0}
 
 
 def prof_tag(tag):
     """Tag (0 .. 7) of the GEMM launches that follow (see include/unimm_hip.h: unimm_prof_tag)."""
-    lib().unimm_prof_tag(C.c_int32(int(tag)))
+    lib().unimm_prof_tag(int(tag))
 
 
 def prof_tagged(ntags=8):
     """-> {tag: (total_ms, total_flops, launches, union_ms)} of the NT launches the last prof_collect() consumed; union_ms = the
     wall time during which at least one launch of the tag was executing (launches of two streams side by side count once)."""
     ms, fl, cnt, un = (C.c_double * ntags)(), (C.c_double * ntags)(), (C.c_int32 * ntags)(), (C.c_double * ntags)()
-    _check(lib().unimm_prof_tagged(ms, fl, cnt, un, C.c_int32(ntags)), "unimm_prof_tagged")
+    _call("unimm_prof_tagged", ms, fl, cnt, un, ntags)
     return {t: (ms[t], fl[t], cnt[t], un[t]) for t in range(ntags)}
 
 
@@ -1046,7 +1043,7 @@ def x3_split(a, out3=None, out32=None, op=X3_COPY, b=None, rows=None, cols=None,
         s = X3SplitArgs()
         st = _tls.x3s = (s, C.addressof(s), lib().unimm_x3_split)
     s, addr, fn = st
-    s.a, s.b, s.out32, s.out3 = a.data_ptr(), _P(b), _P(out32), _P(out3)
+    s.a, s.b, s.out32, s.out3 = a.data_ptr(), _ptr(b), _ptr(out32), _ptr(out3)
     s.rows = a.shape[0] if rows is None else rows
     s.cols = a.shape[1] if cols is None else cols
     s.cp = (out3.shape[1] // 3) if cp is None else cp
@@ -1060,8 +1057,7 @@ def x3_split(a, out3=None, out32=None, op=X3_COPY, b=None, rows=None, cols=None,
 def x3_split_wt(src, dst, R, C_, Rp):
     """transposed w-type split: src fp32 [R, C] -> dst bf16 [C, 3 Rp] (zero-filled by the caller once)."""
     _dev(src, dst)
-    _check(lib().unimm_x3_split_wt(_ptr(src), _ptr(dst), C.c_int32(R), C.c_int32(C_), C.c_int32(src.stride(0)), C.c_int32(Rp),
-                                   _stream()), "unimm_x3_split_wt")
+    _call("unimm_x3_split_wt", _ptr(src), _ptr(dst), R, C_, src.stride(0), Rp)
 
 
 def x3_layernorm_bwd_partials(dy, x, mean, rstd, gamma, dx32, dxd3, partials, M, H, drop=None, out_drop=None, m_dev=None):
@@ -1069,11 +1065,8 @@ def x3_layernorm_bwd_partials(dy, x, mean, rstd, gamma, dx32, dxd3, partials, M,
     out_drop = out_drop or NO_DROP
     _dev(dy, x, mean, rstd, gamma, dx32, dxd3, partials)
     blocks = C.c_int32(0)
-    _check(lib().unimm_x3_layernorm_bwd_partials(
-        _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx32), _ptr(dxd3), _ptr(partials), C.c_int32(M), C.c_int32(H),
-        C.c_uint32(drop[0]), C.c_uint32(drop[1]), C.c_float(drop[2]), C.c_uint32(out_drop[0]), C.c_uint32(out_drop[1]),
-        C.c_float(out_drop[2]), C.byref(blocks), _ptr(m_dev), C.c_void_p(_salt(drop, out_drop)), _stream()),
-        "unimm_x3_layernorm_bwd_partials")
+    _call("unimm_x3_layernorm_bwd_partials", _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx32), _ptr(dxd3),
+          _ptr(partials), M, H, *drop[:3], *out_drop[:3], C.byref(blocks), _ptr(m_dev), _salt(drop, out_drop))
     return blocks.value
 
 
@@ -1081,28 +1074,25 @@ def embed_bwd_f32(ids, pos, typ, word, post, type_, ext, gamma, beta, dy, dword,
                   partials, M, H, type_vocab=2, eps=1e-12, drop=NO_DROP, m_dev=None, rows=None):
     a = _embed_args(ids, pos, typ, word, post, type_, ext, gamma, beta, M, H, type_vocab, eps, drop, m_dev, rows)
     _dev(dy, dword, dpos, dtype, dext, dgamma, dbeta, partials)
-    _check(lib().unimm_embed_bwd_f32(C.byref(a), _ptr(dy), _ptr(dword), _ptr(dpos), _ptr(dtype), _ptr(dext), _ptr(dgamma),
-                                     _ptr(dbeta), _ptr(partials), _stream()), "unimm_embed_bwd_f32")
+    _call("unimm_embed_bwd_f32", C.byref(a), _ptr(dy), _ptr(dword), _ptr(dpos), _ptr(dtype), _ptr(dext), _ptr(dgamma), _ptr(dbeta),
+          _ptr(partials))
 
 
 def x3_lm_loss_bwd(logits, labels, weights, lse, g, inv_denom, out3, n, V, n_dev=None, inv_dev=None):
     _dev(logits, labels, weights, lse, g, out3)
-    _check(lib().unimm_x3_lm_loss_bwd(_ptr(logits), _ptr(labels), _ptr(weights), _ptr(lse), _ptr(g), C.c_float(inv_denom),
-                                      _ptr(out3), C.c_int32(n), C.c_int32(V), C.c_int32(logits.stride(0)),
-                                      C.c_int32(out3.shape[1] // 3), _ptr(n_dev), _ptr(inv_dev), _stream()), "unimm_x3_lm_loss_bwd")
+    _call("unimm_x3_lm_loss_bwd", _ptr(logits), _ptr(labels), _ptr(weights), _ptr(lse), _ptr(g), inv_denom, _ptr(out3), n, V,
+          logits.stride(0), out3.shape[1] // 3, _ptr(n_dev), _ptr(inv_dev))
 
 
 def x3_kl_loss_bwd(pred, target, label, lse, g, inv_denom, out3, rows, Cn, inv_dev=None):
     _dev(pred, target, label, lse, g, out3)
-    _check(lib().unimm_x3_kl_loss_bwd(_ptr(pred), _ptr(target), _ptr(label), _ptr(lse), _ptr(g), C.c_float(inv_denom),
-                                      _ptr(out3), C.c_int32(rows), C.c_int32(Cn), C.c_int32(pred.stride(0)),
-                                      C.c_int32(out3.shape[1] // 3), _ptr(inv_dev), _stream()), "unimm_x3_kl_loss_bwd")
+    _call("unimm_x3_kl_loss_bwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(lse), _ptr(g), inv_denom, _ptr(out3), rows, Cn,
+          pred.stride(0), out3.shape[1] // 3, _ptr(inv_dev))
 
 
 def x3_rows_add(dst, idx, src, n, H):
     _dev(dst, idx, src)
-    _check(lib().unimm_x3_rows_add(_ptr(dst), _ptr(idx), _ptr(src), C.c_int32(n), C.c_int32(H), C.c_int32(dst.stride(0)),
-                                   _stream()), "unimm_x3_rows_add")
+    _call("unimm_x3_rows_add", _ptr(dst), _ptr(idx), _ptr(src), n, H, dst.stride(0))
 
 
 class X3AttnPlanes(C.Structure):
@@ -1121,10 +1111,10 @@ def x3_attn_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, 
         pl.out3, pl.ld3, pl.cp3 = out3.data_ptr(), out3.stride(0), out3.shape[1] // 3
     a = AttnArgs()
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
-    a.out, a.lse, a.ldo = out.data_ptr(), _P(lse), out.stride(0)
+    a.out, a.lse, a.ldo = out.data_ptr(), _ptr(lse), out.stride(0)
     if kshared is not None:
-        a.ks_off, a.ks_len, a.ks_ins = _P(kshared[0]), _P(kshared[1]), int(kshared[2])
-    _check(lib().unimm_x3_attn_fwd(C.byref(a), C.byref(pl) if pl is not None else None, _stream()), "unimm_x3_attn_fwd")
+        a.ks_off, a.ks_len, a.ks_ins = _ptr(kshared[0]), _ptr(kshared[1]), int(kshared[2])
+    _call("unimm_x3_attn_fwd", C.byref(a), C.byref(pl) if pl is not None else None)
 
 
 def x3_attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride,
@@ -1143,16 +1133,26 @@ def x3_attn_bwd(q, k, v, out, dout, lse, delta, dq, dk, dv, mask, B, H, Tq, Tk, 
     if pl is None:
         a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
         a.lddq, a.lddk, a.lddv = dq.stride(0), dk.stride(0), dv.stride(0)
-    _check(lib().unimm_x3_attn_bwd(C.byref(a), C.byref(pl) if pl is not None else None, _stream()), "unimm_x3_attn_bwd")
+    _call("unimm_x3_attn_bwd", C.byref(a), C.byref(pl) if pl is not None else None)
 
 
 def x3_attn_set_impl(impl):
     """1 = fp32 matrix-instruction attention kernels (default), 0 = the vector-ALU kernels (A/B runs)."""
-    _check(lib().unimm_x3_attn_set_impl(int(impl)), "unimm_x3_attn_set_impl")
+    _call("unimm_x3_attn_set_impl", int(impl))
 
 
 def x3_layernorm_fwd(x, gamma, beta, y32, y3, mean, rstd, M, H, eps=1e-12, drop=NO_DROP):
     """LayerNorm forward writing fp32 rows (or None) and the x-type split operand y3 [M, 3 H]."""
     _dev(x, gamma, beta, y32, y3, mean, rstd)
-    _check(lib().unimm_x3_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _P(y32), y3.data_ptr(), _P(mean), _P(rstd),
-                                        M, H, eps, drop[0], drop[1], drop[2], _salt(drop), _stream()), "unimm_x3_layernorm_fwd")
+    _call("unimm_x3_layernorm_fwd", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(y32), y3.data_ptr(), _ptr(mean), _ptr(rstd),
+          M, H, eps, *drop[:3], _salt(drop))
+
+
+# the header's name of every argument struct -> the class above that mirrors it (tests/test_abi.py compares fields and layout)
+STRUCTS = {
+    "unimm_gemm_nt_args": GemmNtArgs, "unimm_gemm_tn_args": GemmTnArgs, "unimm_attn_args": AttnArgs,
+    "unimm_attn_bwd_args": AttnBwdArgs, "unimm_attn_spliced_bwd_args": AttnSplicedBwdArgs, "unimm_finish_desc": FinishDesc,
+    "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
+    "unimm_adamw_args": AdamWArgs, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
+    "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
+}
