@@ -409,7 +409,7 @@ def nsp_loss(nsp_scores, next_sentence_label, nsp_weight=None):
     """Weighted 2-way CE (models/vilbert_dialog.py:1605-1621)."""
     if nsp_weight is None:
         nsp_weight = torch.tensor([1.0, 1.0])
-    w = nsp_weight.squeeze().float()
+    w = nsp_weight.squeeze().to(nsp_scores.dtype)      # (the scores' type: fp32 as in the reference, fp64 when the oracle runs in double)
     w = w / w[0]
     return F.cross_entropy(nsp_scores.view(-1, 2), next_sentence_label.view(-1), weight=w, reduction="mean")
 

@@ -125,9 +125,8 @@ def test_small_config_gradients_match_reference_golden_fp32(golden_dir, small):
 def test_training_mode_dropout_matches_oracle_with_replayed_masks_fp32(golden_dir, small):
     """Train mode: the oracle re-plays the kernels' counter-based dropout masks site by site (same sites and counters as the
     bf16 engine)."""
-    import zlib
     from oracle import vilbert_ref as R
-    from unimm_amd import dropout as DR
+    from tests import grad_ref as GR
     model, ocfg, sd = small
     g = np.load(os.path.join(golden_dir, "small_mixed.npz"))
     args, kw = kwargs_from(g)
@@ -141,20 +140,8 @@ def test_training_mode_dropout_matches_oracle_with_replayed_masks_fp32(golden_di
     assert plan is not None and plan["Mv"] < g["in::input_ids"].size
     rows = plan["rows"].cpu()
 
-    def drop_fn(site, x, p):
-        key = DR.make_key(77, 5, zlib.crc32(site.encode()) & 0xFFFFFFFF)
-        _, thr, scale = DR.drop_arg(p, key)
-        text_rowwise = site == "emb_t" or (site.startswith("bert.encoder.layer.") and site.endswith((".so", ".out"))) \
-            or site.endswith((".bo2", ".tout"))
-        if text_rowwise:
-            n = x.shape[-1]
-            keep_p = torch.from_numpy(DR.keep_mask2d(key, thr, rows.numel(), n))
-            keep = torch.ones((x.shape[0] * x.shape[1], n), dtype=torch.bool)
-            keep[rows] = keep_p
-            keep = keep.view(x.shape)
-        else:
-            keep = torch.from_numpy(DR.keep_mask_nd(key, thr, tuple(x.shape)))
-        return x * keep * scale
+    assert torch.equal(rows.long(), GR.packed_rows(kw["attention_mask"], kw["co_attention_mask"], kw["masked_lm_labels"], kw["lm_weight"]))
+    drop_fn = GR.replay_drop_fn(77, 5, rows)          # device coordinates (packed row, column) for the text row-wise sites
 
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k != R.TIED[0]}
     leaves[R.TIED[0]] = leaves[R.TIED[1]]
