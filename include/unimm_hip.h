@@ -279,6 +279,26 @@ typedef struct {
 } unimm_attn_spliced_bwd_args;
 int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* args, void* stream);
 
+/* The same pair for up to 64 private rows per sequence (added under ABI 24: two new entry points, no signature or struct changed, so
+ * unimm_version() keeps its value): an answer of up to 30 tokens has 1 + 2 (30 + 1) = 63 private rows
+ * (unimm_amd/scoring.py).  The argument structs, the key-position rule (ks_ins included), the group lists, `accumulate` and every
+ * property of the results are those of the pair above; so is what is not read (`delta`, `order`).
+ * Limits of both: D = 64; 1 <= Tq <= 64; Tk <= 256; k_len[b] <= 64 and k_len[b] + ks_len[b] <= 256; q_off .. k_len, ks_off and ks_len
+ * (and g_first, g_seq, G >= 1 for the backward) given; ks_ins >= 0.  Anything else in the HOST arguments: UNIMM_E_ARG (alignment:
+ * UNIMM_E_ALIGN) before any launch, nothing written.  The per-sequence lengths live in device memory and are clamped by the kernels
+ * (q_len to min(Tq, 64), k_len to 64, the segment to 256 rows, group members to [0, B)): a bad length cannot make a launch touch rows
+ * the arguments do not name.
+ * lse is [B, H, Tq] and the dropout counters are those of the padded (B, H, Tq, Tk) box with the Tq PASSED: a launch with Tq = 64 does
+ * not reproduce the dropout pattern of the Tq = 32 launch on the same sequences.
+ * unimm_attn_spliced_wide_fwd: unimm_attn_fwd's launch once more (two query tiles per sequence; without dropout bit-identical to it).
+ * unimm_attn_spliced_wide_bwd: a kernel of its own, one workgroup per (group, head).  Both query tiles of a sequence are staged at
+ * once; a shared key tile's wave adds both into its fp32 dK / dV registers, held over the whole walk and rounded to bf16 once (with
+ * `accumulate`, together with what the rows hold); each of the two private key tiles runs over both query tiles on one wave and is
+ * rounded once per sequence.  No atomics, no workspace, the same bits on every launch.  159 KiB of LDS: one workgroup per CU, as for
+ * the narrow kernel.  Measured once (profiles/README.md, r12a): 2.2x the narrow kernel's time at 20-token answers; not tuned. */
+int unimm_attn_spliced_wide_fwd(const unimm_attn_args* args, void* stream);
+int unimm_attn_spliced_wide_bwd(const unimm_attn_spliced_bwd_args* args, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Row kernels (HBM-bound).
  * ------------------------------------------------------------------------------------------- */

@@ -1,6 +1,6 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
-    python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared]
+    python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared [--max-answer-len 14]]
                                  [--baseline mean|greedy] [--rollout separate|fused ...]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
@@ -26,7 +26,9 @@ over the pairs, the ratios, and whether fused is faster than separate by more th
 `forward_backward` on G x N full sequences (replicated) and `forward_backward(shared_context=<dialog of each sequence>)`, which
 computes each dialog's context and image once -- as alternating pairs in one process after a warm-up: wall time per step between
 device synchronisations (medians, every pair's ratio, the replicated step's run-to-run spread), the device kernels each form
-launches per step with the mean duration of its text self-attention backward kernel (torch.profiler), and the packed row counts."""
+launches per step with the mean duration of its text self-attention backward kernel (torch.profiler), and the packed row counts.
+--max-answer-len (default 14, the figures of earlier rounds): the longest sampled answer; above 14 the shared step is given
+`SharedContext(.., 64)` and runs the two-tile launches when a sampled answer has more than 14 tokens."""
 from __future__ import annotations
 
 import argparse
@@ -177,7 +179,7 @@ def step(G, N, baseline="mean", rollouts=("separate",), pairs=7):
     return dict(summary=res, rows=rows)
 
 
-def shared(G, N, pairs):
+def shared(G, N, pairs, max_answer_len=14):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from bench_generate import dialogs
     from oracle import vilbert_ref as RF
@@ -189,10 +191,12 @@ def shared(G, N, pairs):
     d, c = dialogs(G, seed=3)
     T, R, C = d["input_ids"].shape[1], d["image_feat"].shape[1], eng.cfg.v_target_size
     enc.eval()
-    # (answers of at most 14 tokens: 1 + 2 (14 + 1) = 31 private rows, the shared step's one query tile)
+    # (the default, answers of at most 14 tokens: 1 + 2 (14 + 1) = 31 private rows, the shared step's one query tile and the
+    # figures of earlier rounds; up to 30: two tiles, through SharedContext(.., 64))
+    from unimm_amd import SharedContext
     ans = enc.generate_answers(d["input_ids"], d["image_feat"], d["image_loc"], c, token_type_ids=d["token_type_ids"],
                                position_ids=d["position_ids"], image_attention_mask=d["image_attention_mask"],
-                               samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1, max_answer_len=14)
+                               samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1, max_answer_len=max_answer_len)
     sb = policy.sampled_training_batch(d["input_ids"], d["token_type_ids"], d["position_ids"], c, ans, T)
     K = sb.input_ids.shape[0]
     adv = policy.self_critical_advantage(-ans.lengths.cpu().float(), "mean" if N > 1 else None)
@@ -204,11 +208,12 @@ def shared(G, N, pairs):
               image_label=label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
               lm_advantage=policy.spread(adv, sb), lm_objective=policy.PolicyObjective(entropy_coef=0.01))
     enc.train()
+    ctx_arg = sb.image_index if max_answer_len <= 14 else SharedContext(sb.image_index, 64)
 
     def one(share):
         eng.arena.zero_grads()
         return enc.forward_backward(sb.input_ids, d["image_feat"], d["image_loc"], (1.0, 0.0, 0.0),
-                                    **kw, **(dict(shared_context=sb.image_index) if share else {}))[1]
+                                    **kw, **(dict(shared_context=ctx_arg) if share else {}))[1]
 
     def wall_ms(share, n=3):
         torch.cuda.synchronize()
@@ -227,7 +232,7 @@ def shared(G, N, pairs):
             ev = [e for e in prof.events() if str(e.device_type).endswith("CUDA")]
             attn = {}                                          # the text self-attention backward kernels: launches, mean us
             for e in ev:
-                for key in ("attn_spliced_bwd", "attn_bwd_fused"):
+                for key in ("attn_spliced_bwd", "attn_spliced_wide_bwd", "attn_bwd_fused"):
                     if key in e.name:
                         t = getattr(e, "device_time", None)
                         a = attn.setdefault(key, [0, 0.0])
@@ -248,7 +253,7 @@ def shared(G, N, pairs):
     n_ans = sb.attention_mask.answer.astype(np.int64)
     ctx = (sb.attention_mask.length.astype(np.int64) - n_ans)
     first = np.unique(sb.image_index.numpy(), return_index=True)[1]
-    res = dict(G=G, N=N, sequences=K, replicated_ms=round(m_rep, 3), shared_ms=round(m_sh, 3), ratio=round(m_sh / m_rep, 4),
+    res = dict(G=G, N=N, max_answer_len=max_answer_len, longest_answer=int(n_ans.max()) - 1, sequences=K, replicated_ms=round(m_rep, 3), shared_ms=round(m_sh, 3), ratio=round(m_sh / m_rep, 4),
                pair_ratios=[round(a / b, 3) for a, b in zip(t_sh, t_rep)], replicated_spread=round((max(t_rep) - min(t_rep)) / m_rep, 4),
                text_rows_replicated=int((ctx + 2 * n_ans).sum()), text_rows_shared=int((ctx[first] - 1).sum() + (1 + 2 * n_ans).sum()),
                region_rows_replicated=K * R, region_rows_shared=len(first) * R,
@@ -266,6 +271,8 @@ def main():
     ap.add_argument("--G", type=int, default=8)
     ap.add_argument("--N", type=int, default=8)
     ap.add_argument("--shared", action="store_true", help="time the shared-context train step beside the replicated one")
+    ap.add_argument("--max-answer-len", type=int, default=14,
+                    help="--shared: longest sampled answer (above 14 the step takes SharedContext(.., 64) and may run the two-tile launches)")
     ap.add_argument("--baseline", choices=("mean", "greedy"), default="mean", help="the step's baseline (greedy: with the greedy pass)")
     ap.add_argument("--rollout", choices=("separate", "fused"), nargs="+", default=["separate"],
                     help="how the greedy baseline is decoded; both values: alternating pairs in one process")
@@ -274,7 +281,7 @@ def main():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
     torch.set_num_threads(min(16, torch.get_num_threads()))
     if a.shared:
-        print(json.dumps(dict(shared=shared(a.G, a.N, a.pairs))))
+        print(json.dumps(dict(shared=shared(a.G, a.N, a.pairs, a.max_answer_len))))
         return
     result = dict(rows=a.rows, kernels=kernels(a.rows, a.pairs, a.launches))
     if not a.no_step:

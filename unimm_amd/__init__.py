@@ -5,6 +5,7 @@ Drop-in surface (same names / signatures as the reference):
 """
 from .config import BertConfig
 from .modeling import BertForMultiModalPreTraining, VisualDialogEncoder
+from .scoring import SharedContext
 
 __version__ = "0.1.0"
-__all__ = ["BertConfig", "BertForMultiModalPreTraining", "VisualDialogEncoder"]
+__all__ = ["BertConfig", "BertForMultiModalPreTraining", "VisualDialogEncoder", "SharedContext"]

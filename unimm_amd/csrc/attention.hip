@@ -1733,6 +1733,276 @@ __global__ __launch_bounds__(512, 2) void attn_spliced_bwd_kernel(AttnSplBwdPara
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same for up to 64 private rows per sequence (unimm_attn_spliced_wide_bwd): two query tiles and two private key tiles.
+// Same orientation and the same walk, one workgroup per (group, head), 8 shared key tiles on waves 0 .. 7, the private tiles on
+// wave 7 (the second one on wave 6 when that wave has no shared tile).  What changes:
+//   * BOTH query tiles of a sequence are staged at once (64-row Q / dO images, 64 -lse / delta values, mask words of every
+//     (key tile, query)), so a sequence still costs one staging and two barriers.  A shared wave runs its tile against query
+//     tile 0 then 1 and adds both into its accumulators; a private wave takes its key tiles one after the other, each against
+//     both query tiles, and stores the tile's rows before it starts the next: 64 accumulator registers serve both, and a private
+//     row is still rounded once.  (When the segment has an eighth tile the wave's shared accumulators wait in LDS as before.)
+//   * every (key tile, query tile) pair leaves its own dS^T tile; waves 3 .. 6 form dQ^T of (query tile, 32-wide slice of D) over
+//     the shared tiles then the private tiles, in tile order.
+//   * the V rows of a private tile are read by their own wave only, so ONE private V image serves both tiles: the wave loads it
+//     right before the tile's passes (its own LDS accesses execute in order).
+// LDS: Q / dO images 16 KiB + words 3 KiB + dS tiles 40 KiB + K images 48 KiB (8 shared, 2 x 2 private, alternating) + V images
+// 36 KiB + parking 16 KiB = 159 KiB of the CU's 160: one workgroup per CU, as the narrow kernel's 119 KiB already give.
+// ------------------------------------------------------------------------------------------------
+constexpr int SPLW_NT = 10;                                       // key tiles: 8 shared + 2 private
+constexpr size_t SPLW_LDS = 2 * 8192 + 2 * 64 * sizeof(float) + SPLW_NT * 64 * sizeof(uint32_t) + SPLW_NT * 2 * 2048 +
+                            (size_t)(8 + 4) * 4096 + 9 * 4096 + 64 * 64 * sizeof(float);
+
+__global__ __launch_bounds__(512, 1) void attn_spliced_wide_bwd_kernel(AttnSplBwdParams sp) {
+  constexpr int D = 64, NT = SPLW_NT, PT = 8, PW = 7, IMG = 32 * 2 * D;
+  AttnBwdParams& p = sp.b;
+  drop_resolve(p.drop);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* qimg = smem;                                            // [2 query tiles][32][D] bf16
+  char* doimg = smem + 2 * IMG;
+  float* lse_s = reinterpret_cast<float*>(smem + 4 * IMG);      // [64 queries]
+  float* del_s = lse_s + 64;
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + 64);     // [key tile][64 queries] INVERTED mask words of the tile's keys
+  char* scr = reinterpret_cast<char*>(mw_s + NT * 64);          // [key tile][query tile][32 keys][32 queries] bf16 dS^T
+  char* kimg = scr + NT * 2 * 2048;                             // [8 shared tiles + 2 buffers x 2 private tiles][32 keys][D] bf16
+  char* vimg = kimg + (PT + 4) * IMG;                           // [8 shared tiles + the private tile at work][32 keys][D] bf16
+  float* park = reinterpret_cast<float*>(vimg + (PT + 1) * IMG);   // [64 registers][64 lanes]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int g = blockIdx.x / p.H, head = blockIdx.x % p.H;
+  const int r = lane & 31, h = lane >> 5;
+  const int nw = (p.Tk + 31) >> 5;
+
+  int m0 = sp.g_first[g], m1 = sp.g_first[g + 1];
+  m0 = m0 < 0 ? 0 : m0;
+  m1 = m1 > p.B ? p.B : m1;
+  int slen = 0;
+  size_t soff = 0;
+  for (int m = m0; m < m1 && slen == 0; ++m) {
+    const int b = sp.g_seq[m];
+    if (b < 0 || b >= p.B) continue;
+    const int l = sp.ks_len[b];
+    if (l > 0) { slen = l < 256 ? l : 256; soff = (size_t)sp.ks_off[b]; }
+  }
+  const int nst = (slen + 31) >> 5;
+  // Private key tile 0 is wave 7's.  Tile 1 is wave 6's when that wave has no shared tile (a segment of at most 192 rows): the two
+  // tiles then run side by side, and its V image takes the wave's unused shared slot.  Otherwise wave 7 takes both in turn.
+  const bool split = nst <= PW - 1;
+  const bool is_priv = wave == PW || (split && wave == PW - 1);
+  const int pt0 = wave == PW ? 0 : 1, pt1 = (wave == PW && split) ? 1 : 2;   // the wave's private tiles: [pt0, pt1)
+  const bool both = wave == PW && nst > PW;
+  char* vpriv = vimg + (wave == PW ? PT : PW - 1) * IMG;
+
+  // rows first .. first + n - 1 of a matrix as one 32-row LDS image (rows past n zero)
+  auto load_rows = [&](const bf16_t* mat, int ld, size_t first, int n, char* img) {
+    const bool ok = r < n;
+    const bf16_t* src = mat + (first + (ok ? r : n - 1)) * ld + head * D;
+#pragma unroll
+    for (int ks = 0; ks < D / 16; ++ks) {
+      u32x4 x = *reinterpret_cast<const u32x4*>(src + 16 * ks + 8 * h);
+      if (!ok) x = u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(img + r * (2 * D) + (((2 * ks + h) ^ swz<D>(r)) << 4)) = x;
+    }
+  };
+  const bool shared_on = wave < nst;
+  const int sn = slen - 32 * wave < 32 ? slen - 32 * wave : 32;
+  if (shared_on) {
+    load_rows(p.k, p.ldk, soff + 32 * wave, sn, kimg + wave * IMG);
+    load_rows(p.v, p.ldv, soff + 32 * wave, sn, vimg + wave * IMG);
+  }
+
+  f32x16 dk[D / 32], dv[D / 32];
+#pragma unroll
+  for (int dt = 0; dt < D / 32; ++dt) { dk[dt] = f32x16{}; dv[dt] = f32x16{}; }
+  const uint32_t halfw = ((uint32_t)p.Tk + 1u) >> 1, halfm = halfw * DROP_M1;
+  const float c1 = p.scale * LOG2E;
+  const bool dropping = p.drop.thr != 0u;
+  const uint32_t thr16 = dropping ? (p.drop.thr >> 16) : 0u;
+  const float dsc = dropping ? p.drop.scale : 1.0f;
+  int pbuf = 0;
+
+#pragma unroll 1
+  for (int m = m0; m < m1; ++m) {
+    const int b = sp.g_seq[m];
+    if (b < 0 || b >= p.B) continue;
+    int ql = p.q_len[b], kl = p.k_len[b];
+    ql = ql < 64 ? ql : 64; ql = ql < p.Tq ? ql : p.Tq;
+    kl = kl < 0 ? 0 : (kl < 64 ? kl : 64);
+    const bool has_s = sp.ks_len[b] > 0 && slen > 0;
+    const int Ts = has_s ? slen : 0;
+    if (ql <= 0 || kl + Ts <= 0) continue;                       // (workgroup-uniform)
+    const int ins = sp.ks_ins < kl ? sp.ks_ins : kl;
+    const size_t qbase = (size_t)p.q_off[b], kbase = (size_t)p.k_off[b];
+    const int nsh = has_s ? nst : 0;
+    const int nqt = (ql + 31) >> 5, npt = (kl + 31) >> 5;        // query tiles, private key tiles
+    const bool s_on = wave < nsh, p_on = is_priv && kl > 0;
+    pbuf ^= 1;
+    char* kpriv = kimg + (PT + 2 * pbuf) * IMG;                  // this sequence's private K images
+
+    // ---- stage the sequence's query tiles
+    stage_head<D>(p.q + qbase * p.ldq + head * D, p.ldq, ql, 64, qimg, tid, blockDim.x);
+    stage_head<D>(p.dout + qbase * p.lddo + head * D, p.lddo, ql, 64, doimg, tid, blockDim.x);
+    {                                                            // delta = rowsum(dO o O): 8 lanes share a row
+      const int row = tid >> 3, c = tid & 7;
+      float part = 0.f;
+      if (row < ql) {
+        const u32x4 a = *reinterpret_cast<const u32x4*>(p.dout + (qbase + row) * p.lddo + head * D + 8 * c);
+        const u32x4 o = *reinterpret_cast<const u32x4*>(p.o + (qbase + row) * p.ldo + head * D + 8 * c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          part = fmaf(__uint_as_float(a[e] << 16), __uint_as_float(o[e] << 16), part);
+          part = fmaf(__uint_as_float(a[e] & 0xffff0000u), __uint_as_float(o[e] & 0xffff0000u), part);
+        }
+      }
+#pragma unroll
+      for (int o = 1; o < 8; o <<= 1) part += __shfl_xor(part, o, 64);
+      if (c == 0) del_s[row] = part;
+      if (tid < 64) lse_s[tid] = tid < ql ? -p.lse[((size_t)b * p.H + head) * p.Tq + tid] * LOG2E : -INFINITY;
+    }
+    for (int i = tid; i < NT * 64; i += 512) {                   // mask words of (tile, query), in the tile's key order
+      const int t = i >> 6, qi = i & 63;
+      const int qc = qi < ql ? qi : ql - 1;
+      const uint32_t* mr = p.mask + (size_t)b * p.mask_b_stride + (size_t)qc * p.mask_q_stride;
+      uint32_t bits, pad;
+      int n;
+      if (t < PT) {                                              // shared keys 32 t ..: positions ins + 32 t ..
+        bits = mask_bits_at(mr, nw, ins + 32 * t);
+        n = Ts - 32 * t;
+      } else {                                                   // private key i: position i below ins, else i + Ts
+        const int k0 = 32 * (t - PT), c = ins - k0;              // c: keys of this tile ahead of the segment
+        const uint32_t lo = mask_bits_at(mr, nw, k0), hi = mask_bits_at(mr, nw, k0 + Ts);
+        bits = c >= 32 ? lo : (c <= 0 ? hi : ((lo & ((1u << c) - 1u)) | (hi & ~((1u << c) - 1u))));
+        n = kl - k0;
+      }
+      pad = n >= 32 ? 0u : (n <= 0 ? ~0u : ~0u << n);
+      mw_s[i] = ~bits | pad;
+    }
+    if (p_on)
+      for (int pt = pt0; pt < pt1 && pt < npt; ++pt)
+        load_rows(p.k, p.ldk, kbase + 32 * pt, kl - 32 * pt < 32 ? kl - 32 * pt : 32, kpriv + pt * IMG);
+    stage_wait();
+    __syncthreads();
+
+    // S, dP, P, dS of key tile t (its key on the lane, at position kpos; K / V images kt / vt) against query tile qt
+    auto tile_pass = [&](int t, int qt, const char* kt, const char* vt, int kpos) {
+      const char* qi = qimg + qt * IMG;
+      const char* di = doimg + qt * IMG;
+      char* ws = scr + (t * 2 + qt) * 2048;
+      const uint32_t lin0 = drop_lin(p.drop, (((uint32_t)b * p.H + head) * (uint32_t)p.Tq + 32u * (uint32_t)qt) * halfw + ((uint32_t)kpos >> 1));
+      f32x16 sacc = {}, dpacc = {};
+#pragma unroll
+      for (int ks = 0; ks < D / 16; ++ks) {
+        const bf16x8 qf = read_row_frag<D>(qi, r, 2 * ks + h);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, read_row_frag<D>(kt, r, 2 * ks + h), sacc, 0, 0, 0);
+        const bf16x8 df = read_row_frag<D>(di, r, 2 * ks + h);
+        dpacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(df, read_row_frag<D>(vt, r, 2 * ks + h), dpacc, 0, 0, 0);
+      }
+      float pd[16], ds[16];
+      spl_score_tile(p.drop, lin0, halfm, ((uint32_t)kpos & 1u) << 4, thr16, dsc, c1, dropping, sacc, dpacc, lse_s + 32 * qt, del_s + 32 * qt,
+                     mw_s + t * 64 + 32 * qt, r, h, pd, ds);
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+        *reinterpret_cast<u32x2*>(ws + r * 64 + (((2 * g4 + h) ^ tile64_swz(r)) << 3)) =
+            u32x2{pack2bf(ds[4 * g4], ds[4 * g4 + 1]), pack2bf(ds[4 * g4 + 2], ds[4 * g4 + 3])};
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+        const bf16x8 pf = pack8(pd + 8 * ss);
+        const bf16x8 dsf = pack8(ds + 8 * ss);
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt) {
+          const bf16x8 dotf = read_tr_frag<D>(di, 16 * ss, 32 * dt, lane);
+          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf, pf, dv[dt], 0, 0, 0);
+          const bf16x8 qtf = read_tr_frag<D>(qi, 16 * ss, 32 * dt, lane);
+          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf, dsf, dk[dt], 0, 0, 0);
+        }
+      }
+    };
+#pragma unroll 1
+    for (int job = 0; job < 3; ++job) {                          // the wave's shared tile, private tile 0, private tile 1: one copy of the code
+      const bool priv = job > 0;
+      const int pt = job - 1;
+      if (priv ? !(p_on && pt >= pt0 && pt < pt1 && pt < npt) : !s_on) continue;          // (wave-uniform: the lane swap of the stores needs every lane)
+      const int pn = kl - 32 * pt < 32 ? kl - 32 * pt : 32;      // (private) keys of the tile
+      if (priv) {
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            if (both && pt == pt0) { park[(32 * dt + e) * 64 + lane] = dk[dt][e]; park[(32 * dt + 16 + e) * 64 + lane] = dv[dt][e]; }
+            dk[dt][e] = 0.f; dv[dt][e] = 0.f;
+          }
+      }
+      if (priv) load_rows(p.v, p.ldv, kbase + 32 * pt, pn, vpriv);
+      const int ki = 32 * pt + r;                                // (private) the lane's key
+      const int t = priv ? PT + pt : wave;
+      const char* kt = priv ? kpriv + pt * IMG : kimg + wave * IMG;
+      const int kpos = priv ? (ki < ins ? ki : ki + Ts) : ins + 32 * wave + r;
+#pragma unroll 1
+      for (int qt = 0; qt < nqt; ++qt) tile_pass(t, qt, kt, priv ? vpriv : vimg + wave * IMG, kpos);
+      if (priv) {
+        const bool ok = r < pn;
+        store_acc_row<D>(p.dk + (kbase + (ok ? ki : 0)) * p.lddk + head * D, dk, p.scale, h, ok);
+        store_acc_row<D>(p.dv + (kbase + (ok ? ki : 0)) * p.lddv + head * D, dv, 1.0f, h, ok);
+        if (both && (pt == npt - 1 || pt == pt1 - 1)) {
+#pragma unroll
+          for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { dk[dt][e] = park[(32 * dt + e) * 64 + lane]; dv[dt][e] = park[(32 * dt + 16 + e) * 64 + lane]; }
+        }
+      }
+    }
+    __syncthreads();                                             // every tile's dS^T is in LDS
+    // ---- dQ^T, output-stationary: wave 3 + 2 qt + dt owns the 32-wide slice dt of D of query tile qt over every key tile, in
+    // tile order.  The other waves go on to stage the next sequence: nothing read here is rewritten before the next staging
+    // barrier, the private K images alternate.
+    if (wave >= 3 && wave <= 6) {
+      const int qt = (wave - 3) >> 1, dt = (wave - 3) & 1;
+      if (qt < nqt) {
+        f32x16 dq1[1] = {f32x16{}};
+        const int ntile = nsh + npt;
+        for (int i = 0; i < ntile; ++i) {
+          const int t = i < nsh ? i : PT + (i - nsh);
+          const char* ki = t < PT ? kimg + t * IMG : kpriv + (t - PT) * IMG;
+#pragma unroll
+          for (int ss = 0; ss < 2; ++ss) {
+            const bf16x8 ktf = read_tr_frag<D>(ki, 16 * ss, 32 * dt, lane);
+            const bf16x8 dstf = read_tr_tile64s(scr + (t * 2 + qt) * 2048, 16 * ss, lane);
+            dq1[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf, dstf, dq1[0], 0, 0, 0);
+          }
+        }
+        const int qr = 32 * qt + r;
+        const bool ok = qr < ql;
+        store_acc_row<32>(p.dq + (qbase + (ok ? qr : 0)) * p.lddq + head * D + 32 * dt, dq1, p.scale, h, ok);
+      }
+    }
+  }
+
+  if (shared_on) {                                               // the segment's rows: one rounding of the fp32 sums
+    const bool ok = r < sn;
+    bf16_t* dkg = p.dk + (soff + 32 * wave + (ok ? r : 0)) * p.lddk + head * D;
+    bf16_t* dvg = p.dv + (soff + 32 * wave + (ok ? r : 0)) * p.lddv + head * D;
+    if (!sp.accumulate) {
+      store_acc_row<D>(dkg, dk, p.scale, h, ok);
+      store_acc_row<D>(dvg, dv, 1.0f, h, ok);
+    } else if (ok) {                                             // ... together with what the rows hold
+#pragma unroll
+      for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg) {
+          const int d0 = 32 * dt + 8 * gg + 4 * h;               // registers 4 gg .. 4 gg + 3 = columns d0 .. d0 + 3
+          u32x2* pk = reinterpret_cast<u32x2*>(dkg + d0);
+          u32x2* pv = reinterpret_cast<u32x2*>(dvg + d0);
+          const u32x2 hk = *pk, hv = *pv;
+          *pk = u32x2{pack2bf(fmaf(dk[dt][4 * gg], p.scale, __uint_as_float(hk[0] << 16)),
+                              fmaf(dk[dt][4 * gg + 1], p.scale, __uint_as_float(hk[0] & 0xffff0000u))),
+                      pack2bf(fmaf(dk[dt][4 * gg + 2], p.scale, __uint_as_float(hk[1] << 16)),
+                              fmaf(dk[dt][4 * gg + 3], p.scale, __uint_as_float(hk[1] & 0xffff0000u)))};
+          *pv = u32x2{pack2bf(dv[dt][4 * gg] + __uint_as_float(hv[0] << 16), dv[dt][4 * gg + 1] + __uint_as_float(hv[0] & 0xffff0000u)),
+                      pack2bf(dv[dt][4 * gg + 2] + __uint_as_float(hv[1] << 16), dv[dt][4 * gg + 3] + __uint_as_float(hv[1] & 0xffff0000u))};
+        }
+    }
+  }
+}
+
 // Workgroups per (sequence, head).  Default: one workgroup (up to 8 waves) per item.  Two 4-wave
 // workgroups per item fit two to a CU and overlap each other's staging, but both stage the full K/V
 // (or Q/dO) images: measured 589 vs 545 us for the text fwd+bwd trio, so it stays a tuning knob.
@@ -1962,12 +2232,14 @@ static int attn_fwd_entry(const unimm_attn_args* a, void* stream, bool train_seg
 
 extern "C" int unimm_attn_fwd(const unimm_attn_args* a, void* stream) { return attn_fwd_entry(a, stream, false); }
 
-extern "C" int unimm_attn_spliced_fwd(const unimm_attn_args* a, void* stream) {
+static int attn_spliced_fwd_entry(const unimm_attn_args* a, void* stream, int max_tq) {
   if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->mask || !a->lse) return UNIMM_E_ARG;
   if (!a->q_off || !a->q_len || !a->k_off || !a->k_len || !a->ks_off || !a->ks_len || a->ks_ins < 0) return UNIMM_E_ARG;
-  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > 32 || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > max_tq || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
   return attn_fwd_entry(a, stream, true);
 }
+extern "C" int unimm_attn_spliced_fwd(const unimm_attn_args* a, void* stream) { return attn_spliced_fwd_entry(a, stream, 32); }
+extern "C" int unimm_attn_spliced_wide_fwd(const unimm_attn_args* a, void* stream) { return attn_spliced_fwd_entry(a, stream, 64); }
 
 extern "C" int unimm_attn_probs(const unimm_attn_args* a, float* probs, void* stream) {
   if (a == nullptr || !a->q || !a->k || !a->mask || !probs) return UNIMM_E_ARG;
@@ -2039,12 +2311,13 @@ extern "C" int unimm_attn_bwd(const unimm_attn_bwd_args* a, void* stream) {
   return small_q ? launch_bwd_dkv<128, 2>(p, s) : launch_bwd_dkv<128, 8>(p, s);
 }
 
-extern "C" int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* a, void* stream) {
+// unimm_attn_spliced_bwd (max_tq = 32) and unimm_attn_spliced_wide_bwd (max_tq = 64): the same checks and arguments, their own kernels
+static int attn_spliced_bwd_entry(const unimm_attn_spliced_bwd_args* a, void* stream, int max_tq) {
   if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->dout || !a->lse || !a->dq || !a->dk || !a->dv || !a->mask)
     return UNIMM_E_ARG;
   if (!a->q_off || !a->q_len || !a->k_off || !a->k_len || !a->ks_off || !a->ks_len || a->ks_ins < 0) return UNIMM_E_ARG;
   if (!a->g_first || !a->g_seq || a->G <= 0) return UNIMM_E_ARG;
-  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > 32 || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > max_tq || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
   if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8) || (a->lddo % 8) || (a->lddq % 8) || (a->lddk % 8) ||
       (a->lddv % 8))
     return UNIMM_E_ALIGN;
@@ -2068,9 +2341,18 @@ extern "C" int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* a, void
   sp.ks_off = a->ks_off; sp.ks_len = a->ks_len; sp.ks_ins = a->ks_ins;
   sp.g_first = a->g_first; sp.g_seq = a->g_seq; sp.G = a->G;
   sp.accumulate = a->accumulate;
+  if (max_tq > 32) {
+    if (set_lds(attn_spliced_wide_bwd_kernel, SPLW_LDS) != UNIMM_OK) return UNIMM_E_HIP;
+    hipLaunchKernelGGL(attn_spliced_wide_bwd_kernel, dim3(a->G * a->H), dim3(512), SPLW_LDS, (hipStream_t)stream, sp);
+    UNIMM_CHECK_LAUNCH();
+    return UNIMM_OK;
+  }
   constexpr size_t lds = 2 * 4096 + 2 * 32 * sizeof(float) + 9 * 32 * sizeof(uint32_t) + 9 * 2048 + (size_t)(10 + 9) * 4096 + 64 * 64 * sizeof(float);
   if (set_lds(attn_spliced_bwd_kernel, lds) != UNIMM_OK) return UNIMM_E_HIP;
   hipLaunchKernelGGL(attn_spliced_bwd_kernel, dim3(a->G * a->H), dim3(512), lds, (hipStream_t)stream, sp);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }
+
+extern "C" int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* a, void* stream) { return attn_spliced_bwd_entry(a, stream, 32); }
+extern "C" int unimm_attn_spliced_wide_bwd(const unimm_attn_spliced_bwd_args* a, void* stream) { return attn_spliced_bwd_entry(a, stream, 64); }

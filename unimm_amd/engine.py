@@ -764,7 +764,8 @@ class Engine:
     def _attn_rows(self, q, k, v, ctx, mask, B, H, Tq, Tk, D, qvar=None, kvar=None, kshared=None, drop=L.NO_DROP, lse=None):
         words, mq, mb = mask
         if kshared is not None and lse is not None:          # the spliced launch in its training form
-            L.attn_spliced_fwd(q, k, v, ctx, lse, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar, kvar, kshared)
+            L.attn_spliced_fwd(q, k, v, ctx, lse, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar, kvar, kshared,
+                               wide=Tq > 32)
             return
         L.attn_fwd(q, k, v, ctx, lse, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar=qvar, kvar=kvar,
                    kshared=kshared)
@@ -774,7 +775,7 @@ class Engine:
         gradient and get the groups' sums on top, in one rounding."""
         words, mq, mb = mask
         L.attn_spliced_bwd(q, k, v, ctx, dctx, lse, dq, dk, dv, words, B, H, Tq, Tk, D, 1.0 / math.sqrt(D), mq, mb, drop, qvar, kvar,
-                           kshared, groups, accumulate=True)
+                           kshared, groups, accumulate=True, wide=Tq > 32)
 
     def _ctx_operand(self, ctx):
         return ctx

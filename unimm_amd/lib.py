@@ -43,6 +43,8 @@ SIGNATURES = {
     "unimm_attn_bwd": (_INT, [VP, VP]),
     "unimm_attn_spliced_fwd": (_INT, [VP, VP]),
     "unimm_attn_spliced_bwd": (_INT, [VP, VP]),
+    "unimm_attn_spliced_wide_fwd": (_INT, [VP, VP]),
+    "unimm_attn_spliced_wide_bwd": (_INT, [VP, VP]),
     # row kernels
     "unimm_mask_pack": (_INT, [VP, _INT, VP, I64, I32, VP]),
     "unimm_host_mask_pack": (_INT, [VP, _INT, VP, I64, I32, I32]),
@@ -401,14 +403,15 @@ def group_lists(gid, G=None):
     return g_first, g_seq
 
 
-def attn_spliced_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar, kshared):
-    """attn_fwd with a shared key/value segment in its training form (unimm_attn_spliced_fwd): lse is written, dropout allowed."""
+def attn_spliced_fwd(q, k, v, out, lse, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar, kshared, wide=False):
+    """attn_fwd with a shared key/value segment in its training form (unimm_attn_spliced_fwd): lse is written, dropout allowed.
+    wide: unimm_attn_spliced_wide_fwd, up to 64 private rows per sequence."""
     _dev(q, k, v, out, lse, mask)
     a = AttnArgs()
     _attn_common(a, q, k, v, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar)
     a.out, a.lse, a.ldo = out.data_ptr(), _ptr(lse), out.stride(0)
     a.ks_off, a.ks_len, a.ks_ins = _ptr(kshared[0]), _ptr(kshared[1]), int(kshared[2])
-    _call("unimm_attn_spliced_fwd", C.byref(a))
+    _call("unimm_attn_spliced_wide_fwd" if wide else "unimm_attn_spliced_fwd", C.byref(a))
 
 
 def spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar,
@@ -429,13 +432,14 @@ def spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D,
 
 
 def attn_spliced_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar, kvar,
-                     kshared, groups, accumulate=False):
+                     kshared, groups, accumulate=False, wide=False):
     """Backward of `attn_spliced_fwd` (unimm_attn_spliced_bwd): dq of the private queries, dk / dv of the private keys and -- summed
-    over each group's sequences in fp32, rounded once; accumulate: on top of what the rows hold -- of the groups' shared rows."""
+    over each group's sequences in fp32, rounded once; accumulate: on top of what the rows hold -- of the groups' shared rows.
+    wide: unimm_attn_spliced_wide_bwd, up to 64 private rows per sequence."""
     _dev(q, k, v, out, dout, lse, dq, dk, dv, mask, *groups)
     a = spliced_bwd_args(q, k, v, out, dout, lse, dq, dk, dv, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop, qvar,
                          kvar, kshared, groups, accumulate)
-    _call("unimm_attn_spliced_bwd", C.byref(a))
+    _call("unimm_attn_spliced_wide_bwd" if wide else "unimm_attn_spliced_bwd", C.byref(a))
 
 
 class AttnDecodeArgs(C.Structure):

@@ -259,6 +259,7 @@ class BertForMultiModalPreTraining(nn.Module):
         lm_objective: as in `forward` (the policy-gradient step always runs eagerly).
         shared_context (an extension): one group id per sequence, as in `sequence_log_likelihood` -- the sequences of a group
         share image and dialog context and differ only in the answer (the N sampled answers of a dialog, unimm_amd/policy.py).
+        A bare list admits answers of up to 14 tokens (32 private rows); `SharedContext(ids, 64)` admits up to 30 (ValueError beyond).
         The context rows and the image stream then run ONCE per group, forward and backward (unimm_amd/scoring.py); only the LM
         term is trained: loss_weights must be (c, 0, 0), attention_mask a generative-mode DialogMaskSpec, the engine bf16 with
         its connection layers and no frozen layers (ValueError otherwise).  The image and NSP losses come back as zeros and
@@ -341,7 +342,8 @@ class BertForMultiModalPreTraining(nn.Module):
         """-sum_t CE(pred_t, labels, ignore_index=-1) per sequence, computed on the labelled rows only by
         the fused decoder + log-softmax kernels.  Returns (scores[B] fp32, nsp[B,2]).
         shared_context (an extension): one group id per sequence -- sequences of a group share image and dialog context and
-        differ only in the candidate answer, as the 100 options of a round in val_lm.py:52-121 do (pass the round index).  The
+        differ only in the candidate answer, as the 100 options of a round in val_lm.py:52-121 do (pass the round index).  A bare
+        list admits candidates of up to 14 tokens; `SharedContext(ids, 64)` (unimm_amd/scoring.py) up to 30 (ValueError beyond).  The
         context rows and the image stream are then computed once per group (unimm_amd/scoring.py); a sequence whose context does
         not match its group comes back as NaN.  Both engines; on fp32x3 the two schedules differ only by the summation order
         inside the attention kernels (one unit in the last place of the scores in tests/test_gpu_x3_scoring.py)."""

@@ -32,6 +32,8 @@ blocks below take `st` (train / tape) as `Engine._self_block` / `_conn_block` do
   text self-attention     the S x S launch's backward (unimm_attn_bwd) writes dQ / dK / dV of the S rows; the spliced launch's
                           backward (unimm_attn_spliced_bwd) then writes the P rows and adds each group's fp32 sums onto the S
                           rows' dK / dV, rounding once
+                          (a batch with a sequence of more than 32 private rows, admitted by `SharedContext(ids, 64)`: the
+                          same two launches at a width of 64 private rows, unimm_attn_spliced_wide_fwd / _bwd)
   text attends regions    every text block gets its own copy of its group's region K / V rows, unimm_attn_bwd writes one dK / dV
                           copy per block, unimm_segment_rows_sum_bf16 adds a group's copies in list order
   regions attend text     touches S rows only: today's kernel
@@ -61,11 +63,46 @@ def _rup(x, m):
     return (x + m - 1) // m * m
 
 
-class SharedContextPlan:
-    """Host-side row bookkeeping of one call: which padded rows form the shared (S) and private (P) blocks."""
+class SharedContext:
+    """What `shared_context=` takes besides a bare list of group ids: the ids and a PERMISSION -- how many private rows (row 0,
+    the answer rows and the copy rows: 1 + 2 (tokens + 1)) a sequence may have.  32 is what a bare list means: answers of up to
+    14 tokens, one query tile.  64 admits answers of up to 30 tokens; a call takes the two-tile launches (unimm_attn_spliced_wide_*
+    when it trains) only when some sequence of ITS batch has more than 32 private rows, so a call whose answers are all short runs
+    the launches of the bare list, bit for bit, dropout included."""
 
-    def __init__(self, groups, c, n, length, T, R):
-        groups = np.asarray(groups, dtype=np.int64).reshape(-1)
+    def __init__(self, groups, private_rows=64):
+        if isinstance(private_rows, bool) or private_rows not in (32, 64):
+            raise ValueError(f"SharedContext: private_rows must be 32 or 64, got {private_rows!r}")
+        if isinstance(groups, SharedContext):
+            groups = groups.groups
+        self.groups, self.private_rows = groups, int(private_rows)
+
+    def __len__(self):
+        return len(self.groups)
+
+
+def _group_ids(shared_context):
+    """-> (group ids int64 [B], bound on the private rows) of a bare id list / tensor or a `SharedContext`"""
+    bound = 32
+    if isinstance(shared_context, SharedContext):
+        shared_context, bound = shared_context.groups, shared_context.private_rows
+    if torch.is_tensor(shared_context):
+        shared_context = shared_context.cpu().numpy()
+    return np.asarray(shared_context, dtype=np.int64).reshape(-1), bound
+
+
+class SharedContextPlan:
+    """Host-side row bookkeeping of one call: which padded rows form the shared (S) and private (P) blocks.
+    groups: group ids, or a `SharedContext` (whose bound then replaces `private_rows`); private_rows: the most private rows a
+    sequence may have, 32 or 64.  `width` is the launch width of THIS batch: 32 when every sequence fits one query tile, else 64."""
+
+    def __init__(self, groups, c, n, length, T, R, private_rows=32):
+        if isinstance(groups, SharedContext):
+            groups, private_rows = _group_ids(groups)
+        else:
+            groups = _group_ids(groups)[0]
+        if private_rows not in (32, 64):
+            raise ValueError(f"shared_context: private_rows must be 32 or 64, got {private_rows!r}")
         c, n, length = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (c, n, length))
         B = groups.shape[0]
         if not (c.shape[0] == n.shape[0] == length.shape[0] == B):
@@ -95,8 +132,13 @@ class SharedContextPlan:
         self.P = int(self.p_len.sum())
         self.M = self.S + self.P
         self.pmax = int(self.p_len.max())
-        if self.pmax > 32:
+        if self.pmax > 32 and private_rows == 32:
             raise ValueError(f"shared_context: a candidate with {self.pmax} private rows (answer of {int(n.max()) - 1} tokens) exceeds one 32-row query tile")
+        if self.pmax > 64:
+            raise ValueError(f"shared_context: a candidate with {self.pmax} private rows (answer of {int(n.max()) - 1} tokens) exceeds the "
+                             "64 rows of two query tiles (answers of at most 30 tokens)")
+        self.private_rows = private_rows
+        self.width = W = 32 if self.pmax <= 32 else 64             # private rows per sequence in the launches: query tiles x 32
         # packed row -> padded row (b * T + t); vectorised (this runs between the header's arrival and the first launch)
         rows = np.empty(self.M, dtype=np.int64)
         sg = np.repeat(np.arange(G), self.s_len)                   # group of every S row
@@ -105,7 +147,7 @@ class SharedContextPlan:
         r = np.arange(self.P) - (self.p_off[pb] - self.S)          # index inside the sequence's private block
         pos = np.where(r == 0, 0, c[pb] + r - 1)                   # row 0, then rows c .. length - 1
         rows[self.S:] = pb * T + pos
-        prow = np.zeros((B, 32), dtype=np.int64)                   # [B, 32] position inside the sequence of private row r (pad: 0)
+        prow = np.zeros((B, W), dtype=np.int64)                    # [B, W] position inside the sequence of private row r (pad: 0)
         prow[pb, r] = pos
         self.rows, self.prow = rows, prow
         # decoded rows: the copy rows = the last n private rows of every sequence, in sequence order
@@ -180,8 +222,8 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
         length_h, n_h = np.asarray(hh[:B]), np.asarray(hh[B:2 * B])
     eng._dev_masks = []
     c_h = np.asarray(length_h) - 2 * np.asarray(n_h)
-    plan = SharedContextPlan(groups.cpu().numpy() if torch.is_tensor(groups) else groups, c_h, n_h, length_h, T, R)
-    G, M, S = plan.G, plan.M, plan.S
+    plan = SharedContextPlan(groups, c_h, n_h, length_h, T, R)
+    G, M, S, W = plan.G, plan.M, plan.S, plan.width
     eng._step_rows = M
     eng.last_plan = None
 
@@ -194,8 +236,8 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
     # item order of the candidates' launches: most keys first (unimm_attn_args.order: the tail of a launch is its shortest items)
     p_ord = _i32(np.argsort(-(plan.s_len[plan.gid] + plan.p_len), kind="stable"), dev)
     # P-row masks: rows {0, c .. length) of each sequence's packed mask, key positions unchanged
-    prow = _i64(plan.prow, dev)                                    # [B, 32]
-    pwords = twords.view(B, T, nw)[torch.arange(B, device=dev)[:, None], prow].contiguous()        # [B, 32, nw]
+    prow = _i64(plan.prow, dev)                                    # [B, W]
+    pwords = twords.view(B, T, nw)[torch.arange(B, device=dev)[:, None], prow].contiguous()        # [B, W, nw]
     ones_t = torch.full((G, nw), -1, dtype=torch.int32, device=dev)                                # all-ones key masks (lengths bound them)
 
     # ---- is the context really shared?  (device-side check, folded into `ok`) -----------------------------------------
@@ -306,10 +348,10 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
         da_s = eng._drop(pn + "attn", cfg.attention_probs_dropout_prob, train)
         da_p = eng._drop(pn + "attn.private", cfg.attention_probs_dropout_prob, train)
         lse_s = torch.empty((G, heads, T), dtype=F32, device=dev) if save else None
-        lse_p = torch.empty((B, heads, 32), dtype=F32, device=dev) if save else None
-        s_var, p_var, p_mask, p_ks = (s_off, s_len), (p_off, p_len), (pwords, nw, 32 * nw), (ks_off, ks_len, 1)
+        lse_p = torch.empty((B, heads, W), dtype=F32, device=dev) if save else None
+        s_var, p_var, p_mask, p_ks = (s_off, s_len), (p_off, p_len), (pwords, nw, W * nw), (ks_off, ks_len, 1)
         eng._attn_rows(q, k, v, ctx, (ones_t, 0, nw), G, heads, T, T, D, qvar=s_var, kvar=s_var, **train_kw(da_s, lse_s))
-        eng._attn_rows(q, k, v, ctx, p_mask, B, heads, 32, T, D, qvar=(p_off, p_len, None, p_ord), kvar=p_var, kshared=p_ks,
+        eng._attn_rows(q, k, v, ctx, p_mask, B, heads, W, T, D, qvar=(p_off, p_len, None, p_ord), kvar=p_var, kshared=p_ks,
                        **train_kw(da_p, lse_p))
         x2_32, x2, post_bwd = eng._post_attn(eng._ctx_operand(ctx), x32, so, ff1, ff2, key + ".ln1", key + ".ln2",
                                              eng._drop(pn + "so", cfg.hidden_dropout_prob, train),
@@ -320,7 +362,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
                 dqkv = eng._qkv_grad(qkv)                          # every row is written: S rows by the first launch, P rows by the second
                 dq, dk, dv = dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:3 * H]
                 eng._attn_bwd(q, k, v, ctx, dctx, lse_s, (ones_t, 0, nw), dq, dk, dv, 3 * H, G, heads, T, T, D, da_s, qvar=s_var, kvar=s_var)
-                eng._attn_spliced_bwd(q, k, v, ctx, dctx, lse_p, p_mask, dq, dk, dv, B, heads, 32, T, D, da_p, p_var, p_var, p_ks, groups_dev)
+                eng._attn_spliced_bwd(q, k, v, ctx, dctx, lse_p, p_mask, dq, dk, dv, B, heads, W, T, D, da_p, p_var, p_var, p_ks, groups_dev)
                 return eng._proj_bwd(dqkv, x, qkv_l, dpre1)
             tape.append(("t", key, bwd))
         return x2_32, x2
@@ -433,7 +475,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
 def sequence_log_likelihood_shared(model, input_ids, image_feat, image_loc, masked_lm_labels, shared_context, average=False, **kw):
     """Drop-in for BertForMultiModalPreTraining.sequence_log_likelihood when the caller knows which sequences share their
     dialog context and image (`shared_context`: one group id per sequence -- the round index of val_lm.py's
-    [rounds, options] batch).  Returns (scores [B] fp32, nsp [B, 2]); sequences whose context turns out NOT to match their
+    [rounds, options] batch -- or a `SharedContext` of them, which admits candidates of up to 30 tokens).  Returns (scores [B] fp32, nsp [B, 2]); sequences whose context turns out NOT to match their
     group's first member come back as NaN."""
     eng = model._engine
     eng.ensure(model._device())
@@ -468,7 +510,7 @@ def check_shared_training(cfg, compute_dtype, loss_weights, attention_mask, grou
         raise ValueError("shared_context: attention_mask must be a generative-mode DialogMaskSpec (one descriptor per sequence)")
     n = spec.answer.astype(np.int64)
     length = spec.length.astype(np.int64) + n
-    return SharedContextPlan(groups.cpu().numpy() if torch.is_tensor(groups) else groups, length - 2 * n, n, length, T, R)
+    return SharedContextPlan(groups, length - 2 * n, n, length, T, R)
 
 
 def train_shared(eng, inp, groups, g_lm, train):

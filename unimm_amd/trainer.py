@@ -26,6 +26,7 @@ import torch
 
 from . import harness, metrics, ranking
 from .policy import PolicyObjective, sampled_training_batch, self_critical_advantage, spread
+from .scoring import SharedContext
 
 
 def expand_image_fields(batch: dict) -> dict:
@@ -116,8 +117,9 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     tokens' step_logq.  The train-mode step is `forward_backward` on the LM term alone, with the `batch_multiply` /
     `no_sync` / `sync_gradients` cadence of `train_step`.  seed: of the draws (default iter_id).
     shared_context: the train-mode step computes each dialog's context and image once for its N answers, forward and backward
-    (`forward_backward(shared_context=sb.image_index)`): the same gradient up to summation order, less work.  An answer then
-    has at most 14 tokens (max_answer_len <= 14: 1 + 2 (n + 1) private rows fit one 32-row tile; ValueError otherwise).
+    (`forward_backward(shared_context=SharedContext(sb.image_index, 64))`): the same gradient up to summation order, less work.
+    An answer then has at most 30 tokens (max_answer_len <= 30: its 1 + 2 (n + 1) private rows fit two 32-row tiles; ValueError
+    otherwise).  A step whose sampled answers all have at most 14 tokens runs the one-tile launches, bit for bit.
     rollout: "separate" decodes the greedy baseline in a generate_answers call of its own (beams = 1); "fused" (baseline="greedy"
     only, samples <= 15; ValueError otherwise) decodes it as one more slot of the sampling call, `generate_answers(samples=N,
     greedy=True)`: one prefill and one walk over the decode steps for both.  Only the samples are trained on either way.
@@ -130,6 +132,9 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
         raise ValueError(f"self_critical_step: rollout='fused' decodes the greedy baseline with the samples and needs "
                          f"baseline='greedy', got baseline = {baseline!r}")
     fused = rollout == "fused"
+    if shared_context and max_answer_len > 30:
+        raise ValueError(f"self_critical_step: shared_context trains answers of at most 30 tokens (64 private rows), got "
+                         f"max_answer_len = {max_answer_len}")
     bm = int(params.get("batch_multiply", 1))
     boundary = iter_id % bm == 0
     model = _unwrap(dialog_encoder)
@@ -169,7 +174,7 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
             image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
             lm_advantage=spread(advantage, sb), lm_objective=objective,
             lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None,
-            **(dict(shared_context=sb.image_index) if shared_context else {}))
+            **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}))
     entropy = engine.last_lm_entropy
     if boundary:
         if hasattr(dialog_encoder, "sync_gradients"):
@@ -193,9 +198,10 @@ _EVAL_TEXT = (("tokens", 1), ("segments", 1), ("positions", 1), ("weights", 1), 
               ("hist_len", 0), ("txt_attention_mask", 2), ("co_attention_mask", 2))
 
 
-def _evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk, score_chunk, collect_ranks=None):
+def _evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk, score_chunk, collect_ranks=None, with_groups=False):
     """Shared loop of the two validation passes: flatten an image's (round, option) sequences, score them chunk by
-    chunk with `score_chunk(item) -> [chunk] scores (higher = better answer)`, accumulate the retrieval metrics."""
+    chunk with `score_chunk(item) -> [chunk] scores (higher = better answer)`, accumulate the retrieval metrics.
+    with_groups: an item also carries `group`, the (image, round) index of each of its sequences."""
     sparse, ndcg = metrics.SparseGTMetrics(), metrics.NDCG()
     was_training = dialog_encoder.training
     dialog_encoder.eval()
@@ -212,6 +218,8 @@ def _evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk, score_
             for k in ("image_feat", "image_loc"):
                 flat[k] = img[k].reshape((-1,) + tuple(img[k].shape[-2:]))
             flat["image_mask"] = img["image_mask"].reshape(-1, img["image_mask"].shape[-1])
+            if with_groups:
+                flat["group"] = torch.arange(total) // options
             scores = [score_chunk({k: v[lo:lo + chunk] for k, v in flat.items()}) for lo in range(0, total, chunk)]
             output = torch.cat(scores).view(eval_batch_size, rounds, options)
             dev = output.device
@@ -241,13 +249,17 @@ def visdial_evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk_
     return _evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk, score)
 
 
-def generative_evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk_size=None, average=False, ranks_out=None):
+def generative_evaluate(dataloader, params, eval_batch_size, dialog_encoder, chunk_size=None, average=False, ranks_out=None,
+                        shared_context=False):
     """Generative evaluation (val_lm.py:38-150; token-mean variant val_avg_lm.py:135 with average=True): every
     candidate answer is scored by the sum of its tokens' log-likelihoods under the masked-LM head, the candidates of a
     round are ranked by that score.  The reference decodes all 256 rows of every sequence into [chunk, 256, 30522]
     logits and cross-entropies them; here only the labelled rows are decoded (`sequence_log_likelihood`).  Chunks of
     `250 * n_gpus / 2` rounded down to the reference's size table (val_lm.py:47-49).  `ranks_out`: optional list that
-    receives the [eval_batch_size, rounds, options] rank tensors (what val_lm.py:139-149 writes to its json)."""
+    receives the [eval_batch_size, rounds, options] rank tensors (what val_lm.py:139-149 writes to its json).
+    shared_context: score a chunk with the context and image of every (image, round) computed once for its candidates
+    (`sequence_log_likelihood(shared_context=SharedContext(group, 64))`): the same scores up to the summation order inside the
+    attention kernels.  A chunk that holds a candidate of more than 30 tokens is scored per candidate, as without the option."""
     if chunk_size is None:
         cap = 250 * (int(params.get("n_gpus", 1)) / 2)
         sizes = [1, 2, 4, 5, 100, 1000, 200, 8, 10, 40, 50, 500, 20, 25, 250, 125]
@@ -255,13 +267,17 @@ def generative_evaluate(dataloader, params, eval_batch_size, dialog_encoder, chu
     model = _unwrap(dialog_encoder).bert_pretrained
 
     def score(item):
+        shared = {}
+        if shared_context and int((item["mask"] != -1).sum(-1).max()) <= 31:       # labelled rows = candidate tokens + [SEP]
+            shared = dict(shared_context=SharedContext(item["group"], 64))
         s, _ = model.sequence_log_likelihood(
             item["tokens"], item["image_feat"], item["image_loc"], item["mask"], average=average,
             token_type_ids=item["segments"], position_ids=item["positions"], attention_mask=item["txt_attention_mask"],
-            image_attention_mask=item["image_mask"], co_attention_mask=item["co_attention_mask"])
+            image_attention_mask=item["image_mask"], co_attention_mask=item["co_attention_mask"], **shared)
         return s
 
-    return _evaluate(dataloader, params, eval_batch_size, dialog_encoder, int(chunk_size), score, collect_ranks=ranks_out)
+    return _evaluate(dataloader, params, eval_batch_size, dialog_encoder, int(chunk_size), score, collect_ranks=ranks_out,
+                     with_groups=bool(shared_context))
 
 
 class _null:
