@@ -550,6 +550,40 @@ int unimm_pg_loss_bwd(const float* logits, const int32_t* labels, const int32_t*
                       int32_t n_adv, int32_t mode, float clip_eps, float beta, const float* lse, const float* ent,
                       const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
                       const int32_t* n_dev, const float* inv_dev, void* stream);
+/* The same objective with a per-row penalty kl_coef KL(p || pr) against a FROZEN reference (two entry points added beside the
+ * pair above, whose signatures and results are unchanged: the ABI number stays).  ref_logits: the reference's fp32 rows for
+ * the same n decoded rows, V valid columns, row stride ld_ref >= V, independent of ld.  With p = softmax(z), pr = softmax(zr):
+ *   KL      = sum_i p_i (log p_i - log pr_i)
+ *   rowloss = (unimm_pg_loss_fwd's) + kl_coef KL
+ *   dlogits[row, i] = g inv ( (unimm_pg_loss_bwd's three terms) + kl_coef p_i (log p_i - log pr_i - KL) );  nothing flows into
+ *   the reference.
+ * kl and ref_lse (the reference row's log-sum-exp) are written by the forward and read by the backward; ref_lse is written for
+ * every row, kl is 0 on an ignored row (label < 0 or a position outside [0, n_adv)), whose rowloss, rownll and gradient row are
+ * exactly zero whatever kl_coef is.  A == 0 switches neither the entropy term nor the KL term off.  n_dev, inv_dev, pos, V <=
+ * 65536 and the zero-filled columns V .. ldd: as above; rows past n_dev[0] are neither read nor written (kl, ref_lse included).
+ * One pass per direction: the forward keeps u = sum_i e^(z_i - m)(z_i - zr_i) and the reference row's own (mr, sr) beside the
+ * policy row's (m, s, t), and KL = u / s - lse + ref_lse; the backward uses log p_i - log pr_i = (z_i - lse) - (zr_i - ref_lse).
+ * Each row is read once per direction.  The backward reads each row with 16-byte loads when that row's own stride is a
+ * multiple of 4 floats; the forward walks both rows in the policy row's column order, so there the reference row's 16-byte
+ * loads also need ld % 4 == 0 (a policy row on the scalar path reads both rows one column at a time).
+ * -inf: a policy logit of -inf has p_i = 0 and contributes exactly 0 to KL and to its gradient element, whatever zr_i holds
+ * (finite or -inf).  zr_i = -inf where z_i is finite is OUTSIDE the contract (the engine's decoder never produces it): that
+ * row's kl, rowloss and gradient are then unspecified (inf / NaN); every other row is unaffected.
+ * Bit-exact: (1) lse, ent and rownll, and with kl_coef = 0 also rowloss and dlogits, equal unimm_pg_loss_fwd / _bwd on the same
+ * arguments bit for bit (one template; the KL term is an addend of its own).  (2) With ref_logits == logits and ld_ref == ld,
+ * KL is exactly +0, ref_lse == lse bitwise (the reference row's log-sum-exp takes the policy row's operation sequence) and
+ * dlogits equals unimm_pg_loss_bwd's bit for bit for any kl_coef (a zero KL term is not added).
+ * UNIMM_E_ARG before any launch: ref_logits, kl or ref_lse NULL, ld_ref < V, kl_coef negative or not finite; the refusals of
+ * the pair above apply as well. */
+int unimm_pg_kl_loss_fwd(const float* logits, const int32_t* labels, const int32_t* pos, const float* adv, const float* blogp,
+                         int32_t n_adv, int32_t mode, float clip_eps, float beta, float* rowloss, float* rownll, float* lse,
+                         float* ent, int32_t n, int32_t V, int32_t ld, const int32_t* n_dev, const float* ref_logits,
+                         int32_t ld_ref, float kl_coef, float* kl, float* ref_lse, void* stream);
+int unimm_pg_kl_loss_bwd(const float* logits, const int32_t* labels, const int32_t* pos, const float* adv, const float* blogp,
+                         int32_t n_adv, int32_t mode, float clip_eps, float beta, const float* lse, const float* ent,
+                         const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
+                         const int32_t* n_dev, const float* inv_dev, const float* ref_logits, int32_t ld_ref, float kl_coef,
+                         const float* kl, const float* ref_lse, void* stream);
 /* Masked-region KL (models/vilbert_dialog.py:1569-1574): rowloss = [label==1] * sum_j t_j (log t_j - logp_j) */
 int unimm_kl_loss_fwd(const float* pred, const float* target, const int32_t* label, float* rowloss, float* lse,
                       int32_t rows, int32_t C, int32_t ld, void* stream);

@@ -1,7 +1,7 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
     python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared [--max-answer-len 14]]
-                                 [--baseline mean|greedy] [--rollout separate|fused ...]
+                                 [--baseline mean|greedy] [--rollout separate|fused ...] [--kl]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
 [rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
@@ -28,7 +28,14 @@ computes each dialog's context and image once -- as alternating pairs in one pro
 device synchronisations (medians, every pair's ratio, the replicated step's run-to-run spread), the device kernels each form
 launches per step with the mean duration of its text self-attention backward kernel (torch.profiler), and the packed row counts.
 --max-answer-len (default 14, the figures of earlier rounds): the longest sampled answer; above 14 the shared step is given
-`SharedContext(.., 64)` and runs the two-tile launches when a sampled answer has more than 14 tokens."""
+`SharedContext(.., 64)` and runs the two-tile launches when a sampled answer has more than 14 tokens.
+
+--kl (instead of the above): the cost of the KL leash (PolicyObjective.kl_coef + lm_reference).  Kernels: unimm_pg_kl_loss_fwd +
+_bwd against unimm_pg_loss_fwd + _bwd on the same logits, the reference row a second buffer of the same size, as alternating
+pairs like the kernels above; the KL pair reads twice the bytes per direction, and both byte counts are printed.  Step: one
+self_critical_step at G x N (baseline "mean") without a reference and with `reference=frozen_reference(model)`, kl_coef = 0.05, as
+alternating pairs with the same seed (--pairs of them after a warm-up of each): medians of the train step and of the whole
+step, every pair's ratio and the plain step's min-to-max spread.  The step with a reference adds one inference forward."""
 from __future__ import annotations
 
 import argparse
@@ -99,6 +106,118 @@ def kernels(rows, pairs, launches):
         out[name] = dict(lm_us=round(m_lm * 1e3, 1), pg_us=round(m_pg * 1e3, 1), ratio=round(m_pg / m_lm, 4),
                          lm_spread=round(spread, 4), lm_TBps=round(nbytes / m_lm / 1e9, 3), pg_TBps=round(nbytes / m_pg / 1e9, 3))
     return out
+
+
+def kl_kernels(rows, pairs, launches):
+    from unimm_amd import lib as L
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn((rows, LD), generator=g) * 3).cuda()
+    ref = (logits + torch.randn((rows, LD), generator=g).cuda() * 0.3).contiguous()
+    labels = torch.randint(0, V, (rows,), generator=g).to(torch.int32).cuda()
+    adv = torch.randn(rows, generator=g).cuda()
+    blogp = (-8.0 + torch.randn(rows, generator=g)).cuda()
+    f = lambda: torch.empty(rows, device="cuda")
+    rowloss, rownll, lse, ent, kl, ref_lse = f(), f(), f(), f(), f(), f()
+    dlog = torch.empty((rows, LD), dtype=torch.bfloat16, device="cuda")
+    gvec = torch.ones(1, device="cuda")
+    inv = 1.0 / rows
+
+    def pg(mode, eps, beta):
+        def run():
+            L.pg_loss_fwd(logits, labels, None, adv, blogp, mode, eps, beta, rowloss, rownll, lse, ent, rows, V)
+            L.pg_loss_bwd(logits, labels, None, adv, blogp, mode, eps, beta, lse, ent, gvec, inv, dlog, rows, V)
+        return run
+
+    def pg_kl(mode, eps, beta, kl_coef):
+        def run():
+            L.pg_kl_loss_fwd(logits, labels, None, adv, blogp, mode, eps, beta, rowloss, rownll, lse, ent, rows, V, ref, kl_coef, kl, ref_lse)
+            L.pg_kl_loss_bwd(logits, labels, None, adv, blogp, mode, eps, beta, lse, ent, gvec, inv, dlog, rows, V, ref, kl_coef, kl,
+                             ref_lse)
+        return run
+
+    b_pg, b_kl = 2 * rows * V * 4 + rows * LD * 2, 4 * rows * V * 4 + rows * LD * 2
+    out = {}
+    for name, mode, eps, beta in (("logp_kl", L.PG_LOGP, float("inf"), 0.0), ("logp_entropy_kl", L.PG_LOGP, float("inf"), 0.01),
+                                  ("ratio_clip_entropy_kl", L.PG_RATIO, 0.2, 0.01)):
+        a, b = pg(mode, eps, beta), pg_kl(mode, eps, beta, 0.05)
+        t_pg, t_kl = [], []
+        for _ in range(pairs):
+            t_pg.append(event_ms(a, launches))
+            t_kl.append(event_ms(b, launches))
+        m_pg, m_kl = statistics.median(t_pg), statistics.median(t_kl)
+        spread = (max(t_pg) - min(t_pg)) / m_pg
+        print(f"{name}: pg fwd+bwd {m_pg * 1e3:.1f} us, pg_kl fwd+bwd {m_kl * 1e3:.1f} us, ratio {m_kl / m_pg:.3f} "
+              f"(pairs {[round(p / q, 3) for p, q in zip(t_kl, t_pg)]}; pg spread {spread:.3f}); "
+              f"{b_pg / m_pg / 1e9:.2f} / {b_kl / m_kl / 1e9:.2f} TB/s")
+        out[name] = dict(pg_us=round(m_pg * 1e3, 1), pg_kl_us=round(m_kl * 1e3, 1), ratio=round(m_kl / m_pg, 4),
+                         pg_spread=round(spread, 4), pg_TBps=round(b_pg / m_pg / 1e9, 3), pg_kl_TBps=round(b_kl / m_kl / 1e9, 3))
+    return out
+
+
+def kl_step(G, N, pairs):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_generate import dialogs
+    from oracle import vilbert_ref as RF
+    from unimm_amd import VisualDialogEncoder, policy, trainer
+    from unimm_amd.optim import FusedAdamW, WarmupLinearScheduleNonZero, default_language_weights, reference_param_groups
+    enc = VisualDialogEncoder(CFG_PATH)
+    enc.bert_pretrained.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    enc = enc.cuda()
+    ref = policy.frozen_reference(enc)
+    groups = reference_param_groups(enc, lr=1e-5, image_lr=1e-5, language_weights=default_language_weights(enc))
+    opt = FusedAdamW(groups, enc.bert_pretrained.engine, lr=1e-5)
+    sch = WarmupLinearScheduleNonZero(opt, warmup_steps=2, t_total=100, min_lr=1e-6)
+    d, c = dialogs(G, seed=3)
+    batch = dict(tokens=d["input_ids"], segments=d["token_type_ids"], positions=d["position_ids"], context_len=c,
+                 image_feat=d["image_feat"], image_loc=d["image_loc"], image_mask=d["image_attention_mask"])
+    marks = {}
+
+    def clocked(fn):
+        def run(*a, **kw):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn(*a, **kw)
+            torch.cuda.synchronize()
+            marks["train"] = marks.get("train", 0.0) + (time.perf_counter() - t0) * 1e3
+            return r
+        return run
+
+    enc.forward_backward, opt.step = clocked(enc.forward_backward), clocked(opt.step)
+    reward = lambda tokens, lengths: -lengths.float()
+    eng = enc.bert_pretrained.engine
+
+    def one(it, with_ref, seed):
+        marks.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = trainer.self_critical_step(enc, opt, sch, batch, dict(batch_multiply=1), it, reward, samples=N, baseline="mean",
+                                         objective=policy.PolicyObjective(entropy_coef=0.01, kl_coef=0.05 if with_ref else 0.0),
+                                         temperature=0.8, top_k=50, top_p=0.9, seed=seed, reference=ref if with_ref else None)
+        torch.cuda.synchronize()
+        row = dict(total_ms=round((time.perf_counter() - t0) * 1e3, 2), train_ms=round(marks["train"], 2), loss=out[0],
+                   kl=float(eng.last_lm_kl) if eng.last_lm_kl is not None else None)
+        print(f"self_critical_step {it} (G = {G}, N = {N}, reference = {with_ref}): {row}")
+        return row
+
+    it = 0
+    for _ in range(2):                                       # warm every shape of both forms up
+        for w in (False, True):
+            it += 1
+            one(it, w, 0)
+    rows = {False: [], True: []}
+    for pair in range(1, pairs + 1):
+        for w in (False, True):
+            it += 1
+            rows[w].append(one(it, w, pair))
+    res = dict(G=G, N=N, pairs=pairs)
+    for key in ("train_ms", "total_ms"):
+        med = {w: statistics.median(x[key] for x in rows[w]) for w in (False, True)}
+        res[key] = dict(plain=med[False], with_reference=med[True], ratio=round(med[True] / med[False], 4),
+                        pair_ratios=[round(y[key] / x[key], 3) for x, y in zip(rows[False], rows[True])],
+                        plain_spread=round(max(x[key] for x in rows[False]) - min(x[key] for x in rows[False]), 2))
+    res["mean_kl"] = [x["kl"] for x in rows[True]]
+    print(f"KL leash, step: {res}")
+    return res
 
 
 def step(G, N, baseline="mean", rollouts=("separate",), pairs=7):
@@ -276,10 +395,17 @@ def main():
     ap.add_argument("--baseline", choices=("mean", "greedy"), default="mean", help="the step's baseline (greedy: with the greedy pass)")
     ap.add_argument("--rollout", choices=("separate", "fused"), nargs="+", default=["separate"],
                     help="how the greedy baseline is decoded; both values: alternating pairs in one process")
+    ap.add_argument("--kl", action="store_true", help="time the KL-regularised row kernels and the step with a frozen reference")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
     torch.set_num_threads(min(16, torch.get_num_threads()))
+    if a.kl:
+        result = dict(rows=a.rows, kl_kernels=kl_kernels(a.rows, a.pairs, a.launches))
+        if not a.no_step:
+            result["kl_step"] = kl_step(a.G, a.N, a.pairs)
+        print(json.dumps(result))
+        return
     if a.shared:
         print(json.dumps(dict(shared=shared(a.G, a.N, a.pairs, a.max_answer_len))))
         return

@@ -14,6 +14,7 @@ softmax, log-sum-exp and all loss arithmetic are fp32.  There is no CPU / eager 
 compute step is a C-ABI call and raises if the library is missing."""
 from __future__ import annotations
 
+import copy
 import math
 import os
 import zlib
@@ -88,6 +89,7 @@ class Engine:
         self._anchor = None
         self.last_seq_t = None
         self.last_lm_entropy = None      # fp32 [1]: mean entropy of the rows the last policy-gradient step trained (`_losses`)
+        self.last_lm_kl = None           # fp32 [1]: mean KL(p || p_ref) of those rows when the step had a reference (kl_coef > 0)
         self.unpad = True                # run the text stream on valid rows only (see the plan step of _forward)
         # Weight gradients wait for a grouped launch, per side (0 = text, 1 = image: inside `_img()`).  The ledger, shared with
         # the exchange planner, decides when a side is launched and which gradient buckets that completes; the operands wait here.
@@ -165,6 +167,16 @@ class Engine:
         # or `prune_last_text = False` runs the layer on all rows.
         self.prune_last_text = os.environ.get("UNIMM_PRUNE_LAST_TEXT", "1") != "0"
         self._seq_wanted = True          # the running forward's caller reads the text stream's sequence output (see forward)
+
+    def __deepcopy__(self, memo):
+        """A copied model (policy.frozen_reference) gets an engine of its own: bound to the copy, with this engine's dropout
+        seed / step, and EMPTY -- arena, weight copies, streams and staging ring are built at its first forward."""
+        model = memo.get(id(self.model))
+        if model is None:
+            raise TypeError("an Engine is copied with its model: copy.deepcopy(model)")
+        new = type(self)(model, copy.deepcopy(self.cfg, memo))
+        new.seed, new.step = self.seed, self.step
+        return new
 
     def schedule_key(self):
         """Every schedule attribute that is frozen into a captured launch sequence (unimm_amd/graphs.py keys its entries on
@@ -1158,6 +1170,7 @@ class Engine:
         """want_seq=False: the caller reads neither out["seq_out_t"] nor out["seq32_t"]; a training step may then run its last
         text layer on the rows the losses read (`_prune_rows`) and return those rows only (out["pruned"])."""
         self._seq_wanted = want_seq
+        self._reference_rows(inp)
         try:
             return self._on_text_stream(self._forward, inp, train, save, lm_rows, want_pred_v)
         finally:
@@ -1193,7 +1206,39 @@ class Engine:
         (unimm_amd/scoring.py, `train_shared`) -> the LM loss, fp32 [1] (NaN, and nothing added to the gradients, when a
         sequence's context does not match its group's)."""
         from .scoring import train_shared
+        self._reference_rows(inp, groups)
         return self._on_text_stream(train_shared, self, inp, groups, g_lm, train)
+
+    _REF_DROPS = ("lm_advantage", "lm_behaviour_logp", "lm_objective", "lm_reference", "lm_weight", "image_target", "image_label",
+                  "next_sentence_label", "nsp_weight", "_plan_header", "_lm_ref_logits")
+
+    def _reference_rows(self, inp, groups=None):
+        """The step's objective has kl_coef > 0 (inp["lm_reference"]: the frozen model, unimm_amd/policy.py): the reference's
+        engine runs an inference forward on the step's own inputs -- eval mode, nothing saved, the labelled rows only, on the
+        schedule of the step (`groups`: the shared-context pass) -- and leaves its fp32 logits rows in inp["_lm_ref_logits"]:
+        the same positions in the same order as the rows this engine is about to decode.  Queued ahead of the policy's forward
+        on the caller's stream.  The reference's parameters, gradients, dropout counters and training flag are not touched."""
+        ref = inp.get("lm_reference")
+        obj = inp.get("lm_objective")
+        if ref is None or obj is None or not obj.kl_coef > 0 or inp.get("lm_advantage") is None:
+            return
+        eng = ref._engine
+        eng.ensure(self.arena.device)
+        rinp = {k: v for k, v in inp.items() if k not in self._REF_DROPS}
+        was = eng.lm_bucket
+        eng.lm_bucket = self.lm_bucket         # the same row capacity as the policy's launch (the counts are the step's own)
+        try:
+            with torch.no_grad():
+                if groups is None:
+                    out = eng.forward(rinp, train=False, save=False, lm_rows="labelled", want_pred_v=False)
+                    lm = out.get("lm")
+                    inp["_lm_ref_logits"] = lm["logits"] if lm is not None else None
+                else:
+                    from .scoring import _forward_shared
+                    out = eng._on_text_stream(_forward_shared, eng, rinp, groups, False, None, None, True)
+                    inp["_lm_ref_logits"] = out["logits"]
+        finally:
+            eng.lm_bucket = was
 
     def losses(self, out, inp):
         return self._on_text_stream(self._losses, out, inp)
@@ -1503,22 +1548,33 @@ class Engine:
         obj = inp["lm_objective"]
         flat = lambda t: t.to(dev, dtype=F32, non_blocking=True).contiguous().reshape(-1)
         blogp = inp.get("lm_behaviour_logp")
-        return dict(pos=pos, adv=flat(adv), blogp=flat(blogp) if obj.mode == "ratio" else None,
-                    mode=L.PG_RATIO if obj.mode == "ratio" else L.PG_LOGP, eps=float(obj.clip_eps), beta=float(obj.entropy_coef))
+        pg = dict(pos=pos, adv=flat(adv), blogp=flat(blogp) if obj.mode == "ratio" else None,
+                  mode=L.PG_RATIO if obj.mode == "ratio" else L.PG_LOGP, eps=float(obj.clip_eps), beta=float(obj.entropy_coef))
+        ref = inp.pop("_lm_ref_logits", None)  # the frozen reference's rows (`_reference_rows`): this step's, handed over once
+        if ref is not None:
+            pg.update(ref=ref, kl_coef=float(obj.kl_coef))
+        return pg
 
     def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None, policy=None):
         V = self.cfg.vocab_size
         t1, u, hn, mean, rstd, logits = self._transform_head(xs, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(V, 64), save)
         rowloss, rownll, lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
-        ent = None
-        if policy is not None:                 # the advantage-weighted objective on sampled answers, entropy kept with lse
+        ent = kl = ref_lse = None
+        if policy is not None and policy.get("ref") is not None:   # ... with the KL penalty against the reference's rows
+            ref = policy["ref"]
+            if ref.shape[0] != n:
+                raise L.UnimmHipError(f"the reference decoded {ref.shape[0]} rows, the policy {n}: not the same step's rows")
+            ent, kl, ref_lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
+            L.pg_kl_loss_fwd(logits, lab_sel, policy["pos"], policy["adv"], policy["blogp"], policy["mode"], policy["eps"],
+                             policy["beta"], rowloss, rownll, lse, ent, n, V, ref, policy["kl_coef"], kl, ref_lse, n_dev=n_dev)
+        elif policy is not None:               # the advantage-weighted objective on sampled answers, entropy kept with lse
             ent = torch.empty(n, dtype=F32, device=xs.device)
             L.pg_loss_fwd(logits, lab_sel, policy["pos"], policy["adv"], policy["blogp"], policy["mode"], policy["eps"],
                           policy["beta"], rowloss, rownll, lse, ent, n, V, n_dev=n_dev)
         else:
             L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
         return dict(xs=xs, t1=t1, u=u, hn=hn, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll,
-                    lse=lse, labels=lab_sel, weights=w_sel, policy=policy, ent=ent)
+                    lse=lse, labels=lab_sel, weights=w_sel, policy=policy, ent=ent, kl=kl, ref_lse=ref_lse)
 
     def decode_rows(self, x, n):
         """MLM transform + decoder for n rows of the GEMM operand x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
@@ -1540,6 +1596,13 @@ class Engine:
         n, V = lm["n"], self.cfg.vocab_size          # n is a capacity: the real count lives on the device (n_dev)
         dlog = torch.empty((n, _rup(V, 64)), dtype=BF16, device=self.arena.device)
         pg = lm.get("policy")
+        if pg is not None and pg.get("ref") is not None:
+            L.pg_kl_loss_bwd(lm["logits"], lm["labels"], pg["pos"], pg["adv"], pg["blogp"], pg["mode"], pg["eps"], pg["beta"],
+                             lm["lse"], lm["ent"], self._gvec(g_lm), 1.0 / n, dlog, n, V, pg["ref"], pg["kl_coef"], lm["kl"],
+                             lm["ref_lse"], n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
+            pg["ref"].record_stream(torch.cuda.current_stream())
+            pg["ref"] = None                   # the reference's logits are released here: the backward was their last reader
+            return dlog
         if pg is not None:
             L.pg_loss_bwd(lm["logits"], lm["labels"], pg["pos"], pg["adv"], pg["blogp"], pg["mode"], pg["eps"], pg["beta"],
                           lm["lse"], lm["ent"], self._gvec(g_lm), 1.0 / n, dlog, n, V, n_dev=lm.get("n_dev"),
@@ -1595,6 +1658,11 @@ class Engine:
                 self.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
                 L.reduce_sum(lm["ent"], lm["n"], self.last_lm_entropy, 1.0 / lm["n"], n_dev=lm.get("n_dev"),
                              scale_dev=lm.get("inv_dev"))
+                self.last_lm_kl = None
+                if lm.get("kl") is not None:   # ... and, with a reference, their mean KL to it
+                    self.last_lm_kl = torch.empty(1, dtype=F32, device=dev)
+                    L.reduce_sum(lm["kl"], lm["n"], self.last_lm_kl, 1.0 / lm["n"], n_dev=lm.get("n_dev"),
+                                 scale_dev=lm.get("inv_dev"))
         res["lm_loss"] = lm_loss
         # image KL
         img = out["img"]

@@ -82,6 +82,9 @@ SIGNATURES = {
     "unimm_lm_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP, VP]),
     "unimm_pg_loss_fwd": (_INT, [VP] * 5 + [I32, I32, F32, F32] + [VP] * 4 + [I32] * 3 + [VP, VP]),
     "unimm_pg_loss_bwd": (_INT, [VP] * 5 + [I32, I32, F32, F32, VP, VP, VP, F32, VP] + [I32] * 4 + [VP, VP, VP]),
+    "unimm_pg_kl_loss_fwd": (_INT, [VP] * 5 + [I32, I32, F32, F32] + [VP] * 4 + [I32] * 3 + [VP, VP, I32, F32, VP, VP, VP]),
+    "unimm_pg_kl_loss_bwd": (_INT, [VP] * 5 + [I32, I32, F32, F32, VP, VP, VP, F32, VP] + [I32] * 4 +
+                             [VP, VP, VP, I32, F32, VP, VP, VP]),
     "unimm_kl_loss_fwd": (_INT, [VP] * 5 + [I32] * 3 + [VP]),
     "unimm_kl_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP]),
     "unimm_mse_loss_fwd": (_INT, [VP] * 4 + [I32] * 3 + [VP]),
@@ -839,6 +842,24 @@ def pg_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, ent,
     _dev(logits, labels, pos, adv, blogp, lse, ent, g, dlogits, n_dev, inv_dev)
     _call("unimm_pg_loss_bwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta, _ptr(lse),
           _ptr(ent), _ptr(g), inv_denom, _ptr(dlogits), n, V, logits.stride(0), dlogits.stride(0), _ptr(n_dev), _ptr(inv_dev))
+
+
+def pg_kl_loss_fwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, rowloss, rownll, lse, ent, n, V, ref_logits, kl_coef,
+                   kl, ref_lse, n_dev=None):
+    """Policy-gradient rows with the penalty kl_coef KL(p || p_ref) (include/unimm_hip.h: unimm_pg_kl_loss_fwd).  ref_logits: the
+    frozen reference's fp32 rows for the same n rows (its own row stride); kl / ref_lse: fp32 [n], written here, read by the backward."""
+    _dev(logits, labels, pos, adv, blogp, rowloss, rownll, lse, ent, n_dev, ref_logits, kl, ref_lse)
+    _call("unimm_pg_kl_loss_fwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta,
+          _ptr(rowloss), _ptr(rownll), _ptr(lse), _ptr(ent), n, V, logits.stride(0), _ptr(n_dev), _ptr(ref_logits),
+          ref_logits.stride(0) if ref_logits is not None else 0, kl_coef, _ptr(kl), _ptr(ref_lse))
+
+
+def pg_kl_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, ent, g, inv_denom, dlogits, n, V, ref_logits, kl_coef,
+                   kl, ref_lse, n_dev=None, inv_dev=None):
+    _dev(logits, labels, pos, adv, blogp, lse, ent, g, dlogits, n_dev, inv_dev, ref_logits, kl, ref_lse)
+    _call("unimm_pg_kl_loss_bwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta,
+          _ptr(lse), _ptr(ent), _ptr(g), inv_denom, _ptr(dlogits), n, V, logits.stride(0), dlogits.stride(0), _ptr(n_dev),
+          _ptr(inv_dev), _ptr(ref_logits), ref_logits.stride(0) if ref_logits is not None else 0, kl_coef, _ptr(kl), _ptr(ref_lse))
 
 
 def kl_loss_fwd(pred, target, label, rowloss, lse, rows, Cn):

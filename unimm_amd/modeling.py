@@ -15,7 +15,7 @@ from torch import nn
 from . import params as PM
 from .config import BertConfig
 from .engine import Engine
-from .policy import check_policy_inputs
+from .policy import check_policy_inputs, check_reference
 
 logger = logging.getLogger(__name__)
 
@@ -186,7 +186,7 @@ class BertForMultiModalPreTraining(nn.Module):
                 masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None,
                 output_all_attention_masks=False, nsp_weight=None, lm_weight=None,
                 _want_lm_scores=True, _want_pred_v=True, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
-                lm_objective=None):
+                lm_objective=None, lm_reference=None):
         """Same contract as models/vilbert_dialog.py:1519-1626.  `sep_indices` / `sep_len` are accepted and
         ignored exactly as the reference's embeddings do (:326-356).  Train branch (labels, NSP label and
         image target all given) -> (lm_loss[1], img_loss[1], nsp_loss[1], seq_out_t, pred_t, nsp[B,2]);
@@ -197,10 +197,13 @@ class BertForMultiModalPreTraining(nn.Module):
         (then `co_attention_mask` must be None) and `image_feat` / `image_loc` / `image_target` may hold one
         entry per IMAGE with `image_index` [B] mapping sequences to them.  `lm_advantage` (fp32 [B, T], with
         `lm_behaviour_logp` and `lm_objective`: unimm_amd/policy.py) makes lm_loss the policy-gradient objective on the
-        labelled rows instead of the weighted likelihood; bf16 engine, train branch."""
+        labelled rows instead of the weighted likelihood; bf16 engine, train branch.  `lm_reference` (a frozen model of either
+        class, `policy.frozen_reference`) is what `PolicyObjective(kl_coef > 0)` measures KL(p || p_ref) against: its engine runs
+        an inference forward on this call's inputs first; with kl_coef == 0 it is ignored."""
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                           self.compute_dtype, train_branch)
+                                           self.compute_dtype, train_branch, lm_reference=lm_reference)
+        lm_reference = check_reference(self, lm_reference, lm_objective)
         eng = self._engine
         dev = self._device()
         eng.ensure(dev)
@@ -209,7 +212,7 @@ class BertForMultiModalPreTraining(nn.Module):
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
                    lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
         eng.stage_host_inputs(inp)             # the reference's callers pass CPU tensors (train.py:113-161): pinned ring + copy stream
         B, T = input_ids.shape
         H, V = self.config.hidden_size, self.config.vocab_size
@@ -247,7 +250,7 @@ class BertForMultiModalPreTraining(nn.Module):
                          position_ids=None, attention_mask=None, image_attention_mask=None, co_attention_mask=None,
                          masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None, nsp_weight=None,
                          lm_weight=None, image_index=None, plan_header=None, lm_advantage=None, lm_behaviour_logp=None,
-                         lm_objective=None, shared_context=None):
+                         lm_objective=None, shared_context=None, lm_reference=None):
         """The training step's forward AND backward in one call (an extension; the reference writes
         `loss = c_lm * lm.mean() + c_nsp * nsp.mean() + c_img * img.mean(); loss.backward()`, train.py:164-168, :315).
         loss_weights = (c_lm, c_nsp, c_img).  With the weights known up front the backward does not wait for the host to see
@@ -256,7 +259,8 @@ class BertForMultiModalPreTraining(nn.Module):
         30-sequence step's GPU idles).  Parameter gradients accumulate into `.grad` exactly as with `loss.backward()`.
         -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits).  plan_header: `engine.count_rows(...)` of this batch if the caller
         has it already (a prefetcher: the step then starts without its host sync).  lm_advantage / lm_behaviour_logp /
-        lm_objective: as in `forward` (the policy-gradient step always runs eagerly).
+        lm_objective / lm_reference: as in `forward` (the policy-gradient step always runs eagerly; with a shared context the
+        reference runs the shared pass as well).
         shared_context (an extension): one group id per sequence, as in `sequence_log_likelihood` -- the sequences of a group
         share image and dialog context and differ only in the answer (the N sampled answers of a dialog, unimm_amd/policy.py).
         A bare list admits answers of up to 14 tokens (32 private rows); `SharedContext(ids, 64)` admits up to 30 (ValueError beyond).
@@ -266,7 +270,8 @@ class BertForMultiModalPreTraining(nn.Module):
         nsp_logits as None; when a sequence's context does not match its group's, the loss is NaN and the call adds nothing to
         the gradients.  Always eager."""
         lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                           self.compute_dtype)
+                                           self.compute_dtype, lm_reference=lm_reference)
+        lm_reference = check_reference(self, lm_reference, lm_objective)
         if shared_context is not None:
             from .scoring import check_shared_training
             check_shared_training(self.config, self.compute_dtype, loss_weights, attention_mask, shared_context, input_ids.shape[1],
@@ -282,7 +287,7 @@ class BertForMultiModalPreTraining(nn.Module):
             inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
                        position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                        masked_lm_labels=masked_lm_labels, lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
             eng.stage_host_inputs(inp, pack=())      # (the [B, R] image key mask stays a tensor: the pass indexes it by group)
             if self.training:
                 eng.step += 1
@@ -297,7 +302,7 @@ class BertForMultiModalPreTraining(nn.Module):
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
                    lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
         eng.stage_host_inputs(inp)
         if plan_header is not None:
             inp["_plan_header"] = plan_header
@@ -407,14 +412,15 @@ class VisualDialogEncoder(nn.Module):
                 head_mask=None, random_round_indices=None, output_nsp_scores=False, output_lm_scores=False,
                 image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
                 nsp_weight=None, lm_weight=None, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
-                lm_objective=None):
+                lm_objective=None, lm_reference=None):
         masked_lm_loss = masked_img_loss = nsp_loss = None
         kw = dict(sep_indices=sep_indices, sep_len=sep_len, token_type_ids=token_type_ids,
                   position_ids=token_position_ids, attention_mask=attention_mask, masked_lm_labels=masked_lm_labels,
                   next_sentence_label=next_sentence_label, image_attention_mask=image_attention_mask,
                   co_attention_mask=co_attention_mask, image_label=image_label, image_target=image_target,
                   nsp_weight=nsp_weight, lm_weight=lm_weight, _want_lm_scores=output_lm_scores, image_index=image_index,
-                  lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective)
+                  lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective,
+                  lm_reference=lm_reference)
         if next_sentence_label is not None and masked_lm_labels is not None and image_target is not None:
             masked_lm_loss, masked_img_loss, nsp_loss, _, prediction_scores_t, seq_relationship_score = \
                 self.bert_pretrained(input_ids, image_feat, image_loc, **kw)
@@ -443,7 +449,7 @@ class VisualDialogEncoder(nn.Module):
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
                          image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
                          nsp_weight=None, lm_weight=None, image_index=None, plan_header=None, lm_advantage=None,
-                         lm_behaviour_logp=None, lm_objective=None, shared_context=None):
+                         lm_behaviour_logp=None, lm_objective=None, shared_context=None, lm_reference=None):
         """forward + `(c_lm * lm + c_nsp * nsp + c_img * img).backward()` in one call, loss_weights = (c_lm, c_nsp, c_img)
         (BertForMultiModalPreTraining.forward_backward, shared_context included).  -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits)."""
         return self.bert_pretrained.forward_backward(
@@ -452,4 +458,4 @@ class VisualDialogEncoder(nn.Module):
             co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label, image_target=image_target,
             next_sentence_label=next_sentence_label, nsp_weight=nsp_weight, lm_weight=lm_weight, image_index=image_index,
             plan_header=plan_header, lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective,
-            shared_context=shared_context)
+            shared_context=shared_context, lm_reference=lm_reference)

@@ -9,6 +9,7 @@ sequences becomes (csrc/policy.hip, include/unimm_hip.h: unimm_pg_loss_fwd / _bw
     mode "logp"    -A log p_y                                              REINFORCE / self-critical
     mode "ratio"   -min(r A, clamp(r, 1 - clip_eps, 1 + clip_eps) A)       r = p_y / q_y; clip_eps = inf: importance-weighted
     both           -entropy_coef H(p)                                      entropy bonus of the row's distribution
+    both           +kl_coef KL(p || p_ref)                                 leash on a frozen reference model (kl_coef > 0)
 
 summed over the labelled rows and divided by their number, exactly where the weighted likelihood sits otherwise: the row-sparse
 decoder, the transform head's backward, the weight-gradient ledger and the data-parallel buckets are the training step's.
@@ -16,9 +17,16 @@ decoder, the transform head's backward, the weight-gradient ledger and the data-
 This module is host-side: the objective's description, the refusals, the assembly of the training batch from the sampled
 answers (the layout `utils/data_utils.py:139-288` gives a generative sequence; `oracle/masks.py::encode_gen` restates it) and the
 advantage arithmetic.  The data is small and on the host anyway, where the reward is computed.  `trainer.self_critical_step`
-is the loop body."""
+is the loop body.
+
+The KL leash (unimm_pg_kl_loss_fwd / _bwd): `lm_reference=frozen_reference(model)`, taken before the fine-tune starts, with
+`PolicyObjective(kl_coef=c)`.  Every step the reference's engine first runs an inference forward on the step's own inputs and
+hands over its fp32 logits for exactly the step's decoded rows; the row kernels stream them beside the policy's and add the
+EXACT full-vocabulary c KL(p || p_ref) per row and its gradient (not the sampled estimate log p_y - log p_ref,y).  Nothing
+of the reference changes; `engine.last_lm_kl` reports the mean KL of the trained rows beside `engine.last_lm_entropy`."""
 from __future__ import annotations
 
+import copy
 import math
 from dataclasses import dataclass
 
@@ -32,10 +40,12 @@ SEP, MASK = 102, 103
 
 @dataclass(frozen=True)
 class PolicyObjective:
-    """mode: "logp" | "ratio"; clip_eps: the ratio's clipping range (inf = none); entropy_coef: weight of the entropy bonus."""
+    """mode: "logp" | "ratio"; clip_eps: the ratio's clipping range (inf = none); entropy_coef: weight of the entropy bonus;
+    kl_coef: weight of the per-row KL(p || p_ref) against the frozen `lm_reference` (0 = none, the reference is then ignored)."""
     mode: str = "logp"
     clip_eps: float = math.inf
     entropy_coef: float = 0.0
+    kl_coef: float = 0.0
 
     def __post_init__(self):
         if self.mode not in ("logp", "ratio"):
@@ -44,13 +54,69 @@ class PolicyObjective:
             raise ValueError(f"PolicyObjective: clip_eps must be >= 0 (inf = no clipping), got {self.clip_eps}")
         if not math.isfinite(float(self.entropy_coef)):
             raise ValueError(f"PolicyObjective: entropy_coef must be finite, got {self.entropy_coef}")
+        if not (math.isfinite(float(self.kl_coef)) and float(self.kl_coef) >= 0.0):
+            raise ValueError(f"PolicyObjective: kl_coef must be finite and >= 0, got {self.kl_coef}")
 
 
-def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, compute_dtype, train_branch=True):
+def _pretraining_model(model):
+    """a VisualDialogEncoder or a BertForMultiModalPreTraining -> the latter"""
+    return model.bert_pretrained if hasattr(model, "bert_pretrained") else model
+
+
+def frozen_reference(model):
+    """The thing to pass as `lm_reference`: a deep copy of `model` as it is now, in eval mode, with requires_grad_(False) on
+    every parameter.  (The copy's engine starts empty and builds its own weight copies at its first forward.)"""
+    ref = copy.deepcopy(model)
+    ref.eval()
+    ref.requires_grad_(False)
+    for p in ref.parameters():
+        p.grad = None
+    return ref
+
+
+_REF_CONFIG_KEYS = ("vocab_size", "hidden_size", "v_hidden_size", "bi_hidden_size", "num_hidden_layers", "v_num_hidden_layers",
+                    "num_attention_heads", "v_num_attention_heads", "bi_num_attention_heads", "intermediate_size",
+                    "v_intermediate_size", "bi_intermediate_size", "v_feature_size", "v_target_size", "v_biattention_id",
+                    "t_biattention_id", "with_coattention", "fixed_t_layer", "fixed_v_layer", "max_position_embeddings",
+                    "type_vocab_size")
+
+
+def check_reference(model, lm_reference, obj):
+    """The refused uses of `lm_reference` (ValueError, before anything touches the device) -> the reference's pre-training
+    model when the step's objective reads it (kl_coef > 0), else None.  model: the trained BertForMultiModalPreTraining."""
+    if lm_reference is None:
+        if obj is not None and obj.kl_coef > 0:
+            raise ValueError(f"PolicyObjective(kl_coef={obj.kl_coef}) penalises KL(p || p_ref): pass lm_reference "
+                             "(policy.frozen_reference(model), taken before the fine-tune), or kl_coef=0")
+        return None
+    if obj is None:
+        raise ValueError("lm_reference is the frozen model of the policy-gradient objective's KL term: pass lm_advantage (and "
+                         "PolicyObjective(kl_coef=...)) with it, or drop it for the likelihood objective")
+    ref = _pretraining_model(lm_reference)
+    if ref is model:
+        raise ValueError("lm_reference is the trained model itself: its KL to itself is 0 and it would move with every step; "
+                         "pass a frozen copy, policy.frozen_reference(model)")
+    if not (hasattr(ref, "config") and hasattr(ref, "_engine") and hasattr(ref, "compute_dtype")):
+        raise ValueError(f"lm_reference must be a BertForMultiModalPreTraining or a VisualDialogEncoder, got {type(lm_reference).__name__}")
+    diff = [k for k in _REF_CONFIG_KEYS if getattr(ref.config, k, None) != getattr(model.config, k, None)]
+    if diff:
+        raise ValueError("lm_reference must have the trained model's vocabulary, hidden sizes and layer schedule; its config "
+                         f"differs in {', '.join(diff)}")
+    if ref.compute_dtype != "bf16":
+        raise ValueError(f"lm_reference must run on the bf16 engine (compute_dtype='bf16'), got {ref.compute_dtype!r}")
+    if ref._device() != model._device():
+        raise ValueError(f"lm_reference is on {ref._device()}, the trained model on {model._device()}: move it with .to()")
+    return ref if obj.kl_coef > 0 else None
+
+def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, compute_dtype, train_branch=True,
+                        lm_reference=None):
     """The refused combinations of the policy-gradient arguments of `forward` / `forward_backward` (ValueError, before
     anything touches the device) -> the objective in force (None without `lm_advantage`).  train_branch: whether the call
-    computes the losses (labels, NSP label and image target all given)."""
+    computes the losses (labels, NSP label and image target all given).  lm_reference: only its presence is judged here
+    (`check_reference` judges the model)."""
     if lm_advantage is None:
+        if lm_reference is not None:
+            check_reference(None, lm_reference, None)
         if lm_behaviour_logp is not None or lm_objective is not None:
             raise ValueError("lm_behaviour_logp / lm_objective describe the policy-gradient objective: pass lm_advantage "
                              "(fp32 [B, T]) with them, or drop them for the likelihood objective")
@@ -73,6 +139,8 @@ def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm
             got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
             raise ValueError(f"{name} must be a tensor of shape [B, T] = {(B, T)} like input_ids (one value per token, read on "
                              f"the labelled rows), got {got}: build it with policy.spread")
+    if obj.kl_coef > 0 and lm_reference is None:
+        check_reference(None, None, obj)
     if not train_branch:
         raise ValueError("lm_advantage weighs the LM loss of the train branch: pass masked_lm_labels, next_sentence_label and "
                          "image_target with it (this call computes no loss and would ignore it)")

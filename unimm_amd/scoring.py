@@ -177,9 +177,11 @@ def forward_shared(eng, inp: dict, groups, want_nsp=True, cache=None):
     return eng._on_text_stream(_forward_shared, eng, inp, groups, want_nsp, cache)
 
 
-def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
+def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None, want_logits=False):
     """st (train / tape, as in `Engine._self_block`): None = inference; with a tape the pass saves for backward, draws every
-    dropout mask and returns the LM head's state and the embeddings' backward passes in out['lm'] / out['bwd']."""
+    dropout mask and returns the LM head's state and the embeddings' backward passes in out['lm'] / out['bwd'].
+    want_logits: the decoder logits of the copy rows in out['logits'] WITHOUT the generation caches (the frozen reference of a
+    KL-regularised policy step, `Engine._reference_rows`)."""
     cfg = eng.cfg
     st = dict(train=False, tape=None) if st is None else st
     train, tape = st["train"], st["tape"]
@@ -466,7 +468,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None):
     else:
         lm = eng._lm_head(xs, n, lab_sel, w_sel, False)
     out["rownll"] = lm["rownll"]
-    if cache is not None:
+    if cache is not None or want_logits:
         out["logits"] = lm["logits"]
     out["lm_seq"] = (lm_pos // T).to(torch.int32)
     return out
@@ -528,6 +530,10 @@ def train_shared(eng, inp, groups, g_lm, train):
     if lm.get("ent") is not None:                                  # the policy-gradient step reports the mean entropy of its rows
         eng.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
         L.reduce_sum(lm["ent"], n, eng.last_lm_entropy, 1.0 / n)
+        eng.last_lm_kl = None
+        if lm.get("kl") is not None:                               # ... and, with a reference, their mean KL to it
+            eng.last_lm_kl = torch.empty(1, dtype=F32, device=dev)
+            L.reduce_sum(lm["kl"], n, eng.last_lm_kl, 1.0 / n)
     # ---- backward: the MLM head, then the tape (Engine._backward without poolers, NSP and image head)
     eng.arena.attach_grads()
     eng._bwd_fresh = bool(eng.arena.fresh)

@@ -106,7 +106,7 @@ def dense_finetune_step(dialog_encoder, optimizer, scheduler, batch, params, ite
 
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
                        objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
-                       shared_context=False, rollout="separate"):
+                       shared_context=False, rollout="separate", reference=None):
     """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
@@ -123,6 +123,8 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     rollout: "separate" decodes the greedy baseline in a generate_answers call of its own (beams = 1); "fused" (baseline="greedy"
     only, samples <= 15; ValueError otherwise) decodes it as one more slot of the sampling call, `generate_answers(samples=N,
     greedy=True)`: one prefill and one walk over the decode steps for both.  Only the samples are trained on either way.
+    reference: the frozen model `objective.kl_coef > 0` leashes the policy to (`policy.frozen_reference(model)`, taken before
+    the fine-tune; passed on as `lm_reference`); the step's mean KL is then in `engine.last_lm_kl`.
     -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
     distributions; NaN when the step decoded no row)."""
     greedy_baseline = isinstance(baseline, str) and baseline == "greedy"
@@ -164,6 +166,7 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     C = engine.cfg.v_target_size
     dialog_encoder.train()
     engine.last_lm_entropy = None               # set by this step's losses (never a value an earlier step left behind)
+    engine.last_lm_kl = None
     sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
     with sync_ctx:
         _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
@@ -172,7 +175,7 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
             next_sentence_label=torch.zeros(K, dtype=torch.int64),
             image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
             image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
-            lm_advantage=spread(advantage, sb), lm_objective=objective,
+            lm_advantage=spread(advantage, sb), lm_objective=objective, lm_reference=reference,
             lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None,
             **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}))
     entropy = engine.last_lm_entropy
