@@ -644,6 +644,54 @@ typedef struct {
 
 int unimm_adamw_step(const unimm_adamw_args* args, void* stream);
 
+/* Global-norm gradient clipping and a non-finite guard for the step above, without a host sync: a norm pass over the gradient
+ * arena leaves its result in a device-resident state block, and unimm_adamw_step_clipped takes its gradient scale from there.
+ * The semantics are those of torch.nn.utils.clip_grad_norm_ applied to grad_scale * g (the reference's train.py does not clip;
+ * BERT fine-tuning and policy-gradient recipes clip the global norm at about 1).
+ *
+ * unimm_grad_norm reads g [n] once.  A 64-element chunk COUNTS when group[chunk] < n_groups; ids in [n_groups, 8) (chunks that
+ * take no step) and skip ids >= UNIMM_ADAMW_MAX_GROUPS are not read at all, so they may hold any bit pattern, NaN included.
+ * Every counted element is widened to fp64 and squared there (a product of two fp32 values is exact in fp64, so a finite gradient
+ * of 1e25 gives a finite norm), and every addition is an fp64 addition in a fixed order: per lane over its grid-stride elements,
+ * a fixed cross-lane tree, one partial per workgroup and group written to `workspace`, then a second one-workgroup launch that adds
+ * the partials in a fixed order (lane t takes workgroups t, t + 256, ... in index order, then the same tree).  No float atomics, no "last block done" counter; the grid is a function of n alone, so the same
+ * input gives the same bits on every launch.  One grid-stride pass covers 2048 workgroups x 256 lanes x 2 x 4 = 4,194,304
+ * elements; no serial chain of additions is longer than 2 n / 4,194,304 + 48, so with non-negative terms the relative error of
+ * sumsq stays below (chain length) x 1.1e-16.
+ * The second launch writes the whole state block (fp64 arithmetic):
+ *   group_sumsq[k] = sum of g^2 over the chunks of group k (0 for k >= n_groups);   sumsq = group_sumsq[0] + ... in index order
+ *   norm      = |grad_scale| * sqrt(sumsq)                 the norm of the gradient the update sees, grad_scale * g
+ *   nonfinite = !isfinite(sumsq)                            an inf or NaN in any counted element
+ *   coef      = min(1, max_norm / (norm + 1e-6))            max_norm finite;  1 when max_norm is +inf (measure only) or nonfinite
+ *   scale     = (float)((double)grad_scale * coef)          grad_scale bit for bit when coef == 1
+ *   skipped  += nonfinite                                   a running counter: zero the block once, before its first use
+ * workspace: at least UNIMM_GRAD_NORM_WS_DOUBLES doubles, 16-byte aligned, contents irrelevant before and after the call.
+ * Refused before any launch: UNIMM_E_ARG for a NULL g, group, workspace or state, n_groups outside 1 .. UNIMM_ADAMW_MAX_GROUPS,
+ * a max_norm that is NaN, zero or negative, workspace_doubles < UNIMM_GRAD_NORM_WS_DOUBLES; UNIMM_E_SHAPE for n <= 0 or
+ * n % 64 != 0; UNIMM_E_ALIGN for g, workspace or state off 16-byte alignment. */
+#define UNIMM_GRAD_NORM_WS_DOUBLES 16384
+typedef struct {
+  double group_sumsq[UNIMM_ADAMW_MAX_GROUPS];  /* per (lr, wd) group, of the unscaled g */
+  double sumsq;
+  double norm;
+  double coef;
+  float scale;           /* what unimm_adamw_step_clipped multiplies every gradient element by */
+  int32_t nonfinite;     /* 1 / 0 */
+  int32_t skipped;       /* number of norm passes so far that found a non-finite gradient */
+} unimm_clip_state;
+
+int unimm_grad_norm(const float* g, const uint8_t* group, int64_t n, int32_t n_groups, float grad_scale, double max_norm,
+                    double* workspace, int64_t workspace_doubles, unimm_clip_state* state, void* stream);
+/* unimm_adamw_step with the per-element gradient rnd(g * state->scale): the scale is read from device memory and
+ * args->grad_scale is IGNORED (it went into unimm_grad_norm).  One kernel template with unimm_adamw_step: with state->scale ==
+ * grad_scale bitwise (coef == 1) p, m, v, w16 and g come out bit-equal to unimm_adamw_step's.  skip_nonfinite != 0 and
+ * state->nonfinite != 0: every workgroup leaves p, m, v and w16 untouched; zero_grad still clears g on exactly the chunks the
+ * update would have cleared (ids < UNIMM_ADAMW_MAX_GROUPS: every counted chunk), or the poison would survive into the next
+ * step.  skip_nonfinite == 0: the update runs whatever the flag says, with scale == grad_scale when it is set (coef is 1
+ * then); the two options are independent.  Refusals: those of unimm_adamw_step; UNIMM_E_ARG for a NULL state, UNIMM_E_ALIGN
+ * for a state off 16-byte alignment. */
+int unimm_adamw_step_clipped(const unimm_adamw_args* args, const unimm_clip_state* state, int32_t skip_nonfinite, void* stream);
+
 /* NeuralNDCG-transposed of `slates` independent slates of `n` answer options: value and gradient with
  * respect to the predictions in one launch.  Replaces the deterministic branch of
  * neuralNDCG_transposed (utils/rank_loss.py:518-581: deterministic_neural_sort :79-112, sinkhorn_scaling

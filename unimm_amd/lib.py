@@ -94,6 +94,8 @@ SIGNATURES = {
     "unimm_reduce_sum": (_INT, [VP, I64, VP, F32, VP, VP, VP]),
     "unimm_segment_sum": (_INT, [VP, VP, VP, I64, F32, VP]),
     "unimm_adamw_step": (_INT, [VP, VP]),
+    "unimm_grad_norm": (_INT, [VP, VP, I64, I32, F32, C.c_double, VP, I64, VP, VP]),
+    "unimm_adamw_step_clipped": (_INT, [VP, VP, I32, VP]),
     "unimm_neural_ndcg": (_INT, [VP, VP]),
     # the fp32-accuracy mode (csrc/x3ops.hip)
     "unimm_x3_split": (_INT, [VP, VP]),
@@ -975,8 +977,10 @@ class AdamWArgs(C.Structure):
 
 
 def adamw_step(p, g, m, v, group, lrs, wds, step, beta1=0.9, beta2=0.999, eps=1e-6, w16=None, grad_scale=1.0,
-               correct_bias=True, zero_grad=False):
-    """One fused AdamW step over flat fp32 arenas (see include/unimm_hip.h: unimm_adamw_step)."""
+               correct_bias=True, zero_grad=False, clip_state=None, skip_nonfinite=False):
+    """One fused AdamW step over flat fp32 arenas (see include/unimm_hip.h: unimm_adamw_step).  clip_state: the state block a
+    `grad_norm` call filled; the step then is unimm_adamw_step_clipped, which takes its gradient scale from the block (grad_scale
+    is ignored) and, with skip_nonfinite, updates nothing when the block's non-finite flag is set."""
     _dev(p, g, m, v, group, w16)
     if len(lrs) != len(wds) or not 1 <= len(lrs) <= ADAMW_MAX_GROUPS:
         raise UnimmHipError(f"adamw_step: 1..{ADAMW_MAX_GROUPS} (lr, weight_decay) groups, got {len(lrs)}")
@@ -987,7 +991,46 @@ def adamw_step(p, g, m, v, group, lrs, wds, step, beta1=0.9, beta2=0.999, eps=1e
         a.lr[i], a.weight_decay[i] = float(lr), float(wd)
     a.beta1, a.beta2, a.eps, a.grad_scale = beta1, beta2, eps, grad_scale
     a.correct_bias, a.zero_grad = int(bool(correct_bias)), int(bool(zero_grad))
-    _call("unimm_adamw_step", C.byref(a))
+    if clip_state is None:
+        _call("unimm_adamw_step", C.byref(a))
+    else:
+        _dev(clip_state)
+        _call("unimm_adamw_step_clipped", C.byref(a), clip_state.data_ptr(), int(bool(skip_nonfinite)))
+
+
+GRAD_NORM_WS_DOUBLES = 16384          # UNIMM_GRAD_NORM_WS_DOUBLES: one partial per workgroup (2048) and group (8)
+GRAD_NORM_PASS = 2048 * 256 * 2 * 4   # elements one grid-stride pass of the norm kernel covers (csrc/optim.hip)
+
+
+class ClipState(C.Structure):
+    """The device-resident result of `grad_norm` (include/unimm_hip.h: unimm_clip_state), 104 bytes."""
+    _fields_ = [("group_sumsq", C.c_double * ADAMW_MAX_GROUPS), ("sumsq", C.c_double), ("norm", C.c_double), ("coef", C.c_double),
+                ("scale", C.c_float), ("nonfinite", C.c_int32), ("skipped", C.c_int32)]
+
+
+CLIP_STATE_DOUBLES = C.sizeof(ClipState) // 8
+
+
+def new_clip_state(device):
+    """A zeroed state block as an fp64 tensor (torch allocations are at least 256-byte aligned)."""
+    return torch.zeros(CLIP_STATE_DOUBLES, dtype=torch.float64, device=device)
+
+
+def clip_state_views(state):
+    """Named views of a state block tensor: no copy, no sync."""
+    f32, i32 = state.view(torch.float32), state.view(torch.int32)
+    o = ClipState.scale.offset // 4
+    return dict(group_sumsq=state[:ADAMW_MAX_GROUPS], sumsq=state[ClipState.sumsq.offset // 8],
+                norm=state[ClipState.norm.offset // 8], coef=state[ClipState.coef.offset // 8],
+                scale=f32[o], nonfinite=i32[o + 1], skipped=i32[o + 2])
+
+
+def grad_norm(g, group, n_groups, workspace, state, grad_scale=1.0, max_norm=float("inf")):
+    """Norm of grad_scale * g over the chunks whose group id is below n_groups, and the clip coefficient for max_norm, left in
+    `state` on the device (see include/unimm_hip.h: unimm_grad_norm).  workspace: fp64, >= GRAD_NORM_WS_DOUBLES elements."""
+    _dev(g, group, workspace, state)
+    _call("unimm_grad_norm", g.data_ptr(), group.data_ptr(), g.numel(), int(n_groups), float(grad_scale), float(max_norm),
+          workspace.data_ptr(), workspace.numel(), state.data_ptr())
 
 
 NDCG_MAX_OPTIONS, NDCG_MAX_ITER = 128, 64
@@ -1178,6 +1221,6 @@ STRUCTS = {
     "unimm_gemm_nt_args": GemmNtArgs, "unimm_gemm_tn_args": GemmTnArgs, "unimm_attn_args": AttnArgs,
     "unimm_attn_bwd_args": AttnBwdArgs, "unimm_attn_spliced_bwd_args": AttnSplicedBwdArgs, "unimm_finish_desc": FinishDesc,
     "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
-    "unimm_adamw_args": AdamWArgs, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
+    "unimm_adamw_args": AdamWArgs, "unimm_clip_state": ClipState, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
     "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
 }

@@ -8,6 +8,9 @@ reference's learning-rate schedule.
 `step` per parameter index, train.py:369-385, :505).  The update itself is ONE kernel launch over the
 parameter arena (`unimm_adamw_step`), which also rewrites the bf16 GEMM-operand copy of the weights; the
 per-tensor groups collapse to the distinct (lr, weight_decay) pairs of the step (4 in the reference setup).
+Optional, off by default: global-norm gradient clipping and a non-finite guard (`max_grad_norm`, `skip_nonfinite`), a norm
+pass over the gradient arena in front of the update whose result stays on the device (`unimm_grad_norm`,
+`unimm_adamw_step_clipped`).
 
 `WarmupLinearScheduleNonZero` restates utils/optim_utils.py:8-26 (pinned by tests/golden/sched.npz)."""
 from __future__ import annotations
@@ -66,9 +69,29 @@ def reference_param_groups(model, lr, image_lr, language_weights, weight_decay=0
 
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW of `pytorch_transformers` (betas (0.9, 0.999), eps 1e-6, correct_bias True, decay after the
-    update) as one fused launch.  `engine`: the unimm_amd.engine.Engine whose arena holds the parameters."""
+    update) as one fused launch.  `engine`: the unimm_amd.engine.Engine whose arena holds the parameters.
 
-    def __init__(self, params, engine, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    `max_grad_norm` (a positive finite number, or None): clip the global norm of the gradient the update sees, `grad_scale * g`
+    over every parameter that takes a step, as torch.nn.utils.clip_grad_norm_ does (coef = min(1, max / (norm + 1e-6))).
+    `skip_nonfinite`: a step whose gradient holds an inf or a NaN changes no parameter and no moment (the gradient is left
+    for zero_grad() as always).  Either option puts one read of the gradient arena (`unimm_grad_norm`) in front of the update,
+    which then takes its scale from device memory (`unimm_adamw_step_clipped`): the host learns nothing during the step, so
+    nothing syncs.  `step_count` therefore advances on a skipped step too (the bias correction is formed on the host), and
+    `step` in `state_dict()` counts ATTEMPTED steps; `skipped_steps` is not saved.  With both options off, step() is the one
+    launch it always was.  Data-parallel ranks need no exchange: after the gradient all-reduce they hold the same arena bits,
+    and the norm pass adds in a fixed order, so every rank forms the same scale bits.
+
+    Readouts of the last norm pass (step() with an option set, or grad_norm()), device tensors that are views of the state
+    block and cost no sync: `last_grad_norm`, `last_clip_coef` (fp64), `last_nonfinite` (int32), `last_group_grad_norms()`."""
+
+    def __init__(self, params, engine, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
+                 max_grad_norm=None, skip_nonfinite=False):
+        if max_grad_norm is not None:
+            ok = isinstance(max_grad_norm, (int, float)) and not isinstance(max_grad_norm, bool)
+            if not ok or not (0.0 < float(max_grad_norm) < float("inf")):         # NaN fails both comparisons
+                raise ValueError(f"FusedAdamW: max_grad_norm must be None or a positive finite number, got {max_grad_norm!r}")
+            max_grad_norm = float(max_grad_norm)
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         params = list(params)
         first = params[0]["params"] if isinstance(params[0], dict) else params
         first = first[0] if isinstance(first, (list, tuple)) else next(iter(first))
@@ -100,6 +123,49 @@ class FusedAdamW(torch.optim.Optimizer):
         self._combo_key = None
         self.step_count = 0
         self.grad_scale = 1.0       # set to 1 / batch_multiply (or 1 / loss scale) by the caller when needed
+        # norm pass: workspace and two state blocks, allocated once (step()'s own, whose `skipped` counts, and grad_norm()'s)
+        self._norm_ws = torch.empty(L.GRAD_NORM_WS_DOUBLES, dtype=torch.float64, device=A.flat.device)
+        self._clip_state = L.new_clip_state(A.flat.device)
+        self._measure_state = L.new_clip_state(A.flat.device)
+        self._last = (self._clip_state, (), 1.0)        # (state block, combos, grad_scale) of the last norm pass
+
+    # -- gradient norm, clipping, non-finite guard ---------------------------------------------------
+    def _norm_pass(self, state, combos, max_norm):
+        L.grad_norm(self.arena.grad_flat, self._group_dev, len(combos), self._norm_ws, state, grad_scale=self.grad_scale,
+                    max_norm=max_norm)
+        self._last = (state, tuple(combos), float(self.grad_scale))
+
+    @torch.no_grad()
+    def grad_norm(self):
+        """Run the norm pass now and update nothing: the norm of `grad_scale * g` over the parameters that take a step, an
+        fp64 device scalar (no sync).  For logging, or for choosing max_grad_norm.  Leaves `skipped_steps` alone."""
+        self._norm_pass(self._measure_state, self._sync_groups(), float("inf"))
+        return self.last_grad_norm
+
+    @property
+    def last_grad_norm(self):
+        return L.clip_state_views(self._last[0])["norm"]
+
+    @property
+    def last_clip_coef(self):
+        return L.clip_state_views(self._last[0])["coef"]
+
+    @property
+    def last_nonfinite(self):
+        return L.clip_state_views(self._last[0])["nonfinite"]
+
+    def last_group_grad_norms(self):
+        """{(lr, weight_decay): fp64 device scalar}: the last norm pass's norm per distinct pair of that step (it tells the text
+        tower's gradient from the image tower's, for example).  Their squares add up to last_grad_norm squared."""
+        state, combos, scale = self._last
+        norms = L.clip_state_views(state)["group_sumsq"].sqrt() * abs(scale)
+        return {k: norms[i] for i, k in enumerate(combos)}
+
+    @property
+    def skipped_steps(self):
+        """Number of step() calls so far (with an option set) that found a non-finite gradient: with skip_nonfinite, the steps
+        that were skipped.  A host int: reading it is the one access here that syncs."""
+        return int(L.clip_state_views(self._clip_state)["skipped"].item())
 
     # -- torch.optim.Optimizer surface ------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False):
@@ -117,8 +183,8 @@ class FusedAdamW(torch.optim.Optimizer):
                              f"(the kernel takes {L.ADAMW_MAX_GROUPS})")
         return combos, ids
 
-    @torch.no_grad()
-    def step(self, closure=None):
+    def _sync_groups(self):
+        """-> the step's distinct (lr, weight_decay) pairs, with the device chunk -> group table brought up to date"""
         combos, ids = self._combos()
         # the chunk -> group table only changes when the PARTITION changes, not when the lr values do
         part = tuple(ids)
@@ -130,17 +196,28 @@ class FusedAdamW(torch.optim.Optimizer):
                         self._group_host[lo:hi] = gi
             self._group_dev.copy_(torch.from_numpy(self._group_host), non_blocking=False)
             self._combo_key = part
+        return combos
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        combos = self._sync_groups()
         self.step_count += 1
         b1, b2 = self.defaults["betas"]
         A = self.arena
+        clip = None
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            clip = self._clip_state
+            self._norm_pass(clip, combos, self.max_grad_norm if self.max_grad_norm is not None else float("inf"))
         L.adamw_step(A.flat, A.grad_flat, self.exp_avg, self.exp_avg_sq, self._group_dev,
                      [k[0] for k in combos], [k[1] for k in combos], self.step_count, beta1=b1, beta2=b2,
                      eps=self.defaults["eps"], w16=self.engine.w16, grad_scale=self.grad_scale,
-                     correct_bias=self.defaults["correct_bias"])
+                     correct_bias=self.defaults["correct_bias"], clip_state=clip, skip_nonfinite=self.skip_nonfinite)
         self.engine.refresh_weights(force=True, cast=False)     # transposed copies; the cast is already done
 
     # -- checkpoint format of torch.optim (train.py:369-385, :505) ---------------------------------
     def state_dict(self):
+        """torch.optim's layout.  `step` is step_count: with skip_nonfinite it counts ATTEMPTED steps, skipped ones included
+        (the host never learns which were skipped without a sync); the skip counter itself is not saved."""
         state, groups, idx = {}, [], 0
         for g, rs in zip(self.param_groups, self._ranges):
             ids = []
