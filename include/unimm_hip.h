@@ -584,6 +584,60 @@ int unimm_pg_kl_loss_bwd(const float* logits, const int32_t* labels, const int32
                          const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
                          const int32_t* n_dev, const float* inv_dev, const float* ref_logits, int32_t ld_ref, float kl_coef,
                          const float* kl, const float* ref_lse, void* stream);
+/* Listwise preference objective on the likelihoods of whole candidate answers (csrc/policy.hip; an entry point added beside the
+ * ones above, whose signatures and results are unchanged: the ABI number stays).  It sits between unimm_lm_loss_fwd, which leaves
+ * rownll = -log p_y per decoded row, and unimm_pg_loss_bwd in LOGP mode, which turns a per-row coefficient A into the gradient of
+ * -A log p_y: per-row log-probabilities become per-sequence scores, the sequences of a group (a dialog) are compared with each
+ * other and with a frozen reference, and every row gets its sequence's coefficient.
+ * Row r < min(n, *n_dev) belongs to sequence row_seq[r]; sequence j to group seq_group[j] with target weight seq_weight[j] >= 0.
+ * M_g = the sequences of group g that have at least one row.  For j in M_g, in fp64:
+ *   S_j = -sum_r rownll[r],  R_j = -sum_r ref_rownll[r] (0 without a reference),  L_j = number of rows of j
+ *   D_j = (S_j - R_j) / L_j^lam (lam = 1 if length_normalize else 0),  z_j = beta D_j
+ *   logP_j = z_j - logsumexp_{k in M_g} z_k,  P_j = exp(logP_j),  W_g = sum_{j in M_g} w_j
+ *   group_loss[g] = -sum_{j in M_g} w_j logP_j,  c_j = beta (w_j - W_g P_j) / L_j^lam = -d group_loss[g] / d S_j
+ * A group is ALIVE when W_g > 0; the caller's loss is sum(group_loss) * alive_inv[0].  Two candidates with w = (1, 0) give
+ * -log sigmoid(z_w - z_l) (DPO); softmax(relevance) as w gives the ListNet top-1 form.
+ * Outputs (fp32, each rounded from fp64 once): adv[r] = c_j on every row of j (0 on the rows of a group that is not alive),
+ * seq_score[j] = D_j (NaN for a sequence without rows), seq_prob[j] = P_j (0 for a sequence without rows or outside every
+ * group), group_loss[g] (0 for a group that is not alive), alive_inv[0] = 1 / #alive (NaN when none): alive_inv can serve as
+ * the inv_dev / scale_dev word of unimm_pg_loss_bwd and unimm_reduce_sum.
+ * Order: a sequence's rows are added in ascending row index, a group's members are taken in ascending sequence index, every
+ * sum is a serial chain of fp64 additions in that order.  No float atomics, no arrival counters: the same inputs give the same
+ * bits.  row_seq need not be sorted or contiguous.  Three launches: per sequence (one wave each), per group (one workgroup
+ * each, the members' z, w and L in LDS), per row.
+ * Values the host cannot see never lead out of a buffer: a row_seq outside [0, B) makes the row an ignored one (adv = 0); a
+ * seq_group outside [0, groups) takes the sequence out of every group (its seq_score is still written, seq_prob = 0, adv = 0);
+ * a group with more than UNIMM_PREF_MAX_MEMBERS members, or with a member whose weight is negative or not finite, is not alive
+ * and has group_loss = NaN, its members seq_prob = NaN and adv = 0.  A saturated softmax (z differences of 1e4 and beyond)
+ * gives P of exactly 0 and 1 and finite outputs.
+ * n == 0 or *n_dev == 0: UNIMM_OK, alive_inv = NaN, group_loss zeroed, no other output is touched.
+ * workspace: at least UNIMM_PREF_WS_ITEM_BYTES * (B + groups) bytes, 16-byte aligned, contents irrelevant before and after
+ * (fp64 D [B], fp32 c [B], int32 L [B], int32 alive [groups]).
+ * UNIMM_E_ARG before any launch: a NULL args or required pointer (ref_rownll and n_dev may be NULL; with n == 0 so may the
+ * three arrays of n elements), beta not positive and
+ * finite, groups < 1, B < 1, n < 0, a workspace that is too small; UNIMM_E_ALIGN for a workspace off 16-byte alignment. */
+#define UNIMM_PREF_MAX_MEMBERS 128
+#define UNIMM_PREF_WS_ITEM_BYTES 16
+typedef struct {
+  const float* rownll;       /* [n] -log p_y of the policy's decoded rows */
+  const float* ref_rownll;   /* [n] the same rows under the frozen reference, or NULL */
+  const int32_t* row_seq;    /* [n] sequence of each row */
+  const int32_t* n_dev;      /* device word: rows actually present (n is then a capacity), or NULL */
+  const int32_t* seq_group;  /* [B] */
+  const float* seq_weight;   /* [B] */
+  float* adv;                /* [n] */
+  float* seq_score;          /* [B] */
+  float* seq_prob;           /* [B] */
+  float* group_loss;         /* [groups] */
+  float* alive_inv;          /* [1] */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t n, B, groups;
+  int32_t length_normalize;  /* 0: D = S - R (val_lm's sum);  else: divided by the row count (val_avg_lm's mean) */
+  float beta;
+} unimm_seq_pref_args;
+
+int unimm_seq_pref(const unimm_seq_pref_args* args, void* stream);
 /* Masked-region KL (models/vilbert_dialog.py:1569-1574): rowloss = [label==1] * sum_j t_j (log t_j - logp_j) */
 int unimm_kl_loss_fwd(const float* pred, const float* target, const int32_t* label, float* rowloss, float* lse,
                       int32_t rows, int32_t C, int32_t ld, void* stream);

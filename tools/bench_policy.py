@@ -1,7 +1,7 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
     python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared [--max-answer-len 14]]
-                                 [--baseline mean|greedy] [--rollout separate|fused ...] [--kl]
+                                 [--baseline mean|greedy] [--rollout separate|fused ...] [--kl] [--preference [--reference]]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
 [rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
@@ -35,7 +35,16 @@ _bwd against unimm_pg_loss_fwd + _bwd on the same logits, the reference row a se
 pairs like the kernels above; the KL pair reads twice the bytes per direction, and both byte counts are printed.  Step: one
 self_critical_step at G x N (baseline "mean") without a reference and with `reference=frozen_reference(model)`, kl_coef = 0.05, as
 alternating pairs with the same seed (--pairs of them after a warm-up of each): medians of the train step and of the whole
-step, every pair's ratio and the plain step's min-to-max spread.  The step with a reference adds one inference forward."""
+step, every pair's ratio and the plain step's min-to-max spread.  The step with a reference adds one inference forward.
+
+--preference (instead of the above): the listwise preference objective on given candidates (policy.PreferenceObjective,
+unimm_seq_pref).  The new launch alone, between device events like the kernels above, at 5,016 rows of 64 sequences in 8 groups
+and at 5,016 rows of 800 sequences in 8 groups of 100.  Step: the train step (forward_backward + optimizer.step) on G x N
+candidates of 1 .. 14 tokens, with --shared on the shared schedule, otherwise on the replicated one, as
+alternating pairs after a warm-up of each with the KL-leashed policy-gradient step of --kl on the SAME sequences, schedule and
+reference (`lm_advantage`, PolicyObjective(entropy_coef = 0.01, kl_coef = 0.05)): medians, every pair's ratio, the KL step's
+min-to-max spread.  --reference: the preference step compares against `frozen_reference(model)` (one more inference forward, as
+the KL step always has); without it R = 0."""
 from __future__ import annotations
 
 import argparse
@@ -220,6 +229,92 @@ def kl_step(G, N, pairs):
     return res
 
 
+def pref_kernels(rows, pairs, launches):
+    from unimm_amd import lib as L
+    g = torch.Generator().manual_seed(0)
+    out = {}
+    for name, B, groups in (("64_sequences_8_groups", 64, 8), ("800_sequences_8_groups_of_100", 800, 8)):
+        rownll = (torch.rand(rows, generator=g) * 6).cuda()
+        ref = (torch.rand(rows, generator=g) * 6).cuda()
+        row_seq = (torch.arange(rows) % B).to(torch.int32)[torch.randperm(rows, generator=g)].cuda()
+        seq_group = (torch.arange(B) % groups).to(torch.int32).cuda()
+        weight = torch.softmax(torch.randn(groups, B // groups, generator=g), 1).t().reshape(-1).contiguous().cuda()
+        adv, score, prob = torch.empty(rows, device="cuda"), torch.empty(B, device="cuda"), torch.empty(B, device="cuda")
+        gl, ai = torch.empty(groups, device="cuda"), torch.empty(1, device="cuda")
+        ws = torch.empty(L.PREF_WS_ITEM_BYTES * (B + groups), dtype=torch.uint8, device="cuda")
+        fn = lambda: L.seq_pref(rownll, ref, row_seq, rows, seq_group, weight, groups, 0.1, False, adv, score, prob, gl, ai,
+                                workspace=ws)
+        t = [event_ms(fn, launches) for _ in range(pairs)]
+        m = statistics.median(t)
+        print(f"unimm_seq_pref, {rows} rows, {name}: {m * 1e3:.1f} us per call (three launches; min {min(t) * 1e3:.1f}, max "
+              f"{max(t) * 1e3:.1f} over {pairs} repeats of {launches} calls)")
+        out[name] = dict(rows=rows, sequences=B, groups=groups, us=round(m * 1e3, 1), min_us=round(min(t) * 1e3, 1),
+                         max_us=round(max(t) * 1e3, 1))
+    return out
+
+
+def pref_step(G, N, pairs, with_reference, share):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_generate import dialogs
+    from oracle import vilbert_ref as RF
+    from unimm_amd import SharedContext, VisualDialogEncoder, policy
+    from unimm_amd.optim import FusedAdamW, default_language_weights, reference_param_groups
+    enc = VisualDialogEncoder(CFG_PATH)
+    enc.bert_pretrained.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    enc = enc.cuda()
+    ref = policy.frozen_reference(enc)
+    eng = enc.bert_pretrained.engine
+    groups = reference_param_groups(enc, lr=1e-5, image_lr=1e-5, language_weights=default_language_weights(enc))
+    opt = FusedAdamW(groups, eng, lr=1e-5)
+    d, c = dialogs(G, seed=3)
+    T, R, C = d["input_ids"].shape[1], d["image_feat"].shape[1], eng.cfg.v_target_size
+    rng = np.random.default_rng(1)
+    lengths = torch.from_numpy(rng.integers(2, 16, (G, N)))                       # 1 .. 14 tokens and the [SEP]
+    tokens = torch.from_numpy(rng.integers(1000, 20000, (G, N, 15)))
+    sb = policy.candidate_training_batch(d["input_ids"], d["token_type_ids"], d["position_ids"], c, tokens, lengths, T)
+    K = sb.input_ids.shape[0]
+    w = policy.relevance_targets(torch.from_numpy(rng.integers(0, 5, (G, N)) * 0.5))
+    tg = policy.PreferenceTargets(sb.image_index, w.reshape(-1)[sb.kept])
+    label = torch.zeros((K, R), dtype=torch.int64)
+    label[:, 0] = 1
+    kw = dict(token_type_ids=sb.token_type_ids, token_position_ids=sb.position_ids, attention_mask=sb.attention_mask,
+              masked_lm_labels=sb.masked_lm_labels, next_sentence_label=torch.zeros(K, dtype=torch.int64),
+              image_attention_mask=d["image_attention_mask"][sb.image_index.to(d["image_attention_mask"].device)],
+              image_label=label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+              **(dict(shared_context=SharedContext(sb.image_index, 64)) if share else {}))
+    forms = dict(
+        kl=dict(lm_advantage=policy.spread(torch.from_numpy(rng.standard_normal((G, N))), sb),
+                lm_objective=policy.PolicyObjective(entropy_coef=0.01, kl_coef=0.05), lm_reference=ref),
+        preference=dict(lm_preference=tg, lm_objective=policy.PreferenceObjective(), lm_reference=ref if with_reference else None))
+    enc.train()
+
+    def wall_ms(form, n=3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = enc.forward_backward(sb.input_ids, d["image_feat"], d["image_loc"], (1.0, 0.0, 0.0), **kw, **forms[form])[1]
+            opt.step()
+            opt.zero_grad()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n, float(loss)
+
+    for form in forms:                                       # warm every shape of both forms up
+        wall_ms(form, 2)
+    t = {form: [] for form in forms}
+    loss = {}
+    for _ in range(pairs):
+        for form in forms:
+            ms, loss[form] = wall_ms(form)
+            t[form].append(ms)
+    med = {form: statistics.median(v) for form, v in t.items()}
+    res = dict(G=G, N=N, sequences=K, rows=int(sb.copy_rows.sum()), shared=bool(share), reference=bool(with_reference), pairs=pairs,
+               kl_ms=round(med["kl"], 3), preference_ms=round(med["preference"], 3), ratio=round(med["preference"] / med["kl"], 4),
+               pair_ratios=[round(a / b, 3) for a, b in zip(t["preference"], t["kl"])],
+               kl_spread=round((max(t["kl"]) - min(t["kl"])) / med["kl"], 4), loss=loss)
+    print(f"preference step beside the KL step (G = {G}, N = {N}): {res}")
+    return res
+
+
 def step(G, N, baseline="mean", rollouts=("separate",), pairs=7):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from bench_generate import dialogs
@@ -396,10 +491,18 @@ def main():
     ap.add_argument("--rollout", choices=("separate", "fused"), nargs="+", default=["separate"],
                     help="how the greedy baseline is decoded; both values: alternating pairs in one process")
     ap.add_argument("--kl", action="store_true", help="time the KL-regularised row kernels and the step with a frozen reference")
+    ap.add_argument("--preference", action="store_true", help="time unimm_seq_pref and the preference train step beside the KL step")
+    ap.add_argument("--reference", action="store_true", help="--preference: the step compares against a frozen reference")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
     torch.set_num_threads(min(16, torch.get_num_threads()))
+    if a.preference:
+        result = dict(rows=a.rows, pref_kernels=pref_kernels(a.rows, a.pairs, a.launches))
+        if not a.no_step:
+            result["pref_step"] = pref_step(a.G, a.N, a.pairs, a.reference, a.shared)
+        print(json.dumps(result))
+        return
     if a.kl:
         result = dict(rows=a.rows, kl_kernels=kl_kernels(a.rows, a.pairs, a.launches))
         if not a.no_step:

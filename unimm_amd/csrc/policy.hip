@@ -7,6 +7,8 @@
 // The KL-regularised pair (unimm_pg_kl_loss_*) streams a frozen reference's row beside the policy's in the same pass: a lane
 // also keeps u = sum e^(z-m) (z - zr) and the reference row's own (mr, sr), and KL(p || pr) = u / s - lse + ref_lse.  Both
 // pairs are instantiations of one template, so the policy row's m, s, t are computed by the same source either way.
+// The listwise preference objective over whole candidate answers (unimm_seq_pref, at the end of this file) reads no logits: it
+// turns the likelihood kernel's per-row -log p_y into one coefficient per row for the backward kernel above.
 #include "common.h"
 
 namespace {
@@ -372,6 +374,207 @@ extern "C" int unimm_pg_kl_loss_bwd(const float* logits, const int32_t* labels, 
   hipLaunchKernelGGL(pg_loss_bwd_kernel<true>, dim3(n), dim3(256), 0, (hipStream_t)stream, logits, labels, pos, adv, blogp, n_adv,
                      mode, clip_eps, beta, lse, ent, g, inv_denom, (bf16_t*)dlogits, V, ld, ldd, n_dev, inv_dev, ref_logits, ld_ref,
                      kl_coef, kl, ref_lse);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Listwise preference over the likelihoods of whole candidate answers (unimm_seq_pref, include/unimm_hip.h): per-row -log p_y
+// -> per-sequence scores -> a softmax over each group's sequences against the target weights -> one coefficient per row, which
+// unimm_pg_loss_bwd (LOGP mode) turns into the logits' gradient.  A few thousand floats: everything is fp64 and every sum a
+// serial chain in index order, so the result does not depend on the launch.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the workspace: fp64 D [B] | fp32 c [B] | int32 L [B] | int32 alive [groups]
+struct PrefWs {
+  double* D;
+  float* c;
+  int32_t* L;
+  int32_t* alive;
+};
+__device__ __forceinline__ PrefWs pref_ws(void* ws, int B) {
+  char* p = static_cast<char*>(ws);
+  return PrefWs{reinterpret_cast<double*>(p), reinterpret_cast<float*>(p + 8 * (size_t)B),
+                reinterpret_cast<int32_t*>(p + 12 * (size_t)B), reinterpret_cast<int32_t*>(p + 16 * (size_t)B)};
+}
+// the rows of this launch: n is a capacity when the device word is given
+__device__ __forceinline__ int pref_rows(int n, const int32_t* __restrict__ n_dev) {
+  const int m = n_dev != nullptr ? min(n, n_dev[0]) : n;
+  return m > 0 ? m : 0;
+}
+
+// One wave per sequence j.  The wave walks the rows 64 at a time; the lanes whose row belongs to j vote, and the rows voted
+// for are added one after the other in ascending index (every lane does the same additions: the loads are wave-uniform).
+__global__ __launch_bounds__(256) void pref_seq_kernel(const float* __restrict__ rownll, const float* __restrict__ ref_rownll,
+                                                       const int32_t* __restrict__ row_seq, int n,
+                                                       const int32_t* __restrict__ n_dev, int B, int lnorm,
+                                                       float* __restrict__ seq_score, float* __restrict__ seq_prob, void* wsp) {
+  const int rows = pref_rows(n, n_dev);
+  if (rows == 0) return;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= B) return;
+  const int lane = threadIdx.x & 63;
+  double S = 0.0, R = 0.0;
+  int cnt = 0;
+  for (int base = 0; base < rows; base += 64) {
+    const int r = base + lane;
+    unsigned long long votes = __ballot(r < rows && row_seq[r] == j);
+    while (votes != 0ull) {
+      const int rr = base + __ffsll(votes) - 1;
+      votes &= votes - 1ull;
+      S -= (double)rownll[rr];
+      if (ref_rownll != nullptr) R -= (double)ref_rownll[rr];
+      ++cnt;
+    }
+  }
+  if (lane == 0) {
+    const PrefWs ws = pref_ws(wsp, B);
+    const double D = cnt > 0 ? (S - R) / (lnorm ? (double)cnt : 1.0) : (double)NAN;
+    ws.D[j] = D;
+    ws.L[j] = cnt;
+    ws.c[j] = 0.f;                       // until its group says otherwise (pref_group_kernel)
+    seq_score[j] = (float)D;
+    seq_prob[j] = 0.f;
+  }
+}
+
+// One workgroup per group g.  Its members -- the sequences of g that have rows -- are collected in ascending sequence index
+// (a vote per wave, the waves' counts in LDS), at most UNIMM_PREF_MAX_MEMBERS of them; z, w and the terms of the sums live in
+// LDS and lane 0 adds them in member order.
+__global__ __launch_bounds__(256) void pref_group_kernel(const int32_t* __restrict__ seq_group, const float* __restrict__ seq_weight,
+                                                         int n, const int32_t* __restrict__ n_dev, int B, float beta_f, int lnorm,
+                                                         float* __restrict__ seq_prob, float* __restrict__ group_loss, void* wsp) {
+  constexpr int MAXM = UNIMM_PREF_MAX_MEMBERS;
+  __shared__ int mem[MAXM];
+  __shared__ double zs[MAXM], wd[MAXM], tm[MAXM];
+  __shared__ double bc[2];                // broadcast: log-sum-exp, W
+  __shared__ int wcnt[4];
+  __shared__ int bad;
+  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (pref_rows(n, n_dev) == 0) {
+    if (tid == 0) group_loss[g] = 0.f;
+    return;
+  }
+  const PrefWs ws = pref_ws(wsp, B);
+  if (tid == 0) bad = 0;
+  int count = 0;                          // members so far (the same in every lane)
+  for (int base = 0; base < B; base += 256) {
+    const int j = base + tid;
+    const bool hit = j < B && seq_group[j] == g && ws.L[j] > 0;
+    const unsigned long long votes = __ballot(hit);
+    if (lane == 0) wcnt[wave] = __popcll(votes);
+    __syncthreads();
+    int slot = count + __popcll(votes & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) slot += wcnt[w];
+    if (hit && slot < MAXM) mem[slot] = j;
+    count += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    __syncthreads();
+  }
+  const int M = count;
+  if (M == 0) {                           // nobody to compare: not alive, loss 0
+    if (tid == 0) { group_loss[g] = 0.f; ws.alive[g] = 0; }
+    return;
+  }
+  double w = 0.0, Lp = 1.0;
+  int j = -1;
+  if (M <= MAXM && tid < M) {
+    j = mem[tid];
+    const float wf = seq_weight[j];
+    if (!(wf >= 0.f && wf < INFINITY)) bad = 1;
+    w = (double)wf;
+    Lp = lnorm ? (double)ws.L[j] : 1.0;
+    zs[tid] = (double)beta_f * ws.D[j];
+    wd[tid] = w;
+  }
+  __syncthreads();
+  if (M > MAXM || bad != 0) {             // more members than a slate holds, or a weight that is no weight: NaN, not alive
+    for (int k = tid; k < B; k += 256)
+      if (seq_group[k] == g && ws.L[k] > 0) seq_prob[k] = NAN;
+    if (tid == 0) { group_loss[g] = NAN; ws.alive[g] = 0; }
+    return;
+  }
+  double m = -INFINITY;
+  for (int k = 0; k < M; ++k) m = fmax(m, zs[k]);
+  if (tid < M) tm[tid] = exp(zs[tid] - m);
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0, W = 0.0;
+    for (int k = 0; k < M; ++k) s += tm[k];
+    for (int k = 0; k < M; ++k) W += wd[k];
+    bc[0] = m + log(s);
+    bc[1] = W;
+  }
+  __syncthreads();
+  const double lse = bc[0], W = bc[1];
+  const bool alive = W > 0.0;
+  if (tid < M) {
+    const double logP = zs[tid] - lse;
+    const double P = exp(logP);
+    tm[tid] = w * logP;
+    seq_prob[j] = (float)P;
+    ws.c[j] = alive ? (float)((double)beta_f * (w - W * P) / Lp) : 0.f;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double loss = 0.0;
+    for (int k = 0; k < M; ++k) loss += tm[k];
+    group_loss[g] = alive ? (float)(-loss) : 0.f;
+    ws.alive[g] = alive ? 1 : 0;
+  }
+}
+
+// One lane per row: its sequence's coefficient.  Workgroup 0 also counts the groups that are alive (integers: any order).
+__global__ __launch_bounds__(256) void pref_rows_kernel(const int32_t* __restrict__ row_seq, int n, const int32_t* __restrict__ n_dev,
+                                                        int B, int groups, float* __restrict__ adv, float* __restrict__ alive_inv,
+                                                        void* wsp) {
+  __shared__ int red[4];
+  const int rows = pref_rows(n, n_dev);
+  const PrefWs ws = pref_ws(wsp, B);
+  if (blockIdx.x == 0) {
+    if (rows == 0) {
+      if (threadIdx.x == 0) alive_inv[0] = NAN;
+    } else {
+      int cnt = 0;
+      for (int g = threadIdx.x; g < groups; g += 256) cnt += ws.alive[g];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const int alive = red[0] + red[1] + red[2] + red[3];
+        alive_inv[0] = alive > 0 ? (float)(1.0 / (double)alive) : NAN;
+      }
+    }
+  }
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r < rows) {
+    const int s = row_seq[r];
+    adv[r] = (s >= 0 && s < B) ? ws.c[s] : 0.f;
+  }
+}
+
+}  // namespace
+
+extern "C" int unimm_seq_pref(const unimm_seq_pref_args* a, void* stream) {
+  if (!a || !a->seq_group || !a->seq_weight || !a->seq_score || !a->seq_prob || !a->group_loss || !a->alive_inv || !a->workspace)
+    return UNIMM_E_ARG;
+  if (a->n > 0 && (!a->rownll || !a->row_seq || !a->adv)) return UNIMM_E_ARG;      // (arrays of n elements: not looked at when n == 0)
+  if (!(a->beta > 0.f) || !(a->beta < INFINITY) || a->groups < 1 || a->B < 1 || a->n < 0) return UNIMM_E_ARG;
+  if (a->workspace_bytes < (int64_t)UNIMM_PREF_WS_ITEM_BYTES * ((int64_t)a->B + (int64_t)a->groups)) return UNIMM_E_ARG;
+  if (reinterpret_cast<uintptr_t>(a->workspace) & 15u) return UNIMM_E_ALIGN;
+  const hipStream_t st = (hipStream_t)stream;
+  const int lnorm = a->length_normalize != 0;
+  if (a->n > 0) {
+    hipLaunchKernelGGL(pref_seq_kernel, dim3((a->B + 3) / 4), dim3(256), 0, st, a->rownll, a->ref_rownll, a->row_seq, a->n, a->n_dev,
+                       a->B, lnorm, a->seq_score, a->seq_prob, a->workspace);
+    UNIMM_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(pref_group_kernel, dim3(a->groups), dim3(256), 0, st, a->seq_group, a->seq_weight, a->n, a->n_dev, a->B, a->beta,
+                     lnorm, a->seq_prob, a->group_loss, a->workspace);
+  UNIMM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pref_rows_kernel, dim3(a->n > 0 ? (a->n + 255) / 256 : 1), dim3(256), 0, st, a->row_seq, a->n, a->n_dev, a->B,
+                     a->groups, a->adv, a->alive_inv, a->workspace);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }

@@ -198,6 +198,8 @@ class StepGraphs:
             return False
         if inp.get("lm_advantage") is not None:      # the policy-gradient step (unimm_amd/policy.py) has no replayed form: its
             return False                             # advantages are not among the staged inputs; the eager step runs
+        if inp.get("lm_preference") is not None:     # ... nor has the preference step: its targets are not staged either
+            return False
         for k in _TENSOR_KEYS:
             v = inp.get(k)
             if v is None:

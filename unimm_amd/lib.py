@@ -85,6 +85,7 @@ SIGNATURES = {
     "unimm_pg_kl_loss_fwd": (_INT, [VP] * 5 + [I32, I32, F32, F32] + [VP] * 4 + [I32] * 3 + [VP, VP, I32, F32, VP, VP, VP]),
     "unimm_pg_kl_loss_bwd": (_INT, [VP] * 5 + [I32, I32, F32, F32, VP, VP, VP, F32, VP] + [I32] * 4 +
                              [VP, VP, VP, I32, F32, VP, VP, VP]),
+    "unimm_seq_pref": (_INT, [VP, VP]),
     "unimm_kl_loss_fwd": (_INT, [VP] * 5 + [I32] * 3 + [VP]),
     "unimm_kl_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP]),
     "unimm_mse_loss_fwd": (_INT, [VP] * 4 + [I32] * 3 + [VP]),
@@ -864,6 +865,40 @@ def pg_kl_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, e
           _ptr(inv_dev), _ptr(ref_logits), ref_logits.stride(0) if ref_logits is not None else 0, kl_coef, _ptr(kl), _ptr(ref_lse))
 
 
+PREF_MAX_MEMBERS, PREF_WS_ITEM_BYTES = 128, 16
+
+
+class SeqPrefArgs(C.Structure):
+    _fields_ = [("rownll", C.c_void_p), ("ref_rownll", C.c_void_p), ("row_seq", C.c_void_p), ("n_dev", C.c_void_p),
+                ("seq_group", C.c_void_p), ("seq_weight", C.c_void_p), ("adv", C.c_void_p), ("seq_score", C.c_void_p),
+                ("seq_prob", C.c_void_p), ("group_loss", C.c_void_p), ("alive_inv", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("n", C.c_int32), ("B", C.c_int32), ("groups", C.c_int32),
+                ("length_normalize", C.c_int32), ("beta", C.c_float)]
+
+
+def seq_pref(rownll, ref_rownll, row_seq, n, seq_group, seq_weight, groups, beta, length_normalize, adv, seq_score, seq_prob,
+             group_loss, alive_inv, n_dev=None, workspace=None):
+    """Listwise preference over candidate sequences (include/unimm_hip.h: unimm_seq_pref).  rownll / ref_rownll (or None) / adv:
+    fp32 [>= n]; row_seq int32 [>= n]; seq_group int32 [B], seq_weight fp32 [B]; seq_score / seq_prob fp32 [B]; group_loss fp32
+    [groups]; alive_inv fp32 [1].  workspace: uint8, >= PREF_WS_ITEM_BYTES * (B + groups) bytes (None: allocated here)."""
+    _dev(rownll, ref_rownll, row_seq, seq_group, seq_weight, adv, seq_score, seq_prob, group_loss, alive_inv, n_dev, workspace)
+    B = seq_group.numel()
+    if seq_weight.numel() != B or seq_score.numel() < B or seq_prob.numel() < B or group_loss.numel() < groups:
+        raise UnimmHipError(f"seq_pref: {B} sequences in {groups} groups, but seq_weight / seq_score / seq_prob / group_loss hold "
+                            f"{seq_weight.numel()} / {seq_score.numel()} / {seq_prob.numel()} / {group_loss.numel()} elements")
+    if min(rownll.numel(), row_seq.numel(), adv.numel()) < n or (ref_rownll is not None and ref_rownll.numel() < n):
+        raise UnimmHipError(f"seq_pref: rownll / ref_rownll / row_seq / adv hold fewer than n = {n} rows")
+    if workspace is None:
+        workspace = torch.empty(PREF_WS_ITEM_BYTES * (B + max(int(groups), 0)), dtype=torch.uint8, device=seq_group.device)
+    a = SeqPrefArgs()
+    a.rownll, a.ref_rownll, a.row_seq, a.n_dev = _ptr(rownll), _ptr(ref_rownll), _ptr(row_seq), _ptr(n_dev)
+    a.seq_group, a.seq_weight, a.adv, a.seq_score, a.seq_prob = _ptr(seq_group), _ptr(seq_weight), _ptr(adv), _ptr(seq_score), _ptr(seq_prob)
+    a.group_loss, a.alive_inv, a.workspace, a.workspace_bytes = _ptr(group_loss), _ptr(alive_inv), _ptr(workspace), workspace.numel()
+    a.n, a.B, a.groups, a.length_normalize, a.beta = int(n), B, int(groups), 1 if length_normalize else 0, float(beta)
+    _call("unimm_seq_pref", C.byref(a))
+    workspace.record_stream(torch.cuda.current_stream())
+
+
 def kl_loss_fwd(pred, target, label, rowloss, lse, rows, Cn):
     _dev(pred, target, label, rowloss, lse)
     _call("unimm_kl_loss_fwd", _ptr(pred), _ptr(target), _ptr(label), _ptr(rowloss), _ptr(lse), rows, Cn, pred.stride(0))
@@ -1223,4 +1258,5 @@ STRUCTS = {
     "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
     "unimm_adamw_args": AdamWArgs, "unimm_clip_state": ClipState, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
     "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
+    "unimm_seq_pref_args": SeqPrefArgs,
 }

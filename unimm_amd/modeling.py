@@ -15,7 +15,7 @@ from torch import nn
 from . import params as PM
 from .config import BertConfig
 from .engine import Engine
-from .policy import check_policy_inputs, check_reference
+from .policy import check_policy_inputs, check_preference_inputs, check_reference
 
 logger = logging.getLogger(__name__)
 
@@ -186,7 +186,7 @@ class BertForMultiModalPreTraining(nn.Module):
                 masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None,
                 output_all_attention_masks=False, nsp_weight=None, lm_weight=None,
                 _want_lm_scores=True, _want_pred_v=True, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
-                lm_objective=None, lm_reference=None):
+                lm_objective=None, lm_reference=None, lm_preference=None, shared_context=None):
         """Same contract as models/vilbert_dialog.py:1519-1626.  `sep_indices` / `sep_len` are accepted and
         ignored exactly as the reference's embeddings do (:326-356).  Train branch (labels, NSP label and
         image target all given) -> (lm_loss[1], img_loss[1], nsp_loss[1], seq_out_t, pred_t, nsp[B,2]);
@@ -199,20 +199,55 @@ class BertForMultiModalPreTraining(nn.Module):
         `lm_behaviour_logp` and `lm_objective`: unimm_amd/policy.py) makes lm_loss the policy-gradient objective on the
         labelled rows instead of the weighted likelihood; bf16 engine, train branch.  `lm_reference` (a frozen model of either
         class, `policy.frozen_reference`) is what `PolicyObjective(kl_coef > 0)` measures KL(p || p_ref) against: its engine runs
-        an inference forward on this call's inputs first; with kl_coef == 0 it is ignored."""
+        an inference forward on this call's inputs first; with kl_coef == 0 it is ignored.  `lm_preference`
+        (`policy.PreferenceTargets`: a group id and a target weight per sequence, with `lm_objective=policy.PreferenceObjective`
+        and optionally `lm_reference`) makes lm_loss the listwise preference objective over the candidate answers of each group
+        instead; bf16 engine, train branch; the step's per-sequence results are in `engine.last_lm_preference`.  With
+        `shared_context` (and `lm_preference`; the conditions of `forward_backward(shared_context=)`) that loss is computed on the
+        shared-context schedule, as a value only -- no autograd graph: train with `forward_backward` -- and the call returns
+        (lm_loss, 0, 0, None, None, None)."""
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
-        lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                           self.compute_dtype, train_branch, lm_reference=lm_reference)
+        if shared_context is not None:
+            if lm_preference is None:
+                raise ValueError("forward(shared_context=...) evaluates the preference loss on the shared schedule: pass "
+                                 "lm_preference with it (sequence_log_likelihood and forward_backward take shared_context otherwise)")
+            if masked_lm_labels is None:
+                raise ValueError("forward(shared_context=...) needs masked_lm_labels (the copy rows)")
+            train_branch = True
+        if lm_preference is not None:
+            lm_objective = check_preference_inputs(input_ids.shape, lm_preference, lm_objective, lm_advantage, lm_weight,
+                                                   lm_behaviour_logp, self.compute_dtype, train_branch)
+        else:
+            lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
+                                               self.compute_dtype, train_branch, lm_reference=lm_reference)
         lm_reference = check_reference(self, lm_reference, lm_objective)
+        if shared_context is not None:
+            from .scoring import check_shared_training
+            check_shared_training(self.config, self.compute_dtype, (1.0, 0.0, 0.0), attention_mask, shared_context, input_ids.shape[1],
+                                  image_feat.shape[1])
         eng = self._engine
         dev = self._device()
         eng.ensure(dev)
+        if shared_context is not None:
+            inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
+                       position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
+                       masked_lm_labels=masked_lm_labels, image_index=image_index, lm_objective=lm_objective,
+                       lm_reference=lm_reference, lm_preference=lm_preference)
+            eng.stage_host_inputs(inp, pack=())
+            if self.training:
+                eng.step += 1
+            with torch.no_grad():
+                lm_loss = eng.forward_backward_shared(inp, shared_context, None, self.training)
+                eng.last_seq_t = None
+                zero = torch.zeros(1, dtype=torch.float32, device=dev)
+            return lm_loss, zero, zero.clone(), None, None, None
         inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
                    position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
                    lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
+                   lm_preference=lm_preference)
         eng.stage_host_inputs(inp)             # the reference's callers pass CPU tensors (train.py:113-161): pinned ring + copy stream
         B, T = input_ids.shape
         H, V = self.config.hidden_size, self.config.vocab_size
@@ -250,7 +285,7 @@ class BertForMultiModalPreTraining(nn.Module):
                          position_ids=None, attention_mask=None, image_attention_mask=None, co_attention_mask=None,
                          masked_lm_labels=None, image_label=None, image_target=None, next_sentence_label=None, nsp_weight=None,
                          lm_weight=None, image_index=None, plan_header=None, lm_advantage=None, lm_behaviour_logp=None,
-                         lm_objective=None, shared_context=None, lm_reference=None):
+                         lm_objective=None, shared_context=None, lm_reference=None, lm_preference=None):
         """The training step's forward AND backward in one call (an extension; the reference writes
         `loss = c_lm * lm.mean() + c_nsp * nsp.mean() + c_img * img.mean(); loss.backward()`, train.py:164-168, :315).
         loss_weights = (c_lm, c_nsp, c_img).  With the weights known up front the backward does not wait for the host to see
@@ -268,9 +303,14 @@ class BertForMultiModalPreTraining(nn.Module):
         term is trained: loss_weights must be (c, 0, 0), attention_mask a generative-mode DialogMaskSpec, the engine bf16 with
         its connection layers and no frozen layers (ValueError otherwise).  The image and NSP losses come back as zeros and
         nsp_logits as None; when a sequence's context does not match its group's, the loss is NaN and the call adds nothing to
-        the gradients.  Always eager."""
-        lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                           self.compute_dtype, lm_reference=lm_reference)
+        the gradients.  Always eager.
+        lm_preference / lm_objective=PreferenceObjective / lm_reference: as in `forward`, on either schedule (always eager)."""
+        if lm_preference is not None:
+            lm_objective = check_preference_inputs(input_ids.shape, lm_preference, lm_objective, lm_advantage, lm_weight,
+                                                   lm_behaviour_logp, self.compute_dtype)
+        else:
+            lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
+                                               self.compute_dtype, lm_reference=lm_reference)
         lm_reference = check_reference(self, lm_reference, lm_objective)
         if shared_context is not None:
             from .scoring import check_shared_training
@@ -287,7 +327,8 @@ class BertForMultiModalPreTraining(nn.Module):
             inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
                        position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
                        masked_lm_labels=masked_lm_labels, lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
+                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
+                       lm_preference=lm_preference)
             eng.stage_host_inputs(inp, pack=())      # (the [B, R] image key mask stays a tensor: the pass indexes it by group)
             if self.training:
                 eng.step += 1
@@ -302,7 +343,8 @@ class BertForMultiModalPreTraining(nn.Module):
                    co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
                    image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
                    lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference)
+                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
+                   lm_preference=lm_preference)
         eng.stage_host_inputs(inp)
         if plan_header is not None:
             inp["_plan_header"] = plan_header
@@ -412,7 +454,7 @@ class VisualDialogEncoder(nn.Module):
                 head_mask=None, random_round_indices=None, output_nsp_scores=False, output_lm_scores=False,
                 image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
                 nsp_weight=None, lm_weight=None, image_index=None, lm_advantage=None, lm_behaviour_logp=None,
-                lm_objective=None, lm_reference=None):
+                lm_objective=None, lm_reference=None, lm_preference=None, shared_context=None):
         masked_lm_loss = masked_img_loss = nsp_loss = None
         kw = dict(sep_indices=sep_indices, sep_len=sep_len, token_type_ids=token_type_ids,
                   position_ids=token_position_ids, attention_mask=attention_mask, masked_lm_labels=masked_lm_labels,
@@ -420,8 +462,8 @@ class VisualDialogEncoder(nn.Module):
                   co_attention_mask=co_attention_mask, image_label=image_label, image_target=image_target,
                   nsp_weight=nsp_weight, lm_weight=lm_weight, _want_lm_scores=output_lm_scores, image_index=image_index,
                   lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective,
-                  lm_reference=lm_reference)
-        if next_sentence_label is not None and masked_lm_labels is not None and image_target is not None:
+                  lm_reference=lm_reference, lm_preference=lm_preference, shared_context=shared_context)
+        if shared_context is not None or (next_sentence_label is not None and masked_lm_labels is not None and image_target is not None):
             masked_lm_loss, masked_img_loss, nsp_loss, _, prediction_scores_t, seq_relationship_score = \
                 self.bert_pretrained(input_ids, image_feat, image_loc, **kw)
         else:
@@ -449,7 +491,7 @@ class VisualDialogEncoder(nn.Module):
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
                          image_attention_mask=None, co_attention_mask=None, image_label=None, image_target=None,
                          nsp_weight=None, lm_weight=None, image_index=None, plan_header=None, lm_advantage=None,
-                         lm_behaviour_logp=None, lm_objective=None, shared_context=None, lm_reference=None):
+                         lm_behaviour_logp=None, lm_objective=None, shared_context=None, lm_reference=None, lm_preference=None):
         """forward + `(c_lm * lm + c_nsp * nsp + c_img * img).backward()` in one call, loss_weights = (c_lm, c_nsp, c_img)
         (BertForMultiModalPreTraining.forward_backward, shared_context included).  -> (loss, lm_loss, img_loss, nsp_loss, nsp_logits)."""
         return self.bert_pretrained.forward_backward(
@@ -458,4 +500,4 @@ class VisualDialogEncoder(nn.Module):
             co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label, image_target=image_target,
             next_sentence_label=next_sentence_label, nsp_weight=nsp_weight, lm_weight=lm_weight, image_index=image_index,
             plan_header=plan_header, lm_advantage=lm_advantage, lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective,
-            shared_context=shared_context, lm_reference=lm_reference)
+            shared_context=shared_context, lm_reference=lm_reference, lm_preference=lm_preference)

@@ -23,7 +23,16 @@ The KL leash (unimm_pg_kl_loss_fwd / _bwd): `lm_reference=frozen_reference(model
 `PolicyObjective(kl_coef=c)`.  Every step the reference's engine first runs an inference forward on the step's own inputs and
 hands over its fp32 logits for exactly the step's decoded rows; the row kernels stream them beside the policy's and add the
 EXACT full-vocabulary c KL(p || p_ref) per row and its gradient (not the sampled estimate log p_y - log p_ref,y).  Nothing
-of the reference changes; `engine.last_lm_kl` reports the mean KL of the trained rows beside `engine.last_lm_entropy`."""
+of the reference changes; `engine.last_lm_kl` reports the mean KL of the trained rows beside `engine.last_lm_entropy`.
+
+Preference training (unimm_seq_pref): instead of a reward on answers the model sampled, GIVEN candidate answers with target
+weights -- a chosen and a rejected answer, or the 100 options of a round with their dense relevance annotations.
+`candidate_training_batch` lays the candidates out as `sampled_training_batch` lays out samples, `lm_preference=
+PreferenceTargets(group, weight)` names each sequence's dialog and target weight, and `lm_objective=PreferenceObjective(beta,
+length_normalize)` makes lm_loss, per dialog, the cross-entropy between the targets and the softmax over the dialog's candidates
+of beta (log pi(y) - log pi_ref(y)) (divided by the answer's length with length_normalize): DPO for two candidates and a one-hot
+target (`pair_targets`), the listwise ListNet top-1 form for `relevance_targets`, on exactly the scores `generative_evaluate`
+ranks by.  `lm_reference` is optional (without one log pi_ref = 0).  `trainer.preference_step` is the loop body."""
 from __future__ import annotations
 
 import copy
@@ -58,6 +67,127 @@ class PolicyObjective:
             raise ValueError(f"PolicyObjective: kl_coef must be finite and >= 0, got {self.kl_coef}")
 
 
+@dataclass(frozen=True)
+class PreferenceObjective:
+    """beta: the temperature of the comparison, z = beta (log pi(y) - log pi_ref(y)); length_normalize: divide a candidate's
+    score by its number of decoded rows (the mean val_avg_lm.py ranks by) instead of taking the sum (val_lm.py)."""
+    beta: float = 0.1
+    length_normalize: bool = False
+
+    def __post_init__(self):
+        b = float(self.beta)
+        if not (math.isfinite(b) and b > 0.0):
+            raise ValueError(f"PreferenceObjective: beta must be positive and finite, got {self.beta}")
+
+
+PREF_MAX_MEMBERS = 128        # include/unimm_hip.h: UNIMM_PREF_MAX_MEMBERS
+
+
+class PreferenceTargets:
+    """One group id (the sequence's dialog, an integer >= 0) and one target weight >= 0 per sequence of the step; host data.
+    A group whose weights sum to 0 takes no part in the step."""
+
+    def __init__(self, group, weight):
+        g = np.asarray(group.detach().cpu() if torch.is_tensor(group) else group)
+        w = np.asarray(weight.detach().cpu() if torch.is_tensor(weight) else weight)
+        if g.ndim != 1 or w.ndim != 1 or (g.size and not np.issubdtype(g.dtype, np.integer)):
+            raise ValueError(f"PreferenceTargets: group must be a 1-D integer array and weight a 1-D array (one entry per sequence), "
+                             f"got shapes {g.shape} / {w.shape}, group dtype {g.dtype}")
+        self.group = g.astype(np.int64)
+        self.weight = w.astype(np.float32)
+
+    @property
+    def groups(self):
+        """number of group slots: the largest id + 1"""
+        return int(self.group.max()) + 1 if self.group.size else 0
+
+    def __len__(self):
+        return int(self.group.shape[0])
+
+
+def relevance_targets(gt_relevance, temperature=1.0):
+    """Dense relevance annotations [G, N] -> the row-wise softmax(relevance / temperature), fp32 [G, N] (host)."""
+    r = torch.as_tensor(gt_relevance).detach().to("cpu", torch.float32)
+    if r.dim() != 2:
+        raise ValueError(f"relevance_targets: gt_relevance must be [G, N], got {tuple(r.shape)}")
+    if not (math.isfinite(float(temperature)) and float(temperature) > 0.0):
+        raise ValueError(f"relevance_targets: temperature must be positive and finite, got {temperature}")
+    return torch.softmax(r / float(temperature), dim=1)
+
+
+def pair_targets(chosen, N):
+    """chosen [G] (the index of the preferred candidate of each dialog) -> the one-hot rows, fp32 [G, N] (host)."""
+    c = torch.as_tensor(chosen).detach().to("cpu", torch.int64).reshape(-1)
+    N = int(N)
+    if N < 1 or (c.numel() and (int(c.min()) < 0 or int(c.max()) >= N)):
+        raise ValueError(f"pair_targets: every chosen index must lie in [0, N = {N})")
+    out = torch.zeros((c.shape[0], N), dtype=torch.float32)
+    out[torch.arange(c.shape[0]), c] = 1.0
+    return out
+
+
+def check_preference_inputs(shape, lm_preference, lm_objective, lm_advantage, lm_weight, lm_behaviour_logp, compute_dtype,
+                            train_branch=True):
+    """The refused combinations of the preference arguments of `forward` / `forward_backward` (ValueError, before anything
+    touches the device) -> the objective in force.  `check_reference` judges the reference."""
+    for name, t in (("lm_advantage", lm_advantage), ("lm_weight", lm_weight), ("lm_behaviour_logp", lm_behaviour_logp)):
+        if t is not None:
+            raise ValueError(f"lm_preference (the preference objective over whole answers) and {name} describe two objectives "
+                             "for the same rows: pass one of them")
+    if isinstance(lm_objective, PolicyObjective):
+        raise ValueError("lm_preference takes a policy.PreferenceObjective; a PolicyObjective weighs lm_advantage")
+    if not isinstance(lm_objective, PreferenceObjective):
+        got = "None" if lm_objective is None else type(lm_objective).__name__
+        raise ValueError(f"lm_preference needs lm_objective=policy.PreferenceObjective(...), got {got}")
+    if not isinstance(lm_preference, PreferenceTargets):
+        raise ValueError(f"lm_preference must be a policy.PreferenceTargets, got {type(lm_preference).__name__}")
+    if compute_dtype != "bf16":
+        raise ValueError(f"the preference objective runs on the bf16 engine only: build the model with compute_dtype='bf16' "
+                         f"(got {compute_dtype!r})")
+    b = float(lm_objective.beta)
+    if not (math.isfinite(b) and b > 0.0):
+        raise ValueError(f"PreferenceObjective: beta must be positive and finite, got {lm_objective.beta}")
+    B = int(shape[0])
+    g, w = lm_preference.group, lm_preference.weight
+    if g.shape[0] != B or w.shape[0] != B:
+        raise ValueError(f"lm_preference holds {g.shape[0]} group ids and {w.shape[0]} weights for {B} sequences: one of each per "
+                         "sequence")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("lm_preference: every target weight must be finite and >= 0")
+    if np.any(g < 0) or np.any(g >= 2 ** 31 - 1):
+        raise ValueError("lm_preference: every group id must be an integer >= 0")
+    if B and int(np.bincount(g).max()) > PREF_MAX_MEMBERS:
+        raise ValueError(f"lm_preference: a group has {int(np.bincount(g).max())} sequences, at most {PREF_MAX_MEMBERS} can be "
+                         "compared with each other")
+    if not train_branch:
+        raise ValueError("lm_preference replaces the LM loss of the train branch: pass masked_lm_labels, next_sentence_label and "
+                         "image_target with it (this call computes no loss and would ignore it)")
+    return lm_objective
+
+
+def preference_diagnostics(seq_score, targets):
+    """Two host-side figures of a preference step from its per-sequence scores D (`engine.last_lm_preference["seq_score"]`, NaN
+    for a sequence without rows) and its `PreferenceTargets`, each a mean over the groups that took part (target weights
+    summing to > 0 over the members that have rows): whether the best-scored member is the one with the group's largest weight
+    (the first such member on ties), and D of that member minus the mean D of the group's other members, weighted by their
+    target weights (plainly when those are all 0, as the rejected answer's is).  -> (accuracy, margin); NaN without a group."""
+    D = np.asarray(seq_score.detach().cpu() if torch.is_tensor(seq_score) else seq_score, dtype=np.float64).reshape(-1)
+    hit, margin = [], []
+    for g in np.unique(targets.group):
+        mem = [j for j in np.flatnonzero(targets.group == g) if not math.isnan(D[j])]
+        w = targets.weight[mem].astype(np.float64)
+        if not mem or not w.sum() > 0:
+            continue
+        top = int(np.argmax(w))
+        hit.append(1.0 if int(np.argmax(D[mem])) == top else 0.0)
+        others = [k for k in range(len(mem)) if k != top]
+        if others:
+            wo = w[others] if w[others].sum() > 0 else np.ones(len(others))
+            margin.append(D[mem[top]] - float((wo * D[mem][others]).sum() / wo.sum()))
+    mean = lambda v: float(np.mean(v)) if v else float("nan")
+    return mean(hit), mean(margin)
+
+
 def _pretraining_model(model):
     """a VisualDialogEncoder or a BertForMultiModalPreTraining -> the latter"""
     return model.bert_pretrained if hasattr(model, "bert_pretrained") else model
@@ -83,9 +213,11 @@ _REF_CONFIG_KEYS = ("vocab_size", "hidden_size", "v_hidden_size", "bi_hidden_siz
 
 def check_reference(model, lm_reference, obj):
     """The refused uses of `lm_reference` (ValueError, before anything touches the device) -> the reference's pre-training
-    model when the step's objective reads it (kl_coef > 0), else None.  model: the trained BertForMultiModalPreTraining."""
+    model when the step's objective reads it (kl_coef > 0, or a PreferenceObjective), else None.  model: the trained
+    BertForMultiModalPreTraining."""
+    pref = isinstance(obj, PreferenceObjective)
     if lm_reference is None:
-        if obj is not None and obj.kl_coef > 0:
+        if obj is not None and not pref and obj.kl_coef > 0:
             raise ValueError(f"PolicyObjective(kl_coef={obj.kl_coef}) penalises KL(p || p_ref): pass lm_reference "
                              "(policy.frozen_reference(model), taken before the fine-tune), or kl_coef=0")
         return None
@@ -106,7 +238,7 @@ def check_reference(model, lm_reference, obj):
         raise ValueError(f"lm_reference must run on the bf16 engine (compute_dtype='bf16'), got {ref.compute_dtype!r}")
     if ref._device() != model._device():
         raise ValueError(f"lm_reference is on {ref._device()}, the trained model on {model._device()}: move it with .to()")
-    return ref if obj.kl_coef > 0 else None
+    return ref if (pref or obj.kl_coef > 0) else None
 
 def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, compute_dtype, train_branch=True,
                         lm_reference=None):
@@ -196,6 +328,25 @@ def sampled_training_batch(input_ids, token_type_ids, position_ids, context_len,
     return SampledBatch(input_ids=T_(out_ids), token_type_ids=T_(out_tt), position_ids=T_(out_pp), masked_lm_labels=T_(labels),
                         attention_mask=DialogMaskSpec(np.ones(K), L, n_all), image_index=T_(flat // max(N, 1)),
                         copy_rows=T_(copy), kept=T_(flat), shape=(G, N))
+
+
+def candidate_training_batch(input_ids, token_type_ids, position_ids, context_len, answer_tokens, answer_lengths, T):
+    """`sampled_training_batch` for GIVEN candidates: answer_tokens [G, N, W] holds each candidate's tokens, then [SEP], zero-padded;
+    answer_lengths [G, N] counts the tokens and the [SEP], 0 = the candidate is absent (dropped, as a length-0 sample is) ->
+    the same SampledBatch.  Targets [G, N] reach the step's sequences as `PreferenceTargets(batch.image_index,
+    targets.reshape(-1)[batch.kept])`."""
+    from .generation import GeneratedAnswers
+    tok = torch.as_tensor(answer_tokens).detach().to("cpu", torch.int64)
+    length = torch.as_tensor(answer_lengths).detach().to("cpu", torch.int64)
+    if tok.dim() != 3 or tuple(length.shape) != tuple(tok.shape[:2]):
+        raise ValueError(f"candidate_training_batch: answer_tokens must be [G, N, W] and answer_lengths [G, N], got "
+                         f"{tuple(tok.shape)} / {tuple(length.shape)}")
+    if length.numel() and (int(length.min()) < 0 or int(length.max()) > tok.shape[2]):
+        raise ValueError(f"candidate_training_batch: answer_lengths must lie in [0, W = {tok.shape[2]}]")
+    zeros = torch.zeros(tuple(length.shape), dtype=torch.float32)
+    return sampled_training_batch(input_ids, token_type_ids, position_ids, context_len,
+                                  GeneratedAnswers(tokens=tok, lengths=length, scores=zeros, logp=zeros,
+                                                   step_logp=torch.zeros(tuple(tok.shape), dtype=torch.float32)), T)
 
 
 def spread(values, batch: SampledBatch):

@@ -462,7 +462,8 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None, want_logits
     xs = torch.empty((n, xt.shape[1]), dtype=BF16, device=dev)             # rows of the GEMM operand: H, or the split's 3 H, bf16 words
     L.gather_rows(xt, lm_idx, xs, n, xt.shape[1])
     if save:
-        lm = eng._lm_head(xs, n, lab_sel, w_sel, True, policy=eng._policy_inputs(inp, lm_pos.to(torch.int32), dev))
+        lm = eng._lm_head(xs, n, lab_sel, w_sel, True, policy=eng._policy_inputs(inp, lm_pos.to(torch.int32), dev),
+                          pref=eng._preference_inputs(inp, lm_pos, T, dev))
         lm.update(n=n, idx=lm_idx)
         out["lm"], out["bwd"] = lm, dict(tape=tape, embt=bwd_embt, embv=bwd_embv)
     else:
@@ -518,7 +519,7 @@ def check_shared_training(cfg, compute_dtype, loss_weights, attention_mask, grou
 def train_shared(eng, inp, groups, g_lm, train):
     """Forward and backward of the LM term on the shared schedule -> the LM loss (fp32 [1]).  `ok` -- every sequence's context,
     image and labels are its group's -- stays on the device: it multiplies the loss gradient (a mismatch adds nothing to the
-    gradient arena) and turns the returned loss into NaN."""
+    gradient arena) and turns the returned loss into NaN.  g_lm None: the forward and the loss alone, no backward."""
     dev = eng.arena.device
     cfg = eng.cfg
     out = _forward_shared(eng, inp, groups, False, None, dict(train=train, tape=[]))
@@ -526,7 +527,10 @@ def train_shared(eng, inp, groups, g_lm, train):
     n = lm["n"]
     ok = out["ok"].all().to(F32).reshape(1)
     lm_loss = torch.empty(1, dtype=F32, device=dev)
-    L.reduce_sum(lm["rowloss"], n, lm_loss, 1.0 / n)
+    if lm.get("pref") is not None:                                 # the preference step: sum(group_loss) / #alive
+        lm_loss = eng._preference_loss(lm["pref"])
+    else:
+        L.reduce_sum(lm["rowloss"], n, lm_loss, 1.0 / n)
     if lm.get("ent") is not None:                                  # the policy-gradient step reports the mean entropy of its rows
         eng.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
         L.reduce_sum(lm["ent"], n, eng.last_lm_entropy, 1.0 / n)
@@ -534,6 +538,8 @@ def train_shared(eng, inp, groups, g_lm, train):
         if lm.get("kl") is not None:                               # ... and, with a reference, their mean KL to it
             eng.last_lm_kl = torch.empty(1, dtype=F32, device=dev)
             L.reduce_sum(lm["kl"], n, eng.last_lm_kl, 1.0 / n)
+    if g_lm is None:
+        return torch.where(ok > 0, lm_loss, torch.full_like(lm_loss, float("nan")))
     # ---- backward: the MLM head, then the tape (Engine._backward without poolers, NSP and image head)
     eng.arena.attach_grads()
     eng._bwd_fresh = bool(eng.arena.fresh)

@@ -25,7 +25,8 @@ from typing import Optional
 import torch
 
 from . import harness, metrics, ranking
-from .policy import PolicyObjective, sampled_training_batch, self_critical_advantage, spread
+from .policy import (PolicyObjective, PreferenceObjective, PreferenceTargets, candidate_training_batch, preference_diagnostics,
+                     sampled_training_batch, self_critical_advantage, spread)
 from .scoring import SharedContext
 
 
@@ -188,6 +189,64 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     trained = rewards.reshape(-1)[sb.kept], advantage.reshape(-1)[sb.kept]      # hypotheses of length 0 took no part
     return (float(lm_loss), float(trained[0].mean()), float((trained[0] - trained[1]).mean()),
             float(entropy) if entropy is not None else float("nan"))
+
+
+def preference_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, *, objective=PreferenceObjective(), reference=None,
+                    shared_context=True):
+    """One iteration of preference training of the answer generator on GIVEN candidate answers (unimm_amd/policy.py).
+    `batch` holds G dialog contexts as `self_critical_step` takes them (`tokens` / `segments` / `positions` [G, T],
+    `context_len` [G], `image_feat` / `image_loc` [G, R, .], optionally `image_mask` [G, R]) and their candidates:
+    `answer_tokens` [G, N, W] (tokens, then [SEP], zero-padded), `answer_lengths` [G, N] (0 = absent) and `targets` [G, N], the
+    target weight of each candidate (`policy.pair_targets`, `policy.relevance_targets`).  The train-mode step is
+    `forward_backward` on the LM term alone with `lm_preference` / `lm_objective=objective` / `lm_reference=reference`, with the
+    `batch_multiply` / `no_sync` / `sync_gradients` cadence of `self_critical_step`.  shared_context: each dialog's context and
+    image are computed once for its candidates (`SharedContext(sb.image_index, 64)`); a candidate then has at most 30 tokens
+    before its [SEP] (ValueError beyond).
+    -> (loss, share of the dialogs whose best-scored candidate carries the largest target weight, mean score margin of that
+    candidate over the dialog's others: `policy.preference_diagnostics` of `engine.last_lm_preference`, read after the step)."""
+    lengths = torch.as_tensor(batch["answer_lengths"]).to("cpu", torch.int64)
+    if shared_context and lengths.numel() and int(lengths.max()) - 1 > 30:
+        raise ValueError(f"preference_step: shared_context trains answers of at most 30 tokens (64 private rows), got a candidate "
+                         f"of {int(lengths.max()) - 1}")
+    bm = int(params.get("batch_multiply", 1))
+    boundary = iter_id % bm == 0
+    model = _unwrap(dialog_encoder)
+    T = batch["tokens"].shape[1]
+    sb = candidate_training_batch(batch["tokens"], batch["segments"], batch["positions"], batch["context_len"],
+                                  batch["answer_tokens"], lengths, T)
+    K, (G, R) = sb.input_ids.shape[0], batch["image_feat"].shape[:2]
+    if K == 0:
+        raise ValueError("preference_step: every candidate has length 0, there is nothing to train on")
+    weights = torch.as_tensor(batch["targets"]).to("cpu", torch.float32)
+    if tuple(weights.shape) != tuple(sb.shape):
+        raise ValueError(f"preference_step: targets must be [G, N] = {tuple(sb.shape)}, got {tuple(weights.shape)}")
+    targets = PreferenceTargets(sb.image_index, weights.reshape(-1)[sb.kept])
+    # the step trains the LM term only (loss_weights (1, 0, 0)); the NSP and region terms still run and must stay finite
+    engine = (model.bert_pretrained if hasattr(model, "bert_pretrained") else model).engine
+    image_label = torch.zeros((K, R), dtype=torch.int64)
+    image_label[:, 0] = 1
+    C = engine.cfg.v_target_size
+    dialog_encoder.train()
+    engine.last_lm_preference = None            # set by this step (never what an earlier step left behind)
+    sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
+    with sync_ctx:
+        _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
+            sb.input_ids, batch["image_feat"], batch["image_loc"], (1.0 / bm, 0.0, 0.0), token_type_ids=sb.token_type_ids,
+            token_position_ids=sb.position_ids, attention_mask=sb.attention_mask, masked_lm_labels=sb.masked_lm_labels,
+            next_sentence_label=torch.zeros(K, dtype=torch.int64),
+            image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
+            image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+            lm_preference=targets, lm_objective=objective, lm_reference=reference,
+            **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}))
+    report = engine.last_lm_preference
+    if boundary:
+        if hasattr(dialog_encoder, "sync_gradients"):
+            dialog_encoder.sync_gradients()
+        optimizer.step()
+        optimizer.zero_grad()
+    scheduler.step()
+    accuracy, margin = preference_diagnostics(report["seq_score"], targets)
+    return float(lm_loss), accuracy, margin
 
 
 def eval_chunk_size(n_gpus: int) -> int:
