@@ -81,13 +81,13 @@ class Spy:
         model.engine._lm_loss_grad = self
 
     def __call__(self, lm, g_lm):
-        pg = lm["policy"]
-        rec = dict(logits=lm["logits"].clone(), ref=None if pg.get("ref") is None else pg["ref"].clone(), labels=lm["labels"].clone(),
-                   adv=pg["adv"][pg["pos"].long()].clone(), n=lm["n"], g=float(g_lm.reshape(-1)[0]),
+        pg = lm["objective"]                   # the step's bound lm_objective.PolicyGradient
+        rec = dict(logits=lm["logits"].clone(), ref=None if pg.ref is None else pg.ref.clone(), labels=lm["labels"].clone(),
+                   adv=pg.adv[pg.pos.long()].clone(), n=lm["n"], g=float(g_lm.reshape(-1)[0]),
                    inv=float(lm["inv_dev"][0]) if lm.get("inv_dev") is not None else 1.0 / lm["n"],
                    **{k: None if lm.get(k) is None else lm[k].clone() for k in ("kl", "ref_lse", "rowloss", "lse", "ent")})
         rec["dlog"] = self.inner(lm, g_lm).clone()
-        rec["released"] = pg.get("ref") is None
+        rec["released"] = pg.ref is None
         self.calls.append(rec)
         return rec["dlog"]
 

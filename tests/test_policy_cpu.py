@@ -224,8 +224,10 @@ def test_model_refusals_need_no_device(wrapper, tmp_path):
 
 
 def test_graph_executor_is_not_eligible_with_an_advantage():
-    """graphs.StepGraphs.eligible answers False as soon as lm_advantage is present (the eager step runs)."""
-    from unimm_amd import graphs
+    """graphs.StepGraphs.eligible answers False as soon as the step has a bound objective (the eager step runs)."""
+    from unimm_amd import BertConfig, BertForMultiModalPreTraining, graphs
+    from unimm_amd.lm_objective import KEY
+    from unimm_amd.policy import bind_objective
 
     class Eng:
         text_priority = False
@@ -235,4 +237,5 @@ def test_graph_executor_is_not_eligible_with_an_advantage():
 
     sg = graphs.StepGraphs.__new__(graphs.StepGraphs)
     sg.eng = Eng()
-    assert sg.eligible(dict(lm_advantage=torch.zeros(1, 1)), dict(want_seq=False)) is False
+    model = BertForMultiModalPreTraining(BertConfig.from_dict(json.load(open(os.path.join(ROOT, "tests", "golden", "small_config.json")))))
+    assert sg.eligible({KEY: bind_objective(model, (1, 1), lm_advantage=torch.zeros(1, 1))}, dict(want_seq=False)) is False

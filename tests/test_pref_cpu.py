@@ -287,7 +287,8 @@ def test_check_reference_takes_a_preference_objective():
 
 def test_the_graph_executor_declines_the_step():
     from unimm_amd.graphs import StepGraphs
-    from unimm_amd.policy import PreferenceTargets
+    from unimm_amd.lm_objective import KEY
+    from unimm_amd.policy import PreferenceObjective, PreferenceTargets, bind_objective
 
     class _Eng:
         text_priority = False
@@ -296,4 +297,5 @@ def test_the_graph_executor_declines_the_step():
             predict_feature = False
     sg = StepGraphs.__new__(StepGraphs)
     sg.eng = _Eng()
-    assert sg.eligible(dict(lm_preference=PreferenceTargets([0], [1.0])), dict(want_seq=False)) is False
+    bound = bind_objective(_make(False), (1, 16), lm_preference=PreferenceTargets([0], [1.0]), lm_objective=PreferenceObjective())
+    assert sg.eligible({KEY: bound}, dict(want_seq=False)) is False

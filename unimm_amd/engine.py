@@ -27,6 +27,7 @@ import torch
 from . import bucket_plan as BP
 from . import dropout as DR
 from . import lib as L
+from . import lm_objective as LO
 from . import params as PM
 from .arena import FlatArena
 from .inputs import DialogMaskSpec, HostStager, PackedMask
@@ -88,9 +89,8 @@ class Engine:
         self.grad_bucket_hook = None     # set by the data-parallel wrapper: f(group_name, more_follow_at_once)
         self._anchor = None
         self.last_seq_t = None
-        self.last_lm_entropy = None      # fp32 [1]: mean entropy of the rows the last policy-gradient step trained (`_losses`)
-        self.last_lm_kl = None           # fp32 [1]: mean KL(p || p_ref) of those rows when the step had a reference (kl_coef > 0)
-        self.last_lm_preference = None   # the last preference step's device tensors (`_lm_head`): seq_score, seq_prob, group_loss, adv, row_seq
+        for report in LO.REPORTS:        # last_lm_*: what the last step's LM objective reported (None until one has)
+            setattr(self, report, None)
         self.unpad = True                # run the text stream on valid rows only (see the plan step of _forward)
         # Weight gradients wait for a grouped launch, per side (0 = text, 1 = image: inside `_img()`).  The ledger, shared with
         # the exchange planner, decides when a side is launched and which gradient buckets that completes; the operands wait here.
@@ -1210,23 +1210,18 @@ class Engine:
         self._reference_rows(inp, groups)
         return self._on_text_stream(train_shared, self, inp, groups, g_lm, train)
 
-    _REF_DROPS = ("lm_advantage", "lm_behaviour_logp", "lm_objective", "lm_reference", "lm_weight", "image_target", "image_label",
-                  "next_sentence_label", "nsp_weight", "_plan_header", "_lm_ref_logits", "lm_preference")
+    _REF_DROPS = (LO.KEY, "lm_weight", "image_target", "image_label", "next_sentence_label", "nsp_weight", "_plan_header")
 
     def _reference_rows(self, inp, groups=None):
-        """The step's objective has kl_coef > 0, or is a preference objective with a reference (inp["lm_reference"]: the frozen
-        model, unimm_amd/policy.py): the reference's
+        """The step's objective reads a frozen reference model (`objective.reference`, unimm_amd/lm_objective.py): the reference's
         engine runs an inference forward on the step's own inputs -- eval mode, nothing saved, the labelled rows only, on the
-        schedule of the step (`groups`: the shared-context pass) -- and leaves its fp32 logits rows in inp["_lm_ref_logits"]:
+        schedule of the step (`groups`: the shared-context pass) -- and leaves its fp32 logits rows in `objective.ref`:
         the same positions in the same order as the rows this engine is about to decode.  Queued ahead of the policy's forward
         on the caller's stream.  The reference's parameters, gradients, dropout counters and training flag are not touched."""
-        ref = inp.get("lm_reference")
-        obj = inp.get("lm_objective")
-        if ref is None or obj is None:
+        objective = inp.get(LO.KEY)
+        if objective is None or objective.reference is None:
             return
-        if inp.get("lm_preference") is None and (not getattr(obj, "kl_coef", 0.0) > 0 or inp.get("lm_advantage") is None):
-            return
-        eng = ref._engine
+        eng = objective.reference._engine
         eng.ensure(self.arena.device)
         rinp = {k: v for k, v in inp.items() if k not in self._REF_DROPS}
         was = eng.lm_bucket
@@ -1234,13 +1229,11 @@ class Engine:
         try:
             with torch.no_grad():
                 if groups is None:
-                    out = eng.forward(rinp, train=False, save=False, lm_rows="labelled", want_pred_v=False)
-                    lm = out.get("lm")
-                    inp["_lm_ref_logits"] = lm["logits"] if lm is not None else None
+                    lm = eng.forward(rinp, train=False, save=False, lm_rows="labelled", want_pred_v=False).get("lm")
+                    objective.ref = lm["logits"] if lm is not None else None
                 else:
                     from .scoring import _forward_shared
-                    out = eng._on_text_stream(_forward_shared, eng, rinp, groups, False, None, None, True)
-                    inp["_lm_ref_logits"] = out["logits"]
+                    objective.ref = eng._on_text_stream(_forward_shared, eng, rinp, groups, False, None, None, True)["logits"]
         finally:
             eng.lm_bucket = was
 
@@ -1505,8 +1498,7 @@ class Engine:
                     xs = torch.empty((n, W), dtype=BF16, device=dev)
                     L.gather_rows(seq_t, sel["idx"], xs, n, W, n_dev=dyn["n_lm"])
                 lm = self._lm_head(xs, n, sel["label"], sel["weight"], save, n_dev=dyn["n_lm"],
-                                   policy=self._policy_inputs(inp, sel["pos"], dev),
-                                   pref=self._preference_inputs(inp, sel["pos"], T, dev))
+                                   objective=inp.pop(LO.KEY, LO.LIKELIHOOD), pos=sel["pos"])     # (moved: `inp` keeps nothing of it)
                 lm.update(idx=sel["idx"], pos_idx=sel["pos"], n=n, n_dev=dyn["n_lm"], inv_dev=dyn["inv_lm"])
             out["lm"] = lm
         elif lm_rows == "all":
@@ -1544,87 +1536,17 @@ class Engine:
         _, hn, mean, rstd = self._layernorm(t, ln_key, save, want32=False)
         return t, u, hn, mean, rstd, self._linear(hn, dec, out_f32=True, ldo=ldo)
 
-    def _policy_inputs(self, inp, pos, dev):
-        """`lm_advantage` given (unimm_amd/policy.py): what the policy-gradient row kernels read -- the decoded rows' flat
-        positions, fp32 [B * T] advantages and behaviour log-probabilities on the device, the objective.  None otherwise."""
-        adv = inp.get("lm_advantage")
-        if adv is None:
-            return None
-        obj = inp["lm_objective"]
-        flat = lambda t: t.to(dev, dtype=F32, non_blocking=True).contiguous().reshape(-1)
-        blogp = inp.get("lm_behaviour_logp")
-        pg = dict(pos=pos, adv=flat(adv), blogp=flat(blogp) if obj.mode == "ratio" else None,
-                  mode=L.PG_RATIO if obj.mode == "ratio" else L.PG_LOGP, eps=float(obj.clip_eps), beta=float(obj.entropy_coef))
-        ref = inp.pop("_lm_ref_logits", None)  # the frozen reference's rows (`_reference_rows`): this step's, handed over once
-        if ref is not None:
-            pg.update(ref=ref, kl_coef=float(obj.kl_coef))
-        return pg
-
-    def _preference_inputs(self, inp, pos, T, dev):
-        """`lm_preference` given (unimm_amd/policy.py): what unimm_seq_pref reads beside the row kernels' rownll -- the decoded
-        rows' sequences (flat position // T), the sequences' groups and target weights on the device, the objective, and the
-        frozen reference's logits rows when the step has a reference.  None otherwise."""
-        tg = inp.get("lm_preference")
-        if tg is None:
-            return None
-        obj = inp["lm_objective"]
-        group = torch.as_tensor(tg.group).to(dev, dtype=torch.int32, non_blocking=True).contiguous().reshape(-1)
-        weight = torch.as_tensor(tg.weight).to(dev, dtype=F32, non_blocking=True).contiguous().reshape(-1)
-        return dict(row_seq=(pos // T).to(torch.int32), group=group, weight=weight, groups=int(tg.groups), beta=float(obj.beta),
-                    lnorm=bool(obj.length_normalize), ref=inp.pop("_lm_ref_logits", None))
-
-    def _preference_rows(self, pf, logits, lab_sel, w_sel, rownll, n, n_dev):
-        """The step between the likelihood rows and the policy-gradient backward (include/unimm_hip.h: unimm_seq_pref): the
-        reference's rows go through the same likelihood kernel (weight 1) and are released, then the per-row -log p_y of both
-        become per-sequence scores, each group's softmax against its target weights, and one coefficient per row."""
-        dev, V = logits.device, self.cfg.vocab_size
-        ref_rownll = None
-        ref = pf.pop("ref", None)
-        if ref is not None:
-            if ref.shape[0] != n:
-                raise L.UnimmHipError(f"the reference decoded {ref.shape[0]} rows, the policy {n}: not the same step's rows")
-            scratch, ref_rownll, ref_lse = (torch.empty(n, dtype=F32, device=dev) for _ in range(3))
-            L.lm_loss_fwd(ref, lab_sel, w_sel, scratch, ref_rownll, ref_lse, n, V, n_dev=n_dev)
-            ref.record_stream(torch.cuda.current_stream())
-            del ref                            # the reference's logits are released here: the backward does not read them
-        B, G = pf["group"].numel(), pf["groups"]
-        adv = torch.zeros(n, dtype=F32, device=dev)
-        seq_score, seq_prob = torch.empty(B, dtype=F32, device=dev), torch.empty(B, dtype=F32, device=dev)
-        group_loss, alive_inv = torch.empty(G, dtype=F32, device=dev), torch.empty(1, dtype=F32, device=dev)
-        L.seq_pref(rownll, ref_rownll, pf["row_seq"], n, pf["group"], pf["weight"], G, pf["beta"], pf["lnorm"], adv, seq_score,
-                   seq_prob, group_loss, alive_inv, n_dev=n_dev)
-        pf.update(adv=adv, seq_score=seq_score, seq_prob=seq_prob, group_loss=group_loss, alive_inv=alive_inv)
-        self.last_lm_preference = dict(seq_score=seq_score, seq_prob=seq_prob, group_loss=group_loss, adv=adv, row_seq=pf["row_seq"])
-
-    def _preference_loss(self, pf):
-        """sum(group_loss) / #alive as fp32 [1] (NaN when no group is alive)"""
-        loss = torch.empty(1, dtype=F32, device=pf["group_loss"].device)
-        L.reduce_sum(pf["group_loss"], pf["groups"], loss, 1.0, scale_dev=pf["alive_inv"])
-        return loss
-
-    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None, policy=None, pref=None):
+    def _lm_head(self, xs, n, lab_sel, w_sel, save, n_dev=None, objective=LO.LIKELIHOOD, pos=None):
+        """The MLM head on the n decoded rows xs and the forward row kernels of the step's objective (unimm_amd/lm_objective.py;
+        pos: the rows' flat positions) -> the head's state, which carries the objective to `_losses` and `_lm_loss_grad`."""
         V = self.cfg.vocab_size
+        objective.stage(pos, xs.device)
         t1, u, hn, mean, rstd, logits = self._transform_head(xs, self.lin["lmtr"], "lmtr", self.lin["dec"], _rup(V, 64), save)
         rowloss, rownll, lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
-        ent = kl = ref_lse = None
-        if pref is not None:                   # the listwise preference over whole answers: likelihood rows with weight 1, then
-            L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)     # the step in the middle
-            self._preference_rows(pref, logits, lab_sel, w_sel, rownll, n, n_dev)
-        elif policy is not None and policy.get("ref") is not None:   # ... with the KL penalty against the reference's rows
-            ref = policy["ref"]
-            if ref.shape[0] != n:
-                raise L.UnimmHipError(f"the reference decoded {ref.shape[0]} rows, the policy {n}: not the same step's rows")
-            ent, kl, ref_lse = (torch.empty(n, dtype=F32, device=xs.device) for _ in range(3))
-            L.pg_kl_loss_fwd(logits, lab_sel, policy["pos"], policy["adv"], policy["blogp"], policy["mode"], policy["eps"],
-                             policy["beta"], rowloss, rownll, lse, ent, n, V, ref, policy["kl_coef"], kl, ref_lse, n_dev=n_dev)
-        elif policy is not None:               # the advantage-weighted objective on sampled answers, entropy kept with lse
-            ent = torch.empty(n, dtype=F32, device=xs.device)
-            L.pg_loss_fwd(logits, lab_sel, policy["pos"], policy["adv"], policy["blogp"], policy["mode"], policy["eps"],
-                          policy["beta"], rowloss, rownll, lse, ent, n, V, n_dev=n_dev)
-        else:
-            L.lm_loss_fwd(logits, lab_sel, w_sel, rowloss, rownll, lse, n, V, n_dev=n_dev)
-        return dict(xs=xs, t1=t1, u=u, hn=hn, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll,
-                    lse=lse, labels=lab_sel, weights=w_sel, policy=policy, ent=ent, kl=kl, ref_lse=ref_lse, pref=pref)
+        lm = dict(xs=xs, t1=t1, u=u, hn=hn, mean=mean, rstd=rstd, logits=logits, rowloss=rowloss, rownll=rownll, lse=lse,
+                  labels=lab_sel, weights=w_sel, objective=objective)
+        objective.forward(self, lm, n, n_dev)
+        return lm
 
     def decode_rows(self, x, n):
         """MLM transform + decoder for n rows of the GEMM operand x, fp32 logits [n, Vpad] (no loss, nothing saved)."""
@@ -1645,26 +1567,7 @@ class Engine:
     def _lm_loss_grad(self, lm, g_lm):
         n, V = lm["n"], self.cfg.vocab_size          # n is a capacity: the real count lives on the device (n_dev)
         dlog = torch.empty((n, _rup(V, 64)), dtype=BF16, device=self.arena.device)
-        pg = lm.get("policy")
-        pf = lm.get("pref")
-        if pf is not None:                     # -(c_j / #alive)(onehot_y - p): LOGP rows with A = c_j, the denominator word #alive
-            L.pg_loss_bwd(lm["logits"], lm["labels"], None, pf["adv"], None, L.PG_LOGP, 0.0, 0.0, lm["lse"], lm["lse"],
-                          self._gvec(g_lm), 1.0, dlog, n, V, n_dev=lm.get("n_dev"), inv_dev=pf["alive_inv"])
-            return dlog
-        if pg is not None and pg.get("ref") is not None:
-            L.pg_kl_loss_bwd(lm["logits"], lm["labels"], pg["pos"], pg["adv"], pg["blogp"], pg["mode"], pg["eps"], pg["beta"],
-                             lm["lse"], lm["ent"], self._gvec(g_lm), 1.0 / n, dlog, n, V, pg["ref"], pg["kl_coef"], lm["kl"],
-                             lm["ref_lse"], n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
-            pg["ref"].record_stream(torch.cuda.current_stream())
-            pg["ref"] = None                   # the reference's logits are released here: the backward was their last reader
-            return dlog
-        if pg is not None:
-            L.pg_loss_bwd(lm["logits"], lm["labels"], pg["pos"], pg["adv"], pg["blogp"], pg["mode"], pg["eps"], pg["beta"],
-                          lm["lse"], lm["ent"], self._gvec(g_lm), 1.0 / n, dlog, n, V, n_dev=lm.get("n_dev"),
-                          inv_dev=lm.get("inv_dev"))
-            return dlog
-        L.lm_loss_bwd(lm["logits"], lm["labels"], lm["weights"], lm["lse"], self._gvec(g_lm), 1.0 / n, dlog, n, V,
-                      n_dev=lm.get("n_dev"), inv_dev=lm.get("inv_dev"))
+        lm["objective"].backward(self, lm, self._gvec(g_lm), dlog)
         return dlog
 
     def _img_loss_grad(self, img, gimg, rows):
@@ -1704,23 +1607,8 @@ class Engine:
         B, R = out["B"], out["R"]
         res = {}
         lm = out.get("lm")
-        lm_loss = torch.empty(1, dtype=F32, device=dev)
-        if lm is None:
-            lm_loss.fill_(float("nan"))        # 0 / 0 in the reference when nothing is labelled
-        elif lm.get("pref") is not None:
-            lm_loss = self._preference_loss(lm["pref"])
-        else:
-            L.reduce_sum(lm["rowloss"], lm["n"], lm_loss, 1.0 / lm["n"], n_dev=lm.get("n_dev"), scale_dev=lm.get("inv_dev"))
-            if lm.get("ent") is not None:      # the policy-gradient step reports the mean entropy of the rows it trained
-                self.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
-                L.reduce_sum(lm["ent"], lm["n"], self.last_lm_entropy, 1.0 / lm["n"], n_dev=lm.get("n_dev"),
-                             scale_dev=lm.get("inv_dev"))
-                self.last_lm_kl = None
-                if lm.get("kl") is not None:   # ... and, with a reference, their mean KL to it
-                    self.last_lm_kl = torch.empty(1, dtype=F32, device=dev)
-                    L.reduce_sum(lm["kl"], lm["n"], self.last_lm_kl, 1.0 / lm["n"], n_dev=lm.get("n_dev"),
-                                 scale_dev=lm.get("inv_dev"))
-        res["lm_loss"] = lm_loss
+        # (nothing labelled: 0 / 0 in the reference)
+        res["lm_loss"] = torch.full((1,), float("nan"), dtype=F32, device=dev) if lm is None else lm["objective"].loss(self, lm)
         # image KL
         img = out["img"]
         C = cfg.v_target_size

@@ -40,6 +40,7 @@ import torch
 from . import dropout as DR
 from . import lib as L
 from .inputs import PackedMask
+from .lm_objective import KEY as LM_OBJECTIVE_KEY
 
 _TENSOR_KEYS = ("input_ids", "image_feat", "image_loc", "token_type_ids", "position_ids", "attention_mask",
                 "image_attention_mask", "co_attention_mask", "masked_lm_labels", "image_label", "image_target",
@@ -196,10 +197,8 @@ class StepGraphs:
             return False
         if inp.get("shared_context") is not None:    # the shared-context step (unimm_amd/scoring.py) packs its own rows: eager
             return False
-        if inp.get("lm_advantage") is not None:      # the policy-gradient step (unimm_amd/policy.py) has no replayed form: its
-            return False                             # advantages are not among the staged inputs; the eager step runs
-        if inp.get("lm_preference") is not None:     # ... nor has the preference step: its targets are not staged either
-            return False
+        if inp.get(LM_OBJECTIVE_KEY) is not None:    # a bound objective (policy gradient, preference) has no replayed form: its
+            return False                             # advantages / targets are not among the staged inputs; the eager step runs
         for k in _TENSOR_KEYS:
             v = inp.get(k)
             if v is None:

@@ -15,9 +15,17 @@ from torch import nn
 from . import params as PM
 from .config import BertConfig
 from .engine import Engine
-from .policy import check_policy_inputs, check_preference_inputs, check_reference
+from .lm_objective import KEY as OBJECTIVE_KEY
+from .policy import bind_objective
 
 logger = logging.getLogger(__name__)
+
+# the arguments of `forward` / `forward_backward` that reach the engine as they are; the shared-context pass
+# (unimm_amd/scoring.py) reads, and gets staged, the first ten only
+_SHARED_INPUTS = ("input_ids", "image_feat", "image_loc", "token_type_ids", "position_ids", "attention_mask", "image_attention_mask",
+                  "masked_lm_labels", "lm_weight", "image_index")
+_INPUTS = _SHARED_INPUTS + ("co_attention_mask", "image_label", "image_target", "next_sentence_label", "nsp_weight")
+_OBJECTIVE_ARGS = ("lm_advantage", "lm_behaviour_logp", "lm_objective", "lm_reference", "lm_preference", "lm_weight")
 
 
 def _build_param_tree(root: nn.Module, cfg) -> None:
@@ -206,6 +214,7 @@ class BertForMultiModalPreTraining(nn.Module):
         `shared_context` (and `lm_preference`; the conditions of `forward_backward(shared_context=)`) that loss is computed on the
         shared-context schedule, as a value only -- no autograd graph: train with `forward_backward` -- and the call returns
         (lm_loss, 0, 0, None, None, None)."""
+        args = locals()                        # the call's arguments by name (`_bind_objective`, `_engine_inputs`)
         train_branch = masked_lm_labels is not None and next_sentence_label is not None and image_target is not None
         if shared_context is not None:
             if lm_preference is None:
@@ -214,45 +223,14 @@ class BertForMultiModalPreTraining(nn.Module):
             if masked_lm_labels is None:
                 raise ValueError("forward(shared_context=...) needs masked_lm_labels (the copy rows)")
             train_branch = True
-        if lm_preference is not None:
-            lm_objective = check_preference_inputs(input_ids.shape, lm_preference, lm_objective, lm_advantage, lm_weight,
-                                                   lm_behaviour_logp, self.compute_dtype, train_branch)
-        else:
-            lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                               self.compute_dtype, train_branch, lm_reference=lm_reference)
-        lm_reference = check_reference(self, lm_reference, lm_objective)
-        if shared_context is not None:
-            from .scoring import check_shared_training
-            check_shared_training(self.config, self.compute_dtype, (1.0, 0.0, 0.0), attention_mask, shared_context, input_ids.shape[1],
-                                  image_feat.shape[1])
+        objective = self._bind_objective(args, (1.0, 0.0, 0.0), train_branch)
         eng = self._engine
-        dev = self._device()
-        eng.ensure(dev)
+        inp = self._engine_inputs(objective, shared_context is not None, args)
         if shared_context is not None:
-            inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
-                       position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
-                       masked_lm_labels=masked_lm_labels, image_index=image_index, lm_objective=lm_objective,
-                       lm_reference=lm_reference, lm_preference=lm_preference)
-            eng.stage_host_inputs(inp, pack=())
-            if self.training:
-                eng.step += 1
-            with torch.no_grad():
-                lm_loss = eng.forward_backward_shared(inp, shared_context, None, self.training)
-                eng.last_seq_t = None
-                zero = torch.zeros(1, dtype=torch.float32, device=dev)
+            _, lm_loss, zero = self._shared_step(inp, shared_context, None)
             return lm_loss, zero, zero.clone(), None, None, None
-        inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
-                   position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
-                   co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
-                   image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
-                   lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
-                   lm_preference=lm_preference)
-        eng.stage_host_inputs(inp)             # the reference's callers pass CPU tensors (train.py:113-161): pinned ring + copy stream
         B, T = input_ids.shape
         H, V = self.config.hidden_size, self.config.vocab_size
-        if self.training:
-            eng.step += 1
         if train_branch:
             if torch.is_grad_enabled():
                 lm_loss, img_loss, nsp_loss, nsp = _HotPath.apply(eng._anchor, eng, inp,
@@ -305,51 +283,20 @@ class BertForMultiModalPreTraining(nn.Module):
         nsp_logits as None; when a sequence's context does not match its group's, the loss is NaN and the call adds nothing to
         the gradients.  Always eager.
         lm_preference / lm_objective=PreferenceObjective / lm_reference: as in `forward`, on either schedule (always eager)."""
-        if lm_preference is not None:
-            lm_objective = check_preference_inputs(input_ids.shape, lm_preference, lm_objective, lm_advantage, lm_weight,
-                                                   lm_behaviour_logp, self.compute_dtype)
-        else:
-            lm_objective = check_policy_inputs(input_ids.shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight,
-                                               self.compute_dtype, lm_reference=lm_reference)
-        lm_reference = check_reference(self, lm_reference, lm_objective)
+        args = locals()                        # the call's arguments by name (`_bind_objective`, `_engine_inputs`)
+        objective = self._bind_objective(args, loss_weights, True)
         if shared_context is not None:
-            from .scoring import check_shared_training
-            check_shared_training(self.config, self.compute_dtype, loss_weights, attention_mask, shared_context, input_ids.shape[1],
-                                  image_feat.shape[1])
             if masked_lm_labels is None:
                 raise ValueError("forward_backward(shared_context=...) needs masked_lm_labels (the copy rows)")
         elif masked_lm_labels is None or next_sentence_label is None or image_target is None:
             raise ValueError("forward_backward needs the training inputs (masked_lm_labels, next_sentence_label, image_target)")
-        eng = self._engine
-        dev = self._device()
-        eng.ensure(dev)
+        eng, dev = self._engine, self._device()
+        inp = self._engine_inputs(objective, shared_context is not None, args)
         if shared_context is not None:
-            inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
-                       position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
-                       masked_lm_labels=masked_lm_labels, lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                       lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
-                       lm_preference=lm_preference)
-            eng.stage_host_inputs(inp, pack=())      # (the [B, R] image key mask stays a tensor: the pass indexes it by group)
-            if self.training:
-                eng.step += 1
-            with torch.no_grad():
-                g_lm = torch.full((1,), float(loss_weights[0]), dtype=torch.float32, device=dev)
-                lm_loss = eng.forward_backward_shared(inp, shared_context, g_lm, self.training)
-                eng.last_seq_t = None
-                zero = torch.zeros(1, dtype=torch.float32, device=dev)
-                return (g_lm * lm_loss).reshape(()), lm_loss, zero, zero.clone(), None
-        inp = dict(input_ids=input_ids, image_feat=image_feat, image_loc=image_loc, token_type_ids=token_type_ids,
-                   position_ids=position_ids, attention_mask=attention_mask, image_attention_mask=image_attention_mask,
-                   co_attention_mask=co_attention_mask, masked_lm_labels=masked_lm_labels, image_label=image_label,
-                   image_target=image_target, next_sentence_label=next_sentence_label, nsp_weight=nsp_weight,
-                   lm_weight=lm_weight, image_index=image_index, lm_advantage=lm_advantage,
-                   lm_behaviour_logp=lm_behaviour_logp, lm_objective=lm_objective, lm_reference=lm_reference,
-                   lm_preference=lm_preference)
-        eng.stage_host_inputs(inp)
+            g_lm, lm_loss, zero = self._shared_step(inp, shared_context, loss_weights[0])
+            return (g_lm * lm_loss).reshape(()), lm_loss, zero, zero.clone(), None
         if plan_header is not None:
             inp["_plan_header"] = plan_header
-        if self.training:
-            eng.step += 1
         c_lm, c_nsp, c_img = (float(c) for c in loss_weights)
         key = (c_lm, c_nsp, c_img, dev)
         seeds = self._fb_seeds.get(key) if hasattr(self, "_fb_seeds") else None
@@ -379,6 +326,41 @@ class BertForMultiModalPreTraining(nn.Module):
             eng.last_seq_t = None
             loss = torch.cat((lm_loss.reshape(1), img_loss.reshape(1), nsp_loss.reshape(1))).dot(w).reshape(())
         return loss, lm_loss, img_loss, nsp_loss, nsp
+
+    def _bind_objective(self, args, loss_weights, train_branch):
+        """Every refusal of the objective keywords and of the shared schedule, all on the host -> the call's bound objective or None."""
+        shape = args["input_ids"].shape
+        objective = bind_objective(self, shape, train_branch, **{k: args[k] for k in _OBJECTIVE_ARGS})
+        if args["shared_context"] is not None:
+            from .scoring import check_shared_training
+            check_shared_training(self.config, self.compute_dtype, loss_weights, args["attention_mask"], args["shared_context"],
+                                  shape[1], args["image_feat"].shape[1])
+        return objective
+
+    def _engine_inputs(self, objective, shared, args):
+        """The engine's `inp` of one call: its tensor arguments (on the shared schedule the ones that pass reads; the [B, R]
+        image key mask then stays a tensor, the pass indexes it by group) and the bound objective under its one key, the host
+        tensors staged (the reference's callers pass CPU tensors, train.py:113-161); counts the step."""
+        eng = self._engine
+        eng.ensure(self._device())
+        inp = {k: args[k] for k in (_SHARED_INPUTS if shared else _INPUTS)}
+        if objective is not None:
+            inp[OBJECTIVE_KEY] = objective
+        eng.stage_host_inputs(inp, pack=() if shared else None)
+        if self.training:
+            eng.step += 1
+        return inp
+
+    def _shared_step(self, inp, shared_context, c_lm):
+        """The LM term on the shared-context schedule: forward, loss and (c_lm not None) the backward of c_lm * lm_loss; no
+        autograd graph -> (the gradient seed | None, lm_loss, a zero for the losses that take no part)."""
+        eng, dev = self._engine, self._device()
+        with torch.no_grad():
+            g_lm = None if c_lm is None else torch.full((1,), float(c_lm), dtype=torch.float32, device=dev)
+            lm_loss = eng.forward_backward_shared(inp, shared_context, g_lm, self.training)
+            eng.last_seq_t = None
+            zero = torch.zeros(1, dtype=torch.float32, device=dev)
+        return g_lm, lm_loss, zero
 
     def _device(self):
         return self.bert.embeddings.word_embeddings.weight.device

@@ -42,6 +42,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import lm_objective as LO
 from .inputs import DialogMaskSpec
 
 SEP, MASK = 102, 103
@@ -277,6 +278,22 @@ def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm
         raise ValueError("lm_advantage weighs the LM loss of the train branch: pass masked_lm_labels, next_sentence_label and "
                          "image_target with it (this call computes no loss and would ignore it)")
     return obj
+
+
+def bind_objective(model, shape, train_branch=True, *, lm_advantage=None, lm_behaviour_logp=None, lm_objective=None,
+                   lm_reference=None, lm_preference=None, lm_weight=None):
+    """The objective keywords of `forward` / `forward_backward` (input_ids of `shape`), judged once by the three checks above -> all
+    the engine sees of them: the step's bound objective (unimm_amd/lm_objective.py), None for the likelihood step.  model: the trained one."""
+    if lm_preference is not None:
+        obj = check_preference_inputs(shape, lm_preference, lm_objective, lm_advantage, lm_weight, lm_behaviour_logp,
+                                      model.compute_dtype, train_branch)
+    else:
+        obj = check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, model.compute_dtype, train_branch,
+                                  lm_reference=lm_reference)
+    reference = check_reference(model, lm_reference, obj)
+    if lm_preference is not None:
+        return LO.Preference(lm_preference, obj, shape[1], reference)
+    return None if obj is None else LO.PolicyGradient(lm_advantage, lm_behaviour_logp, obj, reference)
 
 
 @dataclass

@@ -37,7 +37,7 @@ blocks below take `st` (train / tape) as `Engine._self_block` / `_conn_block` do
   text attends regions    every text block gets its own copy of its group's region K / V rows, unimm_attn_bwd writes one dK / dV
                           copy per block, unimm_segment_rows_sum_bf16 adds a group's copies in list order
   regions attend text     touches S rows only: today's kernel
-Only the LM term on the copy rows is trained (either objective `_lm_head` has); poolers, NSP and image head take no part.
+Only the LM term on the copy rows is trained (any objective of unimm_amd/lm_objective.py); poolers, NSP and image head take no part.
 
 Inference (no tape, no dropout) runs on either engine: the pass is written once against the engine's operand hooks
 (unimm_amd/engine.py: `_proj`, `_post_attn`, `_self_block`, `_lm_head`, `_pooled_heads`, and the inference hooks `_ctx_rows` /
@@ -53,6 +53,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import lm_objective as LO
 from . import params as PM
 from .inputs import DialogMaskSpec
 
@@ -462,8 +463,7 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None, want_logits
     xs = torch.empty((n, xt.shape[1]), dtype=BF16, device=dev)             # rows of the GEMM operand: H, or the split's 3 H, bf16 words
     L.gather_rows(xt, lm_idx, xs, n, xt.shape[1])
     if save:
-        lm = eng._lm_head(xs, n, lab_sel, w_sel, True, policy=eng._policy_inputs(inp, lm_pos.to(torch.int32), dev),
-                          pref=eng._preference_inputs(inp, lm_pos, T, dev))
+        lm = eng._lm_head(xs, n, lab_sel, w_sel, True, objective=inp.pop(LO.KEY, LO.LIKELIHOOD), pos=lm_pos.to(torch.int32))
         lm.update(n=n, idx=lm_idx)
         out["lm"], out["bwd"] = lm, dict(tape=tape, embt=bwd_embt, embv=bwd_embv)
     else:
@@ -526,18 +526,7 @@ def train_shared(eng, inp, groups, g_lm, train):
     lm, plan = out["lm"], out["plan"]
     n = lm["n"]
     ok = out["ok"].all().to(F32).reshape(1)
-    lm_loss = torch.empty(1, dtype=F32, device=dev)
-    if lm.get("pref") is not None:                                 # the preference step: sum(group_loss) / #alive
-        lm_loss = eng._preference_loss(lm["pref"])
-    else:
-        L.reduce_sum(lm["rowloss"], n, lm_loss, 1.0 / n)
-    if lm.get("ent") is not None:                                  # the policy-gradient step reports the mean entropy of its rows
-        eng.last_lm_entropy = torch.empty(1, dtype=F32, device=dev)
-        L.reduce_sum(lm["ent"], n, eng.last_lm_entropy, 1.0 / n)
-        eng.last_lm_kl = None
-        if lm.get("kl") is not None:                               # ... and, with a reference, their mean KL to it
-            eng.last_lm_kl = torch.empty(1, dtype=F32, device=dev)
-            L.reduce_sum(lm["kl"], n, eng.last_lm_kl, 1.0 / n)
+    lm_loss = lm["objective"].loss(eng, lm)                        # (this schedule's row count is the host's: no n_dev / inv_dev)
     if g_lm is None:
         return torch.where(ok > 0, lm_loss, torch.full_like(lm_loss, float("nan")))
     # ---- backward: the MLM head, then the tape (Engine._backward without poolers, NSP and image head)

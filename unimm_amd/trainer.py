@@ -25,8 +25,8 @@ from typing import Optional
 import torch
 
 from . import harness, metrics, ranking
-from .policy import (PolicyObjective, PreferenceObjective, PreferenceTargets, candidate_training_batch, preference_diagnostics,
-                     sampled_training_batch, self_critical_advantage, spread)
+from .policy import (PolicyObjective, PreferenceObjective, PreferenceTargets, _pretraining_model, candidate_training_batch,
+                     preference_diagnostics, sampled_training_batch, self_critical_advantage, spread)
 from .scoring import SharedContext
 
 
@@ -105,6 +105,40 @@ def dense_finetune_step(dialog_encoder, optimizer, scheduler, batch, params, ite
     return float(loss.detach()) / bm, {k: v.detach() for k, v in parts.items()}
 
 
+def _lm_term_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sb, shared_context, reports, **lm_kw):
+    """What `self_critical_step` and `preference_step` do with their SampledBatch `sb`: the train-mode `forward_backward` on the
+    LM term alone (loss_weights (1 / bm, 0, 0)) with the objective arguments `lm_kw`, then the `no_sync` / `sync_gradients` /
+    optimizer cadence of `train_step`.  reports: the `engine.last_lm_*` attributes the step sets, cleared first (never a value
+    an earlier step left behind).  The NSP and region terms still run and must stay finite: label 0 everywhere, one labelled
+    region per sequence against a uniform target distribution.  -> (lm_loss, the engine)."""
+    bm = int(params.get("batch_multiply", 1))
+    boundary = iter_id % bm == 0
+    K, (G, R) = sb.input_ids.shape[0], batch["image_feat"].shape[:2]
+    engine = _pretraining_model(_unwrap(dialog_encoder)).engine
+    image_label = torch.zeros((K, R), dtype=torch.int64)
+    image_label[:, 0] = 1
+    C = engine.cfg.v_target_size
+    dialog_encoder.train()
+    for name in reports:
+        setattr(engine, name, None)
+    sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
+    with sync_ctx:
+        _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
+            sb.input_ids, batch["image_feat"], batch["image_loc"], (1.0 / bm, 0.0, 0.0), token_type_ids=sb.token_type_ids,
+            token_position_ids=sb.position_ids, attention_mask=sb.attention_mask, masked_lm_labels=sb.masked_lm_labels,
+            next_sentence_label=torch.zeros(K, dtype=torch.int64),
+            image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
+            image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+            **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}), **lm_kw)
+    if boundary:
+        if hasattr(dialog_encoder, "sync_gradients"):
+            dialog_encoder.sync_gradients()
+        optimizer.step()
+        optimizer.zero_grad()
+    scheduler.step()
+    return lm_loss, engine
+
+
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
                        objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
                        shared_context=False, rollout="separate", reference=None):
@@ -138,8 +172,6 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     if shared_context and max_answer_len > 30:
         raise ValueError(f"self_critical_step: shared_context trains answers of at most 30 tokens (64 private rows), got "
                          f"max_answer_len = {max_answer_len}")
-    bm = int(params.get("batch_multiply", 1))
-    boundary = iter_id % bm == 0
     model = _unwrap(dialog_encoder)
     T = batch["tokens"].shape[1]
     gen_args = (batch["tokens"], batch["image_feat"], batch["image_loc"], batch["context_len"])
@@ -156,36 +188,13 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
         base = baseline
     advantage = self_critical_advantage(rewards, base)
     sb = sampled_training_batch(batch["tokens"], batch["segments"], batch["positions"], batch["context_len"], answers, T)
-    K, (G, R) = sb.input_ids.shape[0], batch["image_feat"].shape[:2]
-    if K == 0:
+    if sb.input_ids.shape[0] == 0:
         raise ValueError("self_critical_step: every sampled answer has length 0, there is nothing to train on")
-    # the step trains the LM term only (loss_weights (1, 0, 0)); the NSP and region terms still run and must stay finite:
-    # label 0 everywhere, one labelled region per sequence against a uniform target distribution
-    engine = (model.bert_pretrained if hasattr(model, "bert_pretrained") else model).engine
-    image_label = torch.zeros((K, R), dtype=torch.int64)
-    image_label[:, 0] = 1
-    C = engine.cfg.v_target_size
-    dialog_encoder.train()
-    engine.last_lm_entropy = None               # set by this step's losses (never a value an earlier step left behind)
-    engine.last_lm_kl = None
-    sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
-    with sync_ctx:
-        _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
-            sb.input_ids, batch["image_feat"], batch["image_loc"], (1.0 / bm, 0.0, 0.0), token_type_ids=sb.token_type_ids,
-            token_position_ids=sb.position_ids, attention_mask=sb.attention_mask, masked_lm_labels=sb.masked_lm_labels,
-            next_sentence_label=torch.zeros(K, dtype=torch.int64),
-            image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
-            image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
-            lm_advantage=spread(advantage, sb), lm_objective=objective, lm_reference=reference,
-            lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None,
-            **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}))
+    lm_loss, engine = _lm_term_step(
+        dialog_encoder, optimizer, scheduler, batch, params, iter_id, sb, shared_context, ("last_lm_entropy", "last_lm_kl"),
+        lm_advantage=spread(advantage, sb), lm_objective=objective, lm_reference=reference,
+        lm_behaviour_logp=spread(answers.step_logq, sb) if objective.mode == "ratio" else None)
     entropy = engine.last_lm_entropy
-    if boundary:
-        if hasattr(dialog_encoder, "sync_gradients"):
-            dialog_encoder.sync_gradients()
-        optimizer.step()
-        optimizer.zero_grad()
-    scheduler.step()
     trained = rewards.reshape(-1)[sb.kept], advantage.reshape(-1)[sb.kept]      # hypotheses of length 0 took no part
     return (float(lm_loss), float(trained[0].mean()), float((trained[0] - trained[1]).mean()),
             float(entropy) if entropy is not None else float("nan"))
@@ -208,43 +217,17 @@ def preference_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id
     if shared_context and lengths.numel() and int(lengths.max()) - 1 > 30:
         raise ValueError(f"preference_step: shared_context trains answers of at most 30 tokens (64 private rows), got a candidate "
                          f"of {int(lengths.max()) - 1}")
-    bm = int(params.get("batch_multiply", 1))
-    boundary = iter_id % bm == 0
-    model = _unwrap(dialog_encoder)
-    T = batch["tokens"].shape[1]
     sb = candidate_training_batch(batch["tokens"], batch["segments"], batch["positions"], batch["context_len"],
-                                  batch["answer_tokens"], lengths, T)
-    K, (G, R) = sb.input_ids.shape[0], batch["image_feat"].shape[:2]
-    if K == 0:
+                                  batch["answer_tokens"], lengths, batch["tokens"].shape[1])
+    if sb.input_ids.shape[0] == 0:
         raise ValueError("preference_step: every candidate has length 0, there is nothing to train on")
     weights = torch.as_tensor(batch["targets"]).to("cpu", torch.float32)
     if tuple(weights.shape) != tuple(sb.shape):
         raise ValueError(f"preference_step: targets must be [G, N] = {tuple(sb.shape)}, got {tuple(weights.shape)}")
     targets = PreferenceTargets(sb.image_index, weights.reshape(-1)[sb.kept])
-    # the step trains the LM term only (loss_weights (1, 0, 0)); the NSP and region terms still run and must stay finite
-    engine = (model.bert_pretrained if hasattr(model, "bert_pretrained") else model).engine
-    image_label = torch.zeros((K, R), dtype=torch.int64)
-    image_label[:, 0] = 1
-    C = engine.cfg.v_target_size
-    dialog_encoder.train()
-    engine.last_lm_preference = None            # set by this step (never what an earlier step left behind)
-    sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
-    with sync_ctx:
-        _, lm_loss, _, _, _ = dialog_encoder.forward_backward(
-            sb.input_ids, batch["image_feat"], batch["image_loc"], (1.0 / bm, 0.0, 0.0), token_type_ids=sb.token_type_ids,
-            token_position_ids=sb.position_ids, attention_mask=sb.attention_mask, masked_lm_labels=sb.masked_lm_labels,
-            next_sentence_label=torch.zeros(K, dtype=torch.int64),
-            image_attention_mask=batch["image_mask"][sb.image_index.to(batch["image_mask"].device)] if "image_mask" in batch else None,
-            image_label=image_label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
-            lm_preference=targets, lm_objective=objective, lm_reference=reference,
-            **(dict(shared_context=SharedContext(sb.image_index, 64)) if shared_context else {}))
+    lm_loss, engine = _lm_term_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sb, shared_context,
+                                    ("last_lm_preference",), lm_preference=targets, lm_objective=objective, lm_reference=reference)
     report = engine.last_lm_preference
-    if boundary:
-        if hasattr(dialog_encoder, "sync_gradients"):
-            dialog_encoder.sync_gradients()
-        optimizer.step()
-        optimizer.zero_grad()
-    scheduler.step()
     accuracy, margin = preference_diagnostics(report["seq_score"], targets)
     return float(lm_loss), accuracy, margin
 
