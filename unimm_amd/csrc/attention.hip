@@ -16,10 +16,36 @@
 //     softmax(raw scores) exactly as models/vilbert_dialog.py:1418 does.
 //   * P (bf16) feeds O^T = V^T . P^T directly from the accumulator registers (its key index is the
 //     MFMA's reduction index); V^T fragments come from ds_read_b64_tr_b16.
+#include <initializer_list>
 #include <type_traits>
 #include "common.h"
 
+// ---- A/B defaults (tools/build_variant.sh passes -D): 1 = what ships ----------------------------
+#ifndef UNIMM_ATTN_TILE_SWZ
+#define UNIMM_ATTN_TILE_SWZ 1      // 0 = the unswizzled dS^T / P tile (tile64_swz)
+#endif
+#ifndef UNIMM_ATTN_FEWQ_FWD
+#define UNIMM_ATTN_FEWQ_FWD 1      // 0 = attn_fwd_kernel<128, 8> for the few-query forward shape, as rounds 1-5
+#endif
+#ifndef UNIMM_ATTN_FEWQ128
+#define UNIMM_ATTN_FEWQ128 1       // 0 = the dQ + dK/dV kernel pair for the 37-query directions too
+#endif
+#ifndef UNIMM_ATTN_FEWK128
+#define UNIMM_ATTN_FEWK128 1       // 0 = the kernel pair for the text-attends-regions direction
+#endif
+
 namespace {
+
+// ---- LDS layouts --------------------------------------------------------------------------------
+// A kernel that carves `extern __shared__ char smem[]` has ONE layout type next to it (…Lds): the byte offset of every region and
+// the total `bytes`.  The kernel forms its pointers as smem + L::region and its launch passes L::bytes, so a region cannot be
+// added on one side only (an LDS access past the allocation does not fault here: it is dropped or reads zero).  Every layout
+// asserts that it fits a CU and that the regions accessed 16 bytes at a time start on a multiple of 16.
+constexpr int LDS_CU_BYTES = 160 * 1024;
+constexpr bool lds_aligned16(std::initializer_list<int> offsets) {
+  for (int o : offsets) if (o % 16 != 0) return false;
+  return true;
+}
 
 struct AttnParams {
   const bf16_t* q; const bf16_t* k; const bf16_t* v;
@@ -157,13 +183,24 @@ __device__ __forceinline__ void store_acc_row(bf16_t* __restrict__ g, const f32x
     }
 }
 
+// LDS of attn_fwd_kernel and attn_bwd_dq_kernel: the K and V images of the (sequence, head)
+template <int D, int NKT>
+struct KvImagesLds {
+  static constexpr int KPAD = NKT * 32;
+  static constexpr int kimg = 0;                          // [KPAD keys][D] bf16, chunk-swizzled (swz)
+  static constexpr int vimg = kimg + KPAD * 2 * D;        // the same of V
+  static constexpr int bytes = vimg + KPAD * 2 * D;
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({kimg, vimg}));
+};
+
 template <int D, int NKT>
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(AttnParams p) {
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = KvImagesLds<D, NKT>;
   constexpr int KPAD = NKT * 32;
-  char* kimg = smem;
-  char* vimg = smem + KPAD * 2 * D;
+  char *kimg = smem + L::kimg, *vimg = smem + L::vimg;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -346,9 +383,9 @@ template <int D, int NKT>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = KvImagesLds<D, NKT>;
   constexpr int KPAD = NKT * 32;
-  char* kimg = smem;
-  char* vimg = smem + KPAD * 2 * D;
+  char *kimg = smem + L::kimg, *vimg = smem + L::vimg;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -486,16 +523,29 @@ __device__ __forceinline__ uint32_t pad_key_bits(int Tk_b, int kt) {
 // ------------------------------------------------------------------------------------------------
 // MAXT = 256: the variant for <= 2 key tiles (37 region keys) -- 2 compute waves + 2 staging helpers, one wave per
 // SIMD, so the D = 128 instance gets 512 registers and stops spilling (148 bytes of scratch at 256)
+// LDS of this kernel -- and what BwdFusedLds and BwdFewq128Lds begin with: their kernels stage an item's queries the same way
+template <int D, int NQT>
+struct BwdDkvLds {
+  static constexpr int QPAD = NQT * 32;
+  static constexpr int qimg = 0;                                    // [QPAD queries][D] bf16, chunk-swizzled (swz)
+  static constexpr int doimg = qimg + QPAD * 2 * D;                 // the same of dO
+  static constexpr int lse_s = doimg + QPAD * 2 * D;                // [QPAD] fp32: -lse log2 e
+  static constexpr int del_s = lse_s + QPAD * (int)sizeof(float);   // [QPAD] fp32: delta
+  static constexpr int mw_s = del_s + QPAD * (int)sizeof(float);    // [8 key tiles (waves)][QPAD] inverted mask words
+  static constexpr int bytes = mw_s + 8 * QPAD * (int)sizeof(uint32_t);
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({qimg, doimg, lse_s, del_s, mw_s}));
+};
+
 template <int D, int NQT, int MAXT = 512>
 __global__ __launch_bounds__(MAXT, MAXT == 256 ? 1 : 2) void attn_bwd_dkv_kernel(AttnBwdParams p) {
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  using L = BwdDkvLds<D, NQT>;
   constexpr int QPAD = NQT * 32;
-  char* qimg = smem;
-  char* doimg = smem + QPAD * 2 * D;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * QPAD * 2 * D);
-  float* del_s = lse_s + QPAD;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + QPAD);   // [key tile (wave)][query] mask words
+  char *qimg = smem + L::qimg, *doimg = smem + L::doimg;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -658,8 +708,8 @@ __global__ __launch_bounds__(MAXT, MAXT == 256 ? 1 : 2) void attn_bwd_dkv_kernel
 //   32 ds_add_f32 per lane and tile (LDS float atomics run at a fraction of the plain rate: the first version of this
 //   kernel took 3x the time of the two-kernel path).  Scaled, rounded and written once at the end.
 //   delta = rowsum(dO o O) is formed while the images are staged (the two-kernel path got it from the dQ kernel).
-// LDS: Q / dO images 64 KiB + accumulator 68 KiB + dS tiles 16 KiB + lse / delta / mask words 10 KiB = 158 KiB: one
-// workgroup per CU -- which the 228-register dK / dV kernel was already (two waves per SIMD).
+// LDS: BwdFusedLds, within 2 KiB of what a CU has: one workgroup per CU -- which the 228-register dK / dV kernel was already
+// (two waves per SIMD).
 // ------------------------------------------------------------------------------------------------
 // What the three one-kernel backward forms put into LDS before their first barrier, per query of the item: -lse log2 e (-inf for
 // padded queries: P = 0 there), delta = sum_d dO[q, d] O[q, d] (D / 8 consecutive lanes share a row, 16-byte chunks, reduced by
@@ -770,10 +820,7 @@ __device__ __forceinline__ bf16x8 read_tr_tile64(const char* tile, int rowbase, 
 // The same tile with its 8-byte chunks XOR-swizzled by the row (chunk c of row r sits at c ^ ((r >> 2) & 7)): rows r and r + 4 are
 // 256 bytes = one pass over the banks apart, so the 8-byte dS^T stores of 16 lanes (rows r .. r + 15, one chunk) hit four bank
 // pairs four times each; swizzled they spread over all of them (SQ_LDS_BANK_CONFLICT was 31 % of the LDS-array cycles of the text
-// backward, profiles/r5x_attention_text_kernels_pmc.txt).
-#ifndef UNIMM_ATTN_TILE_SWZ
-#define UNIMM_ATTN_TILE_SWZ 1      // (A/B builds: 0 = the unswizzled tile)
-#endif
+// backward, profiles/r5x_attention_text_kernels_pmc.txt).  (A/B builds: UNIMM_ATTN_TILE_SWZ = 0 is the unswizzled tile.)
 __device__ __forceinline__ int tile64_swz(int row) { return UNIMM_ATTN_TILE_SWZ ? (row >> 2) & 7 : 0; }
 __device__ __forceinline__ bf16x8 read_tr_tile64s(const char* tile, int rowbase, int lane) {
   const int h = lane >> 5, i = lane & 15, qq = i >> 2, pp = i & 3;
@@ -803,20 +850,27 @@ __device__ __forceinline__ bf16x8 read_tr_tile64s(const char* tile, int rowbase,
 //             O^T[32 d][32 q] over all keys -- no accumulator is shared between waves; row sums are added in wave order.
 // Same scores, masks (-10000, reference :1418), dropout words and lse as attn_fwd_kernel; sums associate differently (per key
 // tile), i.e. results agree to fp32 rounding, and a packed (variable-length) run equals the padded one bit for bit as there.
-// LDS: V image 64 KiB + Q image 16 KiB + P tiles 32 KiB + row statistics 4 KiB = 116 KiB.
+// LDS: FwdFewq128Lds (one workgroup per CU).  (A/B builds: UNIMM_ATTN_FEWQ_FWD = 0 keeps attn_fwd_kernel<128, 8> for this shape.)
 // ------------------------------------------------------------------------------------------------
-#ifndef UNIMM_ATTN_FEWQ_FWD
-#define UNIMM_ATTN_FEWQ_FWD 1      // (A/B builds: 0 = attn_fwd_kernel<128, 8> for this shape, as rounds 1-5)
-#endif
+struct FwdFewq128Lds {
+  static constexpr int D = 128, KPAD = 256, QPAD = 64, NW = 8;
+  static constexpr int vimg = 0;                                       // [KPAD keys][D] bf16, chunk-swizzled (swz)
+  static constexpr int qimg = vimg + KPAD * 2 * D;                     // [QPAD queries][D] bf16, the same
+  static constexpr int pt = qimg + QPAD * 2 * D;                       // [key tile][query tile][32 q][32 keys] bf16
+  static constexpr int mx_w = pt + NW * 2 * 2048;                      // [wave][QPAD] fp32: the key tile's row maximum
+  static constexpr int sm_w = mx_w + NW * QPAD * (int)sizeof(float);   // [wave][QPAD] fp32: its partial row sum
+  static constexpr int bytes = sm_w + NW * QPAD * (int)sizeof(float);
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({vimg, qimg, pt}));
+};
+
 __global__ __launch_bounds__(512, 1) void attn_fwd_fewq128_kernel(AttnParams p) {
-  constexpr int D = 128, KPAD = 256, QPAD = 64, NW = 8;
+  using L = FwdFewq128Lds;
+  constexpr int D = L::D, KPAD = L::KPAD, QPAD = L::QPAD, NW = L::NW;
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* vimg = smem;
-  char* qimg = smem + KPAD * 2 * D;
-  char* pt = qimg + QPAD * 2 * D;                                  // [key tile][query tile][32 q][32 keys] bf16
-  float* mx_w = reinterpret_cast<float*>(pt + NW * 2 * 2048);       // [wave][QPAD]
-  float* sm_w = mx_w + NW * QPAD;
+  char *vimg = smem + L::vimg, *qimg = smem + L::qimg, *pt = smem + L::pt;
+  float *mx_w = reinterpret_cast<float*>(smem + L::mx_w), *sm_w = reinterpret_cast<float*>(smem + L::sm_w);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -958,20 +1012,28 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_fewq128_kernel(AttnParams p) 
 }
 
 template <int NQT>
+struct BwdFusedLds : BwdDkvLds<64, NQT> {                            // qimg, doimg, lse_s, del_s, mw_s, then
+  static constexpr int D = 64, QPAD = NQT * 32;
+  static constexpr int AS = D + 4;                                   // accumulator row stride in floats (16-byte accesses of 16 rows cover all banks)
+  static constexpr int scr = BwdDkvLds<D, NQT>::bytes;               // [wave][32 keys][32 queries] bf16: the wave's dS^T tile
+  static constexpr int acc = scr + 8 * 2048;                         // [QPAD q][AS] fp32: dQ (before the first barrier: the waves' K images)
+  static constexpr int turn = acc + QPAD * AS * (int)sizeof(float);  // [NQT] int: the wave whose turn it is to add its partial of that query tile
+  static constexpr int bytes = turn + NQT * (int)sizeof(int);
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({scr, acc}) && 8 * 32 * 2 * D <= turn - acc);   // (eight 32-row K images borrow the accumulator)
+};
+
+template <int NQT>
 __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnBwdParams p) {
-  constexpr int D = 64;
+  using L = BwdFusedLds<NQT>;
+  constexpr int D = L::D, QPAD = L::QPAD, AS = L::AS;
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int QPAD = NQT * 32;
-  constexpr int AS = D + 4;                                     // accumulator row stride in floats (16-byte accesses of 16 rows cover all banks)
-  char* qimg = smem;
-  char* doimg = smem + QPAD * 2 * D;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * QPAD * 2 * D);
-  float* del_s = lse_s + QPAD;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + QPAD);   // [key tile (wave)][query] mask words
-  char* scr = reinterpret_cast<char*>(mw_s + 8 * QPAD);         // [wave][32 keys][32 queries] bf16
-  float* acc = reinterpret_cast<float*>(scr + 8 * 2048);        // [QPAD q][AS] fp32
-  int* turn = reinterpret_cast<int*>(acc + QPAD * AS);          // [NQT]: the wave whose turn it is to add its partial of that query tile
+  char *qimg = smem + L::qimg, *doimg = smem + L::doimg, *scr = smem + L::scr;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
+  float* acc = reinterpret_cast<float*>(smem + L::acc);
+  int* turn = reinterpret_cast<int*>(smem + L::turn);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -1122,22 +1184,28 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnBwdParams p)
 // them twice, in kernels of 235 and 256 + 27 spilled registers), leaves dS^T in the wave's LDS tiles and keeps P^T / dS^T as bf16
 // MFMA operands (32 registers); dV and dK of the wave's keys then come out one 32-wide slice of D at a time; after a barrier dQ is
 // computed output-stationary (a wave = one 32-wide slice of one query tile, over all key tiles: K^T from the tiles' LDS images).
-// LDS: Q / dO images 32 KiB + K images 64 KiB + dS tiles 32 KiB + words 3 KiB = 131 KiB: one per CU.
+// LDS: BwdFewq128Lds: one workgroup per CU.
 // ------------------------------------------------------------------------------------------------
 template <int NQT>
+struct BwdFewq128Lds : BwdDkvLds<128, NQT> {                       // qimg, doimg, lse_s, del_s, mw_s, then
+  static constexpr int D = 128, QPAD = NQT * 32;
+  static constexpr int scr = BwdDkvLds<D, NQT>::bytes;              // [wave][query tile][32 keys][32 queries] bf16: the wave's dS^T tiles
+  static constexpr int kimgs = scr + 8 * NQT * 2048;                // [wave][32 keys][D] bf16: the wave's K tile, read back transposed for dQ
+  static constexpr int bytes = kimgs + 8 * 32 * 2 * D;
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({scr, kimgs}));
+};
+
+template <int NQT>
 __global__ __launch_bounds__(512, 2) void attn_bwd_fewq128_kernel(AttnBwdParams p) {
-  constexpr int D = 128;
+  using L = BwdFewq128Lds<NQT>;
+  constexpr int D = L::D, QPAD = L::QPAD;
   static_assert(NQT == 2, "the (sequence, head) item's queries are two 32-row tiles: P / dS of both stay in registers for phase 2");
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int QPAD = NQT * 32;
-  char* qimg = smem;
-  char* doimg = smem + QPAD * 2 * D;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * QPAD * 2 * D);
-  float* del_s = lse_s + QPAD;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + QPAD);   // [key tile (wave)][query] mask words
-  char* scr = reinterpret_cast<char*>(mw_s + 8 * QPAD);         // [wave][query tile][32 keys][32 queries] bf16: the wave's dS^T tiles
-  char* kimgs = scr + 8 * NQT * 2048;                           // [wave][32 keys][D] bf16: the wave's K tile, read back transposed for dQ
+  char *qimg = smem + L::qimg, *doimg = smem + L::doimg, *scr = smem + L::scr, *kimgs = smem + L::kimgs;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -1278,20 +1346,31 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fewq128_kernel(AttnBwdParams 
 // two key tiles (registers -> global); dK / dV are sums over ALL queries: every wave leaves its P^T / dS^T as MFMA operands in LDS,
 // and after one barrier wave w computes ONE output -- a 32-wide slice of dK or dV for both key tiles -- over all query tiles,
 // its Q^T / dO^T operand coming straight from global memory through a wave-private 2 KiB tile that is read back transposed
-// (phase 2 in the kernel).  148 KiB of LDS.  Replaces a dQ kernel (98 us per layer at 240 sequences) and a dK/dV kernel
+// (phase 2 in the kernel).  LDS: BwdFewk128Lds.  Replaces a dQ kernel (98 us per layer at 240 sequences) and a dK/dV kernel
 // (110 us, 312 registers) that formed S, dP, P, dS twice: 148 us.
 // ------------------------------------------------------------------------------------------------
+struct BwdFewk128Lds {
+  static constexpr int D = 128, NKT = 2, KPAD = NKT * 32, QMAX = 256, NQT = QMAX / 32;
+  static constexpr int kimg = 0;                                          // [KPAD keys][D] bf16, chunk-swizzled (swz)
+  static constexpr int vimg = kimg + KPAD * 2 * D;                        // the same of V
+  static constexpr int lse_s = vimg + KPAD * 2 * D;                       // [QMAX] fp32: -lse log2 e
+  static constexpr int del_s = lse_s + QMAX * (int)sizeof(float);         // [QMAX] fp32: delta
+  static constexpr int mw_s = del_s + QMAX * (int)sizeof(float);          // [key tile][QMAX] inverted mask words
+  static constexpr int scr = mw_s + NKT * QMAX * (int)sizeof(uint32_t);   // [wave][dS^T tile of key tile 0 | of key tile 1 | slice tile]: 3 x ([32][32] bf16)
+  static constexpr int bfrag = scr + 8 * 6144;                            // [key tile][query tile][dS | P][16-query half]: 1 KiB MFMA operands in register layout
+  static constexpr int bytes = bfrag + NKT * NQT * 2 * 2 * 1024;
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({kimg, vimg, lse_s, del_s, mw_s, scr, bfrag}));
+};
+
 __global__ __launch_bounds__(512, 2) void attn_bwd_fewk128_kernel(AttnBwdParams p) {
-  constexpr int D = 128, NKT = 2, KPAD = NKT * 32, QMAX = 256, NQT = QMAX / 32;
+  using L = BwdFewk128Lds;
+  constexpr int D = L::D, NKT = L::NKT, KPAD = L::KPAD, QMAX = L::QMAX, NQT = L::NQT;
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* kimg = smem;
-  char* vimg = smem + KPAD * 2 * D;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * KPAD * 2 * D);
-  float* del_s = lse_s + QMAX;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + QMAX);   // [key tile][query] mask words
-  char* scr = reinterpret_cast<char*>(mw_s + NKT * QMAX);       // [wave][dS^T tile of key tile 0 | of key tile 1 | slice tile]: 3 x ([32][32] bf16)
-  char* bfrag = scr + 8 * 6144;                                 // [key tile][query tile][dS | P][16-query half]: 1 KiB MFMA operands in register layout
+  char *kimg = smem + L::kimg, *vimg = smem + L::vimg, *scr = smem + L::scr, *bfrag = smem + L::bfrag;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int item = blockIdx.x;
   const int b = p.order != nullptr ? p.order[item / p.H] : item / p.H, head = item % p.H;
@@ -1453,7 +1532,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fewk128_kernel(AttnBwdParams 
 // waves then form dQ^T over all key tiles, in tile order.  The private wave stores its dK / dV per sequence; the shared tiles are
 // rounded to bf16 ONCE, after the walk (with `accumulate`, together with what the rows already hold).  No atomics, no scratch:
 // the result does not depend on how workgroups are scheduled.
-// LDS: Q / dO images 8 KiB + words 1.4 KiB + dS tiles 18 KiB + K images 40 KiB + V images 36 KiB + parking 16 KiB = 119 KiB.
+// LDS: SplicedBwdLds (Q / dO images, row words, dS^T tiles, K and V images, parking): one workgroup per CU.
 // ------------------------------------------------------------------------------------------------
 struct AttnSplBwdParams {
   AttnBwdParams b;
@@ -1498,20 +1577,34 @@ __device__ __forceinline__ void spl_score_tile(const DropoutArg& drop, uint32_t 
   }
 }
 
+// LDS of this kernel (QT = 1) and of attn_spliced_wide_bwd_kernel (QT = 2): QT = query tiles, and private key tiles, of a sequence
+template <int QT>
+struct SplicedBwdLds {
+  static constexpr int D = 64, PT = 8, NT = PT + QT, IMG = 32 * 2 * D;     // key tiles: PT shared, then the private ones; IMG: bytes of a 32-row image
+  static constexpr int qimg = 0;                                           // [QT query tiles][32][D] bf16, chunk-swizzled (swz)
+  static constexpr int doimg = qimg + QT * IMG;                            // the same of dO
+  static constexpr int lse_s = doimg + QT * IMG;                           // [32 QT queries] fp32: -lse log2 e
+  static constexpr int del_s = lse_s + 32 * QT * (int)sizeof(float);       // [32 QT queries] fp32: delta
+  static constexpr int mw_s = del_s + 32 * QT * (int)sizeof(float);        // [key tile][32 QT queries] INVERTED mask words of the tile's keys
+  static constexpr int scr = mw_s + NT * 32 * QT * (int)sizeof(uint32_t);  // [key tile][query tile][32 keys][32 queries] bf16 dS^T
+  static constexpr int kimg = scr + NT * QT * 2048;                        // [PT shared tiles + 2 buffers (alternating) x QT private tiles][32 keys][D] bf16
+  static constexpr int vimg = kimg + (PT + 2 * QT) * IMG;                  // [PT shared tiles + the private tile (at work)][32 keys][D] bf16
+  static constexpr int park = vimg + (PT + 1) * IMG;                       // [64 registers][64 lanes] fp32: see `both` in the kernels
+  static constexpr int bytes = park + 64 * 64 * (int)sizeof(float);
+  static_assert(bytes <= LDS_CU_BYTES);
+  static_assert(lds_aligned16({qimg, doimg, lse_s, del_s, mw_s, scr, kimg, vimg}));
+};
+
 __global__ __launch_bounds__(512, 2) void attn_spliced_bwd_kernel(AttnSplBwdParams sp) {
-  constexpr int D = 64, NT = 9, PT = 8, PW = 7, IMG = 32 * 2 * D;   // PT: the private tile, PW: its wave; IMG: bytes of a 32-row image
+  using L = SplicedBwdLds<1>;
+  constexpr int D = L::D, NT = L::NT, PT = L::PT, PW = 7, IMG = L::IMG;   // PT: the private tile, PW: its wave
   AttnBwdParams& p = sp.b;
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qimg = smem;
-  char* doimg = smem + IMG;
-  float* lse_s = reinterpret_cast<float*>(smem + 2 * IMG);
-  float* del_s = lse_s + 32;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + 32);     // [key tile][query] INVERTED mask words of the tile's keys
-  char* scr = reinterpret_cast<char*>(mw_s + NT * 32);          // [key tile][32 keys][32 queries] bf16 dS^T
-  char* kimg = scr + NT * 2048;                                 // [8 shared tiles + 2 private (alternating)][32 keys][D] bf16
-  char* vimg = kimg + (NT + 1) * IMG;                           // [key tile][32 keys][D] bf16
-  float* park = reinterpret_cast<float*>(vimg + NT * IMG);      // [64 registers][64 lanes]: see `both` below
+  char *qimg = smem + L::qimg, *doimg = smem + L::doimg, *scr = smem + L::scr, *kimg = smem + L::kimg, *vimg = smem + L::vimg;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
+  float* park = reinterpret_cast<float*>(smem + L::park);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int g = blockIdx.x / p.H, head = blockIdx.x % p.H;
   const int r = lane & 31, h = lane >> 5;
@@ -1746,27 +1839,18 @@ __global__ __launch_bounds__(512, 2) void attn_spliced_bwd_kernel(AttnSplBwdPara
 //     the shared tiles then the private tiles, in tile order.
 //   * the V rows of a private tile are read by their own wave only, so ONE private V image serves both tiles: the wave loads it
 //     right before the tile's passes (its own LDS accesses execute in order).
-// LDS: Q / dO images 16 KiB + words 3 KiB + dS tiles 40 KiB + K images 48 KiB (8 shared, 2 x 2 private, alternating) + V images
-// 36 KiB + parking 16 KiB = 159 KiB of the CU's 160: one workgroup per CU, as the narrow kernel's 119 KiB already give.
+// LDS: SplicedBwdLds<2>, within 1 KiB of what a CU has: one workgroup per CU, as the narrow kernel's layout already gives.
 // ------------------------------------------------------------------------------------------------
-constexpr int SPLW_NT = 10;                                       // key tiles: 8 shared + 2 private
-constexpr size_t SPLW_LDS = 2 * 8192 + 2 * 64 * sizeof(float) + SPLW_NT * 64 * sizeof(uint32_t) + SPLW_NT * 2 * 2048 +
-                            (size_t)(8 + 4) * 4096 + 9 * 4096 + 64 * 64 * sizeof(float);
-
 __global__ __launch_bounds__(512, 1) void attn_spliced_wide_bwd_kernel(AttnSplBwdParams sp) {
-  constexpr int D = 64, NT = SPLW_NT, PT = 8, PW = 7, IMG = 32 * 2 * D;
+  using L = SplicedBwdLds<2>;
+  constexpr int D = L::D, NT = L::NT, PT = L::PT, PW = 7, IMG = L::IMG;
   AttnBwdParams& p = sp.b;
   drop_resolve(p.drop);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* qimg = smem;                                            // [2 query tiles][32][D] bf16
-  char* doimg = smem + 2 * IMG;
-  float* lse_s = reinterpret_cast<float*>(smem + 4 * IMG);      // [64 queries]
-  float* del_s = lse_s + 64;
-  uint32_t* mw_s = reinterpret_cast<uint32_t*>(del_s + 64);     // [key tile][64 queries] INVERTED mask words of the tile's keys
-  char* scr = reinterpret_cast<char*>(mw_s + NT * 64);          // [key tile][query tile][32 keys][32 queries] bf16 dS^T
-  char* kimg = scr + NT * 2 * 2048;                             // [8 shared tiles + 2 buffers x 2 private tiles][32 keys][D] bf16
-  char* vimg = kimg + (PT + 4) * IMG;                           // [8 shared tiles + the private tile at work][32 keys][D] bf16
-  float* park = reinterpret_cast<float*>(vimg + (PT + 1) * IMG);   // [64 registers][64 lanes]
+  char *qimg = smem + L::qimg, *doimg = smem + L::doimg, *scr = smem + L::scr, *kimg = smem + L::kimg, *vimg = smem + L::vimg;
+  float *lse_s = reinterpret_cast<float*>(smem + L::lse_s), *del_s = reinterpret_cast<float*>(smem + L::del_s);
+  uint32_t* mw_s = reinterpret_cast<uint32_t*>(smem + L::mw_s);
+  float* park = reinterpret_cast<float*>(smem + L::park);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int g = blockIdx.x / p.H, head = blockIdx.x % p.H;
   const int r = lane & 31, h = lane >> 5;
@@ -2003,23 +2087,15 @@ __global__ __launch_bounds__(512, 1) void attn_spliced_wide_bwd_kernel(AttnSplBw
   }
 }
 
-// Workgroups per (sequence, head).  Default: one workgroup (up to 8 waves) per item.  Two 4-wave
-// workgroups per item fit two to a CU and overlap each other's staging, but both stage the full K/V
-// (or Q/dO) images: measured 589 vs 545 us for the text fwd+bwd trio, so it stays a tuning knob.
-constexpr int g_attn_parts = 0;   // compile-time choice: 0 = one workgroup per item (2 = two 4-wave workgroups, 99 = no helper waves)
+// ---- launches.  A workgroup is one (sequence, head) item: `parts` = 1, written by the fill functions below.  (Two 4-wave workgroups
+// per item fit two to a CU and overlap each other's staging, but both stage the full images: 589 vs 545 us for the text fwd+bwd trio.)
+//
 // Threads per workgroup: one wave per 32-row tile that computes, but never fewer than the staging needs.
 // The co-attention direction with 37 region queries (or keys) has 2 compute waves and 2 x 64 KiB of text
 // K/V (or Q/dO) to stage; with 128 threads that is 32 dependent load->ds_write rounds per image.  Extra
-// waves stage, then leave at the per-wave exit right after the barrier.  (g_attn_parts == 99: off, for A/B.)
-inline int block_threads(int tiles_per_part, int staged_rows) {
-  int waves = tiles_per_part;
-  if (g_attn_parts != 99 && staged_rows >= 128 && waves < 8) waves = 8;
-  return waves * 64;
-}
-inline int parts_for(int tiles, size_t lds) {
-  (void)lds;
-  if (g_attn_parts > 0 && g_attn_parts != 99) return tiles > 4 ? g_attn_parts : 1;
-  return 1;
+// waves stage, then leave at the per-wave exit right after the barrier.
+inline int block_threads(int tiles, int staged_rows) {
+  return (staged_rows >= 128 && tiles < 8 ? 8 : tiles) * 64;
 }
 
 template <typename K>
@@ -2030,105 +2106,35 @@ int set_lds(K kern, size_t lds) {
   return UNIMM_OK;
 }
 
-template <int D, int NKT>
-int launch_bwd_dq(const AttnBwdParams& p, hipStream_t s) {
-  const size_t lds = (size_t)2 * NKT * 32 * 2 * D;
-  auto kern = attn_bwd_dq_kernel<D, NKT>;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnBwdParams q = p;
-  const int tiles = (p.Tq + 31) / 32;
-  q.parts = parts_for(tiles, lds);
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H * q.parts), dim3(block_threads((tiles + q.parts - 1) / q.parts, NKT * 32)), lds, s, q);
+// One launch of `grid` workgroups: lds_bytes is the kernel's layout (L::bytes), and nothing else
+template <typename K, typename P>
+int launch_items(K kern, size_t lds_bytes, int grid, int threads, const P& params, hipStream_t s) {
+  if (set_lds(kern, lds_bytes) != UNIMM_OK) return UNIMM_E_HIP;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds_bytes, s, params);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
+}
+
+template <int D, int NKT>
+int launch_bwd_dq(const AttnBwdParams& p, hipStream_t s) {
+  const int tiles = (p.Tq + 31) / 32;
+  return launch_items(attn_bwd_dq_kernel<D, NKT>, KvImagesLds<D, NKT>::bytes, p.B * p.H, block_threads(tiles, NKT * 32), p, s);
 }
 
 template <int D, int NQT>
 int launch_bwd_dkv(const AttnBwdParams& p, hipStream_t s) {
-  const size_t lds = (size_t)2 * NQT * 32 * 2 * D + 2 * NQT * 32 * sizeof(float) + (size_t)8 * NQT * 32 * sizeof(uint32_t);
-  AttnBwdParams q = p;
   const int tiles = (p.Tk + 31) / 32;
-  q.parts = parts_for(tiles, lds);
   if constexpr (D == 128 && NQT == 8) {   // (the 37x37 image self-attention, NQT = 2, lives on many small workgroups per CU)
-    if (tiles <= 2 && q.parts == 1 && g_attn_parts != 99) {
-      auto k4 = attn_bwd_dkv_kernel<D, NQT, 256>;
-      if (set_lds(k4, lds) != UNIMM_OK) return UNIMM_E_HIP;
-      hipLaunchKernelGGL(k4, dim3(p.B * p.H), dim3(256), lds, s, q);
-      UNIMM_CHECK_LAUNCH();
-      return UNIMM_OK;
-    }
+    if (tiles <= 2) return launch_items(attn_bwd_dkv_kernel<D, NQT, 256>, BwdDkvLds<D, NQT>::bytes, p.B * p.H, 256, p, s);
   }
-  auto kern = attn_bwd_dkv_kernel<D, NQT>;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H * q.parts), dim3(block_threads((tiles + q.parts - 1) / q.parts, NQT * 32)), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
-}
-
-template <int NQT>
-int launch_bwd_fused(const AttnBwdParams& p, hipStream_t s) {
-  constexpr int D = 64, QPAD = NQT * 32;
-  const size_t lds = (size_t)2 * QPAD * 2 * D + 2 * QPAD * sizeof(float) + (size_t)8 * QPAD * sizeof(uint32_t) + 8 * 2048 +
-                     (size_t)QPAD * (D + 4) * sizeof(float) + NQT * sizeof(int);
-  auto kern = attn_bwd_fused_kernel<NQT>;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnBwdParams q = p;
-  q.parts = 1;
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H), dim3(512), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
-}
-
-inline int launch_bwd_fewq128(const AttnBwdParams& p, hipStream_t s) {
-  constexpr int D = 128, NQT = 2, QPAD = NQT * 32;
-  const size_t lds = (size_t)2 * QPAD * 2 * D + 2 * QPAD * sizeof(float) + (size_t)8 * QPAD * sizeof(uint32_t) + 8 * NQT * 2048 +
-                     (size_t)8 * 32 * 2 * D;
-  auto kern = attn_bwd_fewq128_kernel<NQT>;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnBwdParams q = p;
-  q.parts = 1;
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H), dim3(512), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
-}
-
-inline int launch_bwd_fewk128(const AttnBwdParams& p, hipStream_t s) {
-  constexpr int D = 128, KPAD = 64, QMAX = 256;
-  const size_t lds = (size_t)2 * KPAD * 2 * D + 2 * QMAX * sizeof(float) + (size_t)2 * QMAX * sizeof(uint32_t) + 8 * 6144 +
-                     (size_t)2 * (QMAX / 32) * 2 * 2 * 1024;
-  auto kern = attn_bwd_fewk128_kernel;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnBwdParams q = p;
-  q.parts = 1;
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H), dim3(512), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
-}
-
-inline int launch_fwd_fewq128(const AttnParams& p, hipStream_t s) {
-  const size_t lds = (size_t)256 * 2 * 128 + (size_t)64 * 2 * 128 + 8 * 2 * 2048 + 2 * 8 * 64 * sizeof(float);
-  auto kern = attn_fwd_fewq128_kernel;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnParams q = p;
-  q.parts = 1;
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H), dim3(512), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
+  return launch_items(attn_bwd_dkv_kernel<D, NQT>, BwdDkvLds<D, NQT>::bytes, p.B * p.H, block_threads(tiles, NQT * 32), p, s);
 }
 
 template <int D, int NKT>
 int launch_fwd(const AttnParams& p, hipStream_t s) {
-  const int waves = (p.Tq + 31) / 32;
-  const size_t lds = (size_t)2 * NKT * 32 * 2 * D;
-  auto kern = attn_fwd_kernel<D, NKT>;
-  if (set_lds(kern, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  AttnParams q = p;
-  q.parts = parts_for(waves, lds);
-  int threads = block_threads((waves + q.parts - 1) / q.parts, NKT * 32);
-  if (D == 64 && threads > 256 && g_attn_parts != 99) threads = 256;   // 4 waves walk the 8 query tiles: two workgroups per CU
-  hipLaunchKernelGGL(kern, dim3(p.B * p.H * q.parts), dim3(threads), lds, s, q);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
+  int threads = block_threads((p.Tq + 31) / 32, NKT * 32);
+  if (D == 64 && threads > 256) threads = 256;   // 4 waves walk the 8 query tiles: two workgroups per CU
+  return launch_items(attn_fwd_kernel<D, NKT>, KvImagesLds<D, NKT>::bytes, p.B * p.H, threads, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2199,34 +2205,76 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(AttnParams p, float* __
   }
 }
 
-}  // namespace
-
-// unimm_attn_fwd, and (train_seg) unimm_attn_spliced_fwd: the same launch with dropout allowed beside a shared segment
-static int attn_fwd_entry(const unimm_attn_args* a, void* stream, bool train_seg) {
-  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->mask) return UNIMM_E_ARG;
+// ---- arguments -> kernel parameters, one function per argument family.  The order of the checks is part of the interface
+// (tests/test_attention_refusals.py): pointers (UNIMM_E_ARG), shape, alignment, then the words that describe the layout.
+// unimm_attn_args.  values = false: a launch that reads q, k and the mask only (v, out and their strides are not looked at).
+int fill_fwd(const unimm_attn_args* a, AttnParams& p, bool values) {
+  if (a == nullptr || !a->q || !a->k || !a->mask || (values && (!a->v || !a->out))) return UNIMM_E_ARG;
   if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->Tk <= 0 || a->Tq > 256 || a->Tk > 256) return UNIMM_E_SHAPE;
   if (a->D != 64 && a->D != 128) return UNIMM_E_SHAPE;
-  if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8)) return UNIMM_E_ALIGN;   // result rows leave as 16-byte stores (store_acc_row)
-  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) & 15) return UNIMM_E_ALIGN;
-  AttnParams p;
+  if ((a->ldq % 8) || (a->ldk % 8) || (values && ((a->ldv % 8) || (a->ldo % 8)))) return UNIMM_E_ALIGN;   // result rows leave as 16-byte stores (store_acc_row)
+  if (((uintptr_t)a->q | (uintptr_t)a->k) & 15) return UNIMM_E_ALIGN;
+  if (values && (((uintptr_t)a->v | (uintptr_t)a->out) & 15)) return UNIMM_E_ALIGN;
+  if ((a->q_off == nullptr) != (a->q_len == nullptr) || (a->k_off == nullptr) != (a->k_len == nullptr)) return UNIMM_E_ARG;
+  if ((a->ks_off == nullptr) != (a->ks_len == nullptr)) return UNIMM_E_ARG;
+  if (a->ks_off != nullptr && (a->k_off == nullptr || a->ks_ins < 0)) return UNIMM_E_ARG;   // a shared segment: variable-length keys
   p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v;
   p.o = (bf16_t*)a->out; p.lse = a->lse; p.mask = a->mask;
   p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
-  if ((p.q_off == nullptr) != (p.q_len == nullptr) || (p.k_off == nullptr) != (p.k_len == nullptr)) return UNIMM_E_ARG;
-  p.ks_off = a->ks_off; p.ks_len = a->ks_len; p.ks_ins = a->ks_ins;
-  if ((p.ks_off == nullptr) != (p.ks_len == nullptr)) return UNIMM_E_ARG;
-  if (p.ks_off != nullptr && (p.k_off == nullptr || a->ks_ins < 0 || (a->drop_thr != 0u && !train_seg))) return UNIMM_E_ARG;   // variable-length keys, inference
-  if (p.ks_off == nullptr) p.ks_ins = 0;
+  p.ks_off = a->ks_off; p.ks_len = a->ks_len; p.ks_ins = a->ks_off != nullptr ? a->ks_ins : 0;
   p.order = a->order;
   p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
   p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo;
   p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride;
+  p.parts = 1;
   p.scale = a->scale;
-  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt;
+  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt; p.drop.key2 = 0u;
+  return UNIMM_OK;
+}
+
+// unimm_attn_bwd_args and unimm_attn_spliced_bwd_args (the same fields, then the segment and the groups).  `delta` is the caller's
+// to require; bad_shape: what a shape that no kernel takes is called (the spliced entries take one shape: UNIMM_E_ARG).
+template <typename A>
+int fill_bwd(const A* a, AttnBwdParams& p, int bad_shape) {
+  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->dout || !a->lse || !a->dq || !a->dk || !a->dv || !a->mask)
+    return UNIMM_E_ARG;
+  if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->Tk <= 0 || a->Tq > 256 || a->Tk > 256) return bad_shape;
+  if (a->D != 64 && a->D != 128) return bad_shape;
+  if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8) || (a->lddo % 8) || (a->lddq % 8) || (a->lddk % 8) ||
+      (a->lddv % 8))
+    return UNIMM_E_ALIGN;                                         // dQ / dK / dV rows leave as 16-byte stores (store_acc_row)
+  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out | (uintptr_t)a->dout | (uintptr_t)a->dq |
+       (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
+    return UNIMM_E_ALIGN;
+  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v; p.o = (const bf16_t*)a->out;
+  p.dout = (const bf16_t*)a->dout; p.lse = a->lse; p.delta = a->delta;
+  p.dq = (bf16_t*)a->dq; p.dk = (bf16_t*)a->dk; p.dv = (bf16_t*)a->dv; p.mask = a->mask;
+  p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
+  p.order = a->order;
+  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
+  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.lddo = a->lddo;
+  p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
+  p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride;
+  p.parts = 1;
+  p.scale = a->scale;
+  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt; p.drop.key2 = 0u;
+  return UNIMM_OK;
+}
+
+}  // namespace
+
+// unimm_attn_fwd, and (train_seg) unimm_attn_spliced_fwd: the same launch with dropout allowed beside a shared segment
+static int attn_fwd_entry(const unimm_attn_args* a, void* stream, bool train_seg) {
+  AttnParams p;
+  const int rc = fill_fwd(a, p, true);
+  if (rc != UNIMM_OK) return rc;
+  if (p.ks_off != nullptr && a->drop_thr != 0u && !train_seg) return UNIMM_E_ARG;   // a shared segment through unimm_attn_fwd: inference
   hipStream_t s = (hipStream_t)stream;
+  const int items = p.B * p.H;
   const bool small_k = a->Tk <= 64;
   if (a->D == 64) return small_k ? launch_fwd<64, 2>(p, s) : launch_fwd<64, 8>(p, s);
-  if (UNIMM_ATTN_FEWQ_FWD && !small_k && a->Tq <= 64 && p.ks_off == nullptr) return launch_fwd_fewq128(p, s);   // few queries, many keys
+  if (UNIMM_ATTN_FEWQ_FWD && !small_k && a->Tq <= 64 && p.ks_off == nullptr)      // few queries, many keys
+    return launch_items(attn_fwd_fewq128_kernel, FwdFewq128Lds::bytes, items, 512, p, s);
   return small_k ? launch_fwd<128, 2>(p, s) : launch_fwd<128, 8>(p, s);
 }
 
@@ -2242,21 +2290,11 @@ extern "C" int unimm_attn_spliced_fwd(const unimm_attn_args* a, void* stream) { 
 extern "C" int unimm_attn_spliced_wide_fwd(const unimm_attn_args* a, void* stream) { return attn_spliced_fwd_entry(a, stream, 64); }
 
 extern "C" int unimm_attn_probs(const unimm_attn_args* a, float* probs, void* stream) {
-  if (a == nullptr || !a->q || !a->k || !a->mask || !probs) return UNIMM_E_ARG;
+  if (a == nullptr || !probs) return UNIMM_E_ARG;
   if (a->q_off || a->q_len || a->k_off || a->k_len || a->ks_off || a->ks_len) return UNIMM_E_ARG;   // fixed layout only
-  if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->Tk <= 0 || a->Tq > 256 || a->Tk > 256) return UNIMM_E_SHAPE;
-  if (a->D != 64 && a->D != 128) return UNIMM_E_SHAPE;
-  if ((a->ldq % 8) || (a->ldk % 8) || (((uintptr_t)a->q | (uintptr_t)a->k) & 15)) return UNIMM_E_ALIGN;
   AttnParams p;
-  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = nullptr; p.o = nullptr; p.lse = nullptr; p.mask = a->mask;
-  p.q_off = p.q_len = p.k_off = p.k_len = nullptr;
-  p.ks_off = p.ks_len = nullptr; p.ks_ins = 0;
-  p.order = nullptr;
-  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
-  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = 0; p.ldo = 0;
-  p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride; p.parts = 1;
-  p.scale = a->scale;
-  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt; p.drop.key2 = 0u;
+  const int rc = fill_fwd(a, p, false);
+  if (rc != UNIMM_OK) return rc;
   const long rows = (long)a->B * a->H * a->Tq;
   const unsigned blocks = (unsigned)((rows + 3) / 4);
   if (a->D == 64) hipLaunchKernelGGL(attn_probs_kernel<64>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, probs);
@@ -2266,44 +2304,22 @@ extern "C" int unimm_attn_probs(const unimm_attn_args* a, float* probs, void* st
 }
 
 extern "C" int unimm_attn_bwd(const unimm_attn_bwd_args* a, void* stream) {
-  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->dout || !a->lse || !a->delta || !a->dq || !a->dk ||
-      !a->dv || !a->mask)
-    return UNIMM_E_ARG;
-  if (a->B <= 0 || a->H <= 0 || a->Tq <= 0 || a->Tk <= 0 || a->Tq > 256 || a->Tk > 256) return UNIMM_E_SHAPE;
-  if (a->D != 64 && a->D != 128) return UNIMM_E_SHAPE;
-  if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8) || (a->lddo % 8) || (a->lddq % 8) || (a->lddk % 8) ||
-      (a->lddv % 8))
-    return UNIMM_E_ALIGN;                                         // dQ / dK / dV rows leave as 16-byte stores (store_acc_row)
-  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out | (uintptr_t)a->dout | (uintptr_t)a->dq |
-       (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
-    return UNIMM_E_ALIGN;
+  if (a == nullptr || !a->delta) return UNIMM_E_ARG;
   AttnBwdParams p;
-  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v; p.o = (const bf16_t*)a->out;
-  p.dout = (const bf16_t*)a->dout; p.lse = a->lse; p.delta = a->delta;
-  p.dq = (bf16_t*)a->dq; p.dk = (bf16_t*)a->dk; p.dv = (bf16_t*)a->dv; p.mask = a->mask;
-  p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
+  int rc = fill_bwd(a, p, UNIMM_E_SHAPE);
+  if (rc != UNIMM_OK) return rc;
   if ((p.q_off == nullptr) != (p.q_len == nullptr) || (p.k_off == nullptr) != (p.k_len == nullptr)) return UNIMM_E_ARG;
-  p.order = a->order;
-  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
-  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.lddo = a->lddo;
-  p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
-  p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride;
-  p.scale = a->scale;
-  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt;
   hipStream_t s = (hipStream_t)stream;
+  const int items = p.B * p.H;
   const bool small_k = a->Tk <= 64, small_q = a->Tq <= 64;
-  if (a->D == 64 && !small_k && !small_q) return launch_bwd_fused<8>(p, s);   // text self-attention: one kernel
-#ifndef UNIMM_ATTN_FEWQ128
-#define UNIMM_ATTN_FEWQ128 1     // (A/B builds: 0 = the dQ + dK/dV kernel pair for the 37-query directions too)
-#endif
+  if (a->D == 64 && !small_k && !small_q)                         // text self-attention: one kernel
+    return launch_items(attn_bwd_fused_kernel<8>, BwdFusedLds<8>::bytes, items, 512, p, s);
   // regions attend text (37 queries x up to 256 keys): one kernel, 133 against 94 + 134 us per layer at 240 sequences.  (The 37 x 37
   // image self-attention stays on the pair of small workgroups: two active key-tile waves in a one-per-CU workgroup were 95 against 81 us.)
-  if (UNIMM_ATTN_FEWQ128 && a->D == 128 && small_q && !small_k) return launch_bwd_fewq128(p, s);
-#ifndef UNIMM_ATTN_FEWK128
-#define UNIMM_ATTN_FEWK128 1     // (A/B builds: 0 = the kernel pair for the text-attends-regions direction)
-#endif
-  if (UNIMM_ATTN_FEWK128 && a->D == 128 && small_k && !small_q) return launch_bwd_fewk128(p, s);   // text attends regions: one kernel
-  int rc;
+  if (UNIMM_ATTN_FEWQ128 && a->D == 128 && small_q && !small_k)
+    return launch_items(attn_bwd_fewq128_kernel<2>, BwdFewq128Lds<2>::bytes, items, 512, p, s);
+  if (UNIMM_ATTN_FEWK128 && a->D == 128 && small_k && !small_q)   // text attends regions: one kernel
+    return launch_items(attn_bwd_fewk128_kernel, BwdFewk128Lds::bytes, items, 512, p, s);
   if (a->D == 64) rc = small_k ? launch_bwd_dq<64, 2>(p, s) : launch_bwd_dq<64, 8>(p, s);
   else rc = small_k ? launch_bwd_dq<128, 2>(p, s) : launch_bwd_dq<128, 8>(p, s);
   if (rc != UNIMM_OK) return rc;
@@ -2313,45 +2329,20 @@ extern "C" int unimm_attn_bwd(const unimm_attn_bwd_args* a, void* stream) {
 
 // unimm_attn_spliced_bwd (max_tq = 32) and unimm_attn_spliced_wide_bwd (max_tq = 64): the same checks and arguments, their own kernels
 static int attn_spliced_bwd_entry(const unimm_attn_spliced_bwd_args* a, void* stream, int max_tq) {
-  if (a == nullptr || !a->q || !a->k || !a->v || !a->out || !a->dout || !a->lse || !a->dq || !a->dk || !a->dv || !a->mask)
-    return UNIMM_E_ARG;
+  if (a == nullptr) return UNIMM_E_ARG;
   if (!a->q_off || !a->q_len || !a->k_off || !a->k_len || !a->ks_off || !a->ks_len || a->ks_ins < 0) return UNIMM_E_ARG;
   if (!a->g_first || !a->g_seq || a->G <= 0) return UNIMM_E_ARG;
-  if (a->B <= 0 || a->H <= 0 || a->D != 64 || a->Tq <= 0 || a->Tq > max_tq || a->Tk <= 0 || a->Tk > 256) return UNIMM_E_ARG;
-  if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->ldo % 8) || (a->lddo % 8) || (a->lddq % 8) || (a->lddk % 8) ||
-      (a->lddv % 8))
-    return UNIMM_E_ALIGN;
-  if (((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out | (uintptr_t)a->dout | (uintptr_t)a->dq |
-       (uintptr_t)a->dk | (uintptr_t)a->dv) & 15)
-    return UNIMM_E_ALIGN;
+  if (a->D != 64 || a->Tq > max_tq) return UNIMM_E_ARG;           // (the other bounds: fill_bwd)
   AttnSplBwdParams sp;
-  AttnBwdParams& p = sp.b;
-  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.v = (const bf16_t*)a->v; p.o = (const bf16_t*)a->out;
-  p.dout = (const bf16_t*)a->dout; p.lse = a->lse; p.delta = nullptr;
-  p.dq = (bf16_t*)a->dq; p.dk = (bf16_t*)a->dk; p.dv = (bf16_t*)a->dv; p.mask = a->mask;
-  p.q_off = a->q_off; p.q_len = a->q_len; p.k_off = a->k_off; p.k_len = a->k_len;
-  p.order = nullptr;
-  p.B = a->B; p.H = a->H; p.Tq = a->Tq; p.Tk = a->Tk;
-  p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.lddo = a->lddo;
-  p.lddq = a->lddq; p.lddk = a->lddk; p.lddv = a->lddv;
-  p.mask_q_stride = a->mask_q_stride; p.mask_b_stride = a->mask_b_stride;
-  p.parts = 1;
-  p.scale = a->scale;
-  p.drop.key = a->drop_key; p.drop.thr = a->drop_thr; p.drop.scale = a->drop_scale; p.drop.salt = a->drop_salt;
+  const int rc = fill_bwd(a, sp.b, UNIMM_E_ARG);
+  if (rc != UNIMM_OK) return rc;
+  sp.b.delta = nullptr; sp.b.order = nullptr;                     // not read: a workgroup is a (group, head), delta is formed in the kernel
   sp.ks_off = a->ks_off; sp.ks_len = a->ks_len; sp.ks_ins = a->ks_ins;
   sp.g_first = a->g_first; sp.g_seq = a->g_seq; sp.G = a->G;
   sp.accumulate = a->accumulate;
-  if (max_tq > 32) {
-    if (set_lds(attn_spliced_wide_bwd_kernel, SPLW_LDS) != UNIMM_OK) return UNIMM_E_HIP;
-    hipLaunchKernelGGL(attn_spliced_wide_bwd_kernel, dim3(a->G * a->H), dim3(512), SPLW_LDS, (hipStream_t)stream, sp);
-    UNIMM_CHECK_LAUNCH();
-    return UNIMM_OK;
-  }
-  constexpr size_t lds = 2 * 4096 + 2 * 32 * sizeof(float) + 9 * 32 * sizeof(uint32_t) + 9 * 2048 + (size_t)(10 + 9) * 4096 + 64 * 64 * sizeof(float);
-  if (set_lds(attn_spliced_bwd_kernel, lds) != UNIMM_OK) return UNIMM_E_HIP;
-  hipLaunchKernelGGL(attn_spliced_bwd_kernel, dim3(a->G * a->H), dim3(512), lds, (hipStream_t)stream, sp);
-  UNIMM_CHECK_LAUNCH();
-  return UNIMM_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (max_tq > 32) return launch_items(attn_spliced_wide_bwd_kernel, SplicedBwdLds<2>::bytes, a->G * a->H, 512, sp, s);
+  return launch_items(attn_spliced_bwd_kernel, SplicedBwdLds<1>::bytes, a->G * a->H, 512, sp, s);
 }
 
 extern "C" int unimm_attn_spliced_bwd(const unimm_attn_spliced_bwd_args* a, void* stream) { return attn_spliced_bwd_entry(a, stream, 32); }
