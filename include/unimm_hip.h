@@ -967,6 +967,50 @@ int unimm_lm_sample_rows(const float* logits, int32_t rows, int32_t V, int32_t l
                          uint32_t key, const int32_t* stream_ids, int32_t* token, float* logp, float* logq, float* lse,
                          void* stream);
 
+/* A per-row token HISTORY for unimm_lm_topk_hist / unimm_lm_sample_hist: what each row's hypothesis has already said, and the
+ * two rules that depend on it (generate_answers' no_repeat_ngram_size / repetition_penalty / repeat_scope).  Row r has the
+ * SOURCES  a = hist[r, 0:k), k = hist_len[r] clamped to [0, ldh]  (its answer tokens), and, when ctx is not NULL,
+ * s = ctx[i, 0:ctx_len[i]), i = ctx_idx[r] clamped to [0, nctx), the length clamped to [0, ldc]  (its dialog's context tokens).
+ *  - N-GRAM rule, ngram = n in [1, 8] (0 = off): when k >= n - 1, id t is banned for the row if some source s and some end
+ *    e >= n - 1 have s[e-n+1 .. e) == a[k-n+1 .. k) and s[e] == t.  A window lies inside ONE source; overlapping windows count
+ *    (n = 2 after `a a` bans a); n = 1 bans every id of the sources; k < n - 1 bans nothing from either source.  `sep` (this
+ *    struct's) is never banned by the rule; source ids outside [0, V) ban nothing but compare as integers.  Such a ban acts
+ *    exactly like an id of `banned`: -inf after the log-sum-exp, no renormalisation, out of the eligible set of step 1.
+ *  - PENALTY rule, penalty = r != 1: every id i that occurs in a source is SELECTED by x'_i = x_i > 0 ? x_i * inv_penalty :
+ *    x_i * penalty -- one correctly rounded fp32 product, rounded before anything is subtracted from it -- and every other id by
+ *    x_i.  The rank order, top-k, y, q, nucleus, draw and logq of unimm_lm_sample's steps 2-6 are those of the row x'; lse and
+ *    logp are those of the raw row x.  unimm_lm_topk_hist orders its K ids by x' and reports x_i - lse for each.
+ *    inv_penalty is the caller's fp32 1 / r (a product, not a division, so a caller can reproduce x' bit for bit).
+ * Refused before any launch: a NULL struct, penalty or inv_penalty not positive and finite, hist NULL with ngram > 0 or
+ * penalty != 1, hist without hist_len, ctx without ctx_len or ctx_idx (UNIMM_E_ARG); ngram outside [0, 8], ldh outside
+ * [0, 128], ldc outside [0, 256], nctx < 1 with a ctx (UNIMM_E_SHAPE).  With ngram = 0 and penalty = 1 nothing of the
+ * history is used and the launch computes what the plain entry point computes. */
+typedef struct {
+  const int32_t* hist; const int32_t* hist_len;  /* int32 [rows, ldh], int32 [rows], device */
+  const int32_t* ctx; const int32_t* ctx_len; const int32_t* ctx_idx;   /* int32 [nctx, ldc], [nctx], [rows], device; or NULL */
+  int32_t ldh, nctx, ldc;
+  int32_t ngram, sep;
+  float penalty, inv_penalty;
+} unimm_lm_history;
+
+/* unimm_lm_topk with a history (the same kernel template): the bans of the n-gram rule join those of `banned` and the flags,
+ * and under a penalty the K ids come in the order of x' with vals = x - lse (a banned id keeps -inf).  Everything else, the
+ * refusals included, is unimm_lm_topk's; with ngram = 0 and penalty = 1 the outputs are bit-identical to it.  A row depends on
+ * its own logits, flags and history alone. */
+int unimm_lm_topk_hist(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                       const int32_t* flags, int32_t sep, int32_t K, const unimm_lm_history* history, float* vals, int32_t* ids,
+                       float* lse, void* stream);
+
+/* unimm_lm_sample_rows with a history (the same kernel template, per-row temperature / top_k / top_p).  With penalty = 1 row r
+ * is bit-identical to unimm_lm_sample_rows on that row with the rule's bans added to `banned`; with a penalty token and logq
+ * are those of unimm_lm_sample_rows on the row x', lse that of the raw row and logp = x_token - lse.  The second bitmap costs LDS:
+ * this entry point stages the keys for V <= 34816 (136 KiB of keys + 21.6 KiB of static LDS <= 160 KiB; V = 30522 is staged)
+ * and re-reads the row in every pass above that.  Same results either way. */
+int unimm_lm_sample_hist(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
+                         const int32_t* flags, int32_t sep, const float* temperature, const int32_t* top_k, const float* top_p,
+                         uint32_t key, const int32_t* stream_ids, const unimm_lm_history* history, int32_t* token, float* logp,
+                         float* logq, float* lse, void* stream);
+
 /* Launch profiler for bench.py's `roofline` block: HIP events around every GEMM launch on its own
  * stream while enabled.  Variant index: 0..11 = unimm_gemm_nt (epilogue * 2 + out_f32), 12 = unimm_gemm_tn.
  * unimm_prof_collect synchronises the events and returns per-variant summed milliseconds, algorithmic

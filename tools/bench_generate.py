@@ -5,11 +5,18 @@ against the recompute lower bound: sequence_log_likelihood of the same G * beams
 (answers of <= 14 tokens: it takes <= 32 private rows per sequence), the per-sequence path for the longer ones.
 
     python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile] [--samples N]
+                                   [--no-repeat-ngram N] [--repetition-penalty R] [--repeat-scope answer|dialog]
 
 --samples N adds, for G = 80 dialogs: ms/step of sampling N answers per dialog (temperature 0.8, top_k 50, top_p 0.9) against a
 beam run with the same number of hypothesis slots (beams = N) in the same process, the time of one unimm_lm_sample launch against
 one unimm_lm_topk launch on the same [80 N, 30522] logits, and the two ways of appending a step's K | V rows to the private caches
 (tensor indexing in place, which the sampler uses, against unimm_kv_cache_update under an identity parent).
+
+--no-repeat-ngram / --repetition-penalty (either one on) add, at G = 80 and 4 slots per dialog (or --samples): one
+unimm_lm_topk_hist launch against one unimm_lm_topk launch and one unimm_lm_sample_hist launch against one unimm_lm_sample_rows
+launch on the same [80 slots, 30522] logits (10 answer tokens of history per row, and with --repeat-scope dialog the dialogs'
+contexts), and the whole decode loop (20 tokens, beams and samples) with and without the rules -- each as alternating pairs in
+one process: the median of the per-pair ratios, and the spread (max / min) of the plain form over the pairs.
 
 --profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
 process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
@@ -138,6 +145,60 @@ def measure_sampling(model, G, N, reps):
     return row
 
 
+def paired(plain, ruled, pairs):
+    """Alternating pairs plain / ruled -> (median plain, median of the per-pair ratios ruled / plain, max / min of plain)."""
+    a, b = [], []
+    for _ in range(pairs):
+        a.append(plain())
+        b.append(ruled())
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.median(a)), float(np.median(b / a)), float(a.max() / a.min())
+
+
+def measure_constraints(model, G, N, reps, ngram, penalty, scope):
+    """The cost of the history rules: one _hist launch against the plain launch on the same logits, and the decode loop."""
+    from unimm_amd import generation as GN
+    from unimm_amd import lib as L
+    d, c = dialogs(G, seed=G * 10 + N)
+    S, V, HLEN, PAIRS = G * N, 30522, 10, 7
+    gen = torch.Generator().manual_seed(0)
+    logits = torch.randn((S, V), generator=gen).cuda() * 3
+    banned = torch.tensor([0, 101, 103], dtype=torch.int32, device="cuda")
+    flags = torch.zeros(S, dtype=torch.int32, device="cuda")
+    streams = torch.arange(S, dtype=torch.int32, device="cuda")
+    vals = torch.empty((S, N), dtype=torch.float32, device="cuda")
+    ids = torch.empty((S, N), dtype=torch.int32, device="cuda")
+    tok = torch.empty(S, dtype=torch.int32, device="cuda")
+    lp, lq = torch.empty(S, device="cuda"), torch.empty(S, device="cuda")
+    t, k, p = (torch.full((S,), v, dtype=dt, device="cuda") for v, dt in ((0.8, torch.float32), (50, torch.int32), (0.9, torch.float32)))
+    hist = torch.randint(1000, 1040, (S, ANS), generator=gen, dtype=torch.int32).cuda()      # 40 ids: windows do match
+    hlen = torch.full((S,), HLEN, dtype=torch.int32, device="cuda")
+    ctx, ctx_len = GN.context_table(d["input_ids"], c) if scope == "dialog" else (None, None)
+    ctx_idx = torch.arange(S, dtype=torch.int32, device="cuda") // N if ctx is not None else None
+    kpen = penalty if N == 1 else 1.0                                          # a penalised top-K is a beams = 1 launch
+    hs = L.lm_history(hist, hlen, ngram, penalty, 102, ctx, ctx_len, ctx_idx)
+    hk = L.lm_history(hist, hlen, ngram, kpen, 102, ctx, ctx_len, ctx_idx)
+    row = dict(G=G, slots=N, ngram=ngram, penalty=penalty, scope=scope)
+    row["lm_topk_us"], row["lm_topk_hist_ratio"], row["lm_topk_spread"] = paired(
+        lambda: launch_us(lambda: L.lm_topk(logits, S, V, banned, flags, 102, N, vals, ids)),
+        lambda: launch_us(lambda: L.lm_topk_hist(logits, S, V, banned, flags, 102, N, hk, vals, ids)), PAIRS)
+    row["lm_sample_rows_us"], row["lm_sample_hist_ratio"], row["lm_sample_rows_spread"] = paired(
+        lambda: launch_us(lambda: L.lm_sample_rows(logits, S, V, banned, flags, 102, t, k, p, 12345, streams, tok, lp, lq)),
+        lambda: launch_us(lambda: L.lm_sample_hist(logits, S, V, banned, flags, 102, t, k, p, 12345, streams, hs, tok, lp, lq)), PAIRS)
+    rules = dict(no_repeat_ngram_size=ngram, repeat_scope=scope)
+    for name, beams, kw, pen in (("beam", N, {}, kpen), ("sample", 1, dict(samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1), penalty)):
+        def call(**more):
+            t0 = time.perf_counter()
+            res = generate(model, d, c, beams, ANS, **kw, **more)
+            torch.cuda.synchronize()
+            assert bool((res.lengths == ANS + 1).all())
+            return (time.perf_counter() - t0) * 1e3
+        call(), call(repetition_penalty=pen, **rules)                          # warm-up of both
+        row[name + "_call_ms"], row[name + "_ruled_ratio"], row[name + "_call_spread"] = paired(
+            call, lambda: call(repetition_penalty=pen, **rules), max(reps, 3))
+    return {k: round(v, 4) if isinstance(v, float) else v for k, v in row.items()}
+
+
 def recompute_bound(model, d, c, G, beams, reps):
     """Summed ms of scoring G * beams sequences with answers of 1 .. ANS tokens (shared context up to 14 answer tokens)."""
     from unimm_amd.inputs import DialogMaskSpec
@@ -214,6 +275,9 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--samples", type=int, default=0, help="add the sampling comparison at G = 80 with this many samples per dialog")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, help="add the cost of the history rules at G = 80 with this n-gram size")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="... and / or with this repetition penalty")
+    ap.add_argument("--repeat-scope", choices=("answer", "dialog"), default="answer")
     a = ap.parse_args()
     torch.set_num_threads(min(16, torch.get_num_threads()))
     model = build_model()
@@ -232,6 +296,16 @@ def main():
               f"one launch on [{r['G'] * r['slots']}, 30522]: unimm_lm_sample {r['lm_sample_us']:.1f} us (no filter {r['lm_sample_plain_us']:.1f}, "
               f"top-k only {r['lm_sample_top_k_us']:.1f}, nucleus only {r['lm_sample_top_p_us']:.1f}) against unimm_lm_topk {r['lm_topk_us']:.1f} us; "
               f"cache append in place {r['append_in_place_us']:.1f} us against unimm_kv_cache_update {r['append_kv_cache_update_us']:.1f} us")
+    if a.no_repeat_ngram or a.repetition_penalty != 1.0:
+        result["constraints"] = r = measure_constraints(model, 80, a.samples or 4, a.reps, a.no_repeat_ngram, a.repetition_penalty,
+                                                        a.repeat_scope)
+        print(f"history rules (n-gram {r['ngram']}, penalty {r['penalty']}, scope {r['scope']}) at G = {r['G']}, {r['slots']} slots per "
+              f"dialog, median ratio over alternating pairs (spread of the plain form, max / min): "
+              f"unimm_lm_topk_hist / unimm_lm_topk {r['lm_topk_hist_ratio']:.3f} ({r['lm_topk_us']:.1f} us, spread {r['lm_topk_spread']:.3f}); "
+              f"unimm_lm_sample_hist / unimm_lm_sample_rows {r['lm_sample_hist_ratio']:.3f} ({r['lm_sample_rows_us']:.1f} us, spread "
+              f"{r['lm_sample_rows_spread']:.3f}); decode loop with / without the rules: beams {r['beam_ruled_ratio']:.3f} "
+              f"({r['beam_call_ms']:.1f} ms, spread {r['beam_call_spread']:.3f}), samples {r['sample_ruled_ratio']:.3f} "
+              f"({r['sample_call_ms']:.1f} ms, spread {r['sample_call_spread']:.3f})")
     if a.profile:
         result["kernel_mix_80x4"] = profile()
         for m in result["kernel_mix_80x4"]:

@@ -1,7 +1,8 @@
 // Answer generation kernels (include/unimm_hip.h, ABI 19-20): text self-attention of the decode rows against a shared context
 // cache plus per-hypothesis private caches, the per-step private-cache append + reorder, log-softmax + top-K of the
 // decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20; with per-row
-// parameters unimm_lm_sample_rows, ABI 24: the same kernel template).
+// parameters unimm_lm_sample_rows, ABI 24: the same kernel template).  unimm_lm_topk_hist / unimm_lm_sample_hist are the same two
+// kernel templates with HIST on: a per-row token history adds no-repeat n-gram bans and a repetition penalty (apply_history).
 // unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
 #include <math.h>
 
@@ -196,17 +197,90 @@ __global__ __launch_bounds__(NTHREADS) void kv_update_kernel(KvParams a) {
   if (l == 0 && threadIdx.x == 0) a.plen_out[s] = pl + 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Per-row history (unimm_lm_topk_hist / unimm_lm_sample_hist, the HIST instantiations).  A row's sources are its answer tokens
+// a[0, k) and, optionally, one row of a context table; apply_history ORs the ids the no-repeat n-gram rule bans into the
+// launch's `ban` bitmap and, when penalty != 1, marks every id of the sources in `seen`, whose logit then takes part in every
+// SELECTION as x' = x > 0 ? x * inv_penalty : x * penalty (the reported log p stays that of x).  Everything read from device
+// memory is clamped before it indexes anything: k to [0, ldh], the context index to [0, nctx), its length to [0, ldc].
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int HIST_MAX = 128;   // ldh bound: answer tokens per row
+constexpr int CTX_MAX = 256;    // ldc bound: context tokens per row
+
+struct HistParams {
+  const int32_t *hist, *hist_len, *ctx, *ctx_len, *ctx_idx;
+  int ldh, nctx, ldc, ngram, sep;
+  float penalty, inv_penalty;
+};
+
+template <bool HIST>
+struct HistLds {
+  uint32_t seen[VMAX / 32];
+  int src[HIST_MAX + CTX_MAX];                  // [0, HIST_MAX): the answer, [HIST_MAX, ..): the context
+};
+template <>
+struct HistLds<false> {};
+
+// x' of an id of the sources.  The product is rounded to fp32 HERE: the empty asm keeps -ffp-contract=fast from fusing it into a
+// later subtraction, so that x' is the one correctly rounded multiply the header promises.
+__device__ __forceinline__ float penalised(float xv, float penalty, float inv_penalty) {
+  float xp = xv > 0.f ? xv * inv_penalty : xv * penalty;
+  asm volatile("" : "+v"(xp));
+  return xp;
+}
+
+// Every thread calls it, after the launch-wide bans are in `ban` (and a barrier); it ends with a barrier.
+__device__ void apply_history(const HistParams& h, int row, int V, uint32_t* ban, HistLds<true>& l) {
+  const int tid = threadIdx.x;
+  const int k = h.hist != nullptr ? min(max(h.hist_len[row], 0), h.ldh) : 0;
+  const int32_t* a = h.hist != nullptr ? h.hist + (int64_t)row * h.ldh : nullptr;
+  const int32_t* c = nullptr;
+  int cl = 0;
+  if (h.ctx != nullptr) {
+    const int ci = min(max(h.ctx_idx[row], 0), h.nctx - 1);
+    cl = min(max(h.ctx_len[ci], 0), h.ldc);
+    c = h.ctx + (int64_t)ci * h.ldc;
+  }
+  const bool pen = h.penalty != 1.f;
+  if (pen)
+    for (int w = tid; w < (V + 31) / 32; w += NTHREADS) l.seen[w] = 0u;
+  for (int i = tid; i < HIST_MAX + CTX_MAX; i += NTHREADS)
+    l.src[i] = i < HIST_MAX ? (i < k ? a[i] : 0) : (i - HIST_MAX < cl ? c[i - HIST_MAX] : 0);
+  __syncthreads();
+  const int n = h.ngram;
+  const bool grams = n > 0 && k >= n - 1;        // the answer holds the n - 1 tokens a[k-n+1, k) every window is compared with
+  for (int i = tid; i < HIST_MAX + CTX_MAX; i += NTHREADS) {
+    const bool ans = i < HIST_MAX;
+    const int e = ans ? i : i - HIST_MAX;        // the window ends at s[e], wholly inside its own source
+    if (e >= (ans ? k : cl)) continue;
+    const int* s = l.src + (ans ? 0 : HIST_MAX);
+    const int t = s[e];
+    if (t < 0 || t >= V) continue;               // an id outside [0, V) bans nothing (it still compares below, as s[e - d])
+    if (pen) atomicOr(&l.seen[t >> 5], 1u << (t & 31));
+    if (!grams || e < n - 1 || t == h.sep) continue;
+    bool eq = true;
+    for (int d = 1; d < n; ++d) eq = eq && s[e - d] == l.src[k - d];
+    if (eq) atomicOr(&ban[t >> 5], 1u << (t & 31));
+  }
+  __syncthreads();
+}
+
 struct TopkParams {
   const float* logits; const int32_t* banned; const int32_t* flags;
   float* vals; int32_t* ids; float* lse;
   int rows, V, ldl, nbanned, sep, K;
+  HistParams h;                                  // HIST only
 };
 
 // (va, ia) ranks before (vb, ib): value desc, id asc
 __device__ __forceinline__ bool better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
 
+// HIST (unimm_lm_topk_hist): the row's history bans join the bitmap, and with a penalty the order is that of x' while the
+// reported values stay x - lse; nothing else differs.
+template <bool HIST>
 __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
   __shared__ uint32_t ban[VMAX / 32];
+  __shared__ HistLds<HIST> hl;
   __shared__ float lv[TOPK_MAX * NTHREADS];
   __shared__ int li[TOPK_MAX * NTHREADS];
   __shared__ float rm[NTHREADS / 64], rs[NTHREADS / 64];
@@ -221,6 +295,11 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
     if (id >= 0 && id < a.V) atomicOr(&ban[id >> 5], 1u << (id & 31));
   }
   __syncthreads();
+  bool pen = false;
+  if constexpr (HIST) {
+    apply_history(a.h, row, a.V, ban, hl);
+    pen = a.h.penalty != 1.f;
+  }
   const int f = a.flags != nullptr ? a.flags[row] : 0;
   const float* x = a.logits + (int64_t)row * a.ldl;
   const int K = a.K;
@@ -240,7 +319,10 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
       }
     }
     const bool banned = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == a.sep) || ((f & 2) && j != a.sep);
-    const float cv = banned ? -INFINITY : xv;
+    float cv = banned ? -INFINITY : xv;
+    if constexpr (HIST) {
+      if (pen && !banned && ((hl.seen[j >> 5] >> (j & 31)) & 1u)) cv = penalised(xv, a.h.penalty, a.h.inv_penalty);
+    }
     if (n < K || better(cv, j, tv, ti)) {
       int pos = n < K ? n : K - 1;
       while (pos > 0 && better(cv, j, lv[(pos - 1) * NTHREADS + tid], li[(pos - 1) * NTHREADS + tid])) {
@@ -294,6 +376,9 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
     __syncthreads();
     if (hd < n && li[hd * NTHREADS + tid] == bi) ++hd;
     if (tid == 0) {
+      if constexpr (HIST) {                      // ranked by x', reported as the raw log p
+        if (pen && bv > -INFINITY && bi >= 0 && bi < a.V) bv = x[bi];
+      }
       a.vals[(int64_t)row * K + r] = bv - lse;
       a.ids[(int64_t)row * K + r] = bi;
     }
@@ -309,8 +394,13 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
 // 2^-40 fixed point in 64-bit integers: an integer sum does not depend on the order of the atomics, so a launch is reproducible.
 // PER_ROW (unimm_lm_sample_rows): temperature / top_k / top_p come from device arrays indexed by the row, and values the scalar
 // entry point refuses on the host make the row return the `nothing eligible` result; nothing else differs.
+// HIST (unimm_lm_sample_hist): the history's bans join the bitmap and the key of an id of the sources is built from x', so every
+// selection, q and logq are those of the row x'; lse and logp stay those of x.
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int STAGE_MAX = 36864;               // 144 KiB of keys + 12.3 KiB of static LDS <= 160 KiB
+// HIST adds the 8 KiB `seen` bitmap and 1.5 KiB of sources (HistLds): 12,416 + 9,728 = 22,144 B of static LDS, which leaves
+// 163,840 - 22,144 = 141,696 B = 35,424 keys.  34,816 keys (136 KiB: 139,264 + 22,144 = 161,408 B) keep V = 30522 staged.
+constexpr int HIST_STAGE_MAX = 34816;
 constexpr float FIX_ONE = 1099511627776.f;     // 2^40
 static_assert(NTHREADS == 256, "one histogram bin per thread");
 
@@ -321,6 +411,7 @@ struct SampleParams {
   float temperature, top_p;
   uint32_t key;
   const float* temp_rows; const int32_t* topk_rows; const float* topp_rows;   // PER_ROW: [rows] each, instead of the scalars
+  HistParams h;                                  // HIST only
 };
 
 struct SelScratch {
@@ -386,11 +477,12 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
   return t;
 }
 
-template <bool STAGED, bool PER_ROW>
+template <bool STAGED, bool PER_ROW, bool HIST>
 __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint32_t* keys = reinterpret_cast<uint32_t*>(smem);          // [V] when STAGED (no dynamic LDS otherwise)
   __shared__ uint32_t ban[VMAX / 32];
+  __shared__ HistLds<HIST> hl;
   __shared__ SelScratch sel;
   __shared__ float rm[NTHREADS / 64], rs[NTHREADS / 64], wv[NTHREADS / 64];
   __shared__ int wi[NTHREADS / 64];
@@ -405,6 +497,11 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
     if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
   }
   __syncthreads();
+  bool pen = false;
+  if constexpr (HIST) {
+    apply_history(a.h, row, V, ban, hl);
+    pen = a.h.penalty != 1.f;
+  }
   const int f = a.flags != nullptr ? a.flags[row] : 0;
   const float* x = a.logits + (int64_t)row * a.ldl;
   const int sep = a.sep;
@@ -413,9 +510,16 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   const int top_k = PER_ROW ? a.topk_rows[row] : a.top_k;
   const float top_p = PER_ROW ? a.topp_rows[row] : a.top_p;
   const bool bad = PER_ROW && (!(temp > 0.f) || !(temp < INFINITY) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0);
+  // the logit an id is SELECTED by: x' for an id of the sources under a penalty (HIST), the raw logit otherwise
+  auto sel_val = [&](int j, float xv) -> float {
+    if constexpr (HIST) {
+      if (pen && ((hl.seen[j >> 5] >> (j & 31)) & 1u)) return penalised(xv, a.h.penalty, a.h.inv_penalty);
+    }
+    return xv;
+  };
   auto make_key = [&](int j, float xv) -> uint32_t {
     const bool out = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == sep) || ((f & 2) && j != sep) || !(xv > -INFINITY);
-    return out ? 0u : ord_key(xv);
+    return out ? 0u : ord_key(sel_val(j, xv));
   };
   auto key_at = [&](int j) -> uint32_t { return STAGED ? keys[j] : make_key(j, x[j]); };
 
@@ -549,7 +653,7 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
       const float xt = x[bi];
       a.token[row] = bi;
       a.logp[row] = xt - lse;
-      a.logq[row] = (xt - xmax) / temp - logf((float)((double)zf * 9.094947017729282e-13));   // 2^-40
+      a.logq[row] = (sel_val(bi, xt) - xmax) / temp - logf((float)((double)zf * 9.094947017729282e-13));   // 2^-40
     }
   }
 }
@@ -610,33 +714,66 @@ extern "C" int unimm_lm_topk(const float* logits, int32_t rows, int32_t V, int32
   TopkParams p;
   p.logits = logits; p.banned = banned; p.flags = flags; p.vals = vals; p.ids = ids; p.lse = lse;
   p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.K = K;
-  hipLaunchKernelGGL(lm_topk_kernel, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  p.h = HistParams{};
+  hipLaunchKernelGGL(lm_topk_kernel<false>, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }
 
 namespace {
 
-template <bool PER_ROW>
+template <bool PER_ROW, bool HIST>
 int launch_lm_sample(const SampleParams& p, hipStream_t stream) {
-  if (p.V <= STAGE_MAX) {
+  constexpr int BOUND = HIST ? HIST_STAGE_MAX : STAGE_MAX;
+  if (p.V <= BOUND) {
     static bool done = false;                    // one per instantiation
     if (!done) {
-      if (hipFuncSetAttribute((const void*)lm_sample_kernel<true, PER_ROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              STAGE_MAX * (int)sizeof(uint32_t)) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)lm_sample_kernel<true, PER_ROW, HIST>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              BOUND * (int)sizeof(uint32_t)) != hipSuccess)
         return UNIMM_E_HIP;
       done = true;
     }
-    hipLaunchKernelGGL((lm_sample_kernel<true, PER_ROW>), dim3((unsigned)p.rows), dim3(NTHREADS), (size_t)p.V * sizeof(uint32_t),
-                       stream, p);
+    hipLaunchKernelGGL((lm_sample_kernel<true, PER_ROW, HIST>), dim3((unsigned)p.rows), dim3(NTHREADS),
+                       (size_t)p.V * sizeof(uint32_t), stream, p);
   } else {
-    hipLaunchKernelGGL((lm_sample_kernel<false, PER_ROW>), dim3((unsigned)p.rows), dim3(NTHREADS), 0, stream, p);
+    hipLaunchKernelGGL((lm_sample_kernel<false, PER_ROW, HIST>), dim3((unsigned)p.rows), dim3(NTHREADS), 0, stream, p);
   }
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }
 
+// The refusals of a history (before any launch) -> UNIMM_OK and the kernels' form of it
+int read_history(const unimm_lm_history* h, HistParams* out) {
+  if (h == nullptr) return UNIMM_E_ARG;
+  if (!(h->penalty > 0.f) || !(h->penalty < INFINITY) || !(h->inv_penalty > 0.f) || !(h->inv_penalty < INFINITY)) return UNIMM_E_ARG;
+  if (h->ngram < 0 || h->ngram > 8) return UNIMM_E_SHAPE;
+  if (h->hist == nullptr && (h->ngram > 0 || h->penalty != 1.f)) return UNIMM_E_ARG;
+  if (h->hist != nullptr && h->hist_len == nullptr) return UNIMM_E_ARG;
+  if (h->hist != nullptr && (h->ldh < 0 || h->ldh > HIST_MAX)) return UNIMM_E_SHAPE;
+  if (h->ctx != nullptr && (h->ctx_len == nullptr || h->ctx_idx == nullptr)) return UNIMM_E_ARG;
+  if (h->ctx != nullptr && (h->nctx < 1 || h->ldc < 0 || h->ldc > CTX_MAX)) return UNIMM_E_SHAPE;
+  out->hist = h->hist; out->hist_len = h->hist_len; out->ctx = h->ctx; out->ctx_len = h->ctx_len; out->ctx_idx = h->ctx_idx;
+  out->ldh = h->ldh; out->nctx = h->nctx; out->ldc = h->ldc; out->ngram = h->ngram; out->sep = h->sep;
+  out->penalty = h->penalty; out->inv_penalty = h->inv_penalty;
+  return UNIMM_OK;
+}
+
 }  // namespace
+
+extern "C" int unimm_lm_topk_hist(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned,
+                                  int32_t nbanned, const int32_t* flags, int32_t sep, int32_t K, const unimm_lm_history* history,
+                                  float* vals, int32_t* ids, float* lse, void* stream) {
+  if (logits == nullptr || vals == nullptr || ids == nullptr || (nbanned > 0 && banned == nullptr)) return UNIMM_E_ARG;
+  TopkParams p;
+  if (const int rc = read_history(history, &p.h)) return rc;
+  if (rows < 0 || V < 1 || V > VMAX || ldl < V || K < 1 || K > TOPK_MAX || K > V || nbanned < 0) return UNIMM_E_SHAPE;
+  if (rows == 0) return UNIMM_OK;
+  p.logits = logits; p.banned = banned; p.flags = flags; p.vals = vals; p.ids = ids; p.lse = lse;
+  p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.K = K;
+  hipLaunchKernelGGL(lm_topk_kernel<true>, dim3((unsigned)rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
 
 extern "C" int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned, int32_t nbanned,
                                const int32_t* flags, int32_t sep, float temperature, int32_t top_k, float top_p, uint32_t key,
@@ -653,7 +790,8 @@ extern "C" int unimm_lm_sample(const float* logits, int32_t rows, int32_t V, int
   p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = top_k;
   p.temperature = temperature; p.top_p = top_p; p.key = key;
   p.temp_rows = nullptr; p.topk_rows = nullptr; p.topp_rows = nullptr;
-  return launch_lm_sample<false>(p, (hipStream_t)stream);
+  p.h = HistParams{};
+  return launch_lm_sample<false, false>(p, (hipStream_t)stream);
 }
 
 extern "C" int unimm_lm_sample_rows(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned,
@@ -671,5 +809,26 @@ extern "C" int unimm_lm_sample_rows(const float* logits, int32_t rows, int32_t V
   p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = 0;
   p.temperature = 1.f; p.top_p = 1.f; p.key = key;
   p.temp_rows = temperature; p.topk_rows = top_k; p.topp_rows = top_p;
-  return launch_lm_sample<true>(p, (hipStream_t)stream);
+  p.h = HistParams{};
+  return launch_lm_sample<true, false>(p, (hipStream_t)stream);
+}
+
+extern "C" int unimm_lm_sample_hist(const float* logits, int32_t rows, int32_t V, int32_t ldl, const int32_t* banned,
+                                    int32_t nbanned, const int32_t* flags, int32_t sep, const float* temperature,
+                                    const int32_t* top_k, const float* top_p, uint32_t key, const int32_t* stream_ids,
+                                    const unimm_lm_history* history, int32_t* token, float* logp, float* logq, float* lse,
+                                    void* stream) {
+  if (logits == nullptr || stream_ids == nullptr || token == nullptr || logp == nullptr || logq == nullptr ||
+      (nbanned > 0 && banned == nullptr) || temperature == nullptr || top_k == nullptr || top_p == nullptr)
+    return UNIMM_E_ARG;
+  SampleParams p;
+  if (const int rc = read_history(history, &p.h)) return rc;
+  if (rows < 0 || V < 1 || V > VMAX || ldl < V || nbanned < 0) return UNIMM_E_SHAPE;
+  if (rows == 0) return UNIMM_OK;
+  p.logits = logits; p.banned = banned; p.flags = flags; p.stream = stream_ids;
+  p.token = token; p.logp = logp; p.logq = logq; p.lse = lse;
+  p.rows = rows; p.V = V; p.ldl = ldl; p.nbanned = nbanned; p.sep = sep; p.top_k = 0;
+  p.temperature = 1.f; p.top_p = 1.f; p.key = key;
+  p.temp_rows = temperature; p.topk_rows = top_k; p.topp_rows = top_p;
+  return launch_lm_sample<true, true>(p, (hipStream_t)stream);
 }

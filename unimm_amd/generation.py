@@ -67,6 +67,23 @@ without the greedy slot (up to the batch dependence of the logits); the greedy a
 shaped like a beams = 1 result.  With per-draw parameters or a greedy slot the draw is `unimm_lm_sample_rows` (the same kernel
 with per-row parameters, ABI 24); a call that uses neither launches `unimm_lm_sample` as before.  The loop ends when every slot,
 the greedy one included, has finished.
+
+Rules that depend on what a hypothesis has said (`no_repeat_ngram_size`, `repetition_penalty`, `repeat_scope`).  At step k a slot's
+history sources are its own answer tokens a[0, k) ([SEP] is never among them) and, with repeat_scope="dialog", the dialog's context
+tokens input_ids[g, 1:c) as a second source ([CLS] excluded).  no_repeat_ngram_size = n (0 = off, at most 8): once k >= n - 1, id t
+is banned for the slot when some window s[e-n+1 .. e] of ONE source has s[e-n+1 .. e) == a[k-n+1 .. k) and s[e] == t -- overlapping
+windows count, no window spans the context/answer boundary, n = 1 bans every id of the sources, and [SEP] is never banned by the
+rule (the forced end always keeps one eligible id).  Such a ban is an entry of `banned_tokens` for that slot and step: -inf after
+the log-sum-exp, no renormalisation, so step_logp is still `sequence_log_likelihood` of the completed answer.  It works with any
+`beams` and `samples` and applies to the greedy slot too.  repetition_penalty = r (1 = off, finite, > 0) shapes SELECTION only:
+every id i of the sources is ranked, filtered and drawn by x'_i = x_i > 0 ? x_i * fp32(1 / r) : x_i * r, every other id by x_i;
+step_logq is the log-probability under that distribution (what `PolicyObjective(mode="ratio")` weighs by), step_logp stays
+x_i - logsumexp(x).  A beam's cumulative score is the model's log p, and a penalised ranking across hypotheses would be a different
+search, so the penalty is admitted for beams = 1 (which takes the first id of the rank order on x' and reports its raw log p, as
+the greedy slot of a sampling call does) and for sampling.  With any of the rules on, every step -- step 0 on the prefill's row
+included -- launches `unimm_lm_topk_hist` / `unimm_lm_sample_hist` (the two kernels with a per-row history: a device int32
+[slots, width] table that `track_history` reorders by parent and appends to, and the context table built once per call); with all
+of them off the call launches exactly the kernels named above.
 """
 from __future__ import annotations
 
@@ -257,6 +274,60 @@ def slot_parameters(G, temperature, top_k, top_p, greedy=False):
     return tuple(np.tile(np.concatenate([a, np.asarray(e, dtype=a.dtype)]), G) for a, e in zip((temperature, top_k, top_p), extra))
 
 
+MAX_NGRAM, MAX_HISTORY, MAX_CONTEXT = 8, 128, 256  # unimm_lm_history: ngram, ldh and ldc bounds
+REPEAT_SCOPES = ("answer", "dialog")
+
+
+def check_constraints(no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer", beams=1):
+    """The refused history rules (ValueError) -> None when both are off, else dict(ngram, penalty, scope)."""
+    n, r = no_repeat_ngram_size, repetition_penalty
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= MAX_NGRAM:
+        raise ValueError(f"generate_answers: no_repeat_ngram_size must be an integer in [0, {MAX_NGRAM}] (0 = off), got {n!r}")
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not (math.isfinite(r) and r > 0):
+        raise ValueError(f"generate_answers: repetition_penalty must be finite and > 0 (1 = off), got {r!r}")
+    if repeat_scope not in REPEAT_SCOPES:
+        raise ValueError(f"generate_answers: repeat_scope must be one of {REPEAT_SCOPES}, got {repeat_scope!r}")
+    if float(np.float32(r)) != 1.0 and int(beams) > 1:
+        raise ValueError(f"generate_answers: repetition_penalty = {r} needs beams = 1 (got beams = {beams}): a beam's cumulative score is "
+                         f"the model's log p, and ranking hypotheses by penalised logits would be a different search")
+    if n == 0 and float(np.float32(r)) == 1.0:
+        return None
+    return dict(ngram=int(n), penalty=float(np.float32(r)), scope=repeat_scope)
+
+
+def new_history(S, width, device="cpu"):
+    """The answer history of S hypothesis slots: dict(hist int32 [S, width], len int32 [S]), empty."""
+    dev = torch.device(device)
+    return dict(hist=torch.zeros((S, max(int(width), 1)), dtype=torch.int32, device=dev),
+                len=torch.zeros(S, dtype=torch.int32, device=dev))
+
+
+def track_history(h, k, token, parent=None):
+    """Bring the history `h` (new_history) to step k from the arguments a step function gets: slot s continues slot parent[s]
+    (beam search; None: itself, sampling) with answer token k-1 = token[s].  Afterwards h["hist"][s, :h["len"][s]] are the answer
+    tokens a[0, k) of slot s.  Step 0 starts every slot empty."""
+    if k == 0:
+        h["len"].zero_()
+        return h
+    if parent is not None:
+        h["hist"] = h["hist"][parent.to(h["hist"].device, torch.int64)]
+    if k - 1 < h["hist"].shape[1]:
+        h["hist"][:, k - 1] = token.to(h["hist"].device, torch.int32)
+    h["len"].fill_(min(k, h["hist"].shape[1]))
+    return h
+
+
+def context_table(input_ids, context_len):
+    """repeat_scope="dialog": (ctx int32 [G, max c - 1], lengths int32 [G]) of the dialogs' context tokens input_ids[g, 1:c)."""
+    c = torch.as_tensor(np.asarray(context_len), dtype=torch.int64).reshape(-1)
+    w = max(int(c.max()) - 1, 1)
+    ctx = input_ids[:, 1:1 + w].to(torch.int32)
+    if ctx.shape[1] < w:
+        ctx = torch.nn.functional.pad(ctx, (0, w - ctx.shape[1]))
+    keep = torch.arange(w, device=ctx.device)[None] < (c.to(ctx.device) - 1)[:, None]
+    return torch.where(keep, ctx, 0).contiguous(), (c - 1).to(torch.int32).to(ctx.device)
+
+
 def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu", greedy=False):
     """Draw `samples` answers per dialog.  step(k, token, flags) -> (token int [G*samples], logp fp32, logq fp32): the draw of every
     slot at step k with its two log-probabilities, where slot s = g * samples + j continues itself with answer token k-1 =
@@ -322,7 +393,7 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
 def generate_answers(model, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                      length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                     sample_streams=None, greedy=False):
+                     sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer"):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("generate_answers runs on the bf16 engine")
@@ -334,6 +405,10 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     if c_h.shape[0] != G:
         raise ValueError(f"generate_answers: {c_h.shape[0]} context lengths for {G} dialogs")
     limits = check_request(c_h, T, beams, max_answer_len, min_answer_len)
+    constraints = check_constraints(no_repeat_ngram_size, repetition_penalty, repeat_scope, beams)
+    if constraints is not None and (int(limits.max()) > MAX_HISTORY or int(c_h.max()) - 1 > MAX_CONTEXT):
+        raise ValueError(f"generate_answers: no_repeat_ngram_size / repetition_penalty keep a history of at most {MAX_HISTORY} answer "
+                         f"and {MAX_CONTEXT} context tokens per hypothesis (got {int(limits.max())} and {int(c_h.max()) - 1})")
     sampling = None
     if greedy and not samples:
         raise ValueError("generate_answers: greedy=True adds a greedy slot to a sampling call and needs samples >= 1; for greedy "
@@ -349,7 +424,7 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
             streams = np.concatenate([streams, np.zeros((G, 1), dtype=np.int64)], 1)
         sampling = dict(samples=int(samples), greedy=bool(greedy), seed=int(seed),
                         streams=(streams.reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
-        if per_draw or greedy:                             # per-row parameters: unimm_lm_sample_rows
+        if per_draw or greedy or constraints is not None:  # per-row parameters: unimm_lm_sample_rows (_hist takes no other form)
             sampling["rows"] = slot_parameters(G, ts, ks, ps, greedy)
         else:
             sampling.update(temperature=float(ts[0]), top_k=int(ks[0]), top_p=float(ps[0]))
@@ -360,10 +435,11 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     inp = {k: v for k, v in inp.items() if v is not None}
     eng.stage_host_inputs(inp, pack=("attention_mask", "co_attention_mask"))   # the [G, R] image key mask stays a tensor
     return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
-                               tuple(int(t) for t in banned_tokens), sampling)
+                               tuple(int(t) for t in banned_tokens), sampling, constraints)
 
 
-def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None):
+def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None,
+              constraints=None):
     """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples."""
     if sampling is not None:
         beams = sampling["samples"] + sampling["greedy"]
@@ -429,6 +505,16 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     slot_seg = aseg.repeat_interleave(beams)
     NO = L.NO_DROP
     st = dict(cur=0)
+    if constraints is not None:                            # the history rules: every launch below is a _hist entry point
+        answers = new_history(S, pcap, dev)
+        ctx, ctx_len = context_table(ids, c_h) if constraints["scope"] == "dialog" else (None, None)
+        slot_ctx = torch.arange(S, device=dev, dtype=torch.int32) // beams if ctx is not None else None
+        root_ctx = torch.arange(G, device=dev, dtype=torch.int32) if ctx is not None else None
+
+        def history(root=False):
+            """The launch's unimm_lm_history: of the S slots, or (root) of the G rows of the prefill, whose answers are empty."""
+            return L.lm_history(answers["hist"], answers["len"], constraints["ngram"], constraints["penalty"], SEP, ctx, ctx_len,
+                                root_ctx if root else slot_ctx)
 
     def text_block(key, x32, x):
         qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
@@ -466,17 +552,23 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         L.gather_rows(xt, copy_rows, xs, S, H)
         return eng.decode_rows(xs, S)
 
+    def topk(logits, rows, flags, k, parent=None, token=None):
+        if constraints is None:
+            L.lm_topk(logits, rows, V, banned, flags, SEP, beams, vals[:rows], tops[:rows])
+        else:
+            track_history(answers, k, token, parent)
+            L.lm_topk_hist(logits, rows, V, banned, flags, SEP, beams, history(root=k == 0), vals[:rows], tops[:rows])
+
     def step(k, parent, token, flags):
         if k == 0:                                         # copy row 0 is the prefill's decoded row
-            L.lm_topk(pre["logits"], G, V, banned, flags[::beams].contiguous(), SEP, beams, vals[:G], tops[:G])
+            topk(pre["logits"], G, flags[::beams].contiguous(), 0)
             return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
         if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
             cur = st["cur"]
             L.kv_cache_update(priv[cur], priv[1 - cur], stash[0][:, H:], parent.to(torch.int32), plen[cur], plen[1 - cur],
                               nt, S, pcap, 2 * H, M * 3 * H, 2)
             st["cur"] = 1 - cur
-        logits = model_rows(k, token)
-        L.lm_topk(logits, S, V, banned, flags, SEP, beams, vals, tops)
+        topk(model_rows(k, token), S, flags, k, parent, token)
         return vals, tops
 
     if sampling is None:
@@ -489,9 +581,12 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
 
     rows = [torch.from_numpy(a).to(dev) for a in sampling["rows"]] if "rows" in sampling else None
 
-    def draw(k, logits, flags):
+    def draw(k, logits, flags, token=None):
         key = DR.make_key(sampling["seed"], k, SAMPLE_SITE)
-        if rows is not None:
+        if constraints is not None:
+            track_history(answers, k, token)
+            L.lm_sample_hist(logits, S, V, banned, flags, SEP, rows[0], rows[1], rows[2], key, streams, history(), stok, slp, slq)
+        elif rows is not None:
             L.lm_sample_rows(logits, S, V, banned, flags, SEP, rows[0], rows[1], rows[2], key, streams, stok, slp, slq)
         else:
             L.lm_sample(logits, S, V, banned, flags, SEP, sampling["temperature"], sampling["top_k"], sampling["top_p"], key,
@@ -504,7 +599,7 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         if k >= 2:                                         # a slot keeps its own cache: append its answer row k-2 in place
             priv[0][:, :, k - 2] = stash[:, 0::2, H:]
             plen[0].add_(1)
-        return draw(k, model_rows(k, token), flags)
+        return draw(k, model_rows(k, token), flags, token)
 
     return sample_search(sample_step, G, sampling["samples"], limits, max_answer_len, min_answer_len, length_penalty, device=dev,
                          greedy=sampling["greedy"])

@@ -116,6 +116,8 @@ SIGNATURES = {
     "unimm_lm_topk": (_INT, _LM_ROWS + [I32, VP, VP, VP, VP]),
     "unimm_lm_sample": (_INT, _LM_ROWS + [F32, I32, F32, U32] + [VP] * 6),
     "unimm_lm_sample_rows": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 6),
+    "unimm_lm_topk_hist": (_INT, _LM_ROWS + [I32, VP, VP, VP, VP, VP]),
+    "unimm_lm_sample_hist": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 7),
     # launch profiler
     "unimm_prof_enable": (_INT, [I32]),
     "unimm_prof_collect": (_INT, [VP, VP, VP, I32]),
@@ -519,6 +521,47 @@ def lm_sample_rows(logits, rows, V, banned, flags, sep, temperature, top_k, top_
     nb = 0 if banned is None else banned.numel()
     _call("unimm_lm_sample_rows", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, _ptr(temperature),
           _ptr(top_k), _ptr(top_p), key & 0xFFFFFFFF, _ptr(streams), _ptr(token), _ptr(logp), _ptr(logq), _ptr(lse))
+
+
+class LmHistory(C.Structure):
+    _fields_ = [("hist", C.c_void_p), ("hist_len", C.c_void_p), ("ctx", C.c_void_p), ("ctx_len", C.c_void_p), ("ctx_idx", C.c_void_p),
+                ("ldh", C.c_int32), ("nctx", C.c_int32), ("ldc", C.c_int32), ("ngram", C.c_int32), ("sep", C.c_int32),
+                ("penalty", C.c_float), ("inv_penalty", C.c_float)]
+
+
+def lm_history(hist, hist_len, ngram, penalty, sep, ctx=None, ctx_len=None, ctx_idx=None):
+    """The per-row history of lm_topk_hist / lm_sample_hist (unimm_lm_history): hist int32 [rows, ldh] with hist_len int32 [rows],
+    optionally a context table ctx int32 [nctx, ldc] with ctx_len int32 [nctx] and the rows' ctx_idx int32 [rows].  penalty is
+    rounded to fp32 and inv_penalty is the fp32 value of 1 / that.  The struct holds addresses: keep the tensors alive."""
+    _dev(hist, hist_len, ctx, ctx_len, ctx_idx)
+    h = LmHistory()
+    h.hist, h.hist_len, h.ctx, h.ctx_len, h.ctx_idx = _ptr(hist), _ptr(hist_len), _ptr(ctx), _ptr(ctx_len), _ptr(ctx_idx)
+    h.ldh = hist.stride(0) if hist is not None else 0
+    h.nctx, h.ldc = (ctx.shape[0], ctx.stride(0)) if ctx is not None else (0, 0)
+    h.ngram, h.sep = ngram, sep
+    h.penalty = penalty
+    h.inv_penalty = 1.0 / h.penalty                 # 1 / (the fp32 penalty), rounded to fp32 by the field
+    return h
+
+
+def lm_topk_hist(logits, rows, V, banned, flags, sep, K, history, vals, ids, lse=None):
+    """lm_topk with a per-row history (unimm_lm_topk_hist; history: lm_history): no-repeat n-gram bans, and under a repetition
+    penalty the ids in the order of the penalised logits with their unpenalised log p."""
+    _dev(logits, banned, flags, vals, ids, lse)
+    nb = 0 if banned is None else banned.numel()
+    _call("unimm_lm_topk_hist", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, K,
+          C.addressof(history), vals.data_ptr(), ids.data_ptr(), _ptr(lse))
+
+
+def lm_sample_hist(logits, rows, V, banned, flags, sep, temperature, top_k, top_p, key, streams, history, token, logp, logq,
+                   lse=None):
+    """lm_sample_rows with a per-row history (unimm_lm_sample_hist; history: lm_history): the draw, and logq, under the
+    no-repeat n-gram bans and the repetition penalty; logp stays that of the unmodified row."""
+    _dev(logits, banned, flags, temperature, top_k, top_p, streams, token, logp, logq, lse)
+    nb = 0 if banned is None else banned.numel()
+    _call("unimm_lm_sample_hist", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep,
+          _ptr(temperature), _ptr(top_k), _ptr(top_p), key & 0xFFFFFFFF, _ptr(streams), C.addressof(history), _ptr(token),
+          _ptr(logp), _ptr(logq), _ptr(lse))
 
 
 def attn_probs(q, k, probs, mask, B, H, Tq, Tk, D, scale, mask_q_stride, mask_b_stride, drop=NO_DROP):
@@ -1258,5 +1301,5 @@ STRUCTS = {
     "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
     "unimm_adamw_args": AdamWArgs, "unimm_clip_state": ClipState, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
     "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
-    "unimm_seq_pref_args": SeqPrefArgs,
+    "unimm_seq_pref_args": SeqPrefArgs, "unimm_lm_history": LmHistory,
 }

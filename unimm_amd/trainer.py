@@ -141,7 +141,8 @@ def _lm_term_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, 
 
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
                        objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
-                       shared_context=False, rollout="separate", reference=None):
+                       shared_context=False, rollout="separate", reference=None, no_repeat_ngram_size=0, repetition_penalty=1.0,
+                       repeat_scope="answer"):
     """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
@@ -158,6 +159,9 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     rollout: "separate" decodes the greedy baseline in a generate_answers call of its own (beams = 1); "fused" (baseline="greedy"
     only, samples <= 15; ValueError otherwise) decodes it as one more slot of the sampling call, `generate_answers(samples=N,
     greedy=True)`: one prefill and one walk over the decode steps for both.  Only the samples are trained on either way.
+    no_repeat_ngram_size / repetition_penalty / repeat_scope: `generate_answers`' history rules, handed to the sampling call and to
+    the baseline's call alike, so the samples and the greedy baseline decode under one rule on both rollouts (a penalty changes
+    the distribution drawn from: mode "ratio" reads it from step_logq).
     reference: the frozen model `objective.kl_coef > 0` leashes the policy to (`policy.frozen_reference(model)`, taken before
     the fine-tune; passed on as `lm_reference`); the step's mean KL is then in `engine.last_lm_kl`.
     -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
@@ -176,7 +180,8 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     T = batch["tokens"].shape[1]
     gen_args = (batch["tokens"], batch["image_feat"], batch["image_loc"], batch["context_len"])
     gen_kw = dict(token_type_ids=batch["segments"], position_ids=batch["positions"], image_attention_mask=batch.get("image_mask"),
-                  max_answer_len=max_answer_len)
+                  max_answer_len=max_answer_len, no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
+                  repeat_scope=repeat_scope)
     dialog_encoder.eval()
     answers = model.generate_answers(*gen_args, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p,
                                      seed=iter_id if seed is None else seed, **(dict(greedy=True) if fused else {}), **gen_kw)
