@@ -584,6 +584,48 @@ int unimm_pg_kl_loss_bwd(const float* logits, const int32_t* labels, const int32
                          const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
                          const int32_t* n_dev, const float* inv_dev, const float* ref_logits, int32_t ld_ref, float kl_coef,
                          const float* kl, const float* ref_lse, void* stream);
+/* Token-level knowledge distillation against a FROZEN teacher (csrc/distill.hip; two entry points added beside the ones above,
+ * whose signatures and results are unchanged: the ABI number stays).  logits, labels, weights, lse, rownll, n / n_dev / inv_dev,
+ * ld / ldd and the zero-filled columns V .. ldd are those of unimm_lm_loss_*; V <= 65536.  ref_logits: the teacher's fp32 rows
+ * for the same n decoded rows, V valid columns, row stride ld_ref >= V, independent of ld.  With temperature tau > 0, hard-label
+ * share alpha in [0, 1], p = softmax(z / tau), q = softmax(zr / tau):
+ *   hard    = unimm_lm_loss_fwd's rowloss for (y, w)
+ *   KD      = KL(q || p) = sum_i q_i (log q_i - log p_i)
+ *   rowloss = alpha hard + (1 - alpha) tau^2 KD
+ *   dlogits[row, i] = g inv ( alpha (unimm_lm_loss_bwd's element) + (1 - alpha) tau (p_i - q_i) );  nothing flows into the teacher.
+ * A row takes part when y >= 0 and w > 0 or w == -1 (the weights unimm_lm_loss_fwd gives a loss for).  A row that takes no
+ * part has rowloss = kd = 0 and a gradient row of +0 (rownll is still -log p_y where y >= 0, as unimm_lm_loss_fwd writes it).
+ * Forward, one pass over both rows: beside the student row's running maximum m and s = sum e^(z_i - m) a lane keeps
+ * st = sum e^((z_i - m) / tau), and for the teacher row its own mr, sr = sum e^((zr_i - mr) / tau) and
+ * ur = sum e^((zr_i - mr) / tau) (zr_i - z_i); then lse = m + log s, lse_t = m / tau + log st, ref_lse_t = mr / tau + log sr and
+ * KD = ur / (sr tau) - ref_lse_t + lse_t.  It writes rowloss, rownll, lse, lse_t, ref_lse_t and kd (kd: 0 on a row that takes no
+ * part; the log-sum-exps: every row below the count).  Backward: p_i - q_i = e^(z_i / tau - lse_t) - e^(zr_i / tau - ref_lse_t); a
+ * row whose two coefficients are both zero (no part; alpha == 1 with a clamped unlikelihood; g == 0) is filled with +0 without a
+ * logit being read.  Each row is read once per direction.  The backward reads each row with 16-byte loads when that row's own
+ * stride is a multiple of 4 floats; the forward walks both rows in the student row's column order, so there the teacher row's
+ * 16-byte loads also need ld % 4 == 0 (a student row on the scalar path reads both rows one column at a time).
+ * -inf: a teacher logit of -inf has q_i = 0 and contributes exactly 0 to KD and to the gradient element, whatever z_i holds
+ * (finite or -inf); a student logit of -inf has p_i = 0 (on the label the hard term is +inf, and so is rowloss unless alpha == 0:
+ * a share of exactly 0 or 1 adds nothing of the other term, never 0 * inf).  z_i = -inf where zr_i is finite is OUTSIDE the contract (the engine's
+ * decoder never produces it): that row's KD is +inf and its rowloss and gradient are unspecified (inf / NaN); every other row is
+ * unaffected.
+ * Bit-exact: (1) rownll and lse equal unimm_lm_loss_fwd's on the same arguments bit for bit ((m, s) take its operation
+ * sequence) on every row it defines: a row that holds -inf logits can come out of unimm_lm_loss_fwd as NaN (e^(-inf - -inf)),
+ * here it is finite and equals unimm_pg_loss_fwd's.  (2) With alpha == 1 the soft term is not added and the teacher row is not
+ * read (ref_logits may be NULL; ref_lse_t and kd are written as 0): rowloss and dlogits equal unimm_lm_loss_fwd / _bwd bit for bit
+ * for every weight, -1 included, except that a row whose coefficient is zero is +0 throughout where unimm_lm_loss_bwd leaves -0
+ * on its label.  (3) With ref_logits == logits and ld_ref == ld, kd is exactly +0 and ref_lse_t == lse_t bitwise for any tau (the
+ * teacher row's log-sum-exp takes the student row's operation sequence), and the soft term's gradient elements are exactly
+ * zero.  (4) With tau == 1, lse_t == lse bitwise.
+ * UNIMM_E_ARG before any launch: a NULL pointer (ref_logits only when alpha != 1; n_dev and inv_dev may be NULL), ld_ref < V
+ * with a teacher given, tau not finite or <= 0, alpha outside [0, 1] or NaN; UNIMM_E_SHAPE as for unimm_lm_loss_*, and V > 65536. */
+int unimm_distill_loss_fwd(const float* logits, const int32_t* labels, const int32_t* weights, const float* ref_logits,
+                           int32_t ld_ref, float tau, float alpha, float* rowloss, float* rownll, float* lse, float* lse_t,
+                           float* ref_lse_t, float* kd, int32_t n, int32_t V, int32_t ld, const int32_t* n_dev, void* stream);
+int unimm_distill_loss_bwd(const float* logits, const int32_t* labels, const int32_t* weights, const float* ref_logits,
+                           int32_t ld_ref, float tau, float alpha, const float* lse, const float* lse_t, const float* ref_lse_t,
+                           const float* g, float inv_denom, void* dlogits, int32_t n, int32_t V, int32_t ld, int32_t ldd,
+                           const int32_t* n_dev, const float* inv_dev, void* stream);
 /* Listwise preference objective on the likelihoods of whole candidate answers (csrc/policy.hip; an entry point added beside the
  * ones above, whose signatures and results are unchanged: the ABI number stays).  It sits between unimm_lm_loss_fwd, which leaves
  * rownll = -log p_y per decoded row, and unimm_pg_loss_bwd in LOGP mode, which turns a per-row coefficient A into the gradient of

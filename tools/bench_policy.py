@@ -1,7 +1,7 @@
 """The policy-gradient row kernels against the likelihood row kernels, and one self-critical step, at the full config.
 
     python tools/bench_policy.py [--rows 5016] [--pairs 7] [--launches 20] [--no-step] [--G 8] [--N 8] [--shared [--max-answer-len 14]]
-                                 [--baseline mean|greedy] [--rollout separate|fused ...] [--kl] [--preference [--reference]]
+                                 [--baseline mean|greedy] [--rollout separate|fused ...] [--kl] [--preference [--reference]] [--distill]
 
 Kernels: unimm_pg_loss_fwd + unimm_pg_loss_bwd against unimm_lm_loss_fwd + unimm_lm_loss_bwd on the SAME fp32 logits
 [rows, 30528] (30,522 valid columns; 5,016 rows = the decoded rows of the headline step), in one process as alternating pairs
@@ -44,7 +44,16 @@ candidates of 1 .. 14 tokens, with --shared on the shared schedule, otherwise on
 alternating pairs after a warm-up of each with the KL-leashed policy-gradient step of --kl on the SAME sequences, schedule and
 reference (`lm_advantage`, PolicyObjective(entropy_coef = 0.01, kl_coef = 0.05)): medians, every pair's ratio, the KL step's
 min-to-max spread.  --reference: the preference step compares against `frozen_reference(model)` (one more inference forward, as
-the KL step always has); without it R = 0."""
+the KL step always has); without it R = 0.
+
+--distill (instead of the above): token-level knowledge distillation (policy.DistillObjective, unimm_distill_loss_fwd / _bwd).
+Kernels: each direction of the distillation pair (tau = 2, alpha = 0.5) on its own, beside the same direction of the likelihood
+pair and of the KL pair (LOGP, kl_coef = 0.05) on the same logits and the same second buffer, as alternating launches (lm, kl,
+distill; --pairs repeats of --launches launches each): the time, the bytes the direction moves (each row read once; the backward
+also writes rows x 30528 bf16) and the bytes/s.  Step: the train step (forward_backward + optimizer.step) on G x N candidates of
+1 .. 14 tokens with `lm_objective=DistillObjective()` and `lm_reference=frozen_reference(model)`, with --shared on the shared
+schedule, as alternating pairs after a warm-up of each with the KL-leashed policy-gradient step on the SAME sequences, schedule
+and frozen model: medians, every pair's ratio, the KL step's min-to-max spread."""
 from __future__ import annotations
 
 import argparse
@@ -315,6 +324,118 @@ def pref_step(G, N, pairs, with_reference, share):
     return res
 
 
+def distill_kernels(rows, pairs, launches):
+    from unimm_amd import lib as L
+    g = torch.Generator().manual_seed(0)
+    logits = (torch.randn((rows, LD), generator=g) * 3).cuda()
+    ref = (logits + torch.randn((rows, LD), generator=g).cuda() * 0.3).contiguous()
+    labels = torch.randint(0, V, (rows,), generator=g).to(torch.int32).cuda()
+    weights = torch.ones(rows, dtype=torch.int32, device="cuda")
+    adv = torch.randn(rows, generator=g).cuda()
+    f = lambda: torch.empty(rows, device="cuda")
+    rowloss, rownll, lse, ent, kl, ref_lse, lse_t, ref_lse_t, kd = (f() for _ in range(9))
+    dlog = torch.empty((rows, LD), dtype=torch.bfloat16, device="cuda")
+    gvec = torch.ones(1, device="cuda")
+    inv, inf = 1.0 / rows, float("inf")
+    tau, alpha = 2.0, 0.5
+    fns = dict(
+        lm_fwd=lambda: L.lm_loss_fwd(logits, labels, weights, rowloss, rownll, lse, rows, V),
+        lm_bwd=lambda: L.lm_loss_bwd(logits, labels, weights, lse, gvec, inv, dlog, rows, V),
+        kl_fwd=lambda: L.pg_kl_loss_fwd(logits, labels, None, adv, None, L.PG_LOGP, inf, 0.0, rowloss, rownll, lse, ent, rows, V, ref,
+                                        0.05, kl, ref_lse),
+        kl_bwd=lambda: L.pg_kl_loss_bwd(logits, labels, None, adv, None, L.PG_LOGP, inf, 0.0, lse, ent, gvec, inv, dlog, rows, V, ref,
+                                        0.05, kl, ref_lse),
+        distill_fwd=lambda: L.distill_loss_fwd(logits, labels, weights, ref, tau, alpha, rowloss, rownll, lse, lse_t, ref_lse_t, kd,
+                                               rows, V),
+        distill_bwd=lambda: L.distill_loss_bwd(logits, labels, weights, ref, tau, alpha, lse, lse_t, ref_lse_t, gvec, inv, dlog, rows, V))
+    for name in ("lm", "kl", "distill"):                     # every backward reads what its own forward left
+        fns[name + "_fwd"]()
+    one, two = rows * V * 4, 2 * rows * V * 4
+    nbytes = dict(lm_fwd=one, lm_bwd=one + rows * LD * 2, kl_fwd=two, kl_bwd=two + rows * LD * 2, distill_fwd=two,
+                  distill_bwd=two + rows * LD * 2)
+    t = {k: [] for k in fns}
+    for _ in range(pairs):                                   # alternating: lm, kl, distill, each direction on its own
+        for d in ("fwd", "bwd"):
+            for name in ("lm", "kl", "distill"):
+                fns[name + "_fwd"]()
+                t[f"{name}_{d}"].append(event_ms(fns[f"{name}_{d}"], launches))
+    out = dict(rows=rows, tau=tau, alpha=alpha)
+    for k, v in t.items():
+        m = statistics.median(v)
+        out[k] = dict(us=round(m * 1e3, 1), min_us=round(min(v) * 1e3, 1), max_us=round(max(v) * 1e3, 1), bytes=nbytes[k],
+                      TBps=round(nbytes[k] / m / 1e9, 3))
+        print(f"{k}: {m * 1e3:.1f} us (min {min(v) * 1e3:.1f}, max {max(v) * 1e3:.1f} over {pairs} repeats of {launches} launches), "
+              f"{nbytes[k] / 1e6:.1f} MB, {nbytes[k] / m / 1e9:.2f} TB/s")
+    for name in ("lm", "kl", "distill"):
+        us = out[name + "_fwd"]["us"] + out[name + "_bwd"]["us"]
+        b = nbytes[name + "_fwd"] + nbytes[name + "_bwd"]
+        out[name + "_pair"] = dict(us=round(us, 1), TBps=round(b / us / 1e6, 3))
+        print(f"{name} fwd+bwd: {us:.1f} us, {b / us / 1e6:.2f} TB/s")
+    out["distill_over_kl"] = round(out["distill_pair"]["us"] / out["kl_pair"]["us"], 4)
+    return out
+
+
+def distill_step(G, N, pairs, share):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_generate import dialogs
+    from oracle import vilbert_ref as RF
+    from unimm_amd import SharedContext, VisualDialogEncoder, policy
+    from unimm_amd.optim import FusedAdamW, default_language_weights, reference_param_groups
+    enc = VisualDialogEncoder(CFG_PATH)
+    enc.bert_pretrained.load_state_dict(RF.init_state_dict(RF.make_config(CFG_PATH), seed=5), strict=True)
+    enc = enc.cuda()
+    ref = policy.frozen_reference(enc)
+    eng = enc.bert_pretrained.engine
+    groups = reference_param_groups(enc, lr=1e-5, image_lr=1e-5, language_weights=default_language_weights(enc))
+    opt = FusedAdamW(groups, eng, lr=1e-5)
+    d, c = dialogs(G, seed=3)
+    T, R, C = d["input_ids"].shape[1], d["image_feat"].shape[1], eng.cfg.v_target_size
+    rng = np.random.default_rng(1)
+    lengths = torch.from_numpy(rng.integers(2, 16, (G, N)))                       # 1 .. 14 tokens and the [SEP]
+    tokens = torch.from_numpy(rng.integers(1000, 20000, (G, N, 15)))
+    sb = policy.candidate_training_batch(d["input_ids"], d["token_type_ids"], d["position_ids"], c, tokens, lengths, T)
+    K = sb.input_ids.shape[0]
+    label = torch.zeros((K, R), dtype=torch.int64)
+    label[:, 0] = 1
+    kw = dict(token_type_ids=sb.token_type_ids, token_position_ids=sb.position_ids, attention_mask=sb.attention_mask,
+              masked_lm_labels=sb.masked_lm_labels, next_sentence_label=torch.zeros(K, dtype=torch.int64),
+              image_attention_mask=d["image_attention_mask"][sb.image_index.to(d["image_attention_mask"].device)],
+              image_label=label, image_target=torch.full((G, R, C), 1.0 / C), image_index=sb.image_index,
+              **(dict(shared_context=SharedContext(sb.image_index, 64)) if share else {}))
+    forms = dict(
+        kl=dict(lm_advantage=policy.spread(torch.from_numpy(rng.standard_normal((G, N))), sb),
+                lm_objective=policy.PolicyObjective(entropy_coef=0.01, kl_coef=0.05), lm_reference=ref),
+        distill=dict(lm_objective=policy.DistillObjective(2.0, 0.5), lm_reference=ref))
+    enc.train()
+
+    def wall_ms(form, n=3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = enc.forward_backward(sb.input_ids, d["image_feat"], d["image_loc"], (1.0, 0.0, 0.0), **kw, **forms[form])[1]
+            opt.step()
+            opt.zero_grad()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n, float(loss)
+
+    for form in forms:                                       # warm every shape of both forms up
+        wall_ms(form, 2)
+    t = {form: [] for form in forms}
+    loss = {}
+    for _ in range(pairs):
+        for form in forms:
+            ms, loss[form] = wall_ms(form)
+            t[form].append(ms)
+    med = {form: statistics.median(v) for form, v in t.items()}
+    res = dict(G=G, N=N, sequences=K, rows=int(sb.copy_rows.sum()), shared=bool(share), pairs=pairs, kl_ms=round(med["kl"], 3),
+               distill_ms=round(med["distill"], 3), ratio=round(med["distill"] / med["kl"], 4),
+               pair_ratios=[round(a / b, 3) for a, b in zip(t["distill"], t["kl"])],
+               kl_spread=round((max(t["kl"]) - min(t["kl"])) / med["kl"], 4), loss=loss,
+               mean_kd=float(eng.last_lm_distill) if eng.last_lm_distill is not None else None)
+    print(f"distillation step beside the KL step (G = {G}, N = {N}): {res}")
+    return res
+
+
 def step(G, N, baseline="mean", rollouts=("separate",), pairs=7):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from bench_generate import dialogs
@@ -493,6 +614,7 @@ def main():
     ap.add_argument("--kl", action="store_true", help="time the KL-regularised row kernels and the step with a frozen reference")
     ap.add_argument("--preference", action="store_true", help="time unimm_seq_pref and the preference train step beside the KL step")
     ap.add_argument("--reference", action="store_true", help="--preference: the step compares against a frozen reference")
+    ap.add_argument("--distill", action="store_true", help="time the distillation row kernels and the train step with a teacher")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_policy.py measures on the GPU: no device found")
@@ -501,6 +623,12 @@ def main():
         result = dict(rows=a.rows, pref_kernels=pref_kernels(a.rows, a.pairs, a.launches))
         if not a.no_step:
             result["pref_step"] = pref_step(a.G, a.N, a.pairs, a.reference, a.shared)
+        print(json.dumps(result))
+        return
+    if a.distill:
+        result = dict(rows=a.rows, distill_kernels=distill_kernels(a.rows, a.pairs, a.launches))
+        if not a.no_step:
+            result["distill_step"] = distill_step(a.G, a.N, a.pairs, a.shared)
         print(json.dumps(result))
         return
     if a.kl:

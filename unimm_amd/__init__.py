@@ -5,9 +5,9 @@ Drop-in surface (same names / signatures as the reference):
 """
 from .config import BertConfig
 from .modeling import BertForMultiModalPreTraining, VisualDialogEncoder
-from .policy import PolicyObjective, PreferenceObjective, PreferenceTargets, frozen_reference
+from .policy import DistillObjective, PolicyObjective, PreferenceObjective, PreferenceTargets, frozen_reference
 from .scoring import SharedContext
 
 __version__ = "0.1.0"
 __all__ = ["BertConfig", "BertForMultiModalPreTraining", "VisualDialogEncoder", "SharedContext", "PolicyObjective",
-           "frozen_reference", "PreferenceObjective", "PreferenceTargets"]
+           "frozen_reference", "PreferenceObjective", "PreferenceTargets", "DistillObjective"]

@@ -23,7 +23,8 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 
 // log-sum-exp of one fp32 row (16-byte loads when `vec`), block-wide.  csrc/policy.hip's row_lse_ent performs these operations on
 // m and s one for one (plus a third running sum): the policy step with integer advantages equals the weighted-likelihood step
-// bit for bit (tests/test_gpu_policy_model.py), so a change of the order of operations here is made there as well.
+// bit for bit (tests/test_gpu_policy_model.py), so a change of the order of operations here is made there as well -- and in
+// csrc/distill.hip's row_stats, whose (m, s) are these too (tests/test_gpu_distill_edges.py).
 __device__ __forceinline__ float row_lse(const float* __restrict__ z, int V, bool vec, float* red) {
   float m = -INFINITY, s = 0.f;
   if (vec) {

@@ -1210,7 +1210,9 @@ class Engine:
         self._reference_rows(inp, groups)
         return self._on_text_stream(train_shared, self, inp, groups, g_lm, train)
 
-    _REF_DROPS = (LO.KEY, "lm_weight", "image_target", "image_label", "next_sentence_label", "nsp_weight", "_plan_header")
+    # (lm_weight stays: given weights decide which rows the head decodes -- weight != 0 instead of label != -1 -- and the
+    # reference must decode the step's rows; the objectives that refuse lm_weight never carry one)
+    _REF_DROPS = (LO.KEY, "image_target", "image_label", "next_sentence_label", "nsp_weight", "_plan_header")
 
     def _reference_rows(self, inp, groups=None):
         """The step's objective reads a frozen reference model (`objective.reference`, unimm_amd/lm_objective.py): the reference's

@@ -44,7 +44,9 @@ def combine_losses(lm_loss, nsp_loss, img_loss, c_lm, c_nsp, c_img):
 
 
 def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_scores=False, sample_size=None,
-            evaluation=False):
+            evaluation=False, model_kw=None):
+    """model_kw (an extension): further keywords of the encoder's call, passed through as they are (the LM objective's
+    `lm_objective` / `lm_reference`, unimm_amd/policy.py); None: the reference's call."""
     tokens = _flat(batch["tokens"], 1)
     n = tokens.shape[0]
     idx = torch.randperm(n)[:sample_size] if sample_size else torch.arange(n)
@@ -62,6 +64,8 @@ def forward(dialog_encoder, batch, params, output_nsp_scores=False, output_lm_sc
     if not evaluation:
         kw.update(next_sentence_label=take("next_sentence_labels", 0), image_target=take("image_target", 2),
                   image_label=take("image_label", 1))
+    if model_kw:
+        kw.update(model_kw)
     res = dialog_encoder(tokens[idx.to(tokens.device)], take("image_feat", 2), take("image_loc", 2), **kw)
     lm_loss, img_loss, nsp_loss = res[:3]
     extra = list(res[3:])

@@ -85,6 +85,8 @@ SIGNATURES = {
     "unimm_pg_kl_loss_fwd": (_INT, [VP] * 5 + [I32, I32, F32, F32] + [VP] * 4 + [I32] * 3 + [VP, VP, I32, F32, VP, VP, VP]),
     "unimm_pg_kl_loss_bwd": (_INT, [VP] * 5 + [I32, I32, F32, F32, VP, VP, VP, F32, VP] + [I32] * 4 +
                              [VP, VP, VP, I32, F32, VP, VP, VP]),
+    "unimm_distill_loss_fwd": (_INT, [VP] * 4 + [I32, F32, F32] + [VP] * 6 + [I32] * 3 + [VP, VP]),
+    "unimm_distill_loss_bwd": (_INT, [VP] * 4 + [I32, F32, F32] + [VP] * 4 + [F32, VP] + [I32] * 4 + [VP, VP, VP]),
     "unimm_seq_pref": (_INT, [VP, VP]),
     "unimm_kl_loss_fwd": (_INT, [VP] * 5 + [I32] * 3 + [VP]),
     "unimm_kl_loss_bwd": (_INT, [VP] * 5 + [F32, VP] + [I32] * 4 + [VP, VP]),
@@ -906,6 +908,23 @@ def pg_kl_loss_bwd(logits, labels, pos, adv, blogp, mode, clip_eps, beta, lse, e
     _call("unimm_pg_kl_loss_bwd", _ptr(logits), _ptr(labels), _ptr(pos), _ptr(adv), _ptr(blogp), adv.numel(), mode, clip_eps, beta,
           _ptr(lse), _ptr(ent), _ptr(g), inv_denom, _ptr(dlogits), n, V, logits.stride(0), dlogits.stride(0), _ptr(n_dev),
           _ptr(inv_dev), _ptr(ref_logits), ref_logits.stride(0) if ref_logits is not None else 0, kl_coef, _ptr(kl), _ptr(ref_lse))
+
+
+def distill_loss_fwd(logits, labels, weights, ref_logits, tau, alpha, rowloss, rownll, lse, lse_t, ref_lse_t, kd, n, V, n_dev=None):
+    """Knowledge-distillation rows (include/unimm_hip.h: unimm_distill_loss_fwd).  ref_logits: the frozen teacher's fp32 rows for the
+    same n rows (its own row stride; None with alpha == 1); lse_t / ref_lse_t / kd: fp32 [n], written here."""
+    _dev(logits, labels, weights, ref_logits, rowloss, rownll, lse, lse_t, ref_lse_t, kd, n_dev)
+    _call("unimm_distill_loss_fwd", _ptr(logits), _ptr(labels), _ptr(weights), _ptr(ref_logits),
+          ref_logits.stride(0) if ref_logits is not None else 0, tau, alpha, _ptr(rowloss), _ptr(rownll), _ptr(lse), _ptr(lse_t),
+          _ptr(ref_lse_t), _ptr(kd), n, V, logits.stride(0), _ptr(n_dev))
+
+
+def distill_loss_bwd(logits, labels, weights, ref_logits, tau, alpha, lse, lse_t, ref_lse_t, g, inv_denom, dlogits, n, V, n_dev=None,
+                     inv_dev=None):
+    _dev(logits, labels, weights, ref_logits, lse, lse_t, ref_lse_t, g, dlogits, n_dev, inv_dev)
+    _call("unimm_distill_loss_bwd", _ptr(logits), _ptr(labels), _ptr(weights), _ptr(ref_logits),
+          ref_logits.stride(0) if ref_logits is not None else 0, tau, alpha, _ptr(lse), _ptr(lse_t), _ptr(ref_lse_t), _ptr(g),
+          inv_denom, _ptr(dlogits), n, V, logits.stride(0), dlogits.stride(0), _ptr(n_dev), _ptr(inv_dev))
 
 
 PREF_MAX_MEMBERS, PREF_WS_ITEM_BYTES = 128, 16

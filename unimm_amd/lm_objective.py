@@ -4,7 +4,8 @@
 `LIKELIHOOD`); the engine's `inp` carries it under `KEY`, `Engine._lm_head` moves it into the head's state, lm["objective"]:
     stage(pos, dev)               its per-token inputs to the device; pos: the decoded rows' flat positions b * T + t, int32
     forward(eng, lm, n, n_dev)    the row kernels on lm["logits" / "labels" / "weights"] -> lm["rowloss" / "rownll" / "lse"] (+ "ent",
-                                  "kl", "ref_lse"); n, n_dev: the rows' capacity and, on the replicated schedule, device-side count
+                                  "kl", "ref_lse"; "lse_t", "ref_lse_t", "kd"); n, n_dev: the rows' capacity and, on the replicated
+                                  schedule, device-side count
     loss(eng, lm)                 the fp32 [1] LM loss; sets the engine's last_lm_* reports
     backward(eng, lm, g, dlog)    fills dlog, the loss gradient w.r.t. the logits rows (`Engine._lm_loss_grad`)
     reference                     the frozen model whose forward the step needs first (`Engine._reference_rows`: `.ref`), or None"""
@@ -18,7 +19,8 @@ F32 = torch.float32
 KEY = "lm_bound"
 REPORTS = ("last_lm_entropy",        # engine attributes: fp32 [1], mean entropy of the rows the last policy-gradient step trained
            "last_lm_kl",             # fp32 [1]: mean KL(p || p_ref) of those rows when the step had a reference (kl_coef > 0)
-           "last_lm_preference")     # the last preference step's device tensors: seq_score, seq_prob, group_loss, adv, row_seq
+           "last_lm_preference",     # the last preference step's device tensors: seq_score, seq_prob, group_loss, adv, row_seq
+           "last_lm_distill")        # fp32 [1]: mean KL(teacher || student) at the temperature of the rows the last distillation step trained
 
 
 def _row_mean(lm, key):                        # sum(lm[key]) over the step's rows / their number, fp32 [1]
@@ -94,6 +96,46 @@ class PolicyGradient:
         L.pg_kl_loss_bwd(*args, self.ref, self.kl_coef, lm["kl"], lm["ref_lse"], **tail)
         self.ref.record_stream(torch.cuda.current_stream())
         self.ref = None                        # the reference's logits are released here: the backward was their last reader
+
+
+class Distillation:
+    """Token-level knowledge distillation (unimm_distill_loss_*): the weighted likelihood of the labelled rows, share alpha, mixed
+    with tau^2 KL(teacher || student) at temperature tau against the frozen teacher's rows `ref`.  With alpha == 1 nothing of the
+    teacher is read, so `reference` is None and its forward does not run."""
+
+    def __init__(self, objective, reference):
+        self.objective, self.ref = objective, None
+        self.tau, self.alpha = float(objective.temperature), float(objective.alpha)
+        self.reference = reference if self.alpha != 1.0 else None
+
+    def stage(self, pos, dev):
+        pass
+
+    def forward(self, eng, lm, n, n_dev):
+        lm.update((k, torch.empty(n, dtype=F32, device=lm["logits"].device)) for k in ("lse_t", "ref_lse_t", "kd"))
+        if self.ref is not None:
+            _same_rows(self.ref, n)
+        L.distill_loss_fwd(lm["logits"], lm["labels"], lm["weights"], self.ref, self.tau, self.alpha, lm["rowloss"], lm["rownll"],
+                           lm["lse"], lm["lse_t"], lm["ref_lse_t"], lm["kd"], n, eng.cfg.vocab_size, n_dev=n_dev)
+
+    def loss(self, eng, lm):
+        loss = _row_mean(lm, "rowloss")
+        # the mean KD of the rows that took part (a label and a weight > 0 or -1): two sums and a division, all on the device
+        y, w, n = lm["labels"][:lm["n"]], lm["weights"][:lm["n"]], lm["n"]
+        part = ((y >= 0) & ((w > 0) | (w == -1))).to(F32)
+        sums = torch.empty(2, dtype=F32, device=part.device)
+        L.reduce_sum(lm["kd"], n, sums[0:1], 1.0, n_dev=lm.get("n_dev"))
+        L.reduce_sum(part, n, sums[1:2], 1.0, n_dev=lm.get("n_dev"))
+        eng.last_lm_distill = sums[0:1] / sums[1:2]
+        return loss
+
+    def backward(self, eng, lm, g, dlog):
+        L.distill_loss_bwd(lm["logits"], lm["labels"], lm["weights"], self.ref, self.tau, self.alpha, lm["lse"], lm["lse_t"],
+                           lm["ref_lse_t"], g, 1.0 / lm["n"], dlog, lm["n"], eng.cfg.vocab_size, n_dev=lm.get("n_dev"),
+                           inv_dev=lm.get("inv_dev"))
+        if self.ref is not None:
+            self.ref.record_stream(torch.cuda.current_stream())
+            self.ref = None                    # the teacher's logits are released here: the backward was their last reader
 
 
 class Preference(Likelihood):

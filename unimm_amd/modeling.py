@@ -210,7 +210,10 @@ class BertForMultiModalPreTraining(nn.Module):
         an inference forward on this call's inputs first; with kl_coef == 0 it is ignored.  `lm_preference`
         (`policy.PreferenceTargets`: a group id and a target weight per sequence, with `lm_objective=policy.PreferenceObjective`
         and optionally `lm_reference`) makes lm_loss the listwise preference objective over the candidate answers of each group
-        instead; bf16 engine, train branch; the step's per-sequence results are in `engine.last_lm_preference`.  With
+        instead; bf16 engine, train branch; the step's per-sequence results are in `engine.last_lm_preference`.
+        `lm_objective=policy.DistillObjective(temperature, alpha)` with `lm_reference=teacher` (a frozen model of either class, of
+        any depth and width over the same vocabulary and inputs) makes lm_loss the token-level distillation objective on the
+        labelled rows, `lm_weight` still weighing its hard-label share; bf16 engine, train branch; `engine.last_lm_distill`.  With
         `shared_context` (and `lm_preference`; the conditions of `forward_backward(shared_context=)`) that loss is computed on the
         shared-context schedule, as a value only -- no autograd graph: train with `forward_backward` -- and the call returns
         (lm_loss, 0, 0, None, None, None)."""

@@ -32,7 +32,17 @@ PreferenceTargets(group, weight)` names each sequence's dialog and target weight
 length_normalize)` makes lm_loss, per dialog, the cross-entropy between the targets and the softmax over the dialog's candidates
 of beta (log pi(y) - log pi_ref(y)) (divided by the answer's length with length_normalize): DPO for two candidates and a one-hot
 target (`pair_targets`), the listwise ListNet top-1 form for `relevance_targets`, on exactly the scores `generative_evaluate`
-ranks by.  `lm_reference` is optional (without one log pi_ref = 0).  `trainer.preference_step` is the loop body."""
+ranks by.  `lm_reference` is optional (without one log pi_ref = 0).  `trainer.preference_step` is the loop body.
+
+Knowledge distillation (unimm_distill_loss_fwd / _bwd, csrc/distill.hip): a student fits a frozen teacher's softened distribution
+on ordinary training data.  `lm_reference=teacher` with `lm_objective=DistillObjective(temperature, alpha)` makes the LM loss of
+every labelled row
+    alpha (the weighted likelihood / unlikelihood, `lm_weight` as ever) + (1 - alpha) tau^2 KL(softmax(zr / tau) || softmax(z / tau))
+with the teacher's logits zr for the same rows (`Engine._reference_rows`, as for the KL leash) -- the other direction of KL, a
+temperature, and no advantage.  The teacher need not have the student's shape (`check_teacher`): any depth, width, head count or
+layer schedule over the same vocabulary and inputs, typically a larger model in eval() with requires_grad_(False);
+`frozen_reference(model)` serves self-distillation.  `engine.last_lm_distill` reports the mean KL of the trained rows;
+`trainer.distill_step` is the loop body."""
 from __future__ import annotations
 
 import copy
@@ -79,6 +89,28 @@ class PreferenceObjective:
         b = float(self.beta)
         if not (math.isfinite(b) and b > 0.0):
             raise ValueError(f"PreferenceObjective: beta must be positive and finite, got {self.beta}")
+
+
+@dataclass(frozen=True)
+class DistillObjective:
+    """temperature: tau > 0, both distributions are softmax(logits / tau); alpha: the share of the hard-label term (the weighted
+    likelihood of the labels) in [0, 1], the soft term tau^2 KL(teacher || student) has 1 - alpha (1: the teacher is not run)."""
+    temperature: float = 2.0
+    alpha: float = 0.5
+
+    def __post_init__(self):
+        _check_distill_values(self.temperature, self.alpha)
+
+
+def _check_distill_values(temperature, alpha):
+    try:
+        t, a = float(temperature), float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"DistillObjective: temperature and alpha must be numbers, got {temperature!r} / {alpha!r}") from None
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"DistillObjective: temperature must be positive and finite, got {temperature}")
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"DistillObjective: alpha must lie in [0, 1], got {alpha}")
 
 
 PREF_MAX_MEMBERS = 128        # include/unimm_hip.h: UNIMM_PREF_MAX_MEMBERS
@@ -241,6 +273,54 @@ def check_reference(model, lm_reference, obj):
         raise ValueError(f"lm_reference is on {ref._device()}, the trained model on {model._device()}: move it with .to()")
     return ref if (pref or obj.kl_coef > 0) else None
 
+
+_TEACHER_CONFIG_KEYS = ("vocab_size", "v_feature_size", "type_vocab_size", "max_position_embeddings")
+
+
+def check_teacher(model, lm_reference):
+    """The refused teachers of a `DistillObjective` (ValueError, before anything touches the device) -> the teacher's pre-training
+    model.  Unlike `check_reference` it asks only for what the shared inputs and the logits row depend on: the vocabulary, the
+    region feature size, the segment vocabulary and the position table; depth, widths, head counts, intermediate sizes, the
+    connection schedule and the frozen layers are the teacher's own.  model: the trained BertForMultiModalPreTraining."""
+    ref = _pretraining_model(lm_reference)
+    if ref is model:
+        raise ValueError("lm_reference is the trained model itself: the distillation term against itself is 0 and it would move "
+                         "with every step; pass a separate teacher, or policy.frozen_reference(model) for self-distillation")
+    if not (hasattr(ref, "config") and hasattr(ref, "_engine") and hasattr(ref, "compute_dtype")):
+        raise ValueError(f"the teacher (lm_reference) must be a BertForMultiModalPreTraining or a VisualDialogEncoder, got "
+                         f"{type(lm_reference).__name__}")
+    diff = [k for k in _TEACHER_CONFIG_KEYS if getattr(ref.config, k, None) != getattr(model.config, k, None)]
+    if diff:
+        raise ValueError("the teacher (lm_reference) must read the student's inputs and predict over its vocabulary; its config "
+                         f"differs in {', '.join(diff)}")
+    if ref.compute_dtype != "bf16":
+        raise ValueError(f"the teacher (lm_reference) must run on the bf16 engine (compute_dtype='bf16'), got {ref.compute_dtype!r}")
+    if ref._device() != model._device():
+        raise ValueError(f"the teacher (lm_reference) is on {ref._device()}, the trained model on {model._device()}: move it with .to()")
+    return ref
+
+
+def check_distill_inputs(lm_objective, lm_reference, lm_advantage, lm_behaviour_logp, lm_preference, compute_dtype, train_branch=True):
+    """The refused combinations of the distillation arguments of `forward` / `forward_backward` (ValueError, before anything
+    touches the device) -> the objective in force.  `lm_weight` is allowed: it weighs the hard-label term as it weighs the
+    likelihood.  lm_reference: only its presence is judged here (`check_teacher` judges the model)."""
+    for name, t in (("lm_advantage", lm_advantage), ("lm_behaviour_logp", lm_behaviour_logp), ("lm_preference", lm_preference)):
+        if t is not None:
+            raise ValueError(f"lm_objective=DistillObjective (knowledge distillation) and {name} describe two objectives for the "
+                             "same rows: pass one of them")
+    _check_distill_values(lm_objective.temperature, lm_objective.alpha)
+    if lm_reference is None:
+        raise ValueError("DistillObjective fits the student to a teacher's distribution: pass the teacher as lm_reference (a "
+                         "frozen model of either class; policy.frozen_reference(model) for self-distillation)")
+    if compute_dtype != "bf16":
+        raise ValueError(f"the distillation objective runs on the bf16 engine only: build the model with compute_dtype='bf16' "
+                         f"(got {compute_dtype!r})")
+    if not train_branch:
+        raise ValueError("DistillObjective replaces the LM loss of the train branch: pass masked_lm_labels, next_sentence_label and "
+                         "image_target with it (this call computes no loss and would ignore it)")
+    return lm_objective
+
+
 def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm_weight, compute_dtype, train_branch=True,
                         lm_reference=None):
     """The refused combinations of the policy-gradient arguments of `forward` / `forward_backward` (ValueError, before
@@ -282,8 +362,12 @@ def check_policy_inputs(shape, lm_advantage, lm_behaviour_logp, lm_objective, lm
 
 def bind_objective(model, shape, train_branch=True, *, lm_advantage=None, lm_behaviour_logp=None, lm_objective=None,
                    lm_reference=None, lm_preference=None, lm_weight=None):
-    """The objective keywords of `forward` / `forward_backward` (input_ids of `shape`), judged once by the three checks above -> all
+    """The objective keywords of `forward` / `forward_backward` (input_ids of `shape`), judged once by the checks above -> all
     the engine sees of them: the step's bound objective (unimm_amd/lm_objective.py), None for the likelihood step.  model: the trained one."""
+    if isinstance(lm_objective, DistillObjective):
+        obj = check_distill_inputs(lm_objective, lm_reference, lm_advantage, lm_behaviour_logp, lm_preference, model.compute_dtype,
+                                   train_branch)
+        return LO.Distillation(obj, check_teacher(model, lm_reference))
     if lm_preference is not None:
         obj = check_preference_inputs(shape, lm_preference, lm_objective, lm_advantage, lm_weight, lm_behaviour_logp,
                                       model.compute_dtype, train_branch)

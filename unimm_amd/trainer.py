@@ -15,6 +15,7 @@ dataloader and the checkpoint file, without the data plane.
                        NeuralNDCG^T + LM + weighted NSP objective, scheduler stepped before the optimizer.
 * `self_critical_step` - one iteration of policy-gradient fine-tuning of the answer generator on a host-side
                        reward (an extension, unimm_amd/policy.py): sample answers, score them, train on the advantage.
+* `distill_step`     - `train_step` with the LM term distilled from a frozen teacher (an extension, unimm_amd/policy.py).
 * `visdial_evaluate`  - the validation pass of train.py:180-290 (chunked NSP scoring -> SparseGTMetrics + NDCG).
 * `generative_evaluate` - the validation pass of val_lm.py:38-150 (candidates ranked by sequence log-likelihood)."""
 from __future__ import annotations
@@ -25,7 +26,7 @@ from typing import Optional
 import torch
 
 from . import harness, metrics, ranking
-from .policy import (PolicyObjective, PreferenceObjective, PreferenceTargets, _pretraining_model, candidate_training_batch,
+from .policy import (DistillObjective, PolicyObjective, PreferenceObjective, PreferenceTargets, _pretraining_model, candidate_training_batch,
                      preference_diagnostics, sampled_training_batch, self_critical_advantage, spread)
 from .scoring import SharedContext
 
@@ -42,14 +43,15 @@ def expand_image_fields(batch: dict) -> dict:
     return out
 
 
-def train_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sample_size=None):
-    """One loop iteration (iter_id is the 1-based counter of train.py:411).  Returns (loss, lm, nsp, img) floats."""
+def train_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sample_size=None, model_kw=None):
+    """One loop iteration (iter_id is the 1-based counter of train.py:411).  Returns (loss, lm, nsp, img) floats.
+    model_kw: further keywords of the encoder's call (`harness.forward`); None: the reference's step."""
     bm = int(params.get("batch_multiply", 1))
     boundary = iter_id % bm == 0
     dialog_encoder.train()
     sync_ctx = dialog_encoder.no_sync() if (hasattr(dialog_encoder, "no_sync") and not boundary) else _null()
     with sync_ctx:
-        loss, lm_loss, nsp_loss, img_loss = harness.forward(dialog_encoder, batch, params, sample_size=sample_size)
+        loss, lm_loss, nsp_loss, img_loss = harness.forward(dialog_encoder, batch, params, sample_size=sample_size, model_kw=model_kw)
         (loss / bm).backward()
     if boundary:
         if hasattr(dialog_encoder, "sync_gradients"):
@@ -58,6 +60,20 @@ def train_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sam
         optimizer.zero_grad()
     scheduler.step()
     return float(loss.detach()), lm_loss, nsp_loss, img_loss
+
+
+def distill_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, *, teacher, objective=DistillObjective(),
+                 sample_size=None):
+    """One iteration of token-level knowledge distillation (an extension, unimm_amd/policy.py): `train_step` on an ordinary
+    training batch with the LM term replaced by `objective` against the frozen `teacher` (`lm_objective=objective`,
+    `lm_reference=teacher`; the batch's `weights` still weigh the hard-label share).  The NSP and region terms train as usual, the
+    `batch_multiply` / `no_sync` cadence is `train_step`'s.  The teacher may be deeper or wider than the student (a separate model
+    in eval() with requires_grad_(False), or `policy.frozen_reference(model)`); nothing of it changes.  The step's mean
+    KL(teacher || student) is in `engine.last_lm_distill` afterwards.  -> `train_step`'s tuple."""
+    engine = _pretraining_model(_unwrap(dialog_encoder)).engine
+    engine.last_lm_distill = None              # never a value an earlier step left behind
+    return train_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, sample_size=sample_size,
+                      model_kw=dict(lm_objective=objective, lm_reference=teacher))
 
 
 _OPTION_FIELDS = ("tokens", "segments", "positions", "weights", "sep_indices", "mask", "hist_len",
