@@ -400,6 +400,9 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     cfg = model.config
     if not cfg.with_coattention:
         raise NotImplementedError("generate_answers needs the connection layers (with_coattention)")
+    D = cfg.hidden_size // cfg.num_attention_heads
+    if D != 64:                                             # here, before the inputs are staged: nothing reaches the device
+        raise ValueError(f"generate_answers: text head size {D} (unimm_attn_decode takes 64)")
     G, T = input_ids.shape
     c_h = (context_len.cpu().numpy() if torch.is_tensor(context_len) else np.asarray(context_len)).astype(np.int64).reshape(-1)
     if c_h.shape[0] != G:
@@ -451,9 +454,7 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     S = G * beams
     H, Hb, V = cfg.hidden_size, cfg.bi_hidden_size, cfg.vocab_size
     heads, nh = cfg.num_attention_heads, cfg.bi_num_attention_heads
-    D, Db = H // heads, Hb // nh
-    if D != 64:
-        raise ValueError(f"generate_answers: text head size {D} (unimm_attn_decode takes 64)")
+    D, Db = H // heads, Hb // nh                           # (D == 64: generate_answers refused any other before staging)
     R = inp["image_feat"].shape[1]
     ar = torch.arange(G, device=dev)
     c_d = torch.from_numpy(c_h).to(dev)

@@ -159,6 +159,15 @@ class SharedContextPlan:
         self.lm_pos = lb * T + (length[lb] - n[lb]) + k            # its padded position b * T + t
 
 
+def check_shared_head_size(cfg, what):
+    """The shared pass that TRAINS (a tape, dropout, lse) launches unimm_attn_spliced_fwd / _bwd on the text stream, which take a
+    head size of 64 only; inference -- unimm_attn_fwd with a shared segment, unimm_x3_attn_fwd -- takes 64 and 128.  Refused on
+    the host, before anything is launched."""
+    D = cfg.hidden_size // cfg.num_attention_heads
+    if D != 64:
+        raise ValueError(f"{what}: text head size {D} (unimm_attn_spliced_fwd / unimm_attn_spliced_bwd take 64)")
+
+
 def _i32(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=torch.int32, non_blocking=True)
 
@@ -192,6 +201,8 @@ def _forward_shared(eng, inp, groups, want_nsp, cache=None, st=None, want_logits
         raise NotImplementedError("the key/value caches of the shared pass are answer generation's, which runs on the bf16 engine")
     if not cfg.with_coattention:
         raise NotImplementedError("shared-context scoring needs the connection layers (with_coattention)")
+    if save:
+        check_shared_head_size(cfg, "shared_context training")
     eng.refresh_weights()
     ids = inp["input_ids"]
     B, T = ids.shape
@@ -508,6 +519,7 @@ def check_shared_training(cfg, compute_dtype, loss_weights, attention_mask, grou
     if not cfg.with_coattention or cfg.fixed_t_layer or cfg.fixed_v_layer:
         raise ValueError("the shared-context training step needs the connection layers (with_coattention) and no frozen layers "
                          "(fixed_t_layer = fixed_v_layer = 0)")
+    check_shared_head_size(cfg, "shared_context training")
     spec = attention_mask
     if not isinstance(spec, DialogMaskSpec) or len(spec) == 0 or int(spec.mode.min()) != 1:
         raise ValueError("shared_context: attention_mask must be a generative-mode DialogMaskSpec (one descriptor per sequence)")
