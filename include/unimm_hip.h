@@ -722,7 +722,7 @@ int unimm_segment_sum(const float* src, const int32_t* seg, float* dst, int64_t 
 #define UNIMM_ADAMW_MAX_GROUPS 8
 typedef struct {
   float* p;              /* [n] fp32 parameters (updated in place) */
-  const float* g;        /* [n] fp32 gradients */
+  float* g;              /* [n] fp32 gradients (cleared in place when zero_grad != 0: not const) */
   float* m;              /* [n] fp32 exp_avg */
   float* v;              /* [n] fp32 exp_avg_sq */
   void* w16;             /* [n] bf16 copy of p or NULL */

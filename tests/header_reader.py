@@ -98,6 +98,37 @@ def streamed(text):
     return {name for name, _, args in _prototypes(text) if args and args[-1][1:] == ("stream", "void*")}
 
 
+def pointer_params(text):
+    """{prototype name: [(argument index, parameter name, C type text, is const, pointee struct name or None)]} of every pointer
+    parameter: what tests/stream_trace.py checks the raw arguments of each call against."""
+    names = set(structs(text))
+    out = {}
+    for name, _, args in _prototypes(text):
+        rows = []
+        for i, (_, pname, ctext) in enumerate(args):
+            if "*" in ctext:
+                base = ctext.replace("const ", "").replace("*", "").strip()
+                rows.append((i, pname, ctext, ctext.startswith("const "), base if base in names else None))
+        out[name] = rows
+    return out
+
+
+def struct_pointers(text):
+    """{struct name: [(field, is const, array length or None)]} of the pointer fields of every struct."""
+    consts, out = constants(text), {}
+    for body, name in re.findall(_STRUCT, _code(text)):
+        rows = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            m = re.fullmatch(r"((?:const\s+)?\w+)\b\s*(.*)", decl, flags=re.S)
+            for declarator in m.group(2).split(","):
+                d = re.fullmatch(r"(\**)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?", declarator.strip())
+                if d.group(1):
+                    n = d.group(3)
+                    rows.append((d.group(2), m.group(1).startswith("const"), None if n is None else int(n) if n.isdigit() else consts[n]))
+        out[name] = rows
+    return out
+
+
 def _tn(t):
     return getattr(t, "__name__", repr(t))
 

@@ -1068,7 +1068,8 @@ class Engine:
         staged = self._stager.stage(inp, _STAGED_KEYS, pack=pack)
         if staged and self._dual():
             side = self._side_stream()
-            for k in ("image_feat", "image_loc", "image_attention_mask", "image_target", "image_label"):
+            # (the co-attention mask: the regions attend the text on the image stream, forward and backward)
+            for k in ("image_feat", "image_loc", "image_attention_mask", "image_target", "image_label", "co_attention_mask"):
                 v = inp.get(k)
                 self._touch(v.words if isinstance(v, PackedMask) else v, side)
         return staged
@@ -1397,7 +1398,9 @@ class Engine:
         # ---- image embedding first: it does not depend on the plan, so the image stream already has work while the
         # host waits for the header below (models/vilbert_dialog.py:360-383)
         F = cfg.v_feature_size
-        self._to_img()                        # masks are packed (and the previous step is behind us): the image side may start
+        # masks are packed (and the previous step is behind us): the image side may start; it reads the caller's region
+        # features and boxes, which may come from any stream's allocator pool (a prefetcher's copy stream)
+        self._to_img(feat, inp["image_loc"])
         with self._img():                     # image embedding: beside the first text layers
             featd = feat.to(dev, dtype=F32, non_blocking=True)
             locd = inp["image_loc"].to(dev, dtype=F32, non_blocking=True)
@@ -1463,6 +1466,8 @@ class Engine:
         pred_v_out = None
         if want_pred_v or inp.get("image_target") is not None:
             C = cfg.v_target_size
+            if not self.image_head_side:
+                self._to_txt(xv)              # the head runs on the main stream: it reads what the image stream's last block wrote
             with self._img_if(self.image_head_side):
                 tv, uvh, hvn, mh, rh, pred_v = self._transform_head(xv, self.lin["imgtr"], "imgtr", self.lin["imgdec"],
                                                                     _rup(C, 4), save)
