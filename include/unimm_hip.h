@@ -948,6 +948,37 @@ typedef struct {
 } unimm_kv_update_args;
 int unimm_kv_cache_update(const unimm_kv_update_args* args, void* stream);
 
+/* Speculative decoding (unimm_amd/speculative.py).  The pair-structured form of unimm_attn_decode: the nr new rows of a slot are
+ * nr / 2 (answer row, copy row) pairs that go through the blocks at once; new row i of a slot is pair i / 2, kind i % 2 (0 = answer
+ * row, 1 = copy row).  Every new row attends, in this order: the group's shared context rows, the slot's private rows [0, plen[s]),
+ * the new ANSWER rows (even rows) of the pairs <= its own pair, in pair order, and -- a copy row -- itself.  No row attends another
+ * copy row or an answer row of a later pair: with answer rows n-1 .. and copy rows n .. of consecutive steps that is the generative
+ * mask of every one of those steps.  Same struct, same layout of every buffer, same clamps (ctx_len[g] to [0, 256], plen[s] to
+ * [0, min(pcap, 320 - nr - ctx_len[g])]: with ctx_len = 256, nr = 32 a slot sees its first 32 private rows) and the same statement
+ * of what is read and written as unimm_attn_decode; fp32 scores and P.V on the vector ALU in that kernel's order of operations.
+ * nr even, 2 <= nr <= 32, beams * nr <= 32, D = 64, anything else UNIMM_E_SHAPE before a launch.  nr = 2 is unimm_attn_decode's
+ * rule, and `out` is bit-identical to its. */
+int unimm_attn_verify(const unimm_attn_decode_args* args, void* stream);
+
+/* In-place append to the private caches of all `layers` text layers in one launch; the slots keep their parents.  Slot s copies
+ * count[s] new rows into cache rows plen[s] .. plen[s] + count[s] - 1 of every layer: source row j is
+ * new_kv + layer * new_layer_stride + (s * new_row_mul + j * new_row_step) * ld_new (width elements), destination
+ * cache + ((layer * slots + s) * pcap + plen[s] + j) * ldp; plen_out[s] = plen[s] + count[s].  Bit-exact copies.
+ * Clamps: plen[s] is taken as min(max(plen[s], 0), pcap), count[s] as min(max(count[s], 0), max_count, pcap - plen[s]): a full
+ * slot appends nothing and reports plen_out = pcap.  Of the cache exactly the columns [0, width) of the named rows are written;
+ * of the new rows only those columns of the count[s] named rows are read.  width % 8 == 0, strides % 8 == 0, width <= ldp.
+ * plen == plen_out returns UNIMM_E_ARG (every layer's workgroup reads plen[s] while one of them writes plen_out[s]), a
+ * misaligned pointer / width / stride UNIMM_E_ALIGN, both before any launch. */
+typedef struct {
+  void* cache;                                   /* bf16 [layers][slots][pcap][ldp] */
+  const void* new_kv;                            /* bf16 */
+  const int32_t* count; const int32_t* plen; int32_t* plen_out;    /* int32 [slots], device */
+  int32_t layers, slots, pcap, ldp, width, max_count;
+  int64_t new_layer_stride;                      /* elements */
+  int32_t ld_new, new_row_mul, new_row_step;
+} unimm_kv_append_args;
+int unimm_kv_cache_append(const unimm_kv_append_args* args, void* stream);
+
 /* Log-softmax + top-K of fp32 logits [rows, ldl] (models/vilbert_dialog.py:1023-1026 decoder output), one row per
  * workgroup, the vocabulary streamed once with an online log-sum-exp.  logp = logit - lse over ALL V ids (no renormalisation
  * after banning).  Then -inf for: the `nbanned` ids of `banned` (int32, device), id `sep` when flags[row] & 1, every id other

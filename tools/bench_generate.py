@@ -6,6 +6,7 @@ against the recompute lower bound: sequence_log_likelihood of the same G * beams
 
     python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile] [--samples N]
                                    [--no-repeat-ngram N] [--repetition-penalty R] [--repeat-scope answer|dialog]
+                                   [--draft-layers t,v,c --draft-len g [g ...]]
 
 --samples N adds, for G = 80 dialogs: ms/step of sampling N answers per dialog (temperature 0.8, top_k 50, top_p 0.9) against a
 beam run with the same number of hypothesis slots (beams = N) in the same process, the time of one unimm_lm_sample launch against
@@ -17,6 +18,13 @@ unimm_lm_topk_hist launch against one unimm_lm_topk launch and one unimm_lm_samp
 launch on the same [80 slots, 30522] logits (10 answer tokens of history per row, and with --repeat-scope dialog the dialogs'
 contexts), and the whole decode loop (20 tokens, beams and samples) with and without the rules -- each as alternating pairs in
 one process: the median of the per-pair ratios, and the spread (max / min) of the plain form over the pairs.
+
+--draft-layers t,v,c (text, image and connection layers of a randomly initialised draft) with --draft-len g ... adds, at G = 80:
+the time of one plain decode step (two rows per dialog), of one verify pass of the model at each g (2 (g + 1) rows per dialog
+through unimm_attn_verify, the head and the top-1 on g + 1 rows), of one decode step of the draft, the break-even acceptance that
+follows from the three -- a round costs g draft steps + one verify pass and yields (accepted drafts + 1) tokens, a plain step yields
+one -- and the end-to-end time of a speculative call with a frozen copy of the model as the draft against the plain call.  The
+copy's acceptance is near 1: that measures the machinery, not a speed-up (no trained student exists).
 
 --profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
 process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
@@ -199,6 +207,69 @@ def measure_constraints(model, G, N, reps, ngram, penalty, scope):
     return {k: round(v, 4) if isinstance(v, float) else v for k, v in row.items()}
 
 
+def measure_speculative(model, G, layers, gammas, reps):
+    """One plain decode step, one verify pass per draft_len, one step of a random draft of `layers` = (text, image, connection)
+    layers, the break-even acceptance, and a speculative call with a frozen copy as the draft."""
+    from unimm_amd import BertConfig, BertForMultiModalPreTraining
+    from unimm_amd import generation as GN
+    from unimm_amd import speculative as SP
+    from unimm_amd.policy import frozen_reference
+    nt_, nv_, nc_ = layers
+    cfgd = json.load(open(CFG_PATH))
+    cfgd.update(num_hidden_layers=nt_, v_num_hidden_layers=nv_, t_biattention_id=list(range(nt_ - nc_, nt_)),
+                v_biattention_id=list(range(nv_ - nc_, nv_)))
+    torch.manual_seed(7)
+    small = BertForMultiModalPreTraining(BertConfig.from_dict(cfgd)).cuda().eval()
+    d, c = dialogs(G, seed=G * 10 + 1)
+    limits = GN.answer_limits(c, T, ANS)
+    banned = torch.tensor([0, 101, 103], dtype=torch.int32, device="cuda")
+    inp = dict(input_ids=d["input_ids"], image_feat=d["image_feat"], image_loc=d["image_loc"], token_type_ids=d["token_type_ids"],
+               position_ids=d["position_ids"], image_attention_mask=d["image_attention_mask"])
+    gen = torch.Generator().manual_seed(0)
+
+    def side_of(m, pcap):
+        eng = m._engine
+        eng.ensure(m._device())
+        with torch.no_grad():
+            side = eng._on_text_stream(SP._Side, eng, dict(inp), c, limits, pcap, banned)
+        side.plen[side.cur].fill_(ANS // 2)                                  # the middle of an answer: 10 private rows
+        return side
+
+    def pass_ms(side, P):
+        tokens = torch.randint(1000, 30522, (G, P), generator=gen).cuda()
+        k = (ANS // 2 + 1 + torch.arange(P, device="cuda"))[None].expand(G, P).contiguous()
+        flags = torch.zeros(G * P, dtype=torch.int32, device="cuda")
+
+        def run():
+            with torch.no_grad():
+                side.eng._on_text_stream(lambda: side.top1(side.rows(tokens, k, list(range(P))), G * P, flags, P))
+        return launch_us(run, n=max(10, 10 * reps)) / 1e3
+
+    tgt, drf = side_of(model, ANS), side_of(small, ANS + max(gammas))
+    plain_ms, draft_ms = pass_ms(tgt, 1), pass_ms(drf, 1)
+    copy = frozen_reference(model)
+    call_plain = timed(lambda: generate(model, d, c, 1, ANS), reps)
+    row = dict(G=G, draft_layers=list(layers), plain_step_ms=round(plain_ms, 4), draft_step_ms=round(draft_ms, 4),
+               plain_call_ms=round(call_plain, 3), per_draft_len=[])
+    for g in gammas:
+        verify_ms = pass_ms(tgt, g + 1)
+        need = (g * draft_ms + verify_ms) / plain_ms - 1.0                   # accepted drafts per round at which a round pays
+        lo, hi = 0.0, 1.0                                                    # ... and the per-token acceptance with that mean
+        for _ in range(50):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if sum(mid ** j for j in range(1, g + 1)) < need else (lo, mid)
+        res = generate(model, d, c, 1, ANS, draft=copy, draft_len=g)
+        assert bool((res.lengths == ANS + 1).all())
+        sp = res.speculation
+        call = timed(lambda: generate(model, d, c, 1, ANS, draft=copy, draft_len=g), reps)
+        row["per_draft_len"].append(dict(
+            draft_len=g, verify_ms=round(verify_ms, 4), verify_over_plain=round(verify_ms / plain_ms, 3),
+            break_even_accepted_per_round=round(need, 3), break_even_token_acceptance=(round(hi, 3) if need < g else None),
+            copy_call_ms=round(call, 3), copy_call_over_plain=round(call / call_plain, 3), copy_rounds=sp.rounds,
+            copy_acceptance=round(float(sp.accepted.sum()) / max(float(sp.drafted.sum()), 1.0), 3)))
+    return row
+
+
 def recompute_bound(model, d, c, G, beams, reps):
     """Summed ms of scoring G * beams sequences with answers of 1 .. ANS tokens (shared context up to 14 answer tokens)."""
     from unimm_amd.inputs import DialogMaskSpec
@@ -278,6 +349,9 @@ def main():
     ap.add_argument("--no-repeat-ngram", type=int, default=0, help="add the cost of the history rules at G = 80 with this n-gram size")
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="... and / or with this repetition penalty")
     ap.add_argument("--repeat-scope", choices=("answer", "dialog"), default="answer")
+    ap.add_argument("--draft-layers", default=None, help="t,v,c: add the speculative-decoding measurements at G = 80 with a random draft "
+                    "of that many text, image and connection layers")
+    ap.add_argument("--draft-len", type=int, nargs="+", default=[4], help="... at these draft lengths")
     a = ap.parse_args()
     torch.set_num_threads(min(16, torch.get_num_threads()))
     model = build_model()
@@ -306,6 +380,15 @@ def main():
               f"{r['lm_sample_rows_spread']:.3f}); decode loop with / without the rules: beams {r['beam_ruled_ratio']:.3f} "
               f"({r['beam_call_ms']:.1f} ms, spread {r['beam_call_spread']:.3f}), samples {r['sample_ruled_ratio']:.3f} "
               f"({r['sample_call_ms']:.1f} ms, spread {r['sample_call_spread']:.3f})")
+    if a.draft_layers:
+        result["speculative"] = r = measure_speculative(model, 80, tuple(int(x) for x in a.draft_layers.split(",")), a.draft_len, a.reps)
+        print(f"speculative decoding at G = {r['G']}: plain decode step {r['plain_step_ms']:.3f} ms, step of a random "
+              f"{'+'.join(map(str, r['draft_layers']))}-layer draft {r['draft_step_ms']:.3f} ms, plain call {r['plain_call_ms']:.1f} ms")
+        for q in r["per_draft_len"]:
+            print(f"  draft_len {q['draft_len']:>2}: verify pass {q['verify_ms']:.3f} ms = {q['verify_over_plain']:.2f} x a plain step; a round "
+                  f"pays above {q['break_even_accepted_per_round']:.2f} accepted drafts (per-token acceptance "
+                  f"{q['break_even_token_acceptance']}); frozen copy as draft: {q['copy_call_ms']:.1f} ms = {q['copy_call_over_plain']:.2f} x "
+                  f"the plain call, {q['copy_rounds']} rounds, acceptance {q['copy_acceptance']:.3f}")
     if a.profile:
         result["kernel_mix_80x4"] = profile()
         for m in result["kernel_mix_80x4"]:

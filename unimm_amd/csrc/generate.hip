@@ -1,5 +1,6 @@
 // Answer generation kernels (include/unimm_hip.h, ABI 19-20): text self-attention of the decode rows against a shared context
-// cache plus per-hypothesis private caches, the per-step private-cache append + reorder, log-softmax + top-K of the
+// cache plus per-hypothesis private caches (unimm_attn_verify: its pair-structured form for speculative decoding, with the in-place
+// unimm_kv_cache_append), the per-step private-cache append + reorder, log-softmax + top-K of the
 // decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20; with per-row
 // parameters unimm_lm_sample_rows, ABI 24: the same kernel template).  unimm_lm_topk_hist / unimm_lm_sample_hist are the same two
 // kernel templates with HIST on: a per-row token history adds no-repeat n-gram bans and a repetition penalty (apply_history).
@@ -170,6 +171,154 @@ __global__ __launch_bounds__(NTHREADS) void attn_decode_kernel(DecodeParams p) {
       a = fmaf(S[r * KMAX + c + pl + e], bf2f(p.v[(int64_t)(s * p.nr + e) * p.ldv + h * DH + d]), a);
     p.out[(int64_t)(row0 + r) * p.ldo + h * DH + d] = f2bf(a);
   }
+}
+
+// Pair-structured form of the kernel above (unimm_attn_verify): the nr new rows of a slot are nr / 2 (answer row, copy row) pairs.
+// New row i (pair i / 2, kind i % 2) attends the context, the private rows, the ANSWER rows of the pairs <= its own and, a copy
+// row, itself; its keys among the new rows are compacted into score columns [c + pl, c + pl + i / 2 + 1 + i % 2), so the softmax
+// and P.V walk a key prefix exactly as above.  Same staging, dot product, lane order and fma chain: nr = 2 gives the same bits.
+__global__ __launch_bounds__(NTHREADS) void attn_verify_kernel(DecodeParams p) {
+  __shared__ float Qs[QMAX * DH];
+  __shared__ float S[QMAX * KMAX];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  const int nq = p.beams * p.nr;
+  const int row0 = g * nq;
+  const int slot0 = g * p.beams;
+  const int c = min(max(p.ctx_len[g], 0), 256);
+  const int co = p.ctx_off[g];
+  auto plen_of = [&](int s) { return min(min(max(p.plen[s], 0), p.pcap), KMAX - p.nr - c); };
+
+  for (int idx = tid; idx < nq * DH; idx += NTHREADS) {
+    const int r = idx / DH, d = idx % DH;
+    Qs[idx] = bf2f(p.q[(int64_t)(row0 + r) * p.ldq + h * DH + d]) * p.scale;
+  }
+  __syncthreads();
+
+  for (int j = tid; j < c; j += NTHREADS) {
+    float kf[DH];
+    load_row64(p.ctx_k + (int64_t)(co + j) * p.ldc + h * DH, kf);
+    for (int r = 0; r < nq; ++r) S[r * KMAX + j] = dot64(Qs + r * DH, kf);
+  }
+  // private rows: every new row of the slot; new answer row of pair e: the rows of pairs >= e, column pl + e; new copy row i:
+  // row i alone, column pl + i / 2 + 1
+  const int npk = p.pcap + p.nr;
+  for (int t = tid; t < p.beams * npk; t += NTHREADS) {
+    const int b = t / npk, j = t % npk;
+    const int s = slot0 + b;
+    const int pl = plen_of(s);
+    if (j >= pl + p.nr) continue;
+    float kf[DH];
+    if (j < pl) {
+      load_row64(p.priv_k + ((int64_t)s * p.pcap + j) * p.ldp + h * DH, kf);
+      for (int i = 0; i < p.nr; ++i) S[(b * p.nr + i) * KMAX + c + j] = dot64(Qs + (b * p.nr + i) * DH, kf);
+    } else {
+      const int n = j - pl, e = n >> 1;
+      load_row64(p.k + (int64_t)(s * p.nr + n) * p.ldk + h * DH, kf);
+      if (n & 1) {
+        S[(b * p.nr + n) * KMAX + c + pl + e + 1] = dot64(Qs + (b * p.nr + n) * DH, kf);
+      } else {
+        for (int i = n; i < p.nr; ++i) S[(b * p.nr + i) * KMAX + c + pl + e] = dot64(Qs + (b * p.nr + i) * DH, kf);
+      }
+    }
+  }
+  __syncthreads();
+
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int r = wave; r < nq; r += NTHREADS / 64) {
+    const int b = r / p.nr, i = r % p.nr;
+    const int nk = c + plen_of(slot0 + b) + (i >> 1) + 1 + (i & 1);
+    float* Sr = S + r * KMAX;
+    float m = -INFINITY;
+    for (int j = lane; j < nk; j += 64) m = fmaxf(m, Sr[j]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < nk; j += 64) {
+      const float e = expf(Sr[j] - m);
+      Sr[j] = e;
+      sum += e;
+    }
+    const float inv = 1.0f / wave_sum(sum);
+    for (int j = lane; j < nk; j += 64) Sr[j] *= inv;
+  }
+  __syncthreads();
+
+  const int d = tid & (DH - 1), rg = tid >> 6;
+  constexpr int RPT = QMAX / (NTHREADS / DH);
+  float acc[RPT];
+#pragma unroll
+  for (int u = 0; u < RPT; ++u) acc[u] = 0.f;
+  const bf16_t* vcol = p.ctx_v + (int64_t)co * p.ldc + h * DH + d;
+  constexpr int VU = 8;
+  int j = 0;
+  for (; j + VU <= c; j += VU) {
+    float v[VU];
+#pragma unroll
+    for (int e = 0; e < VU; ++e) v[e] = bf2f(vcol[(int64_t)(j + e) * p.ldc]);
+#pragma unroll
+    for (int u = 0; u < RPT; ++u) {
+      const int r = rg + 4 * u;
+      if (r < nq) {
+#pragma unroll
+        for (int e = 0; e < VU; ++e) acc[u] = fmaf(S[r * KMAX + j + e], v[e], acc[u]);
+      }
+    }
+  }
+  for (; j < c; ++j) {
+    const float v = bf2f(vcol[(int64_t)j * p.ldc]);
+#pragma unroll
+    for (int u = 0; u < RPT; ++u) {
+      const int r = rg + 4 * u;
+      if (r < nq) acc[u] = fmaf(S[r * KMAX + j], v, acc[u]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < RPT; ++u) {
+    const int r = rg + 4 * u;
+    if (r >= nq) continue;
+    const int b = r / p.nr, i = r % p.nr, s = slot0 + b;
+    const int pl = plen_of(s);
+    float a = acc[u];
+    const bf16_t* pcol = p.priv_v + (int64_t)s * p.pcap * p.ldp + h * DH + d;
+    int j = 0;
+    for (; j + 4 <= pl; j += 4) {
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = bf2f(pcol[(int64_t)(j + e) * p.ldp]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) a = fmaf(S[r * KMAX + c + j + e], v[e], a);
+    }
+    for (; j < pl; ++j) a = fmaf(S[r * KMAX + c + j], bf2f(pcol[(int64_t)j * p.ldp]), a);
+    for (int e = 0; e <= (i >> 1); ++e)            // the answer rows of the pairs up to its own
+      a = fmaf(S[r * KMAX + c + pl + e], bf2f(p.v[(int64_t)(s * p.nr + 2 * e) * p.ldv + h * DH + d]), a);
+    if (i & 1)                                      // a copy row: itself
+      a = fmaf(S[r * KMAX + c + pl + (i >> 1) + 1], bf2f(p.v[(int64_t)(s * p.nr + i) * p.ldv + h * DH + d]), a);
+    p.out[(int64_t)(row0 + r) * p.ldo + h * DH + d] = f2bf(a);
+  }
+}
+
+struct KvAppendParams {
+  bf16_t* cache; const bf16_t* nkv;
+  const int32_t *count, *plen; int32_t* plen_out;
+  int layers, slots, pcap, ldp, width, max_count;
+  int64_t nls;
+  int ld_new, row_mul, row_step;
+};
+
+// grid (slots, layers): rows [plen[s], plen[s] + count[s]) of slot s of layer l <- the slot's new rows j * row_step
+__global__ __launch_bounds__(NTHREADS) void kv_append_kernel(KvAppendParams a) {
+  const int s = blockIdx.x, l = blockIdx.y;
+  const int pl = min(max(a.plen[s], 0), a.pcap);
+  const int cnt = min(min(max(a.count[s], 0), a.max_count), a.pcap - pl);
+  const int vec = a.width / 8;
+  bf16_t* dst = a.cache + (((int64_t)l * a.slots + s) * a.pcap + pl) * a.ldp;
+  const bf16_t* nrow = a.nkv + l * a.nls + (int64_t)s * a.row_mul * a.ld_new;
+  for (int t = threadIdx.x; t < cnt * vec; t += NTHREADS) {
+    const int r = t / vec, c = t % vec;
+    reinterpret_cast<uint4*>(dst + (int64_t)r * a.ldp)[c] =
+        reinterpret_cast<const uint4*>(nrow + (int64_t)r * a.row_step * a.ld_new)[c];
+  }
+  if (l == 0 && threadIdx.x == 0) a.plen_out[s] = pl + cnt;
 }
 
 struct KvParams {
@@ -662,13 +811,14 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) 
 
 }  // namespace
 
-extern "C" int unimm_attn_decode(const unimm_attn_decode_args* a, void* stream) {
+// the checks and the launch of the two decode-attention entry points: they differ in the admitted nr and in the kernel
+static int launch_decode(const unimm_attn_decode_args* a, void* stream, bool pairs) {
   if (a == nullptr || a->q == nullptr || a->k == nullptr || a->v == nullptr || a->out == nullptr || a->ctx_k == nullptr ||
       a->ctx_v == nullptr || a->ctx_off == nullptr || a->ctx_len == nullptr || a->plen == nullptr)
     return UNIMM_E_ARG;
   if (a->pcap > 0 && (a->priv_k == nullptr || a->priv_v == nullptr)) return UNIMM_E_ARG;
-  if (a->D != DH || a->H < 1 || a->H * DH > 1024 || a->G < 1 || a->beams < 1 || (a->nr != 1 && a->nr != 2) ||
-      a->beams * a->nr > QMAX || a->pcap < 0)
+  if (a->D != DH || a->H < 1 || a->H * DH > 1024 || a->G < 1 || a->beams < 1 ||
+      (pairs ? (a->nr < 2 || a->nr > QMAX || a->nr % 2 != 0) : (a->nr != 1 && a->nr != 2)) || a->beams * a->nr > QMAX || a->pcap < 0)
     return UNIMM_E_SHAPE;
   if (!al16(a->q) || !al16(a->k) || !al16(a->v) || !al16(a->ctx_k) || !al16(a->ctx_v) ||
       (a->pcap > 0 && (!al16(a->priv_k) || !al16(a->priv_v) || a->ldp % 8)) ||
@@ -681,7 +831,34 @@ extern "C" int unimm_attn_decode(const unimm_attn_decode_args* a, void* stream) 
   p.G = a->G; p.beams = a->beams; p.nr = a->nr; p.H = a->H; p.pcap = a->pcap;
   p.ldq = a->ldq; p.ldk = a->ldk; p.ldv = a->ldv; p.ldo = a->ldo; p.ldc = a->ldc; p.ldp = a->ldp;
   p.scale = a->scale;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3((unsigned)(a->G * a->H)), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  if (pairs)
+    hipLaunchKernelGGL(attn_verify_kernel, dim3((unsigned)(a->G * a->H)), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(attn_decode_kernel, dim3((unsigned)(a->G * a->H)), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
+}
+
+extern "C" int unimm_attn_decode(const unimm_attn_decode_args* a, void* stream) { return launch_decode(a, stream, false); }
+
+extern "C" int unimm_attn_verify(const unimm_attn_decode_args* a, void* stream) { return launch_decode(a, stream, true); }
+
+extern "C" int unimm_kv_cache_append(const unimm_kv_append_args* a, void* stream) {
+  if (a == nullptr || a->cache == nullptr || a->new_kv == nullptr || a->count == nullptr || a->plen == nullptr ||
+      a->plen_out == nullptr)
+    return UNIMM_E_ARG;
+  if (a->layers < 1 || a->slots < 1 || a->pcap < 1 || a->width < 8 || a->width > a->ldp || a->max_count < 0 ||
+      a->new_row_mul < 0 || a->new_row_step < 0)
+    return UNIMM_E_SHAPE;
+  if (a->plen == a->plen_out) return UNIMM_E_ARG;
+  if (!al16(a->cache) || !al16(a->new_kv) || a->width % 8 || a->ldp % 8 || a->ld_new % 8 || a->new_layer_stride % 8)
+    return UNIMM_E_ALIGN;
+  KvAppendParams p;
+  p.cache = (bf16_t*)a->cache; p.nkv = (const bf16_t*)a->new_kv;
+  p.count = a->count; p.plen = a->plen; p.plen_out = a->plen_out;
+  p.layers = a->layers; p.slots = a->slots; p.pcap = a->pcap; p.ldp = a->ldp; p.width = a->width; p.max_count = a->max_count;
+  p.nls = a->new_layer_stride; p.ld_new = a->ld_new; p.row_mul = a->new_row_mul; p.row_step = a->new_row_step;
+  hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)a->slots, (unsigned)a->layers), dim3(NTHREADS), 0, (hipStream_t)stream, p);
   UNIMM_CHECK_LAUNCH();
   return UNIMM_OK;
 }

@@ -84,6 +84,17 @@ the greedy slot of a sampling call does) and for sampling.  With any of the rule
 included -- launches `unimm_lm_topk_hist` / `unimm_lm_sample_hist` (the two kernels with a per-row history: a device int32
 [slots, width] table that `track_history` reorders by parent and appends to, and the context table built once per call); with all
 of them off the call launches exactly the kernels named above.
+
+Speculative greedy decoding (`draft`, `draft_len`; unimm_amd/speculative.py states the rounds).  The mask argument at the top covers
+more than one step at a time: answer row k depends on earlier answer rows only and copy row k on the context and the answer rows
+before k, so the draft_len + 1 pairs (answer row n-1+j, copy row n+j) of consecutive steps go through the blocks in ONE pass, as
+long as every new row attends the answer rows of the pairs up to its own, itself if it is a copy row, and no other new row
+(`unimm_attn_verify`).  A draft model -- either class, its own depth and widths, the model's vocabulary and inputs -- proposes
+draft_len greedy tokens per round; the model verifies them in that one pass, keeps the longest prefix it would have produced
+itself plus one token of its own (each with ITS log p), appends the kept rows to its cache in place (`unimm_kv_cache_append`) and
+the draft's cache rolls back.  The result is the beams = 1 result (tokens, lengths, step_logp, logp, scores; up to the batch
+dependence of the logits) with `.speculation` = rounds, drafted and accepted tokens per dialog.  beams = 1 only, no sampling, no
+history rules; with draft=None nothing here runs and a call launches what it always launched.
 """
 from __future__ import annotations
 
@@ -108,6 +119,15 @@ SAMPLE_SITE = zlib.crc32(b"generate.sample") & 0xFFFFFFFF   # the engine's dropo
 
 
 @dataclass
+class Speculation:
+    """What a speculative call (`draft=`) did, per dialog."""
+    rounds: int               # draft + verify rounds of the call
+    drafted: torch.Tensor     # int64 [G]: tokens the draft proposed while the dialog was live (draft_len per round)
+    accepted: torch.Tensor    # int64 [G]: ... of which the model kept
+    per_round: torch.Tensor | None = None   # int64 [rounds, G]: accepted drafts of each round, -1 where the dialog had finished
+
+
+@dataclass
 class GeneratedAnswers:
     tokens: torch.Tensor    # int64 [G, beams, max_answer_len + 1]: answer tokens then [SEP], zero-padded
     lengths: torch.Tensor   # int64 [G, beams], including the [SEP]
@@ -116,6 +136,7 @@ class GeneratedAnswers:
     step_logp: torch.Tensor  # fp32 [G, beams, max_answer_len + 1]: the log p of each token (an extension: per-step checks)
     step_logq: torch.Tensor | None = None   # sampling only: the log q of each token under the distribution it was drawn from
     greedy: "GeneratedAnswers | None" = None   # samples with greedy=True: the greedy answers, shaped like a beams = 1 result
+    speculation: Speculation | None = None  # draft= only (unimm_amd/speculative.py)
 
 
 def answer_limits(context_len, T, max_answer_len):
@@ -393,7 +414,8 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
 def generate_answers(model, input_ids, image_feat, image_loc, context_len, token_type_ids=None, position_ids=None,
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                      length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                     sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer"):
+                     sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
+                     draft=None, draft_len=4):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("generate_answers runs on the bf16 engine")
@@ -412,6 +434,9 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     if constraints is not None and (int(limits.max()) > MAX_HISTORY or int(c_h.max()) - 1 > MAX_CONTEXT):
         raise ValueError(f"generate_answers: no_repeat_ngram_size / repetition_penalty keep a history of at most {MAX_HISTORY} answer "
                          f"and {MAX_CONTEXT} context tokens per hypothesis (got {int(limits.max())} and {int(c_h.max()) - 1})")
+    if draft is not None:                                   # speculative greedy decoding: refused requests, still on the host
+        from .speculative import check_draft
+        draft = check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope)
     sampling = None
     if greedy and not samples:
         raise ValueError("generate_answers: greedy=True adds a greedy slot to a sampling call and needs samples >= 1; for greedy "
@@ -437,6 +462,11 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
                position_ids=position_ids, image_attention_mask=image_attention_mask, image_index=image_index)
     inp = {k: v for k, v in inp.items() if v is not None}
     eng.stage_host_inputs(inp, pack=("attention_mask", "co_attention_mask"))   # the [G, R] image key mask stays a tensor
+    if draft is not None:
+        from .speculative import speculate
+        draft._engine.ensure(model._device())
+        return eng._on_text_stream(speculate, eng, draft._engine, inp, c_h, limits, int(draft_len), max_answer_len, min_answer_len,
+                                   length_penalty, tuple(int(t) for t in banned_tokens))
     return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
                                tuple(int(t) for t in banned_tokens), sampling, constraints)
 

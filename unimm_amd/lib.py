@@ -115,6 +115,8 @@ SIGNATURES = {
     # answer generation (csrc/generate.hip)
     "unimm_attn_decode": (_INT, [VP, VP]),
     "unimm_kv_cache_update": (_INT, [VP, VP]),
+    "unimm_attn_verify": (_INT, [VP, VP]),
+    "unimm_kv_cache_append": (_INT, [VP, VP]),
     "unimm_lm_topk": (_INT, _LM_ROWS + [I32, VP, VP, VP, VP]),
     "unimm_lm_sample": (_INT, _LM_ROWS + [F32, I32, F32, U32] + [VP] * 6),
     "unimm_lm_sample_rows": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 6),
@@ -466,6 +468,13 @@ class KvUpdateArgs(C.Structure):
                 ("parent", C.c_void_p), ("plen", C.c_void_p), ("plen_out", C.c_void_p),
                 ("layers", C.c_int32), ("slots", C.c_int32), ("pcap", C.c_int32), ("ldp", C.c_int32), ("width", C.c_int32),
                 ("new_layer_stride", C.c_int64), ("ld_new", C.c_int32), ("new_row_mul", C.c_int32)]
+
+
+class KvAppendArgs(C.Structure):
+    _fields_ = [("cache", C.c_void_p), ("new_kv", C.c_void_p), ("count", C.c_void_p), ("plen", C.c_void_p), ("plen_out", C.c_void_p),
+                ("layers", C.c_int32), ("slots", C.c_int32), ("pcap", C.c_int32), ("ldp", C.c_int32), ("width", C.c_int32),
+                ("max_count", C.c_int32),
+                ("new_layer_stride", C.c_int64), ("ld_new", C.c_int32), ("new_row_mul", C.c_int32), ("new_row_step", C.c_int32)]
 
 
 def attn_decode(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen, G, beams, nr, H, pcap, scale, D=64):
@@ -1320,5 +1329,6 @@ STRUCTS = {
     "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
     "unimm_adamw_args": AdamWArgs, "unimm_clip_state": ClipState, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
     "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
+    "unimm_kv_append_args": KvAppendArgs,
     "unimm_seq_pref_args": SeqPrefArgs, "unimm_lm_history": LmHistory,
 }
