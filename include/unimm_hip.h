@@ -1084,6 +1084,56 @@ int unimm_lm_sample_hist(const float* logits, int32_t rows, int32_t V, int32_t l
                          uint32_t key, const int32_t* stream_ids, const unimm_lm_history* history, int32_t* token, float* logp,
                          float* logq, float* lse, void* stream);
 
+/* The rejection step of SPECULATIVE SAMPLING (unimm_amd/speculative.py): one workgroup per row, a row = the model's logits x
+ * [rows, ldl], the draft's logits xd [rows, ldd] for the same position, and the token d = draft_token[row] the draft drew there
+ * (-1: the row has no draft).  banned / nbanned / flags / sep / V / stream_ids and the per-row temperature / top_k / top_p
+ * arrays are unimm_lm_sample_rows' and apply to BOTH rows.  Per row, in this order:
+ *  1. P~ is the distribution unimm_lm_sample_rows draws from on the row x with the row's parameters: steps 1-4 of
+ *     unimm_lm_sample (the eligible ids, the rank order, exact top-k with the id tie-break, y_i = (x_i - x_max) / t, the nucleus
+ *     with its fixed-point masses).  K_P is its kept set, log P~_i = y_i - logsumexp_{K_P} y (the sampler's logq of id i).
+ *  2. Q~, K_Q and log Q~_i are the same construction on the row xd: the same banned ids, flags and parameters, xd's own
+ *     finiteness test.  Nothing eligible in xd: K_Q is empty.
+ *  3. A row whose temperature is not positive and finite, whose top_p is outside (0, 1] or whose top_k < 0 returns token = -1,
+ *     accept = 0, logp = logq = log_ratio = -inf (lse is still written): the rule of unimm_lm_sample_rows.
+ *  4. Nothing eligible in x: the same result, lse still written.
+ *  5. A forced-sep row (flags & 2 with a finite x_sep) has K_P = {sep}, so the steps below give token = sep, logq = 0 and
+ *     accept = (d == sep).
+ *  6. RATIO  a = log P~_d - log Q~_d when d is in K_P and in K_Q; +inf when d is in K_P and not in K_Q; -inf when d is outside
+ *     [0, V) or outside K_P.  log_ratio[row] = a (log_ratio may be NULL).
+ *  7. ACCEPT iff logf(u) < a, u = ((h >> 9) + 0.5) * 2^-23 with h the sampler's h_0 of (key_accept, stream_ids[row]), i.e.
+ *     mix32(mix32(key_accept ^ (stream_ids[row] * 0x9E3779B1 + 0x7F4A7C15))).  On accept token = d.
+ *  8. RESIDUAL on reject: rho_i = exp(log Q~_i - log P~_i) on the ids of K_P that are in K_Q, 0 on the others of K_P; the
+ *     candidates are the ids of K_P with rho_i < 1; token = argmax over them of (y_i + log1p(-rho_i)) + g_i (ties to the smaller
+ *     id), g_i the sampler's Gumbel noise of (key_residual, stream_ids[row], i): Gumbel-max on log(P~_i - Q~_i) with the row
+ *     constant dropped, i.e. a draw from the normalised max(0, P~ - Q~).  No candidate (rounding, or P~ <= Q~ on all of K_P):
+ *     token = the first id of P~'s rank order.
+ *  9. logp = x_token - logsumexp(x[0:V]) (the sampler's value; lse likewise), logq = log P~_token: the emitted token of an
+ *     accept-or-residual step is distributed as P~, so this is the log-probability under the distribution sampled from.
+ * Met bit for bit: (i) a row with d = -1 returns the token, logp, logq and lse of unimm_lm_sample_rows launched with
+ * key = key_residual (accept = 0, log_ratio = -inf); (ii) with xd the same buffer as x and d in K_P, log_ratio = 0 exactly and
+ * accept = 1; (iii) a row with top_k = 1 returns the first id unimm_lm_topk reports, logq = 0 and accept = (d == that id),
+ * whatever the keys are; (iv) a row depends on its own inputs alone -- not on its position, the number of rows or an earlier
+ * launch.  The same inputs give the same bits (integer masses, no float atomics).
+ * How Q~ reaches the kernel: the kernel itself runs the sampler's selection on xd first (keys staged in LDS for V <= 36864),
+ * keeps K_Q as a descriptor in registers -- the top-k key and id cut, the nucleus key, xd_max and the log of the kept mass, from
+ * which membership and log Q~_i follow from (xd_i, i) alone -- then runs the selection on x over the same LDS and makes one pass
+ * over K_P that reads xd_i from memory against the descriptor.  Traffic per row: x once, xd twice (a row with d = -1: x only);
+ * V > 36864 re-reads the L2-resident rows in every pass, as the sampler does.  Same results either way.
+ * V <= 65536, ldl >= V, ldd >= V, columns past V are not read; flags, banned (with nbanned = 0) and log_ratio may be NULL, any
+ * other NULL array returns UNIMM_E_ARG before any launch; rows = 0 returns UNIMM_OK without a launch and leaves the outputs
+ * untouched. */
+typedef struct {
+  const float* x; const float* xd;               /* fp32 [rows, ldl], fp32 [rows, ldd], device */
+  const int32_t* draft_token;                    /* int32 [rows] */
+  const int32_t* banned; const int32_t* flags; const int32_t* stream_ids;
+  const float* temperature; const int32_t* top_k; const float* top_p;   /* [rows] each */
+  int32_t* accept; int32_t* token;               /* int32 [rows] */
+  float* logp; float* logq; float* lse; float* log_ratio;               /* fp32 [rows]; log_ratio or NULL */
+  int32_t rows, V, ldl, ldd, nbanned, sep;
+  uint32_t key_accept, key_residual;
+} unimm_lm_spec_verify_args;
+int unimm_lm_spec_verify(const unimm_lm_spec_verify_args* args, void* stream);
+
 /* Launch profiler for bench.py's `roofline` block: HIP events around every GEMM launch on its own
  * stream while enabled.  Variant index: 0..11 = unimm_gemm_nt (epilogue * 2 + out_f32), 12 = unimm_gemm_tn.
  * unimm_prof_collect synchronises the events and returns per-variant summed milliseconds, algorithmic

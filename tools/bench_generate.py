@@ -26,6 +26,11 @@ follows from the three -- a round costs g draft steps + one verify pass and yiel
 one -- and the end-to-end time of a speculative call with a frozen copy of the model as the draft against the plain call.  The
 copy's acceptance is near 1: that measures the machinery, not a speed-up (no trained student exists).
 
+--samples N together with --draft-layers adds, at G = 80 (speculative SAMPLING, draft_accept="rejection"): one
+unimm_lm_spec_verify launch against one unimm_lm_sample_rows launch on the same 80 N (g + 1) rows of [., 30522] logits (the drafts
+drawn from the draft rows, xd = x + noise; the byte count beside it: one read of the model row, two of the draft row), and a
+rejection-sampled call with a frozen copy as the draft against the plain sampling call (temperature 0.8, top_k 50, top_p 0.9).
+
 --profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
 process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
 from __future__ import annotations
@@ -270,6 +275,49 @@ def measure_speculative(model, G, layers, gammas, reps):
     return row
 
 
+def measure_spec_sampling(model, G, N, gammas, reps):
+    """The rejection step alone (one launch against the sampler's on the same rows) and a rejection-sampled call with a frozen copy
+    as the draft against the plain sampling call."""
+    from unimm_amd import lib as L
+    from unimm_amd import speculative as SP
+    from unimm_amd.policy import frozen_reference
+    d, c = dialogs(G, seed=G * 10 + N)
+    V, PAIRS = 30522, 5
+    skw = dict(samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1)
+    copy = frozen_reference(model)
+    call_plain = timed(lambda: generate(model, d, c, 1, ANS, **skw), reps)
+    row = dict(G=G, samples=N, plain_call_ms=round(call_plain, 3), per_draft_len=[])
+    banned = torch.tensor([0, 101, 103], dtype=torch.int32, device="cuda")
+    for g in gammas:
+        rows = G * N * (g + 1)
+        gen = torch.Generator().manual_seed(g)
+        x = torch.randn((rows, V), generator=gen).cuda() * 3
+        xd = x + torch.randn((rows, V), generator=gen).cuda() * 0.5
+        flags = torch.zeros(rows, dtype=torch.int32, device="cuda")
+        streams = torch.arange(rows, dtype=torch.int32, device="cuda")
+        t, k, p = (torch.full((rows,), v, dtype=dt, device="cuda") for v, dt in ((0.8, torch.float32), (50, torch.int32), (0.9, torch.float32)))
+        dtok, acc, tok = (torch.empty(rows, dtype=torch.int32, device="cuda") for _ in range(3))
+        lp, lq, lse = (torch.empty(rows, device="cuda") for _ in range(3))
+        L.lm_sample_rows(xd, rows, V, banned, flags, 102, t, k, p, 777, streams, dtok, lp, lq)
+        sample_us, ratio, spread = paired(
+            lambda: launch_us(lambda: L.lm_sample_rows(x, rows, V, banned, flags, 102, t, k, p, 12345, streams, tok, lp, lq), n=20),
+            lambda: launch_us(lambda: SP.lm_spec_verify(x, xd, rows, V, dtok, banned, flags, 102, t, k, p, 999, 12345, streams, acc, tok,
+                                                        lp, lq, lse), n=20), PAIRS)
+        accepted = float(acc.float().mean())
+        del x, xd
+        res = generate(model, d, c, 1, ANS, draft=copy, draft_len=g, draft_accept="rejection", **skw)
+        assert bool((res.lengths == ANS + 1).all())
+        sp = res.speculation
+        call = timed(lambda: generate(model, d, c, 1, ANS, draft=copy, draft_len=g, draft_accept="rejection", **skw), reps)
+        row["per_draft_len"].append(dict(
+            draft_len=g, rows=rows, lm_sample_rows_us=round(sample_us, 1), spec_verify_over_sample_rows=round(ratio, 3),
+            sample_rows_spread=round(spread, 3), launch_acceptance=round(accepted, 3),
+            mib_read=round(rows * V * 4 * 3 / 2 ** 20, 1), gb_per_s=round(rows * V * 4 * 3 / (sample_us * ratio * 1e-6) / 1e9, 1),
+            copy_call_ms=round(call, 3), copy_call_over_plain=round(call / call_plain, 3), copy_rounds=sp.rounds,
+            copy_acceptance=round(float(sp.accepted.sum()) / max(float(sp.drafted.sum()), 1.0), 3)))
+    return row
+
+
 def recompute_bound(model, d, c, G, beams, reps):
     """Summed ms of scoring G * beams sequences with answers of 1 .. ANS tokens (shared context up to 14 answer tokens)."""
     from unimm_amd.inputs import DialogMaskSpec
@@ -389,6 +437,15 @@ def main():
                   f"pays above {q['break_even_accepted_per_round']:.2f} accepted drafts (per-token acceptance "
                   f"{q['break_even_token_acceptance']}); frozen copy as draft: {q['copy_call_ms']:.1f} ms = {q['copy_call_over_plain']:.2f} x "
                   f"the plain call, {q['copy_rounds']} rounds, acceptance {q['copy_acceptance']:.3f}")
+    if a.draft_layers and a.samples:
+        result["speculative_sampling"] = r = measure_spec_sampling(model, 80, a.samples, a.draft_len, a.reps)
+        print(f"speculative sampling at G = {r['G']}, {r['samples']} samples per dialog: plain sampling call {r['plain_call_ms']:.1f} ms")
+        for q in r["per_draft_len"]:
+            print(f"  draft_len {q['draft_len']:>2}: one launch on [{q['rows']}, 30522]: unimm_lm_spec_verify = "
+                  f"{q['spec_verify_over_sample_rows']:.2f} x unimm_lm_sample_rows ({q['lm_sample_rows_us']:.1f} us, spread "
+                  f"{q['sample_rows_spread']:.3f}; {q['mib_read']:.0f} MiB read = x once + xd twice, {q['gb_per_s']:.0f} GB/s; "
+                  f"{q['launch_acceptance']:.2f} of the rows accepted); frozen copy as draft: {q['copy_call_ms']:.1f} ms = "
+                  f"{q['copy_call_over_plain']:.2f} x the plain call, {q['copy_rounds']} rounds, acceptance {q['copy_acceptance']:.3f}")
     if a.profile:
         result["kernel_mix_80x4"] = profile()
         for m in result["kernel_mix_80x4"]:

@@ -4,6 +4,7 @@
 // decoder logits (beam search), and temperature / top-k / nucleus sampling from them (unimm_lm_sample, ABI 20; with per-row
 // parameters unimm_lm_sample_rows, ABI 24: the same kernel template).  unimm_lm_topk_hist / unimm_lm_sample_hist are the same two
 // kernel templates with HIST on: a per-row token history adds no-repeat n-gram bans and a repetition penalty (apply_history).
+// unimm_lm_spec_verify is the rejection step of speculative sampling: the sampler's selection on a model row and a draft row.
 // unimm_amd/generation.py drives them; the mask argument that makes the cache exact is in its docstring.
 #include <math.h>
 
@@ -493,6 +494,7 @@ __global__ __launch_bounds__(NTHREADS) void lm_topk_kernel(TopkParams a) {
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     const float M = fmaxf(m, m2);
+    // (lse_combine below restates how this build rounds the next line, for unimm_lm_spec_verify: keep the two in step)
     s = (M == -INFINITY) ? 0.f : s * expf(m - M) + s2 * expf(m2 - M);
     m = M;
   }
@@ -696,6 +698,7 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     const float M = fmaxf(m, m2);
+    // (lse_combine below restates how this build rounds the next line, for unimm_lm_spec_verify: keep the two in step)
     s = (M == -INFINITY) ? 0.f : s * expf(m - M) + s2 * expf(m2 - M);
     m = M;
     kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
@@ -804,6 +807,286 @@ __global__ __launch_bounds__(NTHREADS) void lm_sample_kernel(SampleParams a) {
       a.logp[row] = xt - lse;
       a.logq[row] = (sel_val(bi, xt) - xmax) / temp - logf((float)((double)zf * 9.094947017729282e-13));   // 2^-40
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// unimm_lm_spec_verify: the rejection step of speculative sampling, one workgroup per (model row x, draft row xd, draft token d).
+// P~ and Q~ are lm_sample_kernel<., PER_ROW>'s distributions of x and of xd.  row_select below is that kernel's passes up to the
+// draw, statement for statement (lm_sample_kernel keeps its own inline copy so that its instruction stream does not move); it
+// returns the kept set as a DESCRIPTOR: id j with key k is kept iff k > T or (k == T and j <= idcut), and k >= TH; its
+// log-probability is (key_val(k) - xmax) / t - lz.  The kernel runs it on xd first (keys staged in LDS when V <= STAGE_MAX),
+// keeps Q~'s descriptor in registers, runs it again on x over the same LDS, and then makes ONE pass over P~'s kept ids that
+// reads xd_j from global memory against Q~'s descriptor: x is read once, xd twice.  A row without a draft skips the xd phase.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct SpecParams {
+  const float *x, *xd;
+  const int32_t *draft, *banned, *flags, *stream;
+  const float* temp_rows; const int32_t* topk_rows; const float* topp_rows;
+  int32_t *accept, *token;
+  float *logp, *logq, *lse, *log_ratio;
+  int rows, V, ldl, ldd, nbanned, sep;
+  uint32_t key_accept, key_residual;
+};
+
+struct RowSel {
+  unsigned long long cnt;                        // eligible ids; 0: nothing below is defined
+  uint32_t T, TH, kmax;
+  int idcut;
+  float xmax, lz, lse;                           // lz = logf of the kept mass relative to exp(0) at xmax; lse: LSE only
+  __device__ __forceinline__ bool kept(int j, uint32_t k) const { return (k > T || (k == T && j <= idcut)) && k >= TH && k != 0u; }
+};
+
+struct SelLds {
+  SelScratch sel;
+  float rm[NTHREADS / 64], rs[NTHREADS / 64];
+  int wi[NTHREADS / 64];
+  unsigned long long r64[NTHREADS / 64];
+};
+
+// s * e + s2 * e2 of the log-sum-exp's butterfly, ROUNDED AS lm_topk_kernel / lm_sample_kernel round it.  Those kernels leave the
+// expression to -ffp-contract=fast, and their build fuses it as fma(s, e, s2 * e2) in the rounds o = 32 .. 2 and evaluates the
+// last round (o = 1) as two rounded products and a sum; lse must equal theirs bit for bit (property (i) of the header), so the
+// choice is spelled out here instead of being left to the compiler a second time.  tests/test_gpu_spec_sample_edges.py compares
+// lse with both kernels on every row.
+__device__ __forceinline__ float lse_combine(float s, float e, float s2, float e2, bool fused) {
+#pragma clang fp contract(off)
+  const float a = s * e, b = s2 * e2;
+  return fused ? fmaf(s, e, b) : a + b;
+}
+
+// Every thread calls it.  LSE: also the log-sum-exp of x[0:V] (lm_topk's online form).  stop: return after the first pass
+// with cnt = 0 (a row whose parameters the host could not refuse still reports its lse).
+template <bool STAGED, bool LSE>
+__device__ RowSel row_select(const float* x, int V, const uint32_t* ban, int f, int sep, float temp, int top_k, float top_p,
+                             bool stop, uint32_t* keys, SelLds& l) {
+  const int tid = threadIdx.x;
+  auto make_key = [&](int j, float xv) -> uint32_t {
+    const bool out = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == sep) || ((f & 2) && j != sep) || !(xv > -INFINITY);
+    return out ? 0u : ord_key(xv);
+  };
+  auto key_at = [&](int j) -> uint32_t { return STAGED ? keys[j] : make_key(j, x[j]); };
+  RowSel r;
+  r.T = 0u; r.TH = 0u; r.idcut = -1; r.xmax = 0.f; r.lz = 0.f; r.lse = 0.f;
+
+  float m = -INFINITY, s = 0.f;
+  uint32_t kmax = 0u;
+  unsigned long long cnt = 0ull;
+  __syncthreads();                               // the keys of an earlier call are no longer read
+  for (int j = tid; j < V; j += NTHREADS) {
+    const float xv = x[j];
+    if (LSE && xv > -INFINITY) {
+      if (xv > m) {
+        s = s * expf(m - xv) + 1.f;
+        m = xv;
+      } else {
+        s += expf(xv - m);
+      }
+    }
+    const uint32_t k = make_key(j, xv);
+    if (STAGED) keys[j] = k;
+    kmax = max(kmax, k);
+    cnt += k != 0u;
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    if (LSE) {
+      const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+      const float M = fmaxf(m, m2);
+      s = (M == -INFINITY) ? 0.f : lse_combine(s, expf(m - M), s2, expf(m2 - M), o > 1);
+      m = M;
+    }
+    kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
+  }
+  if (lane == 0) { l.rm[wave] = m; l.rs[wave] = s; l.wi[wave] = (int)kmax; }
+  __syncthreads();
+  float M = l.rm[0];
+  kmax = (uint32_t)l.wi[0];
+  for (int w = 1; w < NTHREADS / 64; ++w) {
+    M = fmaxf(M, l.rm[w]);
+    kmax = max(kmax, (uint32_t)l.wi[w]);
+  }
+  if (LSE) {
+    float tot = 0.f;
+    for (int w = 0; w < NTHREADS / 64; ++w)
+      if (l.rm[w] > -INFINITY) tot += l.rs[w] * expf(l.rm[w] - M);
+    r.lse = M + logf(tot);
+  }
+  cnt = block_sum_u64(cnt, l.r64);
+  r.cnt = stop ? 0ull : cnt;
+  r.kmax = kmax;
+  if (r.cnt == 0ull) return r;
+
+  if (top_k > 0 && (unsigned long long)top_k < cnt) {
+    unsigned long long rem, at;
+    r.T = radix_select([&](int j, uint32_t& w, unsigned long long& wt) { w = key_at(j); wt = 1ull; return w != 0u; }, V, 24,
+                       (unsigned long long)top_k, l.sel, &rem, &at);
+    r.idcut = V;
+    if (rem < at) {
+      const uint32_t T = r.T;
+      unsigned long long r2, a2;
+      r.idcut = 0xFFFF - (int)radix_select([&](int j, uint32_t& w, unsigned long long& wt) {
+                                             w = 0xFFFFu - (uint32_t)j; wt = 1ull; return key_at(j) == T; },
+                                           V, 8, rem, l.sel, &r2, &a2);
+    }
+  }
+  const uint32_t T = r.T;
+  const int idcut = r.idcut;
+  auto kept_k = [&](int j, uint32_t k) -> bool { return k > T || (k == T && j <= idcut); };
+  const float xmax = key_val(kmax);
+  r.xmax = xmax;
+  auto rel = [&](uint32_t k) -> float { return (key_val(k) - xmax) / temp; };
+  auto fixed = [&](float d) -> unsigned long long { return (unsigned long long)(expf(d) * FIX_ONE); };
+
+  if (top_p < 1.0f && cnt > 1ull) {
+    unsigned long long z = 0ull;
+    for (int j = tid; j < V; j += NTHREADS) {
+      const uint32_t k = key_at(j);
+      if (kept_k(j, k)) z += fixed(rel(k));
+    }
+    z = block_sum_u64(z, l.r64);
+    const double want = ceil((double)top_p * (double)z);
+    const unsigned long long target = want < 1.0 ? 1ull : (unsigned long long)want;
+    unsigned long long rem, at;
+    r.TH = radix_select([&](int j, uint32_t& w, unsigned long long& wt) {
+                          w = key_at(j);
+                          const bool on = kept_k(j, w);
+                          wt = on ? fixed(rel(w)) : 0ull;
+                          return on; },
+                        V, 24, target, l.sel, &rem, &at);
+  }
+  unsigned long long zf = 0ull;
+  for (int j = tid; j < V; j += NTHREADS) {
+    const uint32_t k = key_at(j);
+    if (r.kept(j, k)) zf += fixed(rel(k));
+  }
+  zf = block_sum_u64(zf, l.r64);
+  r.lz = logf((float)((double)zf * 9.094947017729282e-13));                    // 2^-40
+  return r;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(NTHREADS) void lm_spec_verify_kernel(SpecParams a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* keys = reinterpret_cast<uint32_t*>(smem);          // [V] when STAGED: xd's keys, then x's
+  __shared__ uint32_t ban[VMAX / 32];
+  __shared__ SelLds l;
+  __shared__ float wv[NTHREADS / 64];
+  __shared__ int wb[NTHREADS / 64], wf[NTHREADS / 64];
+  const int tid = threadIdx.x, row = blockIdx.x;
+  const int V = a.V;
+  const int nw = (V + 31) / 32;
+  for (int w = tid; w < nw; w += NTHREADS) ban[w] = 0u;
+  __syncthreads();
+  for (int b = tid; b < a.nbanned; b += NTHREADS) {
+    const int id = a.banned[b];
+    if (id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+  }
+  __syncthreads();
+  const int f = a.flags != nullptr ? a.flags[row] : 0;
+  const float* x = a.x + (int64_t)row * a.ldl;
+  const float* xd = a.xd + (int64_t)row * a.ldd;
+  const int sep = a.sep;
+  const int d = a.draft[row];
+  const float temp = a.temp_rows[row];
+  const int top_k = a.topk_rows[row];
+  const float top_p = a.topp_rows[row];
+  const bool bad = !(temp > 0.f) || !(temp < INFINITY) || !(top_p > 0.f && top_p <= 1.f) || top_k < 0;
+  auto make_key = [&](int j, float xv) -> uint32_t {
+    const bool out = ((ban[j >> 5] >> (j & 31)) & 1u) || ((f & 1) && j == sep) || ((f & 2) && j != sep) || !(xv > -INFINITY);
+    return out ? 0u : ord_key(xv);
+  };
+
+  RowSel q = {};                                 // no draft (d = -1), or nothing eligible in xd: K_Q is empty
+  if (d != -1 && !bad) q = row_select<STAGED, false>(xd, V, ban, f, sep, temp, top_k, top_p, false, keys, l);
+  const bool has_q = q.cnt != 0ull;
+  const RowSel p = row_select<STAGED, true>(x, V, ban, f, sep, temp, top_k, top_p, bad, keys, l);
+  if (p.cnt == 0ull) {                           // nothing eligible, or parameters the host could not refuse
+    if (tid == 0) {
+      a.lse[row] = p.lse;
+      a.token[row] = -1;
+      a.accept[row] = 0;
+      a.logp[row] = -INFINITY;
+      a.logq[row] = -INFINITY;
+      if (a.log_ratio != nullptr) a.log_ratio[row] = -INFINITY;
+    }
+    return;
+  }
+  auto key_p = [&](int j) -> uint32_t { return STAGED ? keys[j] : make_key(j, x[j]); };
+  auto log_p = [&](uint32_t k) -> float { return (key_val(k) - p.xmax) / temp - p.lz; };
+  auto log_q = [&](uint32_t k) -> float { return (key_val(k) - q.xmax) / temp - q.lz; };
+
+  // the residual draw: Gumbel-max on y + log(1 - Q~/P~) over K_P; and the first id of P~'s rank order, the fallback
+  const uint32_t sk = mix32(a.key_residual ^ ((uint32_t)a.stream[row] * 0x9E3779B1u + 0x7F4A7C15u));
+  float bv = -INFINITY;
+  int bi = 0x7fffffff, fi = 0x7fffffff;
+  for (int j = tid; j < V; j += NTHREADS) {
+    const uint32_t k = key_p(j);
+    if (!p.kept(j, k)) continue;
+    if (k == p.kmax) fi = min(fi, j);
+    const float y = (key_val(k) - p.xmax) / temp;
+    float l1 = 0.f;
+    if (has_q) {
+      const uint32_t kq = make_key(j, xd[j]);
+      if (q.kept(j, kq)) {
+        const float rho = expf(log_q(kq) - (y - p.lz));
+        if (!(rho < 1.f)) continue;
+        l1 = log1pf(-rho);
+      }
+    }
+    const uint32_t h = mix32(sk + (uint32_t)j * 0x85EBCA77u);
+    const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;        // 2^-23
+    const float v = (y + l1) - logf(-logf(u));
+    if (better(v, j, bv, bi)) { bv = v; bi = j; }
+  }
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(bv, o, 64);
+    const int i2 = __shfl_xor(bi, o, 64);
+    if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+    fi = min(fi, __shfl_xor(fi, o, 64));
+  }
+  if (lane == 0) { wv[wave] = bv; wb[wave] = bi; wf[wave] = fi; }
+  __syncthreads();
+  if (tid != 0) return;
+  bv = wv[0];
+  bi = wb[0];
+  fi = wf[0];
+  for (int w = 1; w < NTHREADS / 64; ++w) {
+    if (better(wv[w], wb[w], bv, bi)) { bv = wv[w]; bi = wb[w]; }
+    fi = min(fi, wf[w]);
+  }
+  // the acceptance ratio of d
+  float ratio = -INFINITY;
+  if (d >= 0 && d < V) {
+    const uint32_t kd = key_p(d);
+    if (p.kept(d, kd)) {
+      ratio = INFINITY;
+      if (has_q) {
+        const uint32_t kq = make_key(d, xd[d]);
+        if (q.kept(d, kq)) ratio = log_p(kd) - log_q(kq);
+      }
+    }
+  }
+  const uint32_t ha = mix32(mix32(a.key_accept ^ ((uint32_t)a.stream[row] * 0x9E3779B1u + 0x7F4A7C15u)));
+  const float ua = ((float)(ha >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  const bool acc = logf(ua) < ratio;
+  int tok = acc ? d : (bi >= 0 && bi < V ? bi : fi);
+  a.lse[row] = p.lse;
+  a.accept[row] = acc ? 1 : 0;
+  if (a.log_ratio != nullptr) a.log_ratio[row] = ratio;
+  if (tok < 0 || tok >= V) {                     // cannot happen (the top-ranked id is always in K_P); never index with it
+    a.token[row] = -1;
+    a.accept[row] = 0;
+    a.logp[row] = -INFINITY;
+    a.logq[row] = -INFINITY;
+  } else {
+    const float xt = x[tok];
+    a.token[row] = tok;
+    a.logp[row] = xt - p.lse;
+    a.logq[row] = (xt - p.xmax) / temp - p.lz;
   }
 }
 
@@ -1008,4 +1291,34 @@ extern "C" int unimm_lm_sample_hist(const float* logits, int32_t rows, int32_t V
   p.temperature = 1.f; p.top_p = 1.f; p.key = key;
   p.temp_rows = temperature; p.topk_rows = top_k; p.topp_rows = top_p;
   return launch_lm_sample<true, true>(p, (hipStream_t)stream);
+}
+
+extern "C" int unimm_lm_spec_verify(const unimm_lm_spec_verify_args* a, void* stream) {
+  if (a == nullptr || a->x == nullptr || a->xd == nullptr || a->draft_token == nullptr || a->stream_ids == nullptr ||
+      a->temperature == nullptr || a->top_k == nullptr || a->top_p == nullptr || a->accept == nullptr || a->token == nullptr ||
+      a->logp == nullptr || a->logq == nullptr || a->lse == nullptr || (a->nbanned > 0 && a->banned == nullptr))
+    return UNIMM_E_ARG;
+  if (a->rows < 0 || a->V < 1 || a->V > VMAX || a->ldl < a->V || a->ldd < a->V || a->nbanned < 0) return UNIMM_E_SHAPE;
+  if (a->rows == 0) return UNIMM_OK;
+  SpecParams p;
+  p.x = a->x; p.xd = a->xd; p.draft = a->draft_token; p.banned = a->banned; p.flags = a->flags; p.stream = a->stream_ids;
+  p.temp_rows = a->temperature; p.topk_rows = a->top_k; p.topp_rows = a->top_p;
+  p.accept = a->accept; p.token = a->token; p.logp = a->logp; p.logq = a->logq; p.lse = a->lse; p.log_ratio = a->log_ratio;
+  p.rows = a->rows; p.V = a->V; p.ldl = a->ldl; p.ldd = a->ldd; p.nbanned = a->nbanned; p.sep = a->sep;
+  p.key_accept = a->key_accept; p.key_residual = a->key_residual;
+  if (p.V <= STAGE_MAX) {
+    static bool done = false;
+    if (!done) {
+      if (hipFuncSetAttribute((const void*)lm_spec_verify_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              STAGE_MAX * (int)sizeof(uint32_t)) != hipSuccess)
+        return UNIMM_E_HIP;
+      done = true;
+    }
+    hipLaunchKernelGGL(lm_spec_verify_kernel<true>, dim3((unsigned)p.rows), dim3(NTHREADS), (size_t)p.V * sizeof(uint32_t),
+                       (hipStream_t)stream, p);
+  } else {
+    hipLaunchKernelGGL(lm_spec_verify_kernel<false>, dim3((unsigned)p.rows), dim3(NTHREADS), 0, (hipStream_t)stream, p);
+  }
+  UNIMM_CHECK_LAUNCH();
+  return UNIMM_OK;
 }

@@ -93,8 +93,19 @@ long as every new row attends the answer rows of the pairs up to its own, itself
 draft_len greedy tokens per round; the model verifies them in that one pass, keeps the longest prefix it would have produced
 itself plus one token of its own (each with ITS log p), appends the kept rows to its cache in place (`unimm_kv_cache_append`) and
 the draft's cache rolls back.  The result is the beams = 1 result (tokens, lengths, step_logp, logp, scores; up to the batch
-dependence of the logits) with `.speculation` = rounds, drafted and accepted tokens per dialog.  beams = 1 only, no sampling, no
+dependence of the logits) with `.speculation` = rounds, drafted and accepted tokens per dialog.  beams = 1 only, no
 history rules; with draft=None nothing here runs and a call launches what it always launched.
+
+Speculative SAMPLING (`samples=N, draft=..., draft_accept="rejection"`; "match", the default, is the greedy form above and still
+refuses `samples`).  The draft DRAWS its proposals from its own filtered distribution Q~; the model's one pass is followed by one
+`unimm_lm_spec_verify` launch that accepts each draft with probability min(1, P~ / Q~) or draws from the normalised residual
+max(0, P~ - Q~), P~ the distribution the plain sampling call draws from -- so the answers are distributed exactly as that call's,
+only in fewer passes of the model.  The result is sampling-shaped: the samples in draw order with step_logp (the model's log p) and
+step_logq (log P~ of the emitted token), `.greedy` when asked (a top_k = 1 slot on both sides), `.speculation` with [G, N]
+counters.  Keys are per ABSOLUTE step and the streams those of the plain call; a seed fixes the answers for a GIVEN draft_len only
+(whether a step is a drafted row or the bonus row, a plain draw, depends on draft_len): the distribution is the same, the draws not.
+Needs samples >= 1 and a draft; every refusal of the greedy form applies (the history rules included), and `beams` follows the
+sampling call's rule.
 """
 from __future__ import annotations
 
@@ -415,7 +426,7 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                      length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                      sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                     draft=None, draft_len=4):
+                     draft_accept="match", draft=None, draft_len=4):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("generate_answers runs on the bf16 engine")
@@ -434,9 +445,14 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
     if constraints is not None and (int(limits.max()) > MAX_HISTORY or int(c_h.max()) - 1 > MAX_CONTEXT):
         raise ValueError(f"generate_answers: no_repeat_ngram_size / repetition_penalty keep a history of at most {MAX_HISTORY} answer "
                          f"and {MAX_CONTEXT} context tokens per hypothesis (got {int(limits.max())} and {int(c_h.max()) - 1})")
-    if draft is not None:                                   # speculative greedy decoding: refused requests, still on the host
+    if draft_accept not in ("match", "rejection"):
+        raise ValueError(f"generate_answers: draft_accept must be 'match' or 'rejection', got {draft_accept!r}")
+    if draft is None and draft_accept == "rejection":
+        raise ValueError("generate_answers: draft_accept='rejection' is speculative sampling and needs a draft model (draft=...)")
+    if draft is not None:                                   # speculative decoding: refused requests, still on the host
         from .speculative import check_draft
-        draft = check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope)
+        draft = check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope,
+                            draft_accept)
     sampling = None
     if greedy and not samples:
         raise ValueError("generate_answers: greedy=True adds a greedy slot to a sampling call and needs samples >= 1; for greedy "
@@ -452,7 +468,8 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
             streams = np.concatenate([streams, np.zeros((G, 1), dtype=np.int64)], 1)
         sampling = dict(samples=int(samples), greedy=bool(greedy), seed=int(seed),
                         streams=(streams.reshape(-1) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
-        if per_draw or greedy or constraints is not None:  # per-row parameters: unimm_lm_sample_rows (_hist takes no other form)
+        if per_draw or greedy or constraints is not None or draft is not None:   # per-row parameters: unimm_lm_sample_rows (_hist
+            # and the rejection step take no other form)
             sampling["rows"] = slot_parameters(G, ts, ks, ps, greedy)
         else:
             sampling.update(temperature=float(ts[0]), top_k=int(ks[0]), top_p=float(ps[0]))
@@ -466,7 +483,7 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
         from .speculative import speculate
         draft._engine.ensure(model._device())
         return eng._on_text_stream(speculate, eng, draft._engine, inp, c_h, limits, int(draft_len), max_answer_len, min_answer_len,
-                                   length_penalty, tuple(int(t) for t in banned_tokens))
+                                   length_penalty, tuple(int(t) for t in banned_tokens), sampling)
     return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
                                tuple(int(t) for t in banned_tokens), sampling, constraints)
 

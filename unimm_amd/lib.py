@@ -122,6 +122,7 @@ SIGNATURES = {
     "unimm_lm_sample_rows": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 6),
     "unimm_lm_topk_hist": (_INT, _LM_ROWS + [I32, VP, VP, VP, VP, VP]),
     "unimm_lm_sample_hist": (_INT, _LM_ROWS + [VP, VP, VP, U32] + [VP] * 7),
+    "unimm_lm_spec_verify": (_INT, [VP, VP]),
     # launch profiler
     "unimm_prof_enable": (_INT, [I32]),
     "unimm_prof_collect": (_INT, [VP, VP, VP, I32]),
@@ -475,6 +476,16 @@ class KvAppendArgs(C.Structure):
                 ("layers", C.c_int32), ("slots", C.c_int32), ("pcap", C.c_int32), ("ldp", C.c_int32), ("width", C.c_int32),
                 ("max_count", C.c_int32),
                 ("new_layer_stride", C.c_int64), ("ld_new", C.c_int32), ("new_row_mul", C.c_int32), ("new_row_step", C.c_int32)]
+
+
+class LmSpecVerifyArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("xd", C.c_void_p), ("draft_token", C.c_void_p),
+                ("banned", C.c_void_p), ("flags", C.c_void_p), ("stream_ids", C.c_void_p),
+                ("temperature", C.c_void_p), ("top_k", C.c_void_p), ("top_p", C.c_void_p),
+                ("accept", C.c_void_p), ("token", C.c_void_p),
+                ("logp", C.c_void_p), ("logq", C.c_void_p), ("lse", C.c_void_p), ("log_ratio", C.c_void_p),
+                ("rows", C.c_int32), ("V", C.c_int32), ("ldl", C.c_int32), ("ldd", C.c_int32), ("nbanned", C.c_int32),
+                ("sep", C.c_int32), ("key_accept", C.c_uint32), ("key_residual", C.c_uint32)]
 
 
 def attn_decode(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen, G, beams, nr, H, pcap, scale, D=64):
@@ -1329,6 +1340,6 @@ STRUCTS = {
     "unimm_embed_args": EmbedArgs, "unimm_transpose_desc": TransposeDesc, "unimm_linear_f32_args": LinearF32Args,
     "unimm_adamw_args": AdamWArgs, "unimm_clip_state": ClipState, "unimm_ndcg_args": NdcgArgs, "unimm_x3_split_args": X3SplitArgs,
     "unimm_x3_attn_planes": X3AttnPlanes, "unimm_attn_decode_args": AttnDecodeArgs, "unimm_kv_update_args": KvUpdateArgs,
-    "unimm_kv_append_args": KvAppendArgs,
+    "unimm_kv_append_args": KvAppendArgs, "unimm_lm_spec_verify_args": LmSpecVerifyArgs,
     "unimm_seq_pref_args": SeqPrefArgs, "unimm_lm_history": LmHistory,
 }

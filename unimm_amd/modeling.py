@@ -407,7 +407,7 @@ class BertForMultiModalPreTraining(nn.Module):
                          image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                          length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                          sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                         draft=None, draft_len=4):
+                         draft_accept="match", draft=None, draft_len=4):
         """Beam-search answers for the dialogs whose first context_len[g] tokens are `[CLS] caption [SEP] ... q_r [SEP]`, with the
         context and image computed once and a per-layer key/value cache (an extension; unimm_amd/generation.py states the
         semantics).  -> GeneratedAnswers(tokens, lengths, scores, logp).  bf16 engine.
@@ -424,15 +424,18 @@ class BertForMultiModalPreTraining(nn.Module):
         call SPECULATIVE greedy decoding (beams = 1, no sampling, no history rules): the draft proposes draft_len in [1, 15] tokens
         per round, this model verifies them in one pass and keeps the prefix it would have produced itself plus one token of its
         own.  The answers are those of the plain beams = 1 call; `.speculation` counts rounds, drafted and accepted tokens
-        (unimm_amd/speculative.py)."""
+        (unimm_amd/speculative.py).  draft_accept="rejection" (with samples >= 1) makes it speculative SAMPLING instead: the draft
+        draws its proposals, the model accepts each with probability min(1, P / Q) or draws from the normalised max(0, P - Q)
+        (`unimm_lm_spec_verify`), so the answers are distributed exactly as the plain sampling call's and carry step_logp / step_logq
+        (and `.greedy` when asked); `.speculation` then counts per (dialog, draw)."""
         from .generation import generate_answers
         return generate_answers(self, input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids,
                                 image_attention_mask, image_index, beams=beams, max_answer_len=max_answer_len,
                                 min_answer_len=min_answer_len, length_penalty=length_penalty, banned_tokens=banned_tokens,
                                 samples=samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                 sample_streams=sample_streams, greedy=greedy, no_repeat_ngram_size=no_repeat_ngram_size,
-                                repetition_penalty=repetition_penalty, repeat_scope=repeat_scope, draft=draft,
-                                draft_len=draft_len)
+                                repetition_penalty=repetition_penalty, repeat_scope=repeat_scope,
+                                draft_accept=draft_accept, draft=draft, draft_len=draft_len)
 
 
 class VisualDialogEncoder(nn.Module):
@@ -477,14 +480,15 @@ class VisualDialogEncoder(nn.Module):
                          image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                          length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                          sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                         draft=None, draft_len=4):
+                         draft_accept="match", draft=None, draft_len=4):
         """BertForMultiModalPreTraining.generate_answers."""
         return self.bert_pretrained.generate_answers(
             input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids, image_attention_mask, image_index,
             beams=beams, max_answer_len=max_answer_len, min_answer_len=min_answer_len, length_penalty=length_penalty,
             banned_tokens=banned_tokens, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
             sample_streams=sample_streams, greedy=greedy, no_repeat_ngram_size=no_repeat_ngram_size,
-            repetition_penalty=repetition_penalty, repeat_scope=repeat_scope, draft=draft, draft_len=draft_len)
+            repetition_penalty=repetition_penalty, repeat_scope=repeat_scope, draft_accept=draft_accept, draft=draft,
+            draft_len=draft_len)
 
     def forward_backward(self, input_ids, image_feat, image_loc, loss_weights, sep_indices=None, sep_len=None, token_type_ids=None,
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,

@@ -1,4 +1,5 @@
-"""Speculative greedy answer generation: a draft model proposes, the model verifies (`generate_answers(draft=..., draft_len=g)`).
+"""Speculative answer generation: a draft model proposes, the model verifies (`generate_answers(draft=..., draft_len=g)`): greedy
+decoding first, speculative SAMPLING at the end.
 
 The answers are those of the plain beams = 1 call (up to the batch dependence of the logits, the caveat of `generation.py`): the
 draft only decides how many of them one pass of the model yields.  The mask argument of `generation.py` is what makes it exact:
@@ -34,13 +35,50 @@ rollback).  Rows a finished slot or a step past a dialog's limit still pushes ar
 at the limit's, and every cache index is clamped by the kernels.
 
 `speculative_search` is written against abstract step functions, as `beam_search` is (the CPU tests drive it with table models);
-`speculate` supplies the engines'.  The Python wrappers of the two entry points live here, not in `lib.py`: answer generation is
+`speculate` supplies the engines'.  The Python wrappers of the entry points live here, not in `lib.py`: answer generation is
 outside the stream-order check.
+
+Speculative SAMPLING (`generate_answers(samples=N, draft=..., draft_accept="rejection")`, `speculative_sample_search`).  The same
+rounds with one slot per (dialog, draw) -- S = G * N slots, plus one greedy slot per dialog with greedy=True -- and the standard
+rejection rule in place of the comparison of tokens, so that the answers are distributed EXACTLY as the plain sampling call's:
+
+1. DRAFT.  The draft DRAWS d_j from its own filtered distribution Q~ (`unimm_lm_sample_rows` with the slot's temperature / top_k /
+   top_p, the model's, and the step rules of step n + j) and keeps the logits row it drew from.
+2. VERIFY.  After the model's one pass, ONE `unimm_lm_spec_verify` launch on the S (g + 1) copy rows: row j < g accepts d_j with
+   probability min(1, P~(d_j) / Q~(d_j)) and otherwise draws from the normalised residual max(0, P~ - Q~); row g (no draft) is a
+   plain draw from P~, the bonus token after a fully accepted round.  P~ is the distribution the plain call samples from.
+3. ACCEPT.  The match mask is the kernel's `accept`, the emitted tokens are its `token` at positions 0 .. a (the a accepted drafts,
+   then the residual or bonus draw), each with the model's log p (step_logp) and log P~ (step_logq: the token of an
+   accept-or-residual step is distributed as P~, which is what `PolicyObjective(mode="ratio")` needs).  The cut after an accepted
+   [SEP], the counters, the flags and the one synchronisation per round are the greedy loop's (`_rounds` is both).
+4. COMMIT as above.
+
+Slots and groups.  `unimm_attn_verify` takes beams * nr <= 32 query rows per group, so every slot is a group of its own (G' = S,
+beams = 1, the dialog's context range, region range and key mask repeated per slot): draft_len <= 15 holds for any samples <= 16,
+and no attention kernel changes.  `_Side` keeps S slots over a prefill of G dialogs.
+
+Noise.  Token k of slot s is decided by three independent words per id: the draft's Gumbel noise, the accept uniform and the
+residual's Gumbel noise, keyed by dropout.make_key(seed, k, site) with site = DRAFT_SITE / ACCEPT_SITE / RESIDUAL_SITE and the
+stream of the plain sampling call (sample_streams[g] * N + j) -- k is the ABSOLUTE step of the token, not the round.  That stays
+exact: a draft of step k + 1 that is discarded was discarded because of decisions at steps <= k, which read the noise of steps <= k
+only; the noise of step k + 1 is independent of them, so when step k + 1 is drafted again after another prefix it is fresh for
+that prefix.  A seed fixes the answers for a GIVEN draft_len only: which steps are drafted rows and which the bonus row, a plain
+draw, depends on draft_len, so another draft_len gives other draws of the same distribution.  A launch carries one key, and the
+rows of a launch stand at different steps; since make_key is site_key ^ step_salt and the sampler hashes key ^ affine(stream),
+`step_streams` moves the step's salt into the stream id, and one launch keyed by site_key draws for every row what a launch keyed
+by its own step would.
+Token 0 and the bonus token are plain draws keyed by RESIDUAL_SITE (a row without a draft is `unimm_lm_sample_rows`, bit for bit).
+A greedy slot is a top_k = 1 row on both sides: the draft's first id, accept = (draft == the model's first id), log q = 0.
+
+Memory.  The draft's logits rows of a round stay alive until the verify launch: fp32 [S, draft_len + 1, Vpad] (row draft_len of
+every slot is the bonus row's placeholder and never read), next to the model's own [S (draft_len + 1), Vpad] -- 80 dialogs x 8
+samples at draft_len 4 and Vpad 30528: 391 MB each.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import zlib
 from collections import namedtuple
 
 import numpy as np
@@ -51,6 +89,8 @@ from . import params as PM
 from .generation import (BF16, F32, MASK, SEP, SEP_BANNED, SEP_FORCED, GeneratedAnswers, Speculation)
 from .inputs import DialogMaskSpec
 
+DRAFT_SITE, ACCEPT_SITE, RESIDUAL_SITE = (zlib.crc32(b) & 0xFFFFFFFF for b in (b"generate.spec.draft", b"generate.spec.accept",
+                                                                           b"generate.spec.residual"))   # as SAMPLE_SITE
 MAX_DRAFT_LEN = 15                               # 2 * (draft_len + 1) <= 32 query rows per slot (unimm_attn_verify)
 _DRAFT_CONFIG_KEYS = ("vocab_size", "v_feature_size", "type_vocab_size", "max_position_embeddings")   # policy.check_teacher's
 
@@ -61,6 +101,13 @@ _DRAFT_CONFIG_KEYS = ("vocab_size", "v_feature_size", "type_vocab_size", "max_po
 # commit(n, emit [G], live [G]): slot s keeps `emit[s]` of the round's tokens (0 for a slot that was not live)
 # n: int64 [G]; hist: int64 [G, W + g + 1], the emitted tokens (read only)
 SpecSteps = namedtuple("SpecSteps", "root draft verify commit")
+# The sampling loop's: one slot per (dialog, draw), S = G * slots of them in place of G.
+# root(flags [S]) -> (logp [S], logq [S], id [S]): the model's plain DRAW of token 0
+# draft(j, n, token, flags [S], hist) -> id [S]: the draft's DRAW of step n[s] + j from its filtered distribution Q~
+# verify(n, last, drafts [S, g], flags [S, g + 1], hist) -> (logp, logq, id, accept), [S, g + 1] each: row j < g accepts drafts[s, j]
+#   with probability min(1, P~ / Q~) (accept = 1, id = the draft) or draws id from the residual; row g is a plain draw of the model
+# commit: as above
+SpecSampleSteps = namedtuple("SpecSampleSteps", "root draft verify commit")
 
 
 def row_flags(k, limits, min_answer_len):
@@ -73,23 +120,24 @@ def pair_keys(i):
     return list(range(0, i // 2 * 2 + 1, 2)) + ([i] if i % 2 else [])
 
 
-def speculative_search(steps, G, limits, max_answer_len, draft_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
-    """Run the rounds of the module docstring -> GeneratedAnswers shaped like beam_search(beams=1)'s, with `.speculation`."""
-    g, W = int(draft_len), max_answer_len + 1
-    dev = torch.device(device)
-    limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev)
+def _rounds(steps, S, limits, W, g, min_answer_len, dev, rejection):
+    """The rounds of the module docstring over S slots -> dict(toks [S, W], lp, lq (rejection only), lengths, rounds, drafted,
+    accepted, per_round).  rejection: the match mask is the verify step's `accept`, not the equality of draft and model token."""
     WW = W + g + 1                                                          # room for a round's writes past the end: dropped
-    toks = torch.zeros((G, WW), dtype=torch.int64, device=dev)
-    lp = torch.zeros((G, WW), dtype=F32, device=dev)
-    ar = torch.arange(G, device=dev)
+    toks = torch.zeros((S, WW), dtype=torch.int64, device=dev)
+    lp = torch.zeros((S, WW), dtype=F32, device=dev)
+    lq = torch.zeros((S, WW), dtype=F32, device=dev) if rejection else None
+    ar = torch.arange(S, device=dev)
     jj = torch.arange(g + 1, device=dev)[None]
-    v0, t0 = steps.root(row_flags(torch.zeros_like(limits), limits, min_answer_len))
-    toks[:, 0] = t0.to(dev, torch.int64)
-    lp[:, 0] = v0.to(dev, F32)
+    root = steps.root(row_flags(torch.zeros_like(limits), limits, min_answer_len))
+    toks[:, 0] = root[-1].to(dev, torch.int64)
+    lp[:, 0] = root[0].to(dev, F32)
+    if rejection:
+        lq[:, 0] = root[1].to(dev, F32)
     done = toks[:, 0] == SEP
-    n = torch.ones(G, dtype=torch.int64, device=dev)
-    drafted = torch.zeros(G, dtype=torch.int64, device=dev)
-    accepted = torch.zeros(G, dtype=torch.int64, device=dev)
+    n = torch.ones(S, dtype=torch.int64, device=dev)
+    drafted = torch.zeros(S, dtype=torch.int64, device=dev)
+    accepted = torch.zeros(S, dtype=torch.int64, device=dev)
     record, rounds = [], 0
     while not bool(done.all()):                                             # the round's one device -> host synchronisation
         rounds += 1
@@ -101,9 +149,12 @@ def speculative_search(steps, G, limits, max_answer_len, draft_len, min_answer_l
             drafts.append(token)
         drafts = torch.stack(drafts, 1)
         steps_k = n[:, None] + jj
-        vals, ids = steps.verify(n, last, drafts, row_flags(steps_k, limits[:, None], min_answer_len), toks)
-        vals, ids = vals.to(dev, F32), ids.to(dev, torch.int64)
-        match = torch.cumprod((drafts == ids[:, :g]).to(torch.int64), 1)
+        out = steps.verify(n, last, drafts, row_flags(steps_k, limits[:, None], min_answer_len), toks)
+        vals, ids = out[0].to(dev, F32), out[2 if rejection else 1].to(dev, torch.int64)
+        if rejection:
+            match = torch.cumprod(out[3].to(dev, torch.int64)[:, :g].clamp(0, 1), 1)
+        else:
+            match = torch.cumprod((drafts == ids[:, :g]).to(torch.int64), 1)
         a_raw = match.sum(1)
         is_sep = (ids == SEP) & (jj <= a_raw[:, None])
         sep_pos = torch.where(is_sep.any(1), is_sep.to(torch.int64).argmax(1), g + 1)
@@ -114,30 +165,94 @@ def speculative_search(steps, G, limits, max_answer_len, draft_len, min_answer_l
         keep = jj < emit[:, None]
         toks.scatter_(1, steps_k, torch.where(keep, ids, toks.gather(1, steps_k)))
         lp.scatter_(1, steps_k, torch.where(keep, vals, lp.gather(1, steps_k)))
+        if rejection:
+            lq.scatter_(1, steps_k, torch.where(keep, out[1].to(dev, F32), lq.gather(1, steps_k)))
         steps.commit(n, emit, live)
         drafted = drafted + torch.where(live, g, 0)
         accepted = accepted + acc
         record.append(torch.where(live, acc, -1))
         n = n + emit
         done = done | (live & (sep_pos <= a_raw))
-    lengths = n
-    toks, lp = toks[:, :W].contiguous(), lp[:, :W].contiguous()
-    logp = torch.zeros(G, dtype=F32, device=dev)
-    for k in range(W):                                                       # beam_search's sum: in step order, fp32
+    return dict(toks=toks[:, :W].contiguous(), lp=lp[:, :W].contiguous(), lq=lq[:, :W].contiguous() if rejection else None,
+                lengths=n, rounds=rounds, drafted=drafted, accepted=accepted,
+                per_round=torch.stack(record) if record else torch.zeros((0, S), dtype=torch.int64, device=dev))
+
+
+def _greedy_sums(lp, lengths, W, length_penalty, dev):
+    """beam_search's arithmetic of one slot per row: logp summed in step order in fp32, scores = logp / length ** penalty."""
+    logp = torch.zeros(lp.shape[0], dtype=F32, device=dev)
+    for k in range(W):
         logp = torch.where(lengths > k, logp + lp[:, k], logp)
     div = torch.tensor([float((k + 1) ** length_penalty) for k in range(W)], dtype=F32, device=dev)
-    scores = logp / div[lengths - 1]
-    spec = Speculation(rounds=rounds, drafted=drafted, accepted=accepted,
-                       per_round=torch.stack(record) if record else torch.zeros((0, G), dtype=torch.int64, device=dev))
+    return logp, logp / div[lengths - 1]
+
+
+def speculative_search(steps, G, limits, max_answer_len, draft_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
+    """Run the rounds of the module docstring -> GeneratedAnswers shaped like beam_search(beams=1)'s, with `.speculation`."""
+    g, W = int(draft_len), max_answer_len + 1
+    dev = torch.device(device)
+    limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev)
+    r = _rounds(steps, G, limits, W, g, min_answer_len, dev, False)
+    toks, lp, lengths = r["toks"], r["lp"], r["lengths"]
+    logp, scores = _greedy_sums(lp, lengths, W, length_penalty, dev)
+    spec = Speculation(rounds=r["rounds"], drafted=r["drafted"], accepted=r["accepted"], per_round=r["per_round"])
     return GeneratedAnswers(tokens=toks.view(G, 1, W), lengths=lengths.view(G, 1), scores=scores.view(G, 1), logp=logp.view(G, 1),
                             step_logp=lp.view(G, 1, W), speculation=spec)
+
+
+def speculative_sample_search(steps, G, samples, limits, max_answer_len, draft_len, min_answer_len=1, length_penalty=0.0,
+                              device="cpu", greedy=False):
+    """The rounds with the REJECTION rule (SpecSampleSteps) over G * (samples + greedy) slots, slot s = g * slots + j as in
+    `generation.sample_search` -> GeneratedAnswers shaped like that function's: the samples in draw order with step_logp and
+    step_logq, `.greedy` (shaped and summed like a beams = 1 result) when asked, `.speculation` with [G, samples] counters
+    (`.greedy.speculation`: [G])."""
+    N, B = int(samples), int(samples) + bool(greedy)
+    g, W, S = int(draft_len), max_answer_len + 1, G * B
+    dev = torch.device(device)
+    limits = torch.as_tensor(np.asarray(limits), dtype=torch.int64).to(dev).repeat_interleave(B)
+    r = _rounds(steps, S, limits, W, g, min_answer_len, dev, True)
+    toks, lp, lq = (r[k].view(G, B, W) for k in ("toks", "lp", "lq"))
+    lengths = r["lengths"].view(G, B)
+    logp = lp.sum(2)
+    scores = logp / lengths.clamp_min(1).to(F32) ** float(length_penalty)
+    drafted, accepted, per = r["drafted"].view(G, B), r["accepted"].view(G, B), r["per_round"].view(-1, G, B)
+    out = GeneratedAnswers(tokens=toks[:, :N].contiguous(), lengths=lengths[:, :N].contiguous(), scores=scores[:, :N].contiguous(),
+                           logp=logp[:, :N].contiguous(), step_logp=lp[:, :N].contiguous(), step_logq=lq[:, :N].contiguous(),
+                           speculation=Speculation(rounds=r["rounds"], drafted=drafted[:, :N].contiguous(),
+                                                   accepted=accepted[:, :N].contiguous(), per_round=per[:, :, :N].contiguous()))
+    if greedy:
+        glp, glen = lp[:, N].contiguous(), lengths[:, N].contiguous()
+        gsum, gscore = _greedy_sums(glp, glen, W, length_penalty, dev)
+        out.greedy = GeneratedAnswers(tokens=toks[:, N:].contiguous(), lengths=glen.view(G, 1), scores=gscore.view(G, 1),
+                                      logp=gsum.view(G, 1), step_logp=glp.view(G, 1, W),
+                                      speculation=Speculation(rounds=r["rounds"], drafted=drafted[:, N].contiguous(),
+                                                              accepted=accepted[:, N].contiguous(), per_round=per[:, :, N].contiguous()))
+    return out
+
+
+def step_streams(streams, k, salts):
+    """The stream ids that make ONE launch key its rows by their own steps.  The sampler hashes (key, stream) as
+    mix32(key ^ (stream * 0x9E3779B1 + 0x7F4A7C15)), and dropout.make_key(seed, k, site) = site_key(seed, site) ^ step_salt(seed, k);
+    the affine map of the stream id is a bijection of the 32-bit words, so a launch keyed by site_key(seed, site) alone with
+    stream' = ((stream * A + B) ^ step_salt(seed, k)) - B) * A^-1 draws, for that row, exactly what a launch keyed by
+    make_key(seed, k, site) draws for `stream` -- for every site at once.  streams: int32 (any shape); k: int64 steps
+    (broadcastable); salts: int64 [>= max k + 1], salts[k] = step_salt(seed, k) -> int32 of the broadcast shape."""
+    A, B, M = 0x9E3779B1, 0x7F4A7C15, 0xFFFFFFFF
+
+    def mul32(x, c):                                                         # low 32 bits of x * c without leaving int64
+        return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & M
+
+    f = ((mul32(streams.to(torch.int64) & M, A) + B) & M) ^ salts[k.clamp(0, salts.shape[0] - 1)]
+    low = mul32((f - B) & M, pow(A, -1, 2 ** 32))
+    return torch.where(low >= 2 ** 31, low - 2 ** 32, low).to(torch.int32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the refused requests
 # ---------------------------------------------------------------------------------------------------------------------------
-def check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope):
-    """The refused uses of `draft` (ValueError, before anything is staged) -> the draft's pre-training model."""
+def check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope, accept="match"):
+    """The refused uses of `draft` (ValueError, before anything is staged) -> the draft's pre-training model.  accept: "match"
+    (greedy: the model keeps the drafts that are its own tokens) or "rejection" (speculative sampling, needs samples >= 1)."""
     from .policy import _pretraining_model
     d = _pretraining_model(draft)
     if not (hasattr(d, "config") and hasattr(d, "_engine") and hasattr(d, "compute_dtype")):
@@ -147,10 +262,15 @@ def check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, r
         raise ValueError("generate_answers: draft is the model itself (or shares its engine): the two keep separate key/value "
                          "caches; pass a separate model, or policy.frozen_reference(model) to self-draft")
     if int(beams) != 1:
+        if accept == "rejection":                # the sampling call's rule, in its words (generation.check_sampling)
+            raise ValueError(f"generate_answers: samples > 0 draws independent answers and needs beams = 1, got beams = {beams}")
         raise ValueError(f"generate_answers: draft makes the call speculative GREEDY decoding and needs beams = 1, got beams = {beams}")
-    if samples:
-        raise ValueError(f"generate_answers: draft with samples = {samples}: speculative sampling needs a rejection step on p / q "
-                         "and is not implemented; drop draft, or samples")
+    if samples and accept != "rejection":
+        raise ValueError(f"generate_answers: draft with samples = {samples}: speculative sampling needs a rejection step on p / q, "
+                         "which draft_accept='match' does not take; pass draft_accept='rejection', or drop draft or samples")
+    if accept == "rejection" and not samples:
+        raise ValueError("generate_answers: draft_accept='rejection' is speculative SAMPLING and needs samples >= 1; for greedy "
+                         "decoding use draft_accept='match'")
     if no_repeat_ngram_size or float(np.float32(repetition_penalty)) != 1.0 or repeat_scope != "answer":
         raise ValueError("generate_answers: draft does not take the history rules (no_repeat_ngram_size, repetition_penalty, "
                          "repeat_scope='dialog'): drop draft, or the rules")
@@ -207,33 +327,57 @@ def kv_cache_append(cache, new_kv, count, plen, plen_out, layers, slots, pcap, w
     L._call("unimm_kv_cache_append", C.byref(a))
 
 
+def lm_spec_verify(x, xd, rows, V, draft_token, banned, flags, sep, temperature, top_k, top_p, key_accept, key_residual, streams,
+                   accept, token, logp, logq, lse, log_ratio=None):
+    """unimm_lm_spec_verify: accept the draft's token of every row with probability min(1, P~ / Q~) or draw from the residual.
+    x / xd: fp32 logits [rows, >= V] of the model and the draft (2-D views, row stride = stride(0)); draft_token int32 [rows]
+    (-1: no draft, a plain draw keyed by key_residual); the rest as `lib.lm_sample_rows`.  accept / token int32 [rows],
+    logp / logq / lse (/ log_ratio) fp32 [rows]."""
+    L._dev(x, xd, draft_token, banned, flags, temperature, top_k, top_p, streams, accept, token, logp, logq, lse, log_ratio)
+    a = L.LmSpecVerifyArgs()
+    a.x, a.xd, a.draft_token = L._ptr(x), L._ptr(xd), L._ptr(draft_token)
+    a.banned, a.flags, a.stream_ids = L._ptr(banned), L._ptr(flags), L._ptr(streams)
+    a.temperature, a.top_k, a.top_p = L._ptr(temperature), L._ptr(top_k), L._ptr(top_p)
+    a.accept, a.token = L._ptr(accept), L._ptr(token)
+    a.logp, a.logq, a.lse, a.log_ratio = L._ptr(logp), L._ptr(logq), L._ptr(lse), L._ptr(log_ratio)
+    a.rows, a.V, a.ldl, a.ldd = rows, V, x.stride(0) if x is not None else 0, xd.stride(0) if xd is not None else 0
+    a.nbanned, a.sep = 0 if banned is None else banned.numel(), sep
+    a.key_accept, a.key_residual = key_accept & 0xFFFFFFFF, key_residual & 0xFFFFFFFF
+    L._call("unimm_lm_spec_verify", C.byref(a))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the engines' step functions
 # ---------------------------------------------------------------------------------------------------------------------------
 class _Side:
-    """One model's side of a speculative call: the prefill and its caches, the private cache of every slot, and `rows`: P pairs
-    of new rows per slot through the blocks (the decode step of `generation._generate` with beams = 1 and 2 P rows per slot)."""
+    """One model's side of a speculative call: the prefill of the G dialogs and its caches, the private cache of every slot
+    (B slots per dialog, slot s = g * B + j, all reading dialog g's context), and `rows`: P pairs of new rows per slot through the
+    blocks (the decode step of `generation._generate` with 2 P rows per slot).  Text self-attention takes every slot as a group of
+    its own (`unimm_attn_verify` with G' = S, beams = 1 and the dialog's context range repeated per slot), so 2 P <= 32 bounds the
+    pairs whatever B is; so do the connection layers (the dialog's region range and key mask repeated per slot)."""
 
-    def __init__(self, eng, inp, c_h, limits, pcap, banned):
+    def __init__(self, eng, inp, c_h, limits, pcap, banned, B=1):
         from .scoring import _forward_shared
         self.eng, cfg, dev = eng, eng.cfg, eng.arena.device
         self.cfg, self.dev = cfg, dev
         ids = inp["input_ids"].to(dev, non_blocking=True)
         G, T = ids.shape
         self.G, self.T, self.R = G, T, inp["image_feat"].shape[1]
+        self.B, self.S = B, G * B
+        S = self.S
         ar = torch.arange(G, device=dev)
         c_d = torch.from_numpy(c_h).to(dev)
         tt = inp.get("token_type_ids")
         tt = tt.to(dev, non_blocking=True).long() if tt is not None else torch.zeros((G, T), dtype=torch.int64, device=dev)
         pp = inp.get("position_ids")
         pp = pp.to(dev, non_blocking=True).long() if pp is not None else torch.arange(T, device=dev).repeat(G, 1)
-        self.slot_pos, self.slot_seg = pp[ar, c_d - 1] + 1, tt[ar, c_d - 1] ^ 1       # generation.answer_ids of token 0
+        pos0, seg0 = pp[ar, c_d - 1] + 1, tt[ar, c_d - 1] ^ 1                         # generation.answer_ids of token 0
         pid, ptt, ppp = ids.long().clone(), tt.clone(), pp.clone()
         lab = torch.full((G, T), -1, dtype=torch.int64, device=dev)
         for j, tok in ((0, SEP), (1, MASK)):
             pid[ar, c_d + j] = tok
-            ptt[ar, c_d + j] = self.slot_seg
-            ppp[ar, c_d + j] = self.slot_pos
+            ptt[ar, c_d + j] = seg0
+            ppp[ar, c_d + j] = pos0
         lab[ar, c_d + 1] = SEP
         pin = dict(input_ids=pid, image_feat=inp["image_feat"], image_loc=inp["image_loc"], token_type_ids=ptt, position_ids=ppp,
                    masked_lm_labels=lab, attention_mask=DialogMaskSpec(np.ones(G), c_h + 1, np.ones(G)))
@@ -243,39 +387,42 @@ class _Side:
         self.cache = {}
         self.pre = _forward_shared(eng, pin, np.arange(G), False, self.cache)
         plan = self.pre["plan"]
-        self.s_off, self.s_len = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (plan.s_off, plan.s_len))
+        per_slot = (lambda a: a.repeat_interleave(B, 0)) if B > 1 else (lambda a: a)
+        self.slot_pos, self.slot_seg = per_slot(pos0), per_slot(seg0)
+        self.s_off, self.s_len = (per_slot(torch.from_numpy(a.astype(np.int32)).to(dev)) for a in (plan.s_off, plan.s_len))
         self.sched = PM.encoder_schedule(cfg)
         tkeys = [f"t{i}" for kind, i in self.sched if kind == "t"]
         self.nt, self.lidx = len(tkeys), {key: n for n, key in enumerate(tkeys)}
         self.pcap = pcap
         H = cfg.hidden_size
-        self.priv = torch.zeros((self.nt, G, pcap, 2 * H), dtype=BF16, device=dev)
-        self.plen = [torch.zeros(G, dtype=torch.int32, device=dev) for _ in range(2)]
+        self.priv = torch.zeros((self.nt, S, pcap, 2 * H), dtype=BF16, device=dev)
+        self.plen = [torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2)]
         self.cur = 0
-        self.limits = torch.from_numpy(np.asarray(limits, dtype=np.int64)).to(dev)
+        self.limits = per_slot(torch.from_numpy(np.asarray(limits, dtype=np.int64)).to(dev))
         self.banned = banned
-        self.k_off = (ar * self.R).to(torch.int32)
-        self.k_len = torch.full((G,), self.R, dtype=torch.int32, device=dev)
+        self.k_off = per_slot((ar * self.R).to(torch.int32))
+        self.k_len = torch.full((S,), self.R, dtype=torch.int32, device=dev)
+        self.vwords = per_slot(self.cache["vwords"])
         self.per_P = {}
 
     def _buffers(self, P):
         """What depends on the pairs per slot: the per-layer projection stash, the connection layers' query ranges, the scratch
         of the top-1."""
         if P not in self.per_P:
-            G, dev, M = self.G, self.dev, self.G * 2 * P
-            ar = torch.arange(G, device=dev)
+            G, S, B, dev, M = self.G, self.S, self.B, self.dev, self.S * 2 * P
+            ar = torch.arange(S, device=dev)
             self.per_P[P] = dict(stash=torch.empty((self.nt, M, 3 * self.cfg.hidden_size), dtype=BF16, device=dev),
-                                 q_off=(ar * 2 * P).to(torch.int32), q_len=torch.full((G,), 2 * P, dtype=torch.int32, device=dev),
-                                 vals=torch.empty((G * P, 1), dtype=F32, device=dev),
-                                 tops=torch.empty((G * P, 1), dtype=torch.int32, device=dev))
+                                 q_off=(ar * 2 * P).to(torch.int32), q_len=torch.full((S,), 2 * P, dtype=torch.int32, device=dev),
+                                 vals=torch.empty((S * P, 1), dtype=F32, device=dev),
+                                 tops=torch.empty((S * P, 1), dtype=torch.int32, device=dev))
         return self.per_P[P]
 
     def rows(self, tokens, k, decode):
-        """tokens int64 [G, P]: the token of answer row k[s, j] - 1; k int64 [G, P]: the step of pair j's copy row.  The slots'
-        private rows are [0, plen[cur]).  decode: the pairs whose copy rows are decoded -> fp32 logits [G * len(decode), Vpad]."""
-        eng, cfg, dev, G = self.eng, self.cfg, self.dev, self.G
+        """tokens int64 [S, P]: the token of answer row k[s, j] - 1; k int64 [S, P]: the step of pair j's copy row.  The slots'
+        private rows are [0, plen[cur]).  decode: the pairs whose copy rows are decoded -> fp32 logits [S * len(decode), Vpad]."""
+        eng, cfg, dev, G, S = self.eng, self.cfg, self.dev, self.G, self.S
         P = tokens.shape[1]
-        M = G * 2 * P
+        M = S * 2 * P
         buf = self._buffers(P)
         H, Hb = cfg.hidden_size, cfg.bi_hidden_size
         heads, nh = cfg.num_attention_heads, cfg.bi_num_attention_heads
@@ -295,10 +442,10 @@ class _Side:
                 qkv = eng._linear(xt, qkv_l, out=buf["stash"][li])
                 ctxq = self.cache[key]
                 ctx = torch.empty((M, H), dtype=BF16, device=dev)
-                pv = self.priv[li].view(G * self.pcap, 2 * H)
+                pv = self.priv[li].view(S * self.pcap, 2 * H)
                 attn = L.attn_decode if P == 1 else attn_verify
                 attn(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, ctxq[:, H:2 * H], ctxq[:, 2 * H:], self.s_off, self.s_len,
-                     pv[:, :H], pv[:, H:], plen, G, 1, 2 * P, heads, self.pcap, 1.0 / math.sqrt(D))
+                     pv[:, :H], pv[:, H:], plen, S, 1, 2 * P, heads, self.pcap, 1.0 / math.sqrt(D))
                 xt32, xt = eng._post_attn(ctx, xt32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
             elif kind == "c":
                 key = f"c{i}"
@@ -306,13 +453,13 @@ class _Side:
                 qkv1 = self.cache[key]
                 qkv2 = eng._linear(xt, lq2)
                 ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
-                vwords = self.cache["vwords"]
-                L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, G, nh, self.T, self.R, Db,
+                vwords = self.vwords
+                L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, S, nh, self.T, self.R, Db,
                            1.0 / math.sqrt(Db), 0, vwords.shape[1], NO, qvar=(buf["q_off"], buf["q_len"]),
                            kvar=(self.k_off, self.k_len))
                 xt32, xt = eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)[:2]
-        n = G * len(decode)
-        sel = (torch.arange(G, device=dev)[:, None] * 2 * P + 2 * torch.as_tensor(decode, device=dev)[None] + 1).reshape(n)
+        n = S * len(decode)
+        sel = (torch.arange(S, device=dev)[:, None] * 2 * P + 2 * torch.as_tensor(decode, device=dev)[None] + 1).reshape(n)
         xs = torch.empty((n, H), dtype=BF16, device=dev)
         L.gather_rows(xt, sel.to(torch.int32), xs, n, H)
         return eng.decode_rows(xs, n)
@@ -328,28 +475,49 @@ class _Side:
         """Append the first count[s] answer rows the last `rows` call with P pairs pushed to the private cache of slot s."""
         cur, H = self.cur, self.cfg.hidden_size
         stash = self._buffers(P)["stash"]
-        kv_cache_append(self.priv, stash[0][:, H:], count.to(torch.int32), self.plen[cur], self.plen[1 - cur], self.nt, self.G,
+        kv_cache_append(self.priv, stash[0][:, H:], count.to(torch.int32), self.plen[cur], self.plen[1 - cur], self.nt, self.S,
                         self.pcap, 2 * H, P, stash.shape[1] * 3 * H, 2 * P, 2)
         self.cur = 1 - cur
 
 
-def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer_len, length_penalty, banned_tokens):
-    """The engines' step functions of `speculative_search`; runs on the model's text stream, the draft's engine entries on the
-    draft's (the same stream unless an engine keeps a stream of its own for the text side)."""
+def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None):
+    """The engines' step functions of `speculative_search` (sampling None) or of `speculative_sample_search` (sampling: the dict
+    `generate_answers` builds, with per-slot `rows`); runs on the model's text stream, the draft's engine entries on the draft's
+    (the same stream unless an engine keeps a stream of its own for the text side)."""
     dev = eng.arena.device
     g = int(draft_len)
     banned = torch.tensor(banned_tokens, dtype=torch.int32, device=dev) if banned_tokens else None
     pcap = max(int(limits.max()), 1)
-    tgt = _Side(eng, inp, c_h, limits, pcap, banned)
-    drf = deng._on_text_stream(_Side, deng, inp, c_h, limits, pcap + g, banned)
-    G = tgt.G
+    B = sampling["samples"] + sampling["greedy"] if sampling is not None else 1
+    tgt = _Side(eng, inp, c_h, limits, pcap, banned, B)
+    drf = deng._on_text_stream(_Side, deng, inp, c_h, limits, pcap + g, banned, B)
+    G, S = tgt.G, tgt.S
     V = eng.cfg.vocab_size
-    ones = torch.ones(G, dtype=torch.int64, device=dev)
+    ones = torch.ones(S, dtype=torch.int64, device=dev)
     st = dict(round=0)
+    if sampling is not None:
+        from . import dropout as DR
+        seed, Vpad = sampling["seed"], tgt.pre["logits"].shape[1]
+        k_draft, k_accept, k_residual = (DR.site_key(seed, site) for site in (DRAFT_SITE, ACCEPT_SITE, RESIDUAL_SITE))
+        salts = torch.tensor([DR.step_salt(seed, k) for k in range(max_answer_len + g + 3)], dtype=torch.int64, device=dev)
+        streams = torch.from_numpy(sampling["streams"]).to(dev)
+        par = [torch.from_numpy(a).to(dev) for a in sampling["rows"]]                    # per slot: the draft's draws use them too
+        par_v = [a.repeat_interleave(g + 1) for a in par]                                # per verified row
+        xd = torch.zeros((S, g + 1, Vpad), dtype=F32, device=dev)        # the draft's logits rows of the round (row g: never read)
+        dtok = torch.full((S, g + 1), -1, dtype=torch.int32, device=dev)
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)    # noqa: E731
+        f32 = lambda n: torch.empty(n, dtype=F32, device=dev)            # noqa: E731
+        d_tok, d_lp, d_lq = i32(S), f32(S), f32(S)
+        v_acc, v_tok, v_lp, v_lq, v_lse = i32(S * (g + 1)), i32(S * (g + 1)), f32(S * (g + 1)), f32(S * (g + 1)), f32(S * (g + 1))
 
     def root(flags):
-        v, t = tgt.top1(tgt.pre["logits"], G, flags, 1)
-        return v.clone(), t.clone()
+        if sampling is None:
+            v, t = tgt.top1(tgt.pre["logits"], G, flags, 1)
+            return v.clone(), t.clone()
+        logits = tgt.pre["logits"].repeat_interleave(B, 0) if B > 1 else tgt.pre["logits"]
+        L.lm_sample_rows(logits, S, V, banned, flags.contiguous(), SEP, par[0], par[1], par[2], k_residual,
+                         step_streams(streams, torch.zeros_like(ones), salts), d_tok, d_lp, d_lq)
+        return d_lp.clone(), d_lq.clone(), d_tok.clone()
 
     def draft_step(j, n, token, flags, hist):
         if j == 0:
@@ -361,7 +529,14 @@ def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer
         else:
             tokens, k, P = token[:, None], (n + j)[:, None], 1
         logits = drf.rows(tokens, k, [P - 1])
-        _, t = drf.top1(logits, G, flags, P)
+        if sampling is None:
+            _, t = drf.top1(logits, S, flags, P)
+        else:                                                                # a draw from Q~, and the row it was drawn from
+            L.lm_sample_rows(logits, S, V, banned, flags.contiguous(), SEP, par[0], par[1], par[2], k_draft,
+                             step_streams(streams, n + j, salts), d_tok, d_lp, d_lq)
+            xd[:, j].copy_(logits)
+            dtok[:, j].copy_(d_tok)
+            t = d_tok
         t = t.to(torch.int64).clamp_min(0)
         drf.append(ones * P, P)                                              # (a finished slot's rows are computed and dropped)
         return t
@@ -373,12 +548,20 @@ def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer
         tokens = torch.cat([last[:, None], drafts], 1)
         k = n[:, None] + torch.arange(g + 1, device=dev)[None]
         logits = tgt.rows(tokens, k, list(range(g + 1)))
-        v, t = tgt.top1(logits, G * (g + 1), flags, g + 1)
-        return v.view(G, g + 1), t.view(G, g + 1)
+        if sampling is None:
+            v, t = tgt.top1(logits, S * (g + 1), flags, g + 1)
+            return v.view(S, g + 1), t.view(S, g + 1)
+        lm_spec_verify(logits, xd.view(S * (g + 1), Vpad), S * (g + 1), V, dtok.view(-1), banned, flags.reshape(-1).contiguous(), SEP,
+                       par_v[0], par_v[1], par_v[2], k_accept, k_residual, step_streams(streams[:, None], k, salts).reshape(-1),
+                       v_acc, v_tok, v_lp, v_lq, v_lse)
+        return tuple(a.view(S, g + 1) for a in (v_lp, v_lq, v_tok.clamp_min(0), v_acc))
 
     def commit(n, emit, live):
         tgt.append(emit, g + 1)
 
     assert V <= tgt.pre["logits"].shape[1]
-    return speculative_search(SpecSteps(root, draft, verify, commit), G, limits, max_answer_len, g, min_answer_len, length_penalty,
-                              device=dev)
+    if sampling is None:
+        return speculative_search(SpecSteps(root, draft, verify, commit), G, limits, max_answer_len, g, min_answer_len,
+                                  length_penalty, device=dev)
+    return speculative_sample_search(SpecSampleSteps(root, draft, verify, commit), G, sampling["samples"], limits, max_answer_len, g,
+                                     min_answer_len, length_penalty, device=dev, greedy=sampling["greedy"])

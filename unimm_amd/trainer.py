@@ -158,7 +158,7 @@ def _lm_term_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, 
 def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter_id, reward_fn, *, samples, baseline="greedy",
                        objective=PolicyObjective(), temperature=1.0, top_k=0, top_p=1.0, max_answer_len=20, seed=None,
                        shared_context=False, rollout="separate", reference=None, no_repeat_ngram_size=0, repetition_penalty=1.0,
-                       repeat_scope="answer"):
+                       repeat_scope="answer", draft=None, draft_len=4):
     """One iteration of self-critical / policy-gradient training of the answer generator (unimm_amd/policy.py).
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
@@ -178,6 +178,9 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     no_repeat_ngram_size / repetition_penalty / repeat_scope: `generate_answers`' history rules, handed to the sampling call and to
     the baseline's call alike, so the samples and the greedy baseline decode under one rule on both rollouts (a penalty changes
     the distribution drawn from: mode "ratio" reads it from step_logq).
+    draft / draft_len: a draft model for the rollout (`generate_answers(draft=...)`, off by default): the sampling call runs
+    with draft_accept="rejection" -- the samples stay distributed exactly as the model's own draws, with the step_logp / step_logq
+    the objective reads -- and the separate rollout's greedy call with draft_accept="match".  The history rules are refused then.
     reference: the frozen model `objective.kl_coef > 0` leashes the policy to (`policy.frozen_reference(model)`, taken before
     the fine-tune; passed on as `lm_reference`); the step's mean KL is then in `engine.last_lm_kl`.
     -> (loss, mean reward and mean baseline of the samples that were trained on, mean entropy of the trained rows'
@@ -198,12 +201,14 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     gen_kw = dict(token_type_ids=batch["segments"], position_ids=batch["positions"], image_attention_mask=batch.get("image_mask"),
                   max_answer_len=max_answer_len, no_repeat_ngram_size=no_repeat_ngram_size, repetition_penalty=repetition_penalty,
                   repeat_scope=repeat_scope)
+    spec = dict(draft=draft, draft_len=draft_len) if draft is not None else {}
     dialog_encoder.eval()
     answers = model.generate_answers(*gen_args, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p,
-                                     seed=iter_id if seed is None else seed, **(dict(greedy=True) if fused else {}), **gen_kw)
+                                     seed=iter_id if seed is None else seed, **(dict(greedy=True) if fused else {}),
+                                     **(dict(spec, draft_accept="rejection") if spec else {}), **gen_kw)
     rewards = torch.as_tensor(reward_fn(answers.tokens.cpu(), answers.lengths.cpu())).to("cpu", torch.float32)
     if greedy_baseline:
-        greedy = answers.greedy if fused else model.generate_answers(*gen_args, beams=1, **gen_kw)
+        greedy = answers.greedy if fused else model.generate_answers(*gen_args, beams=1, **spec, **gen_kw)
         base = torch.as_tensor(reward_fn(greedy.tokens.cpu(), greedy.lengths.cpu())).to("cpu", torch.float32).reshape(-1)
     else:
         base = baseline
