@@ -255,7 +255,7 @@ int unimm_attn_bwd(const unimm_attn_bwd_args* args, void* stream);
  *               (unimm_attn_bwd over the segments) writes its dk / dv into the same rows first.
  * P is recomputed from Q, K and lse, the dropout mask from the key, delta = rowsum(dO o out) of the GIVEN out inside the kernel:
  * `delta` and `order` are not read (a workgroup is one (group, head): list the largest groups first).  One workgroup walks its group's
- * sequences in list order and holds the segment's dK / dV in registers: no atomics, no scratch, the same bits on every launch.
+ * sequences in list order and holds the segment's dK / dV in registers: no atomics, the same bits on every launch (4 of its 256 registers are spilled: 20 bytes of scratch per lane).
  * A segment no listed sequence names gets nothing written. */
 int unimm_attn_spliced_fwd(const unimm_attn_args* args, void* stream);
 typedef struct {

@@ -522,7 +522,11 @@ __device__ __forceinline__ uint32_t pad_key_bits(int Tk_b, int kt) {
 //   transposed operands read from the Q / dO images.  No atomics, no cross-wave reduction.
 // ------------------------------------------------------------------------------------------------
 // MAXT = 256: the variant for <= 2 key tiles (37 region keys) -- 2 compute waves + 2 staging helpers, one wave per
-// SIMD, so the D = 128 instance gets 512 registers and stops spilling (148 bytes of scratch at 256)
+// SIMD and a 512-register budget.  Only launch_bwd_dkv<128, 8> names it, for Tq > 64 and Tk <= 64 -- the shape unimm_attn_bwd
+// hands to attn_bwd_fewk128_kernel first, so attn_bwd_dkv_kernel<128, 8, 256> (312 registers, no spills) is reached only by a
+// UNIMM_ATTN_FEWK128 = 0 build, and <128, 2, 256> is never instantiated.  What a launch reaches at D = 128 are the MAXT = 512 instances,
+// two waves per SIMD, and both spill: <128, 2, 512> (Tq, Tk <= 64: the 37 x 37 image self-attention) is 256 registers with 27 spilled,
+// 112 bytes of scratch per lane; <128, 8, 512> (Tq, Tk > 64) 256 with 16 spilled, 68 bytes (tests/test_kernel_resources_cpu.py).
 // LDS of this kernel -- and what BwdFusedLds and BwdFewq128Lds begin with: their kernels stage an item's queries the same way
 template <int D, int NQT>
 struct BwdDkvLds {
@@ -1530,8 +1534,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fewk128_kernel(AttnBwdParams 
 // -lse, delta and the mask words of every key tile (re-aligned from key POSITIONS to the tile's keys) are staged in LDS, every
 // wave forms S, dP, P, dS of its tile against the one query tile, adds into its dK / dV and leaves dS^T in its LDS tile; two
 // waves then form dQ^T over all key tiles, in tile order.  The private wave stores its dK / dV per sequence; the shared tiles are
-// rounded to bf16 ONCE, after the walk (with `accumulate`, together with what the rows already hold).  No atomics, no scratch:
-// the result does not depend on how workgroups are scheduled.
+// rounded to bf16 ONCE, after the walk (with `accumulate`, together with what the rows already hold).  No atomics:
+// the result does not depend on how workgroups are scheduled.  Registers: 256, 4 of them spilled (20 bytes of scratch per lane).
 // LDS: SplicedBwdLds (Q / dO images, row words, dS^T tiles, K and V images, parking): one workgroup per CU.
 // ------------------------------------------------------------------------------------------------
 struct AttnSplBwdParams {
@@ -1840,6 +1844,8 @@ __global__ __launch_bounds__(512, 2) void attn_spliced_bwd_kernel(AttnSplBwdPara
 //   * the V rows of a private tile are read by their own wave only, so ONE private V image serves both tiles: the wave loads it
 //     right before the tile's passes (its own LDS accesses execute in order).
 // LDS: SplicedBwdLds<2>, within 1 KiB of what a CU has: one workgroup per CU, as the narrow kernel's layout already gives.
+// __launch_bounds__(512, 1) asks for one wave per SIMD at least, which the LDS already settles; it buys no registers: the workgroup's
+// eight waves are two per SIMD, so 256 is the most a wave can get, and the kernel takes 256 with 63 spilled (256 bytes of scratch per lane).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512, 1) void attn_spliced_wide_bwd_kernel(AttnSplBwdParams sp) {
   using L = SplicedBwdLds<2>;

@@ -95,6 +95,9 @@ struct Cfg {
   static constexpr int RING_BYTES = STAGES * WB + XS * XB;
   static constexpr int LDS = RING_BYTES > SLAB_BYTES ? RING_BYTES : SLAB_BYTES;
   static constexpr int WG_PER_CU = LDS <= 53 * 1024 ? 3 : (LDS <= 80 * 1024 ? 2 : 1);
+  // waves per SIMD the launch bounds ask for.  As built, every instance has them, and one spills: the persistent 256x256 kernel
+  // with EPI_BIAS_DROP_RESID and a bf16 output takes 256 registers with 8 spilled (36 bytes of scratch per lane; its fp32 sibling
+  // fits 256).  The same epilogue on the 128x128 three-slot tile takes 260: one wave per SIMD, which is all its MIN_WAVES = 1 asks.
   static constexpr int MIN_WAVES = (WG_PER_CU * NW + 3) / 4;
   static_assert((BM + BN) % (RPI * NW) == 0, "tile rows must split evenly over the waves");
 };

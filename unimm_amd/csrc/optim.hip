@@ -200,7 +200,7 @@ static int adamw_prepare(const unimm_adamw_args* a, AdamWParams& p, size_t& bloc
   p.zero_grad = a->zero_grad;
   const size_t nvec = p.n >> 2;
   blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;       // grid-stride: 16 workgroups of 4 waves per CU
+  if (blocks > 256 * 16) blocks = 256 * 16;       // grid-stride: 16 workgroups of 4 waves per CU, 8 of them resident at a time (8 waves per SIMD)
   return UNIMM_OK;
 }
 

@@ -1049,6 +1049,7 @@ __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_bwd_dq_ker
 }
 
 // dK, dV: the wave's 16 keys in registers (K and V as B operands), Q and dO rows staged with their lse / delta / mask words
+// (at two waves per SIMD the D = 128 instance takes all 256 registers and spills 3: 16 bytes of scratch per lane; D = 64: 206)
 template <int D>
 __global__ __launch_bounds__(XM_T, UNIMM_X3M_MIN_WAVES) void x3m_attn_bwd_dkv_kernel(AttnF32 p) {
   constexpr bool OWN_Q = false;
