@@ -154,9 +154,13 @@ TABLE = {
     "attn_bwd": dict(_ATT_BWD),
     "attn_decode": dict(out=W("out")),
     "kv_cache_update": dict(dst=W("dst"), plen_out=W("plen_out")),
+    "attn_verify": dict(out=W("out")),
+    "kv_cache_append": dict(cache=W("cache"), plen_out=W("plen_out")),
     "lm_topk": dict(vals=W("vals"), ids=W("ids"), lse=W("lse")),
     "lm_sample": dict(_LM_OUT),
     "lm_sample_rows": dict(_LM_OUT),
+    "lm_spec_verify": dict(accept=W("accept"), token=W("token"), logp=W("logp"), logq=W("logq"), lse=W("lse"),
+                           log_ratio=W("log_ratio")),
     "lm_topk_hist": dict(vals=W("vals"), ids=W("ids"), lse=W("lse")),
     "lm_sample_hist": dict(_LM_OUT),
     # ---- row kernels

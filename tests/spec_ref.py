@@ -182,7 +182,7 @@ def measure(cases=None):
 
 # ---- kv_cache_append -------------------------------------------------------------------------------------------------------
 def kv_cache_append(cache, new_kv, count, plen, layers, slots, pcap, width, max_count, new_layer_stride, new_row_mul, new_row_step):
-    """The arguments of unimm_amd.speculative.kv_cache_append as HOST tensors (cache [layers, slots, pcap, ldp] BEFORE the launch;
+    """The arguments of unimm_amd.lib.kv_cache_append as HOST tensors (cache [layers, slots, pcap, ldp] BEFORE the launch;
     new_kv a 2-D view at the first K column of layer 0's new rows, inside a buffer that holds every layer's).
     -> (cache after the launch, plen_out int32 [slots]); compare bit patterns."""
     want = cache.clone()

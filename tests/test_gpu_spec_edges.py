@@ -16,7 +16,7 @@ DEV = "cuda"
 
 
 def launch(case, fn):
-    """One launch of `fn` (speculative.attn_verify or lib.attn_decode) on device copies of the case's buffers -> out [R, H D]
+    """One launch of `fn` (lib.attn_verify or lib.attn_decode) on device copies of the case's buffers -> out [R, H D]
     float64; checks that nothing else was written."""
     HD, R = case["H"] * 64, case["R"]
     new, ctx = case["new"].to(DEV), case["ctx"].to(DEV)
@@ -36,7 +36,7 @@ def launch(case, fn):
 
 
 def check_verify(case, what):
-    from unimm_amd.speculative import attn_verify
+    from unimm_amd.lib import attn_verify
     got = launch(case, attn_verify)
     ref = SR.attn_verify(*GR.decode_args(case, GR.decode_views(case)))
     assert torch.isfinite(ref["out"]).all()
@@ -90,7 +90,7 @@ def test_attn_verify_key_set_probes():
 @pytest.mark.parametrize("H,G,beams", [(1, 1, 1), (3, 3, 16), (12, 2, 5)])
 def test_attn_verify_nr2_is_attn_decode_bit_for_bit(H, G, beams):
     from unimm_amd import lib as L
-    from unimm_amd.speculative import attn_verify
+    from unimm_amd.lib import attn_verify
     pls = (0, 1, 3, 4, 5, 20, 22, -1)
     case = GR.decode_case(600 + H, H, beams, 2, G, 20, [(9, 256, 64)[g % 3] for g in range(G)],
                           [pls[s % len(pls)] for s in range(G * beams)])
@@ -99,7 +99,7 @@ def test_attn_verify_nr2_is_attn_decode_bit_for_bit(H, G, beams):
 
 def test_attn_verify_refusals():
     from unimm_amd import lib as L
-    from unimm_amd.speculative import attn_verify
+    from unimm_amd.lib import attn_verify
     for beams, nr in ((1, 3), (1, 1), (1, 34), (2, 18), (17, 2), (1, 0)):
         case = GR.decode_case(1, 1, 1, 2, 1, 4, [5], [0])
         case.update(beams=beams, nr=nr)
@@ -125,7 +125,7 @@ def append_case(layers, slots, pcap, max_count, count, plen, seed, step=2):
 
 
 def run_append(c):
-    from unimm_amd.speculative import kv_cache_append
+    from unimm_amd.lib import kv_cache_append
     cache, stash = c["cache"].to(DEV), c["stash"].to(DEV)
     po = torch.full((c["slots"] + 2,), -7, dtype=torch.int32, device=DEV)
     kv_cache_append(cache, stash[0][:, 64:], c["count"].to(DEV), c["plen"].to(DEV), po[1:-1], c["layers"], c["slots"], c["pcap"],
@@ -158,7 +158,7 @@ def test_kv_cache_append_bit_exact(layers, slots):
 
 def test_kv_cache_append_error_codes():
     from unimm_amd import lib as L
-    from unimm_amd.speculative import kv_cache_append
+    from unimm_amd.lib import kv_cache_append
     layers, slots, pcap, width = 2, 3, 4, 64
     cache = torch.full((layers, slots, pcap, width + 8), SENT, dtype=BF16, device=DEV)
     stash = torch.zeros((layers, slots * 4, width + 8), dtype=BF16, device=DEV)
@@ -182,7 +182,7 @@ def test_kv_cache_append_error_codes():
 def test_append_then_verify_chain():
     """The two kernels the way speculative.py uses them: three rounds of attn_verify on every layer's new rows, then one
     kv_cache_append of a varying number of each slot's answer rows (ping-pong plen); the restatement keeps the cache on the host."""
-    from unimm_amd.speculative import attn_verify, kv_cache_append
+    from unimm_amd.lib import attn_verify, kv_cache_append
     g_ = torch.Generator().manual_seed(31)
     layers, G, nr, pcap, H = 2, 3, 8, 9, 2
     HD, P = H * 64, nr // 2

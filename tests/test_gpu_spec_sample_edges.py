@@ -45,7 +45,7 @@ class Buffers:
 
     def launch(self, params, draft, x=None, xd=None, keys=(R.KEY_ACCEPT, R.KEY_RESIDUAL), rows=None, sel=None, ratio=True):
         """One unimm_lm_spec_verify launch on the rows `sel` (default: all, in order) -> dict of host arrays."""
-        from unimm_amd import speculative as SP
+        from unimm_amd import lib as SP
         x, xd = self.x if x is None else x, self.xd if xd is None else xd
         flags, streams = self.flags, self.streams
         t, k, p, d = (torch.as_tensor(a) for a in (*params, draft))
@@ -254,7 +254,7 @@ def test_invalid_rows_and_rows_with_nothing_eligible(V):
 
 def test_refusals_and_zero_rows():
     from unimm_amd import lib as L
-    from unimm_amd import speculative as SP
+    from unimm_amd import lib as SP
     V = 257
     b = Buffers(V)
     n = b.n
@@ -285,7 +285,7 @@ def test_the_rule_against_both_distributions_on_the_device():
     expected count below 5 pooled, below the 0.1 % critical value.  The mirror passes with the same keys on the CPU
     (tests/test_spec_sample_cpu.py)."""
     from unimm_amd import lib as L
-    from unimm_amd import speculative as SP
+    from unimm_amd import lib as SP
     V, n, temp = 16, 65536, 0.7
     x1, xd1 = R.pair16()
     x = torch.from_numpy(x1).to(DEV)[None].repeat(n, 1)

@@ -217,7 +217,7 @@ def measure_speculative(model, G, layers, gammas, reps):
     layers, the break-even acceptance, and a speculative call with a frozen copy as the draft."""
     from unimm_amd import BertConfig, BertForMultiModalPreTraining
     from unimm_amd import generation as GN
-    from unimm_amd import speculative as SP
+    from unimm_amd.decoding import DecodeSide
     from unimm_amd.policy import frozen_reference
     nt_, nv_, nc_ = layers
     cfgd = json.load(open(CFG_PATH))
@@ -236,7 +236,7 @@ def measure_speculative(model, G, layers, gammas, reps):
         eng = m._engine
         eng.ensure(m._device())
         with torch.no_grad():
-            side = eng._on_text_stream(SP._Side, eng, dict(inp), c, limits, pcap, banned)
+            side = eng._on_text_stream(DecodeSide, eng, dict(inp), c, limits, pcap, banned, 1, 1)   # the beams = 1 call's side
         side.plen[side.cur].fill_(ANS // 2)                                  # the middle of an answer: 10 private rows
         return side
 
@@ -279,7 +279,6 @@ def measure_spec_sampling(model, G, N, gammas, reps):
     """The rejection step alone (one launch against the sampler's on the same rows) and a rejection-sampled call with a frozen copy
     as the draft against the plain sampling call."""
     from unimm_amd import lib as L
-    from unimm_amd import speculative as SP
     from unimm_amd.policy import frozen_reference
     d, c = dialogs(G, seed=G * 10 + N)
     V, PAIRS = 30522, 5
@@ -301,8 +300,8 @@ def measure_spec_sampling(model, G, N, gammas, reps):
         L.lm_sample_rows(xd, rows, V, banned, flags, 102, t, k, p, 777, streams, dtok, lp, lq)
         sample_us, ratio, spread = paired(
             lambda: launch_us(lambda: L.lm_sample_rows(x, rows, V, banned, flags, 102, t, k, p, 12345, streams, tok, lp, lq), n=20),
-            lambda: launch_us(lambda: SP.lm_spec_verify(x, xd, rows, V, dtok, banned, flags, 102, t, k, p, 999, 12345, streams, acc, tok,
-                                                        lp, lq, lse), n=20), PAIRS)
+            lambda: launch_us(lambda: L.lm_spec_verify(x, xd, rows, V, dtok, banned, flags, 102, t, k, p, 999, 12345, streams, acc, tok,
+                                                       lp, lq, lse), n=20), PAIRS)
         accepted = float(acc.float().mean())
         del x, xd
         res = generate(model, d, c, 1, ANS, draft=copy, draft_len=g, draft_accept="rejection", **skw)

@@ -38,11 +38,11 @@ Search semantics (k = tokens generated so far, excluding [SEP]):
 * beams = 1 is greedy decoding; length_penalty = 0 returns the summed log p of val_lm.py, 1 the token mean of val_avg_lm.py.
 
 `beam_search` is written against an abstract step function (tests drive it with a table model on the CPU); `generate_answers`
-supplies the engine's: the decode step runs the existing NT GEMM / LayerNorm kernels on M = 2 * slots rows (after each
-attention, the engine's `_post_attn`),
-`unimm_attn_decode` for text self-attention, `unimm_attn_fwd` (variable-length) against the cached regions for the
-text-attends-regions half of a connection layer, the MLM head on the copy rows, `unimm_lm_topk` on the fp32 logits, and
-`unimm_kv_cache_update` (append + reorder of the private caches of all text layers) between steps.  Beam selection runs as
+supplies the engine's: the prefill, the caches and the decode step are a `decoding.DecodeSide` (the existing NT GEMM / LayerNorm
+kernels on M = 2 * slots rows with the engine's `_post_attn` after each attention, `unimm_attn_decode` for text self-attention,
+`unimm_attn_fwd` against the cached regions for the text half of a connection layer, the MLM head on the copy rows), followed by
+`unimm_lm_topk` on the fp32 logits, with `unimm_kv_cache_update` (append + reorder of the private caches of all text layers)
+between steps.  Beam selection runs as
 torch ops on the [G, beams * beams] candidates; the only device->host synchronisation of a step is the "all dialogs
 stopped" flag.  Inference only, bf16 engine with the connection layers.
 
@@ -118,11 +118,8 @@ import torch
 
 from . import dropout as DR
 from . import lib as L
-from . import params as PM
-from .inputs import DialogMaskSpec
+from .decoding import F32, SEP, DecodeSide, answer_ids  # noqa: F401  (answer_ids: stated there for the side, part of this module)
 
-SEP, MASK = 102, 103
-BF16, F32 = torch.bfloat16, torch.float32
 MAX_BEAMS = 16
 MAX_SAMPLES = 16                               # unimm_attn_decode takes 2 * slots <= 32 query rows per dialog
 SEP_BANNED, SEP_FORCED = 1, 2                  # per-row flags of unimm_lm_topk / unimm_lm_sample
@@ -156,6 +153,21 @@ def answer_limits(context_len, T, max_answer_len):
     return np.minimum(max_answer_len, (T - c) // 2 - 1)
 
 
+def check_model(m, draft=False):
+    """What a decode side needs of its model -- the call's, or (draft) its draft: the bf16 engine, the connection layers and text
+    heads of 64 (NotImplementedError / ValueError, in the words of each)."""
+    dtype, D = getattr(m, "compute_dtype", "bf16"), m.config.hidden_size // m.config.num_attention_heads
+    if dtype != "bf16":
+        raise (ValueError(f"generate_answers: draft must run on the bf16 engine (compute_dtype='bf16'), got {dtype!r}") if draft
+               else NotImplementedError("generate_answers runs on the bf16 engine"))
+    if not m.config.with_coattention:
+        raise (ValueError("generate_answers: draft needs the connection layers (with_coattention)") if draft
+               else NotImplementedError("generate_answers needs the connection layers (with_coattention)"))
+    if D != 64:
+        whose = "draft's " if draft else ""
+        raise ValueError(f"generate_answers: {whose}text head size {D} (unimm_attn_decode takes 64)")
+
+
 def check_request(context_len, T, beams, max_answer_len, min_answer_len):
     """The refused cases (ValueError): -> per-dialog limits (np.int64 [G])."""
     if not 1 <= int(beams) <= MAX_BEAMS:
@@ -174,17 +186,15 @@ def check_request(context_len, T, beams, max_answer_len, min_answer_len):
     return lim
 
 
-def answer_ids(pos_last, seg_last, k):
-    """(position id, segment id) of answer token k (and of its [MASK] copy) after a context whose last token has them."""
-    return pos_last + 1 + k, seg_last ^ 1
+def row_flags(k, limits, min_answer_len):
+    """int32 flags (any shape) of rows that stand at step k (an int, or int64 of limits' shape or broadcastable to it): SEP_BANNED
+    while k < min_answer_len, SEP_FORCED once k reaches the dialog's limit."""
+    return (torch.where(limits <= k, SEP_FORCED, 0) | (k < min_answer_len) * SEP_BANNED).to(torch.int32)
 
 
 def step_flags(k, limits, beams, min_answer_len):
-    """int32 [G * beams] flags of step k: SEP_BANNED while k < min_answer_len, SEP_FORCED once k reaches the dialog's limit."""
-    f = torch.where(limits <= k, SEP_FORCED, 0).to(torch.int32)
-    if k < min_answer_len:
-        f = f | SEP_BANNED
-    return f.repeat_interleave(beams)
+    """int32 [G * beams] flags of step k: row_flags of the dialogs, per hypothesis slot."""
+    return row_flags(k, limits, min_answer_len).repeat_interleave(beams)
 
 
 def beam_search(step, G, beams, limits, max_answer_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
@@ -402,21 +412,32 @@ def sample_search(step, G, samples, limits, max_answer_len, min_answer_len=1, le
         token = tok.clamp_min(0)
         if bool(done.all()):                                                  # the step's one device -> host synchronisation
             break
-    logp = lp.sum(1)
+    lengths = lengths.view(G, samples)
+    return sampled_answers(toks.view(G, samples, W), lp.view(G, samples, W), lq.view(G, samples, W), lengths, N, length_penalty,
+                           (torch.where(lengths[:, N] > 0, gcum, float("-inf")), gscore) if greedy else None)
+
+
+def sampled_answers(toks, lp, lq, lengths, N, length_penalty, greedy=None):
+    """The result of a sampling call from its [G, N (+ 1), ...] tables: the N draws as the call without the greedy slot returns
+    them (contiguous [G, N, ...]); greedy = (logp [G], scores [G]) of slot N, in beam_search's arithmetic -> `.greedy`, that slot
+    on its own."""
+    logp = lp.sum(2)
     scores = logp / lengths.clamp_min(1).to(F32) ** float(length_penalty)
-    shape = (G, samples)
-    if not greedy:
-        return GeneratedAnswers(tokens=toks.view(*shape, W), lengths=lengths.view(shape), scores=scores.view(shape),
-                                logp=logp.view(shape), step_logp=lp.view(*shape, W), step_logq=lq.view(*shape, W))
-    # the draws as the call without the greedy slot returns them (contiguous [G, N, ...]), and the greedy slot on its own
-    toks, lp, lq = (a.view(*shape, W) for a in (toks, lp, lq))
-    lengths, scores, logp = (a.view(shape) for a in (lengths, scores, logp))
-    best = GeneratedAnswers(tokens=toks[:, N:].contiguous(), lengths=lengths[:, N:].contiguous(), scores=gscore.view(G, 1),
-                            logp=torch.where(lengths[:, N:] > 0, gcum.view(G, 1), float("-inf")),
-                            step_logp=lp[:, N:].contiguous())
-    return GeneratedAnswers(tokens=toks[:, :N].contiguous(), lengths=lengths[:, :N].contiguous(), scores=scores[:, :N].contiguous(),
-                            logp=logp[:, :N].contiguous(), step_logp=lp[:, :N].contiguous(), step_logq=lq[:, :N].contiguous(),
-                            greedy=best)
+    out = GeneratedAnswers(tokens=toks[:, :N].contiguous(), lengths=lengths[:, :N].contiguous(), scores=scores[:, :N].contiguous(),
+                           logp=logp[:, :N].contiguous(), step_logp=lp[:, :N].contiguous(), step_logq=lq[:, :N].contiguous())
+    if greedy is not None:
+        out.greedy = GeneratedAnswers(tokens=toks[:, N:].contiguous(), lengths=lengths[:, N:].contiguous(),
+                                      scores=greedy[1].view(-1, 1), logp=greedy[0].view(-1, 1), step_logp=lp[:, N:].contiguous())
+    return out
+
+
+def _greedy_sums(lp, lengths, W, length_penalty, dev):
+    """beam_search's arithmetic of one slot per row: logp summed in step order in fp32, scores = logp / length ** penalty."""
+    logp = torch.zeros(lp.shape[0], dtype=F32, device=dev)
+    for k in range(W):
+        logp = torch.where(lengths > k, logp + lp[:, k], logp)
+    div = torch.tensor([float((k + 1) ** length_penalty) for k in range(W)], dtype=F32, device=dev)
+    return logp, logp / div[lengths - 1]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -428,14 +449,7 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
                      sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
                      draft_accept="match", draft=None, draft_len=4):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
-    if getattr(model, "compute_dtype", "bf16") != "bf16":
-        raise NotImplementedError("generate_answers runs on the bf16 engine")
-    cfg = model.config
-    if not cfg.with_coattention:
-        raise NotImplementedError("generate_answers needs the connection layers (with_coattention)")
-    D = cfg.hidden_size // cfg.num_attention_heads
-    if D != 64:                                             # here, before the inputs are staged: nothing reaches the device
-        raise ValueError(f"generate_answers: text head size {D} (unimm_attn_decode takes 64)")
+    check_model(model)                                      # here, before the inputs are staged: nothing reaches the device
     G, T = input_ids.shape
     c_h = (context_len.cpu().numpy() if torch.is_tensor(context_len) else np.asarray(context_len)).astype(np.int64).reshape(-1)
     if c_h.shape[0] != G:
@@ -493,69 +507,16 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples."""
     if sampling is not None:
         beams = sampling["samples"] + sampling["greedy"]
-    from .scoring import _forward_shared
-    cfg = eng.cfg
-    dev = eng.arena.device
-    ids = inp["input_ids"].to(dev, non_blocking=True)
-    G, T = ids.shape
-    S = G * beams
-    H, Hb, V = cfg.hidden_size, cfg.bi_hidden_size, cfg.vocab_size
-    heads, nh = cfg.num_attention_heads, cfg.bi_num_attention_heads
-    D, Db = H // heads, Hb // nh                           # (D == 64: generate_answers refused any other before staging)
-    R = inp["image_feat"].shape[1]
-    ar = torch.arange(G, device=dev)
-    c_d = torch.from_numpy(c_h).to(dev)
-    tt = inp.get("token_type_ids")
-    tt = tt.to(dev, non_blocking=True).long() if tt is not None else torch.zeros((G, T), dtype=torch.int64, device=dev)
-    pp = inp.get("position_ids")
-    pp = pp.to(dev, non_blocking=True).long() if pp is not None else torch.arange(T, device=dev).repeat(G, 1)
-    pos_last, seg_last = pp[ar, c_d - 1], tt[ar, c_d - 1]
-    apos, aseg = answer_ids(pos_last, seg_last, 0)
-
-    # ---- prefill: `context [SEP] [MASK]` per dialog through the shared-context pass, keeping the caches ---------------------
-    pid, ptt, ppp = ids.long().clone(), tt.clone(), pp.clone()
-    lab = torch.full((G, T), -1, dtype=torch.int64, device=dev)
-    for j, tok in ((0, SEP), (1, MASK)):
-        pid[ar, c_d + j] = tok
-        ptt[ar, c_d + j] = aseg
-        ppp[ar, c_d + j] = apos
-    lab[ar, c_d + 1] = SEP
-    pin = dict(input_ids=pid, image_feat=inp["image_feat"], image_loc=inp["image_loc"], token_type_ids=ptt, position_ids=ppp,
-               masked_lm_labels=lab, attention_mask=DialogMaskSpec(np.ones(G), c_h + 1, np.ones(G)))
-    for k in ("image_attention_mask", "image_index"):
-        if k in inp:
-            pin[k] = inp[k]
-    cache = {}
-    pre = _forward_shared(eng, pin, np.arange(G), False, cache)
-    plan = pre["plan"]
-    s_off, s_len = (torch.from_numpy(a.astype(np.int32)).to(dev) for a in (plan.s_off, plan.s_len))
-    vwords = cache["vwords"]
-    nwv = vwords.shape[1]
-
-    sched = PM.encoder_schedule(cfg)
-    tkeys = [f"t{i}" for kind, i in sched if kind == "t"]
-    nt = len(tkeys)
-    lidx = {key: n for n, key in enumerate(tkeys)}
+    dev, V = eng.arena.device, eng.cfg.vocab_size
     pcap = max(int(limits.max()), 1)
-    priv = [torch.zeros((nt, S, pcap, 2 * H), dtype=BF16, device=dev) for _ in range(2)]
-    plen = [torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2)]
-    M = 2 * S
-    stash = torch.empty((nt, M, 3 * H), dtype=BF16, device=dev)               # the step's fused projections, per text layer
     banned = torch.tensor(banned_tokens, dtype=torch.int32, device=dev) if banned_tokens else None
+    side = DecodeSide(eng, inp, c_h, limits, pcap, banned, beams, beams)      # a dialog's slots are one attention group
+    pre, G, S = side.pre, side.G, side.S
     vals = torch.empty((S, beams), dtype=F32, device=dev)
     tops = torch.empty((S, beams), dtype=torch.int32, device=dev)
-    q_off = (ar * 2 * beams).to(torch.int32)
-    q_len = torch.full((G,), 2 * beams, dtype=torch.int32, device=dev)
-    k_off = (ar * R).to(torch.int32)
-    k_len = torch.full((G,), R, dtype=torch.int32, device=dev)
-    copy_rows = torch.arange(1, M, 2, device=dev, dtype=torch.int32)
-    slot_pos = apos.repeat_interleave(beams)
-    slot_seg = aseg.repeat_interleave(beams)
-    NO = L.NO_DROP
-    st = dict(cur=0)
     if constraints is not None:                            # the history rules: every launch below is a _hist entry point
         answers = new_history(S, pcap, dev)
-        ctx, ctx_len = context_table(ids, c_h) if constraints["scope"] == "dialog" else (None, None)
+        ctx, ctx_len = context_table(inp["input_ids"].to(dev), c_h) if constraints["scope"] == "dialog" else (None, None)
         slot_ctx = torch.arange(S, device=dev, dtype=torch.int32) // beams if ctx is not None else None
         root_ctx = torch.arange(G, device=dev, dtype=torch.int32) if ctx is not None else None
 
@@ -563,42 +524,6 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
             """The launch's unimm_lm_history: of the S slots, or (root) of the G rows of the prefill, whose answers are empty."""
             return L.lm_history(answers["hist"], answers["len"], constraints["ngram"], constraints["penalty"], SEP, ctx, ctx_len,
                                 root_ctx if root else slot_ctx)
-
-    def text_block(key, x32, x):
-        qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
-        li = lidx[key]
-        qkv = eng._linear(x, qkv_l, out=stash[li])
-        ctxq = cache[key]
-        ctx = torch.empty((M, H), dtype=BF16, device=dev)
-        pv = priv[st["cur"]][li].view(S * pcap, 2 * H)
-        L.attn_decode(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, ctxq[:, H:2 * H], ctxq[:, 2 * H:], s_off, s_len,
-                      pv[:, :H], pv[:, H:], plen[st["cur"]], G, beams, 2, heads, pcap, 1.0 / math.sqrt(D))
-        return eng._post_attn(ctx, x32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
-
-    def conn_block(key, xt32, xt):
-        """The text half of a connection layer: the regions' side is the prefill's (they never attend the answer)."""
-        lq2, d2, tff1, tff2 = (eng.lin[key + s] for s in (".qkv2", ".d2", ".tff1", ".tff2"))
-        qkv1 = cache[key]
-        qkv2 = eng._linear(xt, lq2)
-        ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
-        L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, G, nh, T, R, Db, 1.0 / math.sqrt(Db),
-                   0, nwv, NO, qvar=(q_off, q_len), kvar=(k_off, k_len))
-        return eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)[:2]
-
-    def model_rows(k, token):
-        """The model part of step k >= 1: the new rows (answer row k-1, copy row k) of every slot -> fp32 logits of the copy rows."""
-        ids32 = torch.stack([token, torch.full_like(token, MASK)], 1).reshape(M).to(torch.int32)
-        pos32 = torch.stack([slot_pos + (k - 1), slot_pos + k], 1).reshape(M).to(torch.int32)
-        typ32 = slot_seg.repeat_interleave(2).to(torch.int32)
-        xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, None, NO, False, None)
-        for kind, i in sched:
-            if kind == "t":
-                xt32, xt = text_block(f"t{i}", xt32, xt)
-            elif kind == "c":
-                xt32, xt = conn_block(f"c{i}", xt32, xt)
-        xs = torch.empty((S, H), dtype=BF16, device=dev)
-        L.gather_rows(xt, copy_rows, xs, S, H)
-        return eng.decode_rows(xs, S)
 
     def topk(logits, rows, flags, k, parent=None, token=None):
         if constraints is None:
@@ -612,11 +537,8 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
             topk(pre["logits"], G, flags[::beams].contiguous(), 0)
             return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
         if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
-            cur = st["cur"]
-            L.kv_cache_update(priv[cur], priv[1 - cur], stash[0][:, H:], parent.to(torch.int32), plen[cur], plen[1 - cur],
-                              nt, S, pcap, 2 * H, M * 3 * H, 2)
-            st["cur"] = 1 - cur
-        topk(model_rows(k, token), S, flags, k, parent, token)
+            side.reorder(parent)
+        topk(side.rows(token[:, None], k, [0]), S, flags, k, parent, token)   # answer row k-1 and copy row k of every slot
         return vals, tops
 
     if sampling is None:
@@ -645,9 +567,8 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
         if k == 0:                                         # every slot of a dialog draws from the prefill's copy row 0
             return draw(k, pre["logits"][:, :V].repeat_interleave(beams, 0), flags)
         if k >= 2:                                         # a slot keeps its own cache: append its answer row k-2 in place
-            priv[0][:, :, k - 2] = stash[:, 0::2, H:]
-            plen[0].add_(1)
-        return draw(k, model_rows(k, token), flags, token)
+            side.append_in_place(k - 2)
+        return draw(k, side.rows(token[:, None], k, [0]), flags, token)
 
     return sample_search(sample_step, G, sampling["samples"], limits, max_answer_len, min_answer_len, length_penalty, device=dev,
                          greedy=sampling["greedy"])

@@ -519,6 +519,37 @@ def kv_cache_update(src, dst, new_kv, parent, plen, plen_out, layers, slots, pca
     _call("unimm_kv_cache_update", C.byref(a))
 
 
+def attn_verify(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen, G, beams, nr, H, pcap, scale, D=64):
+    """unimm_attn_verify: the arguments of `attn_decode`; nr even, the new rows of a slot are nr / 2 (answer, copy) pairs."""
+    _dev(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen)
+    a = AttnDecodeArgs()
+    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.ctx_k, a.ctx_v, a.ctx_off, a.ctx_len = ctx_k.data_ptr(), ctx_v.data_ptr(), ctx_off.data_ptr(), ctx_len.data_ptr()
+    a.priv_k, a.priv_v, a.plen = _ptr(priv_k), _ptr(priv_v), plen.data_ptr()
+    a.G, a.beams, a.nr, a.H, a.D, a.pcap = G, beams, nr, H, D, pcap
+    a.ldq, a.ldk, a.ldv, a.ldo, a.ldc = q.stride(0), k.stride(0), v.stride(0), out.stride(0), ctx_k.stride(0)
+    if ctx_v.stride(0) != ctx_k.stride(0):
+        raise UnimmHipError("attn_verify: ctx_k and ctx_v need one row stride")
+    a.ldp = priv_k.stride(0) if priv_k is not None else 0
+    if priv_v is not None and priv_v.stride(0) != a.ldp:
+        raise UnimmHipError("attn_verify: priv_k and priv_v need one row stride")
+    a.scale = scale
+    _call("unimm_attn_verify", C.byref(a))
+
+
+def kv_cache_append(cache, new_kv, count, plen, plen_out, layers, slots, pcap, width, max_count, new_layer_stride, new_row_mul,
+                    new_row_step):
+    """unimm_kv_cache_append.  cache: bf16 [layers, slots, pcap, ldp]; new_kv: 2-D bf16 view (row stride = stride(0)) at the first
+    K column of layer 0's new rows; new row j of slot s is row s * new_row_mul + j * new_row_step."""
+    _dev(cache, new_kv, count, plen, plen_out)
+    a = KvAppendArgs()
+    a.cache, a.new_kv = cache.data_ptr(), new_kv.data_ptr()
+    a.count, a.plen, a.plen_out = count.data_ptr(), plen.data_ptr(), plen_out.data_ptr()
+    a.layers, a.slots, a.pcap, a.ldp, a.width, a.max_count = layers, slots, pcap, cache.shape[-1], width, max_count
+    a.new_layer_stride, a.ld_new, a.new_row_mul, a.new_row_step = new_layer_stride, new_kv.stride(0), new_row_mul, new_row_step
+    _call("unimm_kv_cache_append", C.byref(a))
+
+
 def lm_topk(logits, rows, V, banned, flags, sep, K, vals, ids, lse=None):
     """log-softmax + top-K of fp32 logits [rows, >= V] (unimm_lm_topk): vals fp32 [rows, K], ids int32 [rows, K]."""
     _dev(logits, banned, flags, vals, ids, lse)
@@ -543,6 +574,25 @@ def lm_sample_rows(logits, rows, V, banned, flags, sep, temperature, top_k, top_
     nb = 0 if banned is None else banned.numel()
     _call("unimm_lm_sample_rows", logits.data_ptr(), rows, V, logits.stride(0), _ptr(banned), nb, _ptr(flags), sep, _ptr(temperature),
           _ptr(top_k), _ptr(top_p), key & 0xFFFFFFFF, _ptr(streams), _ptr(token), _ptr(logp), _ptr(logq), _ptr(lse))
+
+
+def lm_spec_verify(x, xd, rows, V, draft_token, banned, flags, sep, temperature, top_k, top_p, key_accept, key_residual, streams,
+                   accept, token, logp, logq, lse, log_ratio=None):
+    """unimm_lm_spec_verify: accept the draft's token of every row with probability min(1, P~ / Q~) or draw from the residual.
+    x / xd: fp32 logits [rows, >= V] of the model and the draft (2-D views, row stride = stride(0)); draft_token int32 [rows]
+    (-1: no draft, a plain draw keyed by key_residual); the rest as `lm_sample_rows`.  accept / token int32 [rows],
+    logp / logq / lse (/ log_ratio) fp32 [rows]."""
+    _dev(x, xd, draft_token, banned, flags, temperature, top_k, top_p, streams, accept, token, logp, logq, lse, log_ratio)
+    a = LmSpecVerifyArgs()
+    a.x, a.xd, a.draft_token = _ptr(x), _ptr(xd), _ptr(draft_token)
+    a.banned, a.flags, a.stream_ids = _ptr(banned), _ptr(flags), _ptr(streams)
+    a.temperature, a.top_k, a.top_p = _ptr(temperature), _ptr(top_k), _ptr(top_p)
+    a.accept, a.token = _ptr(accept), _ptr(token)
+    a.logp, a.logq, a.lse, a.log_ratio = _ptr(logp), _ptr(logq), _ptr(lse), _ptr(log_ratio)
+    a.rows, a.V, a.ldl, a.ldd = rows, V, x.stride(0) if x is not None else 0, xd.stride(0) if xd is not None else 0
+    a.nbanned, a.sep = 0 if banned is None else banned.numel(), sep
+    a.key_accept, a.key_residual = key_accept & 0xFFFFFFFF, key_residual & 0xFFFFFFFF
+    _call("unimm_lm_spec_verify", C.byref(a))
 
 
 class LmHistory(C.Structure):

@@ -35,8 +35,7 @@ rollback).  Rows a finished slot or a step past a dialog's limit still pushes ar
 at the limit's, and every cache index is clamped by the kernels.
 
 `speculative_search` is written against abstract step functions, as `beam_search` is (the CPU tests drive it with table models);
-`speculate` supplies the engines'.  The Python wrappers of the entry points live here, not in `lib.py`: answer generation is
-outside the stream-order check.
+`speculate` supplies the engines': two sides of `decoding.py`, the model's and the draft's.
 
 Speculative SAMPLING (`generate_answers(samples=N, draft=..., draft_accept="rejection")`, `speculative_sample_search`).  The same
 rounds with one slot per (dialog, draw) -- S = G * N slots, plus one greedy slot per dialog with greedy=True -- and the standard
@@ -53,9 +52,8 @@ rejection rule in place of the comparison of tokens, so that the answers are dis
    [SEP], the counters, the flags and the one synchronisation per round are the greedy loop's (`_rounds` is both).
 4. COMMIT as above.
 
-Slots and groups.  `unimm_attn_verify` takes beams * nr <= 32 query rows per group, so every slot is a group of its own (G' = S,
-beams = 1, the dialog's context range, region range and key mask repeated per slot): draft_len <= 15 holds for any samples <= 16,
-and no attention kernel changes.  `_Side` keeps S slots over a prefill of G dialogs.
+Slots and groups.  `unimm_attn_verify` takes beams * nr <= 32 query rows per group, so every slot is a group of its own
+(`decoding.DecodeSide` with per_group = 1): draft_len <= 15 holds for any samples <= 16, and no attention kernel changes.
 
 Noise.  Token k of slot s is decided by three independent words per id: the draft's Gumbel noise, the accept uniform and the
 residual's Gumbel noise, keyed by dropout.make_key(seed, k, site) with site = DRAFT_SITE / ACCEPT_SITE / RESIDUAL_SITE and the
@@ -76,8 +74,6 @@ samples at draft_len 4 and Vpad 30528: 391 MB each.
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 import zlib
 from collections import namedtuple
 
@@ -85,9 +81,9 @@ import numpy as np
 import torch
 
 from . import lib as L
-from . import params as PM
-from .generation import (BF16, F32, MASK, SEP, SEP_BANNED, SEP_FORCED, GeneratedAnswers, Speculation)
-from .inputs import DialogMaskSpec
+from .decoding import DecodeSide
+from .generation import (F32, SEP, GeneratedAnswers, Speculation, _greedy_sums, check_model, row_flags, sampled_answers)
+from .lib import attn_verify, kv_cache_append, lm_spec_verify  # noqa: F401  (the names they had here before they joined lib.py)
 
 DRAFT_SITE, ACCEPT_SITE, RESIDUAL_SITE = (zlib.crc32(b) & 0xFFFFFFFF for b in (b"generate.spec.draft", b"generate.spec.accept",
                                                                            b"generate.spec.residual"))   # as SAMPLE_SITE
@@ -108,11 +104,6 @@ SpecSteps = namedtuple("SpecSteps", "root draft verify commit")
 #   with probability min(1, P~ / Q~) (accept = 1, id = the draft) or draws id from the residual; row g is a plain draw of the model
 # commit: as above
 SpecSampleSteps = namedtuple("SpecSampleSteps", "root draft verify commit")
-
-
-def row_flags(k, limits, min_answer_len):
-    """int32 flags (any shape) of rows that stand at step k (int64, same shape as limits or broadcastable to it)."""
-    return (torch.where(limits <= k, SEP_FORCED, 0) | torch.where(k < min_answer_len, SEP_BANNED, 0)).to(torch.int32)
 
 
 def pair_keys(i):
@@ -178,15 +169,6 @@ def _rounds(steps, S, limits, W, g, min_answer_len, dev, rejection):
                 per_round=torch.stack(record) if record else torch.zeros((0, S), dtype=torch.int64, device=dev))
 
 
-def _greedy_sums(lp, lengths, W, length_penalty, dev):
-    """beam_search's arithmetic of one slot per row: logp summed in step order in fp32, scores = logp / length ** penalty."""
-    logp = torch.zeros(lp.shape[0], dtype=F32, device=dev)
-    for k in range(W):
-        logp = torch.where(lengths > k, logp + lp[:, k], logp)
-    div = torch.tensor([float((k + 1) ** length_penalty) for k in range(W)], dtype=F32, device=dev)
-    return logp, logp / div[lengths - 1]
-
-
 def speculative_search(steps, G, limits, max_answer_len, draft_len, min_answer_len=1, length_penalty=0.0, device="cpu"):
     """Run the rounds of the module docstring -> GeneratedAnswers shaped like beam_search(beams=1)'s, with `.speculation`."""
     g, W = int(draft_len), max_answer_len + 1
@@ -213,20 +195,14 @@ def speculative_sample_search(steps, G, samples, limits, max_answer_len, draft_l
     r = _rounds(steps, S, limits, W, g, min_answer_len, dev, True)
     toks, lp, lq = (r[k].view(G, B, W) for k in ("toks", "lp", "lq"))
     lengths = r["lengths"].view(G, B)
-    logp = lp.sum(2)
-    scores = logp / lengths.clamp_min(1).to(F32) ** float(length_penalty)
     drafted, accepted, per = r["drafted"].view(G, B), r["accepted"].view(G, B), r["per_round"].view(-1, G, B)
-    out = GeneratedAnswers(tokens=toks[:, :N].contiguous(), lengths=lengths[:, :N].contiguous(), scores=scores[:, :N].contiguous(),
-                           logp=logp[:, :N].contiguous(), step_logp=lp[:, :N].contiguous(), step_logq=lq[:, :N].contiguous(),
-                           speculation=Speculation(rounds=r["rounds"], drafted=drafted[:, :N].contiguous(),
-                                                   accepted=accepted[:, :N].contiguous(), per_round=per[:, :, :N].contiguous()))
+    spec = lambda j: Speculation(rounds=r["rounds"], drafted=drafted[:, j].contiguous(), accepted=accepted[:, j].contiguous(),  # noqa: E731
+                                 per_round=per[:, :, j].contiguous())
+    out = sampled_answers(toks, lp, lq, lengths, N, length_penalty,
+                          _greedy_sums(lp[:, N].contiguous(), lengths[:, N].contiguous(), W, length_penalty, dev) if greedy else None)
+    out.speculation = spec(slice(N))
     if greedy:
-        glp, glen = lp[:, N].contiguous(), lengths[:, N].contiguous()
-        gsum, gscore = _greedy_sums(glp, glen, W, length_penalty, dev)
-        out.greedy = GeneratedAnswers(tokens=toks[:, N:].contiguous(), lengths=glen.view(G, 1), scores=gscore.view(G, 1),
-                                      logp=gsum.view(G, 1), step_logp=glp.view(G, 1, W),
-                                      speculation=Speculation(rounds=r["rounds"], drafted=drafted[:, N].contiguous(),
-                                                              accepted=accepted[:, N].contiguous(), per_round=per[:, :, N].contiguous()))
+        out.greedy.speculation = spec(N)
     return out
 
 
@@ -277,13 +253,7 @@ def check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, r
     if isinstance(draft_len, bool) or not isinstance(draft_len, (int, np.integer)) or not 1 <= draft_len <= MAX_DRAFT_LEN:
         raise ValueError(f"generate_answers: draft_len must be an integer in [1, {MAX_DRAFT_LEN}] (unimm_attn_verify takes "
                          f"2 * (draft_len + 1) <= 32 rows per dialog), got {draft_len!r}")
-    if d.compute_dtype != "bf16":
-        raise ValueError(f"generate_answers: draft must run on the bf16 engine (compute_dtype='bf16'), got {d.compute_dtype!r}")
-    if not d.config.with_coattention:
-        raise ValueError("generate_answers: draft needs the connection layers (with_coattention)")
-    D = d.config.hidden_size // d.config.num_attention_heads
-    if D != 64:
-        raise ValueError(f"generate_answers: draft's text head size {D} (unimm_attn_decode takes 64)")
+    check_model(d, draft=True)
     diff = [k for k in _DRAFT_CONFIG_KEYS if getattr(d.config, k, None) != getattr(model.config, k, None)]
     if diff:
         raise ValueError("generate_answers: draft must read the model's inputs and predict over its vocabulary; its config differs "
@@ -294,192 +264,8 @@ def check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, r
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the two entry points
-# ---------------------------------------------------------------------------------------------------------------------------
-def attn_verify(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen, G, beams, nr, H, pcap, scale, D=64):
-    """unimm_attn_verify: the arguments of `lib.attn_decode`; nr even, the new rows of a slot are nr / 2 (answer, copy) pairs."""
-    L._dev(q, k, v, out, ctx_k, ctx_v, ctx_off, ctx_len, priv_k, priv_v, plen)
-    a = L.AttnDecodeArgs()
-    a.q, a.k, a.v, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
-    a.ctx_k, a.ctx_v, a.ctx_off, a.ctx_len = ctx_k.data_ptr(), ctx_v.data_ptr(), ctx_off.data_ptr(), ctx_len.data_ptr()
-    a.priv_k, a.priv_v, a.plen = L._ptr(priv_k), L._ptr(priv_v), plen.data_ptr()
-    a.G, a.beams, a.nr, a.H, a.D, a.pcap = G, beams, nr, H, D, pcap
-    a.ldq, a.ldk, a.ldv, a.ldo, a.ldc = q.stride(0), k.stride(0), v.stride(0), out.stride(0), ctx_k.stride(0)
-    if ctx_v.stride(0) != ctx_k.stride(0):
-        raise L.UnimmHipError("attn_verify: ctx_k and ctx_v need one row stride")
-    a.ldp = priv_k.stride(0) if priv_k is not None else 0
-    if priv_v is not None and priv_v.stride(0) != a.ldp:
-        raise L.UnimmHipError("attn_verify: priv_k and priv_v need one row stride")
-    a.scale = scale
-    L._call("unimm_attn_verify", C.byref(a))
-
-
-def kv_cache_append(cache, new_kv, count, plen, plen_out, layers, slots, pcap, width, max_count, new_layer_stride, new_row_mul,
-                    new_row_step):
-    """unimm_kv_cache_append.  cache: bf16 [layers, slots, pcap, ldp]; new_kv: 2-D bf16 view (row stride = stride(0)) at the first
-    K column of layer 0's new rows; new row j of slot s is row s * new_row_mul + j * new_row_step."""
-    L._dev(cache, new_kv, count, plen, plen_out)
-    a = L.KvAppendArgs()
-    a.cache, a.new_kv = cache.data_ptr(), new_kv.data_ptr()
-    a.count, a.plen, a.plen_out = count.data_ptr(), plen.data_ptr(), plen_out.data_ptr()
-    a.layers, a.slots, a.pcap, a.ldp, a.width, a.max_count = layers, slots, pcap, cache.shape[-1], width, max_count
-    a.new_layer_stride, a.ld_new, a.new_row_mul, a.new_row_step = new_layer_stride, new_kv.stride(0), new_row_mul, new_row_step
-    L._call("unimm_kv_cache_append", C.byref(a))
-
-
-def lm_spec_verify(x, xd, rows, V, draft_token, banned, flags, sep, temperature, top_k, top_p, key_accept, key_residual, streams,
-                   accept, token, logp, logq, lse, log_ratio=None):
-    """unimm_lm_spec_verify: accept the draft's token of every row with probability min(1, P~ / Q~) or draw from the residual.
-    x / xd: fp32 logits [rows, >= V] of the model and the draft (2-D views, row stride = stride(0)); draft_token int32 [rows]
-    (-1: no draft, a plain draw keyed by key_residual); the rest as `lib.lm_sample_rows`.  accept / token int32 [rows],
-    logp / logq / lse (/ log_ratio) fp32 [rows]."""
-    L._dev(x, xd, draft_token, banned, flags, temperature, top_k, top_p, streams, accept, token, logp, logq, lse, log_ratio)
-    a = L.LmSpecVerifyArgs()
-    a.x, a.xd, a.draft_token = L._ptr(x), L._ptr(xd), L._ptr(draft_token)
-    a.banned, a.flags, a.stream_ids = L._ptr(banned), L._ptr(flags), L._ptr(streams)
-    a.temperature, a.top_k, a.top_p = L._ptr(temperature), L._ptr(top_k), L._ptr(top_p)
-    a.accept, a.token = L._ptr(accept), L._ptr(token)
-    a.logp, a.logq, a.lse, a.log_ratio = L._ptr(logp), L._ptr(logq), L._ptr(lse), L._ptr(log_ratio)
-    a.rows, a.V, a.ldl, a.ldd = rows, V, x.stride(0) if x is not None else 0, xd.stride(0) if xd is not None else 0
-    a.nbanned, a.sep = 0 if banned is None else banned.numel(), sep
-    a.key_accept, a.key_residual = key_accept & 0xFFFFFFFF, key_residual & 0xFFFFFFFF
-    L._call("unimm_lm_spec_verify", C.byref(a))
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
 # the engines' step functions
 # ---------------------------------------------------------------------------------------------------------------------------
-class _Side:
-    """One model's side of a speculative call: the prefill of the G dialogs and its caches, the private cache of every slot
-    (B slots per dialog, slot s = g * B + j, all reading dialog g's context), and `rows`: P pairs of new rows per slot through the
-    blocks (the decode step of `generation._generate` with 2 P rows per slot).  Text self-attention takes every slot as a group of
-    its own (`unimm_attn_verify` with G' = S, beams = 1 and the dialog's context range repeated per slot), so 2 P <= 32 bounds the
-    pairs whatever B is; so do the connection layers (the dialog's region range and key mask repeated per slot)."""
-
-    def __init__(self, eng, inp, c_h, limits, pcap, banned, B=1):
-        from .scoring import _forward_shared
-        self.eng, cfg, dev = eng, eng.cfg, eng.arena.device
-        self.cfg, self.dev = cfg, dev
-        ids = inp["input_ids"].to(dev, non_blocking=True)
-        G, T = ids.shape
-        self.G, self.T, self.R = G, T, inp["image_feat"].shape[1]
-        self.B, self.S = B, G * B
-        S = self.S
-        ar = torch.arange(G, device=dev)
-        c_d = torch.from_numpy(c_h).to(dev)
-        tt = inp.get("token_type_ids")
-        tt = tt.to(dev, non_blocking=True).long() if tt is not None else torch.zeros((G, T), dtype=torch.int64, device=dev)
-        pp = inp.get("position_ids")
-        pp = pp.to(dev, non_blocking=True).long() if pp is not None else torch.arange(T, device=dev).repeat(G, 1)
-        pos0, seg0 = pp[ar, c_d - 1] + 1, tt[ar, c_d - 1] ^ 1                         # generation.answer_ids of token 0
-        pid, ptt, ppp = ids.long().clone(), tt.clone(), pp.clone()
-        lab = torch.full((G, T), -1, dtype=torch.int64, device=dev)
-        for j, tok in ((0, SEP), (1, MASK)):
-            pid[ar, c_d + j] = tok
-            ptt[ar, c_d + j] = seg0
-            ppp[ar, c_d + j] = pos0
-        lab[ar, c_d + 1] = SEP
-        pin = dict(input_ids=pid, image_feat=inp["image_feat"], image_loc=inp["image_loc"], token_type_ids=ptt, position_ids=ppp,
-                   masked_lm_labels=lab, attention_mask=DialogMaskSpec(np.ones(G), c_h + 1, np.ones(G)))
-        for k in ("image_attention_mask", "image_index"):
-            if k in inp:
-                pin[k] = inp[k]
-        self.cache = {}
-        self.pre = _forward_shared(eng, pin, np.arange(G), False, self.cache)
-        plan = self.pre["plan"]
-        per_slot = (lambda a: a.repeat_interleave(B, 0)) if B > 1 else (lambda a: a)
-        self.slot_pos, self.slot_seg = per_slot(pos0), per_slot(seg0)
-        self.s_off, self.s_len = (per_slot(torch.from_numpy(a.astype(np.int32)).to(dev)) for a in (plan.s_off, plan.s_len))
-        self.sched = PM.encoder_schedule(cfg)
-        tkeys = [f"t{i}" for kind, i in self.sched if kind == "t"]
-        self.nt, self.lidx = len(tkeys), {key: n for n, key in enumerate(tkeys)}
-        self.pcap = pcap
-        H = cfg.hidden_size
-        self.priv = torch.zeros((self.nt, S, pcap, 2 * H), dtype=BF16, device=dev)
-        self.plen = [torch.zeros(S, dtype=torch.int32, device=dev) for _ in range(2)]
-        self.cur = 0
-        self.limits = per_slot(torch.from_numpy(np.asarray(limits, dtype=np.int64)).to(dev))
-        self.banned = banned
-        self.k_off = per_slot((ar * self.R).to(torch.int32))
-        self.k_len = torch.full((S,), self.R, dtype=torch.int32, device=dev)
-        self.vwords = per_slot(self.cache["vwords"])
-        self.per_P = {}
-
-    def _buffers(self, P):
-        """What depends on the pairs per slot: the per-layer projection stash, the connection layers' query ranges, the scratch
-        of the top-1."""
-        if P not in self.per_P:
-            G, S, B, dev, M = self.G, self.S, self.B, self.dev, self.S * 2 * P
-            ar = torch.arange(S, device=dev)
-            self.per_P[P] = dict(stash=torch.empty((self.nt, M, 3 * self.cfg.hidden_size), dtype=BF16, device=dev),
-                                 q_off=(ar * 2 * P).to(torch.int32), q_len=torch.full((S,), 2 * P, dtype=torch.int32, device=dev),
-                                 vals=torch.empty((S * P, 1), dtype=F32, device=dev),
-                                 tops=torch.empty((S * P, 1), dtype=torch.int32, device=dev))
-        return self.per_P[P]
-
-    def rows(self, tokens, k, decode):
-        """tokens int64 [S, P]: the token of answer row k[s, j] - 1; k int64 [S, P]: the step of pair j's copy row.  The slots'
-        private rows are [0, plen[cur]).  decode: the pairs whose copy rows are decoded -> fp32 logits [S * len(decode), Vpad]."""
-        eng, cfg, dev, G, S = self.eng, self.cfg, self.dev, self.G, self.S
-        P = tokens.shape[1]
-        M = S * 2 * P
-        buf = self._buffers(P)
-        H, Hb = cfg.hidden_size, cfg.bi_hidden_size
-        heads, nh = cfg.num_attention_heads, cfg.bi_num_attention_heads
-        D, Db = H // heads, Hb // nh
-        NO = L.NO_DROP
-        kc = torch.minimum(k, self.limits[:, None]).clamp_min(0)            # rows past a dialog's limit are dropped: keep their ids inside
-        ids32 = torch.stack([tokens, torch.full_like(tokens, MASK)], 2).reshape(M).to(torch.int32)
-        pos32 = (self.slot_pos[:, None, None] + torch.stack([(kc - 1).clamp_min(0), kc], 2)).reshape(M).to(torch.int32)
-        typ32 = self.slot_seg.repeat_interleave(2 * P).to(torch.int32)
-        xt32, xt, _ = eng._embed_text(ids32, pos32, typ32, M, None, NO, False, None)
-        plen = self.plen[self.cur]
-        for kind, i in self.sched:
-            if kind == "t":
-                key = f"t{i}"
-                qkv_l, so, ff1, ff2 = (eng.lin[key + s] for s in (".qkv", ".so", ".ff1", ".ff2"))
-                li = self.lidx[key]
-                qkv = eng._linear(xt, qkv_l, out=buf["stash"][li])
-                ctxq = self.cache[key]
-                ctx = torch.empty((M, H), dtype=BF16, device=dev)
-                pv = self.priv[li].view(S * self.pcap, 2 * H)
-                attn = L.attn_decode if P == 1 else attn_verify
-                attn(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], ctx, ctxq[:, H:2 * H], ctxq[:, 2 * H:], self.s_off, self.s_len,
-                     pv[:, :H], pv[:, H:], plen, S, 1, 2 * P, heads, self.pcap, 1.0 / math.sqrt(D))
-                xt32, xt = eng._post_attn(ctx, xt32, so, ff1, ff2, key + ".ln1", key + ".ln2", NO, NO, False)[:2]
-            elif kind == "c":
-                key = f"c{i}"
-                lq2, d2, tff1, tff2 = (eng.lin[key + s] for s in (".qkv2", ".d2", ".tff1", ".tff2"))
-                qkv1 = self.cache[key]
-                qkv2 = eng._linear(xt, lq2)
-                ctx_t = torch.empty((M, Hb), dtype=BF16, device=dev)
-                vwords = self.vwords
-                L.attn_fwd(qkv2[:, :Hb], qkv1[:, Hb:2 * Hb], qkv1[:, 2 * Hb:], ctx_t, None, vwords, S, nh, self.T, self.R, Db,
-                           1.0 / math.sqrt(Db), 0, vwords.shape[1], NO, qvar=(buf["q_off"], buf["q_len"]),
-                           kvar=(self.k_off, self.k_len))
-                xt32, xt = eng._post_attn(ctx_t, xt32, d2, tff1, tff2, key + ".lnb2", key + ".lnt", NO, NO, False)[:2]
-        n = S * len(decode)
-        sel = (torch.arange(S, device=dev)[:, None] * 2 * P + 2 * torch.as_tensor(decode, device=dev)[None] + 1).reshape(n)
-        xs = torch.empty((n, H), dtype=BF16, device=dev)
-        L.gather_rows(xt, sel.to(torch.int32), xs, n, H)
-        return eng.decode_rows(xs, n)
-
-    def top1(self, logits, rows, flags, P):
-        """The greedy token of every row and its log p under the rows' flags (unimm_lm_topk, K = 1) -> (logp [rows], id [rows])."""
-        buf = self._buffers(P)
-        L.lm_topk(logits, rows, self.cfg.vocab_size, self.banned, flags.reshape(rows).contiguous(), SEP, 1, buf["vals"][:rows],
-                  buf["tops"][:rows])
-        return buf["vals"][:rows, 0], buf["tops"][:rows, 0]
-
-    def append(self, count, P):
-        """Append the first count[s] answer rows the last `rows` call with P pairs pushed to the private cache of slot s."""
-        cur, H = self.cur, self.cfg.hidden_size
-        stash = self._buffers(P)["stash"]
-        kv_cache_append(self.priv, stash[0][:, H:], count.to(torch.int32), self.plen[cur], self.plen[1 - cur], self.nt, self.S,
-                        self.pcap, 2 * H, P, stash.shape[1] * 3 * H, 2 * P, 2)
-        self.cur = 1 - cur
-
-
 def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None):
     """The engines' step functions of `speculative_search` (sampling None) or of `speculative_sample_search` (sampling: the dict
     `generate_answers` builds, with per-slot `rows`); runs on the model's text stream, the draft's engine entries on the draft's
@@ -489,8 +275,8 @@ def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer
     banned = torch.tensor(banned_tokens, dtype=torch.int32, device=dev) if banned_tokens else None
     pcap = max(int(limits.max()), 1)
     B = sampling["samples"] + sampling["greedy"] if sampling is not None else 1
-    tgt = _Side(eng, inp, c_h, limits, pcap, banned, B)
-    drf = deng._on_text_stream(_Side, deng, inp, c_h, limits, pcap + g, banned, B)
+    tgt = DecodeSide(eng, inp, c_h, limits, pcap, banned, B, 1)             # every slot an attention group of its own
+    drf = deng._on_text_stream(DecodeSide, deng, inp, c_h, limits, pcap + g, banned, B, 1)
     G, S = tgt.G, tgt.S
     V = eng.cfg.vocab_size
     ones = torch.ones(S, dtype=torch.int64, device=dev)
@@ -551,9 +337,9 @@ def speculate(eng, deng, inp, c_h, limits, draft_len, max_answer_len, min_answer
         if sampling is None:
             v, t = tgt.top1(logits, S * (g + 1), flags, g + 1)
             return v.view(S, g + 1), t.view(S, g + 1)
-        lm_spec_verify(logits, xd.view(S * (g + 1), Vpad), S * (g + 1), V, dtok.view(-1), banned, flags.reshape(-1).contiguous(), SEP,
-                       par_v[0], par_v[1], par_v[2], k_accept, k_residual, step_streams(streams[:, None], k, salts).reshape(-1),
-                       v_acc, v_tok, v_lp, v_lq, v_lse)
+        L.lm_spec_verify(logits, xd.view(S * (g + 1), Vpad), S * (g + 1), V, dtok.view(-1), banned, flags.reshape(-1).contiguous(), SEP,
+                         par_v[0], par_v[1], par_v[2], k_accept, k_residual, step_streams(streams[:, None], k, salts).reshape(-1),
+                         v_acc, v_tok, v_lp, v_lq, v_lse)
         return tuple(a.view(S, g + 1) for a in (v_lp, v_lq, v_tok.clamp_min(0), v_acc))
 
     def commit(n, emit, live):
