@@ -7,6 +7,7 @@ against the recompute lower bound: sequence_log_likelihood of the same G * beams
     python tools/bench_generate.py [--reps 3] [--shapes 1,1 80,4] [--profile] [--samples N]
                                    [--no-repeat-ngram N] [--repetition-penalty R] [--repeat-scope answer|dialog]
                                    [--draft-layers t,v,c --draft-len g [g ...]]
+                                   [--ensemble K [--ensemble-mode prob|logit]]
 
 --samples N adds, for G = 80 dialogs: ms/step of sampling N answers per dialog (temperature 0.8, top_k 50, top_p 0.9) against a
 beam run with the same number of hypothesis slots (beams = N) in the same process, the time of one unimm_lm_sample launch against
@@ -30,6 +31,13 @@ copy's acceptance is near 1: that measures the machinery, not a speed-up (no tra
 unimm_lm_spec_verify launch against one unimm_lm_sample_rows launch on the same 80 N (g + 1) rows of [., 30522] logits (the drafts
 drawn from the draft rows, xd = x + noise; the byte count beside it: one read of the model row, two of the draft row), and a
 rejection-sampled call with a frozen copy as the draft against the plain sampling call (temperature 0.8, top_k 50, top_p 0.9).
+
+--ensemble K (members, 2 .. 5; --ensemble-mode prob or logit) adds, at G = 80: one unimm_lm_mix launch on K blocks of [640, 30522]
+logits (row stride 30528) beside one unimm_lm_topk launch on one of them -- microseconds, the bytes the launch moves (every member
+row once in logit mode, twice in prob mode, the mixed row written once) and TB/s -- and the call with K - 1 frozen copies of the
+model as partners beside the plain call, at beams = 1 and at 8 samples per dialog (temperature 0.8, top_k 50, top_p 0.9).  The
+expectation to read the ratios against is K decode steps plus the mix.  The copies measure the machinery: no trained ensemble
+exists, and no answer quality is measured.
 
 --profile adds the kernel mix of one call at (80, 4) from a `rocprofv3 --kernel-trace --stats` run of this tool in a child
 process (per decode step = the call's launches / 20; the prefill's own kernels run once and are listed with it)."""
@@ -317,6 +325,48 @@ def measure_spec_sampling(model, G, N, gammas, reps):
     return row
 
 
+def measure_ensemble(model, G, K, mode, reps):
+    """One unimm_lm_mix launch beside one unimm_lm_topk launch on the same rows, and the call with K - 1 frozen copies as partners
+    beside the plain call: greedy and 8 samples per dialog."""
+    from unimm_amd import lib as L
+    from unimm_amd import mix as MX
+    from unimm_amd.policy import frozen_reference
+    N, V, LD, PAIRS = 8, 30522, 30528, 5
+    S = G * N
+    gen = torch.Generator().manual_seed(0)
+    blocks = [(torch.randn((S, LD), generator=gen) * 3).cuda() for _ in range(K)]
+    out = torch.empty((S, LD), device="cuda")
+    banned = torch.tensor([0, 101, 103], dtype=torch.int32, device="cuda")
+    flags = torch.zeros(S, dtype=torch.int32, device="cuda")
+    vals = torch.empty((S, 1), dtype=torch.float32, device="cuda")
+    ids = torch.empty((S, 1), dtype=torch.int32, device="cuda")
+    weights = [1.0 / K] * K
+    row = dict(G=G, members=K, mode=mode, rows=S)
+    topk_us, ratio, spread = paired(
+        lambda: launch_us(lambda: L.lm_topk(blocks[0], S, V, banned, flags, 102, 1, vals, ids), n=20),
+        lambda: launch_us(lambda: MX.lm_mix(blocks, weights, mode, V, banned, flags, 102, float("-inf"), out), n=20), PAIRS)
+    nbytes = S * V * 4 * (K * (2 if mode == "prob" else 1) + 1)
+    mix_us = topk_us * ratio
+    row.update(lm_topk_us=round(topk_us, 1), lm_mix_us=round(mix_us, 1), lm_mix_over_topk=round(ratio, 3), lm_topk_spread=round(spread, 3),
+               lm_mix_mib=round(nbytes / 2 ** 20, 1), lm_mix_tb_per_s=round(nbytes / (mix_us * 1e-6) / 1e12, 3))
+    cut_us = launch_us(lambda: MX.lm_mix(blocks, weights, mode, V, banned, flags, 102, float(np.log(0.1)), out), n=20)
+    row["lm_mix_cut_us"] = round(cut_us, 1)
+    del blocks, out
+    d, c = dialogs(G, seed=G * 10 + 1)
+    partners = [frozen_reference(model) for _ in range(K - 1)]
+    ekw = dict(ensemble=partners, ensemble_mode=mode)
+    for name, kw in (("greedy", {}), ("sample", dict(samples=N, temperature=0.8, top_k=50, top_p=0.9, seed=1))):
+        def call(**more):
+            t0 = time.perf_counter()
+            res = generate(model, d, c, 1, ANS, **kw, **more)
+            torch.cuda.synchronize()
+            assert bool((res.lengths == ANS + 1).all())
+            return (time.perf_counter() - t0) * 1e3
+        call(), call(**ekw)                                                  # warm-up of both
+        row[name + "_call_ms"], row[name + "_ensemble_ratio"], row[name + "_call_spread"] = paired(call, lambda: call(**ekw), max(reps, 3))
+    return {k: round(v, 4) if isinstance(v, float) else v for k, v in row.items()}
+
+
 def recompute_bound(model, d, c, G, beams, reps):
     """Summed ms of scoring G * beams sequences with answers of 1 .. ANS tokens (shared context up to 14 answer tokens)."""
     from unimm_amd.inputs import DialogMaskSpec
@@ -399,6 +449,8 @@ def main():
     ap.add_argument("--draft-layers", default=None, help="t,v,c: add the speculative-decoding measurements at G = 80 with a random draft "
                     "of that many text, image and connection layers")
     ap.add_argument("--draft-len", type=int, nargs="+", default=[4], help="... at these draft lengths")
+    ap.add_argument("--ensemble", type=int, default=0, help="add the ensemble measurements at G = 80 with this many members (2 .. 5)")
+    ap.add_argument("--ensemble-mode", choices=("prob", "logit"), default="prob")
     a = ap.parse_args()
     torch.set_num_threads(min(16, torch.get_num_threads()))
     model = build_model()
@@ -445,6 +497,14 @@ def main():
                   f"{q['sample_rows_spread']:.3f}; {q['mib_read']:.0f} MiB read = x once + xd twice, {q['gb_per_s']:.0f} GB/s; "
                   f"{q['launch_acceptance']:.2f} of the rows accepted); frozen copy as draft: {q['copy_call_ms']:.1f} ms = "
                   f"{q['copy_call_over_plain']:.2f} x the plain call, {q['copy_rounds']} rounds, acceptance {q['copy_acceptance']:.3f}")
+    if a.ensemble:
+        result["ensemble"] = r = measure_ensemble(model, 80, a.ensemble, a.ensemble_mode, a.reps)
+        print(f"ensemble of {r['members']} ({r['mode']}) at G = {r['G']}: one launch on {r['members']} x [{r['rows']}, 30522]: unimm_lm_mix "
+              f"{r['lm_mix_us']:.1f} us ({r['lm_mix_mib']:.0f} MiB moved, {r['lm_mix_tb_per_s']:.2f} TB/s; with a cut {r['lm_mix_cut_us']:.1f} us) "
+              f"= {r['lm_mix_over_topk']:.2f} x unimm_lm_topk ({r['lm_topk_us']:.1f} us, spread {r['lm_topk_spread']:.3f}); frozen copies as "
+              f"partners over the plain call, median of alternating pairs: beams = 1 {r['greedy_ensemble_ratio']:.2f} x "
+              f"({r['greedy_call_ms']:.1f} ms, spread {r['greedy_call_spread']:.3f}), 8 samples {r['sample_ensemble_ratio']:.2f} x "
+              f"({r['sample_call_ms']:.1f} ms, spread {r['sample_call_spread']:.3f})")
     if a.profile:
         result["kernel_mix_80x4"] = profile()
         for m in result["kernel_mix_80x4"]:

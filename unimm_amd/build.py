@@ -1,4 +1,5 @@
-"""Build libunimm_hip.so (all HIP kernels + the C ABI) in-tree with hipcc for gfx950.
+"""Build libunimm_hip.so (all HIP kernels + the C ABI) in-tree with hipcc for gfx950, and beside it the extension library
+libunimm_mix.so (csrc/mix/, include/unimm_mix.h: ensemble answer generation) the same way.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the .so travels
 to the GPU box with the repo snapshot (it is git-ignored, not gpurun-ignored)."""
@@ -14,12 +15,14 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libunimm_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
+MIX_SRC = os.path.join(CSRC, "mix")
+MIX_LIB = os.path.join(PKG, "libunimm_mix.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 
 
-def sources():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+def sources(directory=CSRC):
+    return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(".hip"))
 
 
 def _stale(target, deps):
@@ -36,11 +39,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(PKG), "include", "unimm_hip.h"))
+    mix_headers = headers + [os.path.join(os.path.dirname(PKG), "include", "unimm_mix.h")]
+    mix_obj = lambda s: os.path.join(OBJ, "mix_" + os.path.basename(s)[:-4] + ".o")     # noqa: E731
     jobs = []
     for src in sources():
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
         if force or _stale(obj, [src] + headers):
             jobs.append((src, obj))
+    mix_jobs = [(src, mix_obj(src)) for src in sources(MIX_SRC) if force or _stale(mix_obj(src), [src] + mix_headers)]
 
     def compile_one(job):
         src, obj = job
@@ -52,10 +58,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print("compiled", os.path.basename(src), file=sys.stderr)
 
     with ThreadPoolExecutor(max_workers=8) as ex:
-        list(ex.map(compile_one, jobs))
+        list(ex.map(compile_one, jobs + mix_jobs))
     objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + ".o") for s in sources()]
     if force or jobs or _stale(LIB, objs):
         r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs,
+                           capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n" + r.stderr)
+    objs = [mix_obj(s) for s in sources(MIX_SRC)]
+    if force or mix_jobs or _stale(MIX_LIB, objs):
+        r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", MIX_LIB] + objs,
                            capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n" + r.stderr)

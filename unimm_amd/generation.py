@@ -106,6 +106,26 @@ counters.  Keys are per ABSOLUTE step and the streams those of the plain call; a
 (whether a step is a drafted row or the bonus row, a plain draw, depends on draft_len): the distribution is the same, the draws not.
 Needs samples >= 1 and a draft; every refusal of the greedy form applies (the history rules included), and `beams` follows the
 sampling call's rule.
+
+Ensemble and contrastive decoding (`ensemble=[partners]`, `ensemble_weights`, `ensemble_mode`, `plausibility`).  The call's model
+is member 0 and `ensemble` names 1 to 4 partners of either class -- their own depth, widths and layer schedule, the model's
+vocabulary and inputs, each on a bf16 engine of its own (`policy.frozen_reference(model)` for a second copy of the same weights).
+Every member gets a `DecodeSide` with the same slots and groups; a step pushes the SAME tokens through every side, one
+`unimm_lm_mix` launch (the extension library libunimm_mix.so, bound by unimm_amd/mix.py) turns the K logits blocks into one
+[slots, Vpad] block (at step 0: the K prefill rows), and the selection launch of the plain call -- top-k, a draw, with or without a history -- reads that block.  `reorder` / `append_in_place` are applied
+to every side; the searches see a step function and do not change.  ensemble_mode="prob" (the default) is the arithmetic mixture
+z_i = log sum_m w_m p_m(i), the usual checkpoint ensemble: weights >= 0 that sum to 1 (within 1e-6), w_0 > 0, default uniform;
+the mixed row sums to 1, so step_logp = log sum_m w_m p_m(token).  "logit" is the log-linear mixture z_i = sum_m w_m x_m,i with
+finite weights of any sign, w_0 > 0; softmax(z) is the normalised product of the p_m ** w_m and step_logp the log-probability
+under it.  plausibility = alpha in (0, 1) cuts, before the selection, every id but [SEP] whose logit under THE MODEL (member 0) is
+below its best eligible logit + fp32(log alpha) -- p_0(i) < alpha max p_0 -- so that weights (1 + b, -b) with a cut are contrastive
+decoding (expert minus amateur on the ids the expert finds plausible); step_logp is then normalised over the plausible set.  The
+step rules, beams, sampling with per-draw parameters, greedy=True and length_penalty work as in the plain call, the history rules
+too but not together with a cut (a ban could empty the plausible set).  Refused on the host before anything is staged: `ensemble`
+with `draft`, no or more than 4 partners, a partner that is the model, a repeated partner or a shared engine, a partner of another
+device, engine, vocabulary, input shape or head size, weights of the wrong number or outside the mode's rule, an unknown mode,
+`plausibility` outside [0, 1), and `ensemble_weights` or a cut without `ensemble`.  With ensemble=None nothing here runs and a call
+launches what it always launched.  A step costs K decode steps plus the mix (tools/bench_generate.py --ensemble K).
 """
 from __future__ import annotations
 
@@ -337,6 +357,91 @@ def check_constraints(no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_sco
     return dict(ngram=int(n), penalty=float(np.float32(r)), scope=repeat_scope)
 
 
+MAX_PARTNERS = 4                               # unimm_lm_mix takes K <= 5 rows: the model and four partners
+ENSEMBLE_MODES = ("prob", "logit")
+_PARTNER_CONFIG_KEYS = ("vocab_size", "v_feature_size", "type_vocab_size", "max_position_embeddings")
+
+
+def check_partner(model, partner, index):
+    """What member `index` >= 1 of an ensemble must be (ValueError) -> its pre-training model: a model of either class, not the
+    call's model, on its device and the bf16 engine, with the connection layers, text heads of 64, the model's vocabulary and
+    inputs.  Depth, widths and the layer schedule are its own."""
+    from .policy import _pretraining_model
+    p, who = _pretraining_model(partner), f"ensemble member {index}"
+    if not (hasattr(p, "config") and hasattr(p, "_engine") and hasattr(p, "compute_dtype")):
+        raise ValueError(f"generate_answers: {who} must be a BertForMultiModalPreTraining or a VisualDialogEncoder, got "
+                         f"{type(partner).__name__}")
+    if p is model or p._engine is model._engine:
+        raise ValueError(f"generate_answers: {who} is the model itself (or shares its engine): every member keeps its own key/value "
+                         "caches; pass a separate model, or policy.frozen_reference(model) for a second copy of the same weights")
+    if p.compute_dtype != "bf16":
+        raise ValueError(f"generate_answers: {who} must run on the bf16 engine (compute_dtype='bf16'), got {p.compute_dtype!r}")
+    if not p.config.with_coattention:
+        raise ValueError(f"generate_answers: {who} needs the connection layers (with_coattention)")
+    D = p.config.hidden_size // p.config.num_attention_heads
+    if D != 64:
+        raise ValueError(f"generate_answers: {who} has text head size {D} (unimm_attn_decode takes 64)")
+    diff = [k for k in _PARTNER_CONFIG_KEYS if getattr(p.config, k, None) != getattr(model.config, k, None)]
+    if diff:
+        raise ValueError(f"generate_answers: {who} must read the model's inputs and predict over its vocabulary; its config differs "
+                         f"in {', '.join(diff)}")
+    if p._device() != model._device():
+        raise ValueError(f"generate_answers: {who} is on {p._device()}, the model on {model._device()}: move it with .to()")
+    return p
+
+
+def check_ensemble(model, ensemble, ensemble_weights=None, ensemble_mode="prob", plausibility=0.0, draft=None,
+                   no_repeat_ngram_size=0, repetition_penalty=1.0):
+    """The refused ensemble requests (ValueError, before anything is staged) -> None without `ensemble`, else dict(partners: the
+    partners' pre-training models, weights: K floats with the model's first, mode, log_alpha: fp32(log plausibility), -inf = off)."""
+    a = plausibility
+    if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not 0.0 <= a < 1.0:
+        raise ValueError(f"generate_answers: plausibility must be in [0, 1) (0 = off), got {a!r}")
+    if ensemble_mode not in ENSEMBLE_MODES:
+        raise ValueError(f"generate_answers: ensemble_mode must be one of {ENSEMBLE_MODES}, got {ensemble_mode!r}")
+    if ensemble is None:
+        if ensemble_weights is not None or a > 0:
+            raise ValueError("generate_answers: ensemble_weights and plausibility shape the mixture of an ensemble and need partner "
+                             "models (ensemble=[...])")
+        return None
+    if draft is not None:
+        raise ValueError("generate_answers: ensemble with draft: a speculative call verifies ONE model's tokens; drop one of the two")
+    if isinstance(ensemble, torch.nn.Module) or not isinstance(ensemble, (list, tuple)):
+        raise ValueError(f"generate_answers: ensemble must be a sequence of 1 to {MAX_PARTNERS} partner models, got "
+                         f"{type(ensemble).__name__}")
+    if not 1 <= len(ensemble) <= MAX_PARTNERS:
+        raise ValueError(f"generate_answers: ensemble takes 1 to {MAX_PARTNERS} partner models (unimm_lm_mix mixes at most "
+                         f"{MAX_PARTNERS + 1} rows), got {len(ensemble)}")
+    partners = []
+    for i, m in enumerate(ensemble):
+        p = check_partner(model, m, i + 1)
+        if any(p is q or p._engine is q._engine for q in partners):
+            raise ValueError(f"generate_answers: ensemble member {i + 1} is an earlier member again (or shares its engine): every "
+                             "member keeps its own key/value caches; use policy.frozen_reference for a copy")
+        partners.append(p)
+    K = len(partners) + 1
+    if ensemble_weights is None:
+        w = [1.0 / K] * K
+    else:
+        w = ensemble_weights.tolist() if torch.is_tensor(ensemble_weights) or isinstance(ensemble_weights, np.ndarray) \
+            else list(ensemble_weights)
+        if len(w) != K:
+            raise ValueError(f"generate_answers: {len(w)} ensemble_weights for {K} members (the model's first, then one per partner)")
+        if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) for v in w):
+            raise ValueError(f"generate_answers: ensemble_weights must be finite numbers, got {w!r}")
+        w = [float(v) for v in w]
+    if not w[0] > 0:
+        raise ValueError(f"generate_answers: the model's own weight (ensemble_weights[0]) must be > 0, got {w[0]}")
+    if ensemble_mode == "prob" and (min(w) < 0 or abs(sum(w) - 1.0) > 1e-6):
+        raise ValueError(f"generate_answers: ensemble_mode='prob' mixes probabilities: the weights must be >= 0 and sum to 1 "
+                         f"(within 1e-6), got {w!r}")
+    if a > 0 and (no_repeat_ngram_size or float(np.float32(repetition_penalty)) != 1.0):
+        raise ValueError("generate_answers: plausibility > 0 with no_repeat_ngram_size or repetition_penalty: a ban of the history "
+                         "rules could empty the plausible set; drop the cut, or the rules")
+    log_alpha = float(np.float32(np.log(np.float64(a)))) if a > 0 else float("-inf")
+    return dict(partners=partners, weights=w, mode=ensemble_mode, log_alpha=log_alpha)
+
+
 def new_history(S, width, device="cpu"):
     """The answer history of S hypothesis slots: dict(hist int32 [S, width], len int32 [S]), empty."""
     dev = torch.device(device)
@@ -447,7 +552,8 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
                      image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                      length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                      sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                     draft_accept="match", draft=None, draft_len=4):
+                     ensemble=None, ensemble_weights=None, ensemble_mode="prob", plausibility=0.0, draft_accept="match", draft=None,
+                     draft_len=4):
     """BertForMultiModalPreTraining.generate_answers (see the module docstring) -> GeneratedAnswers on the model's device."""
     check_model(model)                                      # here, before the inputs are staged: nothing reaches the device
     G, T = input_ids.shape
@@ -463,6 +569,8 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
         raise ValueError(f"generate_answers: draft_accept must be 'match' or 'rejection', got {draft_accept!r}")
     if draft is None and draft_accept == "rejection":
         raise ValueError("generate_answers: draft_accept='rejection' is speculative sampling and needs a draft model (draft=...)")
+    ensemble = check_ensemble(model, ensemble, ensemble_weights, ensemble_mode, plausibility, draft, no_repeat_ngram_size,
+                              repetition_penalty)
     if draft is not None:                                   # speculative decoding: refused requests, still on the host
         from .speculative import check_draft
         draft = check_draft(model, draft, draft_len, beams, samples, no_repeat_ngram_size, repetition_penalty, repeat_scope,
@@ -498,13 +606,19 @@ def generate_answers(model, input_ids, image_feat, image_loc, context_len, token
         draft._engine.ensure(model._device())
         return eng._on_text_stream(speculate, eng, draft._engine, inp, c_h, limits, int(draft_len), max_answer_len, min_answer_len,
                                    length_penalty, tuple(int(t) for t in banned_tokens), sampling)
+    if ensemble is not None:                                # every member decodes on an engine of its own
+        ensemble["engines"] = [p._engine for p in ensemble["partners"]]
+        for peng in ensemble["engines"]:
+            peng.ensure(model._device())
     return eng._on_text_stream(_generate, eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty,
-                               tuple(int(t) for t in banned_tokens), sampling, constraints)
+                               tuple(int(t) for t in banned_tokens), sampling, constraints, ensemble)
 
 
 def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, length_penalty, banned_tokens, sampling=None,
-              constraints=None):
-    """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples."""
+              constraints=None, ensemble=None):
+    """The engine's step functions.  `beams` below is the number of hypothesis slots per dialog: the beams, or the samples.
+    ensemble (check_ensemble's dict with the partners' `engines`): one DecodeSide per member, stepped in lockstep on the same
+    tokens; the selection launches then read the rows unimm_lm_mix makes of the members' logits."""
     if sampling is not None:
         beams = sampling["samples"] + sampling["greedy"]
     dev, V = eng.arena.device, eng.cfg.vocab_size
@@ -514,6 +628,28 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
     pre, G, S = side.pre, side.G, side.S
     vals = torch.empty((S, beams), dtype=F32, device=dev)
     tops = torch.empty((S, beams), dtype=torch.int32, device=dev)
+    sides = [side]
+    if ensemble is not None:                               # the partners: the same slots and groups, each on its own engine
+        sides += [p._on_text_stream(DecodeSide, p, inp, c_h, limits, pcap, banned, beams, beams) for p in ensemble["engines"]]
+        # the mixed rows: columns [V, Vpad) stay 0 and are never rewritten -- the mix writes, and the selection kernels read, [0, V)
+        mixed = torch.zeros((S, pre["logits"].shape[1]), dtype=F32, device=dev)
+
+    def on(s, fn, *args):
+        """One entry of a side, a partner's on its engine's text stream (the model's, unless that engine keeps one of its own)."""
+        return fn(*args) if s is side else s.eng._on_text_stream(fn, *args)
+
+    def mix(blocks, rows, flags):
+        from . import mix as MX                            # the extension library: loaded by the calls that mix
+        MX.lm_mix([b[:rows] for b in blocks], ensemble["weights"], ensemble["mode"], V, banned, flags, SEP, ensemble["log_alpha"],
+                  mixed[:rows])
+        return mixed[:rows]
+
+    def step_logits(token, k, flags):
+        """The rows the selection reads at step k >= 1: answer row k-1 and copy row k of every slot through every member."""
+        if ensemble is None:
+            return side.rows(token[:, None], k, [0])
+        return mix([on(s, s.rows, token[:, None], k, [0]) for s in sides], S, flags)
+
     if constraints is not None:                            # the history rules: every launch below is a _hist entry point
         answers = new_history(S, pcap, dev)
         ctx, ctx_len = context_table(inp["input_ids"].to(dev), c_h) if constraints["scope"] == "dialog" else (None, None)
@@ -534,11 +670,13 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
 
     def step(k, parent, token, flags):
         if k == 0:                                         # copy row 0 is the prefill's decoded row
-            topk(pre["logits"], G, flags[::beams].contiguous(), 0)
+            root = flags[::beams].contiguous()
+            topk(pre["logits"] if ensemble is None else mix([s.pre["logits"] for s in sides], G, root), G, root, 0)
             return vals[:G].repeat_interleave(beams, 0), tops[:G].repeat_interleave(beams, 0)
         if k >= 2:                                         # children inherit their parent's cache + its answer row k-2
-            side.reorder(parent)
-        topk(side.rows(token[:, None], k, [0]), S, flags, k, parent, token)   # answer row k-1 and copy row k of every slot
+            for s in sides:
+                on(s, s.reorder, parent)
+        topk(step_logits(token, k, flags), S, flags, k, parent, token)        # answer row k-1 and copy row k of every slot
         return vals, tops
 
     if sampling is None:
@@ -565,10 +703,12 @@ def _generate(eng, inp, c_h, limits, beams, max_answer_len, min_answer_len, leng
 
     def sample_step(k, token, flags):
         if k == 0:                                         # every slot of a dialog draws from the prefill's copy row 0
-            return draw(k, pre["logits"][:, :V].repeat_interleave(beams, 0), flags)
+            root = pre["logits"] if ensemble is None else mix([s.pre["logits"] for s in sides], G, flags[::beams].contiguous())
+            return draw(k, root[:, :V].repeat_interleave(beams, 0), flags)
         if k >= 2:                                         # a slot keeps its own cache: append its answer row k-2 in place
-            side.append_in_place(k - 2)
-        return draw(k, side.rows(token[:, None], k, [0]), flags, token)
+            for s in sides:
+                on(s, s.append_in_place, k - 2)
+        return draw(k, step_logits(token, k, flags), flags, token)
 
     return sample_search(sample_step, G, sampling["samples"], limits, max_answer_len, min_answer_len, length_penalty, device=dev,
                          greedy=sampling["greedy"])

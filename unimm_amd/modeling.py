@@ -407,7 +407,8 @@ class BertForMultiModalPreTraining(nn.Module):
                          image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                          length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                          sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                         draft_accept="match", draft=None, draft_len=4):
+                         ensemble=None, ensemble_weights=None, ensemble_mode="prob", plausibility=0.0, draft_accept="match",
+                         draft=None, draft_len=4):
         """Beam-search answers for the dialogs whose first context_len[g] tokens are `[CLS] caption [SEP] ... q_r [SEP]`, with the
         context and image computed once and a per-layer key/value cache (an extension; unimm_amd/generation.py states the
         semantics).  -> GeneratedAnswers(tokens, lengths, scores, logp).  bf16 engine.
@@ -427,7 +428,14 @@ class BertForMultiModalPreTraining(nn.Module):
         (unimm_amd/speculative.py).  draft_accept="rejection" (with samples >= 1) makes it speculative SAMPLING instead: the draft
         draws its proposals, the model accepts each with probability min(1, P / Q) or draws from the normalised max(0, P - Q)
         (`unimm_lm_spec_verify`), so the answers are distributed exactly as the plain sampling call's and carry step_logp / step_logq
-        (and `.greedy` when asked); `.speculation` then counts per (dialog, draw)."""
+        (and `.greedy` when asked); `.speculation` then counts per (dialog, draw).
+        ensemble = 1 to 4 partner models of either class (their own depth and widths, this model's vocabulary and inputs;
+        policy.frozen_reference(model) for a second copy of the same weights) makes every step decode all members on the same
+        tokens and select from the MIXTURE of their next-token distributions (`unimm_lm_mix`): ensemble_mode="prob" the arithmetic
+        mixture sum_m w_m p_m (ensemble_weights >= 0 summing to 1, this model's first, default uniform), "logit" the log-linear
+        one sum_m w_m x_m with finite weights of any sign -- (1 + b, -b) with plausibility = alpha in (0, 1) is contrastive
+        decoding: ids with p(id) < alpha * max p under THIS model are cut.  Beams, sampling, greedy=True and the step rules work
+        unchanged, the history rules without a cut; step_logp is the log-probability under the normalised mixture."""
         from .generation import generate_answers
         return generate_answers(self, input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids,
                                 image_attention_mask, image_index, beams=beams, max_answer_len=max_answer_len,
@@ -435,7 +443,8 @@ class BertForMultiModalPreTraining(nn.Module):
                                 samples=samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
                                 sample_streams=sample_streams, greedy=greedy, no_repeat_ngram_size=no_repeat_ngram_size,
                                 repetition_penalty=repetition_penalty, repeat_scope=repeat_scope,
-                                draft_accept=draft_accept, draft=draft, draft_len=draft_len)
+                                draft_accept=draft_accept, draft=draft, draft_len=draft_len, ensemble=ensemble,
+                                ensemble_weights=ensemble_weights, ensemble_mode=ensemble_mode, plausibility=plausibility)
 
 
 class VisualDialogEncoder(nn.Module):
@@ -480,7 +489,8 @@ class VisualDialogEncoder(nn.Module):
                          image_attention_mask=None, image_index=None, *, beams=1, max_answer_len=20, min_answer_len=1,
                          length_penalty=0.0, banned_tokens=(0, 101, 103), samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                          sample_streams=None, greedy=False, no_repeat_ngram_size=0, repetition_penalty=1.0, repeat_scope="answer",
-                         draft_accept="match", draft=None, draft_len=4):
+                         ensemble=None, ensemble_weights=None, ensemble_mode="prob", plausibility=0.0, draft_accept="match",
+                         draft=None, draft_len=4):
         """BertForMultiModalPreTraining.generate_answers."""
         return self.bert_pretrained.generate_answers(
             input_ids, image_feat, image_loc, context_len, token_type_ids, position_ids, image_attention_mask, image_index,
@@ -488,7 +498,8 @@ class VisualDialogEncoder(nn.Module):
             banned_tokens=banned_tokens, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
             sample_streams=sample_streams, greedy=greedy, no_repeat_ngram_size=no_repeat_ngram_size,
             repetition_penalty=repetition_penalty, repeat_scope=repeat_scope, draft_accept=draft_accept, draft=draft,
-            draft_len=draft_len)
+            draft_len=draft_len, ensemble=ensemble, ensemble_weights=ensemble_weights, ensemble_mode=ensemble_mode,
+            plausibility=plausibility)
 
     def forward_backward(self, input_ids, image_feat, image_loc, loss_weights, sep_indices=None, sep_len=None, token_type_ids=None,
                          token_position_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
