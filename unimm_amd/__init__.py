@@ -3,6 +3,7 @@
 Drop-in surface (same names / signatures as the reference):
     from unimm_amd import VisualDialogEncoder, BertForMultiModalPreTraining, BertConfig
 """
+from . import reward
 from .config import BertConfig
 from .modeling import BertForMultiModalPreTraining, VisualDialogEncoder
 from .policy import DistillObjective, PolicyObjective, PreferenceObjective, PreferenceTargets, frozen_reference
@@ -10,4 +11,4 @@ from .scoring import SharedContext
 
 __version__ = "0.1.0"
 __all__ = ["BertConfig", "BertForMultiModalPreTraining", "VisualDialogEncoder", "SharedContext", "PolicyObjective",
-           "frozen_reference", "PreferenceObjective", "PreferenceTargets", "DistillObjective"]
+           "frozen_reference", "PreferenceObjective", "PreferenceTargets", "DistillObjective", "reward"]

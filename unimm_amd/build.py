@@ -1,5 +1,6 @@
 """Build libunimm_hip.so (all HIP kernels + the C ABI) in-tree with hipcc for gfx950, and beside it the extension library
-libunimm_mix.so (csrc/mix/, include/unimm_mix.h: ensemble answer generation) the same way.
+libraries libunimm_mix.so (csrc/mix/, include/unimm_mix.h: ensemble answer generation) and libunimm_reward.so (csrc/reward/,
+include/unimm_reward.h: the CIDEr-D consensus reward) the same way.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the .so travels
 to the GPU box with the repo snapshot (it is git-ignored, not gpurun-ignored)."""
@@ -17,6 +18,8 @@ LIB = os.path.join(PKG, "libunimm_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
 MIX_SRC = os.path.join(CSRC, "mix")
 MIX_LIB = os.path.join(PKG, "libunimm_mix.so")
+REWARD_SRC = os.path.join(CSRC, "reward")
+REWARD_LIB = os.path.join(PKG, "libunimm_reward.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 
@@ -47,6 +50,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if force or _stale(obj, [src] + headers):
             jobs.append((src, obj))
     mix_jobs = [(src, mix_obj(src)) for src in sources(MIX_SRC) if force or _stale(mix_obj(src), [src] + mix_headers)]
+    reward_headers = headers + [os.path.join(os.path.dirname(PKG), "include", "unimm_reward.h")]
+    reward_obj = lambda s: os.path.join(OBJ, "reward_" + os.path.basename(s)[:-4] + ".o")     # noqa: E731
+    reward_jobs = [(src, reward_obj(src)) for src in sources(REWARD_SRC) if force or _stale(reward_obj(src), [src] + reward_headers)]
 
     def compile_one(job):
         src, obj = job
@@ -58,7 +64,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print("compiled", os.path.basename(src), file=sys.stderr)
 
     with ThreadPoolExecutor(max_workers=8) as ex:
-        list(ex.map(compile_one, jobs + mix_jobs))
+        list(ex.map(compile_one, jobs + mix_jobs + reward_jobs))
     objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + ".o") for s in sources()]
     if force or jobs or _stale(LIB, objs):
         r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs,
@@ -68,6 +74,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objs = [mix_obj(s) for s in sources(MIX_SRC)]
     if force or mix_jobs or _stale(MIX_LIB, objs):
         r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", MIX_LIB] + objs,
+                           capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n" + r.stderr)
+    objs = [reward_obj(s) for s in sources(REWARD_SRC)]
+    if force or reward_jobs or _stale(REWARD_LIB, objs):
+        r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", REWARD_LIB] + objs,
                            capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n" + r.stderr)

@@ -11,6 +11,29 @@ import torch
 from .harness import scores_to_ranks
 
 
+def cider_d(answers_or_tokens, lengths, reference_tokens, reference_lengths, reference_weights=None, table=None, sigma=6.0):
+    """The generation metric for what `generate_answers` writes: the CIDEr-D consensus (include/unimm_reward.h, computed on the
+    device by `reward.CiderD(table, sigma)`) of every hypothesis with its dialog's references.  answers_or_tokens: a
+    `GeneratedAnswers` (lengths then None) or tokens [G, N, W] / [G, W] with lengths [G, N] / [G]; reference_tokens [G, M, Wr],
+    reference_lengths [G, M], reference_weights [G, M] or None.
+    -> (mean over the present hypotheses (length > 0; NaN without any), the per-hypothesis values, fp32 shaped like lengths)."""
+    from .reward import CiderD
+    if hasattr(answers_or_tokens, "tokens") and hasattr(answers_or_tokens, "lengths"):
+        if lengths is not None:
+            raise ValueError("cider_d: lengths come with the GeneratedAnswers, pass None")
+        answers_or_tokens, lengths = answers_or_tokens.tokens, answers_or_tokens.lengths
+    tokens, lengths = torch.as_tensor(answers_or_tokens), torch.as_tensor(lengths)
+    if tokens.dim() not in (2, 3) or tuple(lengths.shape) != tuple(tokens.shape[:-1]):
+        raise ValueError(f"cider_d: tokens must be [G, N, W] or [G, W] with lengths [G, N] or [G], got {tuple(tokens.shape)} and "
+                         f"{tuple(lengths.shape)}")
+    G, W = tokens.shape[0], tokens.shape[-1]
+    values = CiderD(table, sigma).score(tokens.reshape(G, -1, W), lengths.reshape(G, -1), reference_tokens, reference_lengths,
+                                        reference_weights).view(lengths.shape)
+    present = lengths.to(values.device) > 0
+    mean = float(values[present].double().mean()) if bool(present.any()) else float("nan")
+    return mean, values
+
+
 class SparseGTMetrics:
     def __init__(self):
         self.num_rounds = None

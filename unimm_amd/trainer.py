@@ -28,6 +28,7 @@ import torch
 from . import harness, metrics, ranking
 from .policy import (DistillObjective, PolicyObjective, PreferenceObjective, PreferenceTargets, _pretraining_model, candidate_training_batch,
                      preference_diagnostics, sampled_training_batch, self_critical_advantage, spread)
+from .reward import DeviceReward
 from .scoring import SharedContext
 
 
@@ -163,8 +164,11 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     `batch` holds G dialog contexts: `tokens` / `segments` / `positions` [G, T] with the context `[CLS] caption [SEP] ... q_r
     [SEP]` in the first `context_len[g]` positions, `image_feat` / `image_loc` [G, R, .] and optionally `image_mask` [G, R].
     The model draws `samples` answers per dialog in eval mode (and, for baseline="greedy", its greedy answer);
-    `reward_fn(tokens [G, N, W], lengths [G, N]) -> rewards [G, N]` scores them on the host; the advantage (reward minus the
-    greedy reward, minus the mean of the dialog's other samples for "mean", or the reward itself for None) weighs the
+    `reward_fn(tokens [G, N, W], lengths [G, N]) -> rewards [G, N]` scores them on the host -- or, when `reward_fn` is a
+    `reward.DeviceReward` (`reward.CiderD`), on the device against `batch["reference_tokens"]` [G, M, Wr] /
+    `batch["reference_lengths"]` [G, M] / optionally `batch["reference_weights"]` [G, M] (ValueError before the rollout when a
+    key is missing), samples and greedy baseline alike, and only the [G, N] rewards come to the host; the advantage (reward minus
+    the greedy reward, minus the mean of the dialog's other samples for "mean", or the reward itself for None) weighs the
     `objective` on every token of its answer; mode "ratio" corrects for temperature / top-k / nucleus sampling with the
     tokens' step_logq.  The train-mode step is `forward_backward` on the LM term alone, with the `batch_multiply` /
     `no_sync` / `sync_gradients` cadence of `train_step`.  seed: of the draws (default iter_id).
@@ -195,6 +199,17 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     if shared_context and max_answer_len > 30:
         raise ValueError(f"self_critical_step: shared_context trains answers of at most 30 tokens (64 private rows), got "
                          f"max_answer_len = {max_answer_len}")
+    if isinstance(reward_fn, DeviceReward):
+        missing = [k for k in ("reference_tokens", "reference_lengths") if k not in batch]
+        if missing:
+            raise ValueError(f"self_critical_step: a DeviceReward scores against the batch's references; batch lacks {missing}")
+        refs = (batch["reference_tokens"], batch["reference_lengths"], batch.get("reference_weights"))
+
+        def score(tokens, lengths):              # on the device, as the answers are; only the [G, N] rewards come to the host
+            return reward_fn.score(tokens, lengths, *refs)
+    else:
+        def score(tokens, lengths):
+            return reward_fn(tokens.cpu(), lengths.cpu())
     model = _unwrap(dialog_encoder)
     T = batch["tokens"].shape[1]
     gen_args = (batch["tokens"], batch["image_feat"], batch["image_loc"], batch["context_len"])
@@ -206,10 +221,10 @@ def self_critical_step(dialog_encoder, optimizer, scheduler, batch, params, iter
     answers = model.generate_answers(*gen_args, samples=samples, temperature=temperature, top_k=top_k, top_p=top_p,
                                      seed=iter_id if seed is None else seed, **(dict(greedy=True) if fused else {}),
                                      **(dict(spec, draft_accept="rejection") if spec else {}), **gen_kw)
-    rewards = torch.as_tensor(reward_fn(answers.tokens.cpu(), answers.lengths.cpu())).to("cpu", torch.float32)
+    rewards = torch.as_tensor(score(answers.tokens, answers.lengths)).to("cpu", torch.float32)
     if greedy_baseline:
         greedy = answers.greedy if fused else model.generate_answers(*gen_args, beams=1, **spec, **gen_kw)
-        base = torch.as_tensor(reward_fn(greedy.tokens.cpu(), greedy.lengths.cpu())).to("cpu", torch.float32).reshape(-1)
+        base = torch.as_tensor(score(greedy.tokens, greedy.lengths)).to("cpu", torch.float32).reshape(-1)
     else:
         base = baseline
     advantage = self_critical_advantage(rewards, base)
