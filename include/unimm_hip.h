@@ -703,7 +703,9 @@ int unimm_nsp_loss_fwd(const float* logits, const int32_t* labels, float w0, flo
 int unimm_nsp_loss_bwd(const float* logits, const int32_t* labels, float w0, float w1, const float* g, const float* extra,
                        float* dlogits, int32_t B, int32_t ld, int32_t ldd, void* stream);
 /* dst[0] = scale * sum(src) (fixed order, deterministic); dst[seg[i]] += sign * src[i].  n_dev (or NULL): only src[0 .. min(n, *n_dev))
- * is read; scale_dev (or NULL): a device word that replaces scale */
+ * is read; scale_dev (or NULL): a device word that replaces scale.  segment_sum adds the entries of a segment that follow one
+ * another in index order and hands each such run (cut at every 256th entry) to dst with one atomic: segments listed together
+ * and no longer than 256 entries -- the per-sequence scores -- come out the same bits in every launch */
 int unimm_reduce_sum(const float* src, int64_t n, float* dst, float scale, const int32_t* n_dev, const float* scale_dev,
                      void* stream);
 int unimm_segment_sum(const float* src, const int32_t* seg, float* dst, int64_t n, float sign, void* stream);

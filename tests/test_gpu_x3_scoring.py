@@ -111,7 +111,8 @@ def test_shared_context_scoring_fp32x3(small, T):
     assert float((got_h - got).abs().max()) <= 1e-4 and float((nsp_h - nsp).abs().max()) <= 1e-4
     # a context that is not shared is reported, not silently scored against the wrong rows; nothing else changes.  "Nothing" is
     # asserted bit for bit where the arithmetic has a fixed order: the log-likelihoods of the decoded rows.  A score is the sum of
-    # its sequence's n <= 15 rows by fp32 atomic adds (unimm_segment_sum), whose order differs from launch to launch: two orders
+    # its sequence's n <= 15 rows (unimm_segment_sum: in row order since tests/test_gpu_information_flow.py, by one fp32 atomic per
+    # row in arrival order when this bound was set): two orders
     # of n terms of one sign differ by less than n 2^-23 |score| (each rounds n - 1 times, by at most 2^-24 of a partial sum <= |score|)
     slack = n.to(got) * 2.0 ** -23 * got.abs()
     def only_nan_at(ids, loc, i):

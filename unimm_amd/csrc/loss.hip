@@ -277,10 +277,21 @@ __global__ __launch_bounds__(256) void reduce_sum_kernel(const float* __restrict
 }
 
 // dst[seg[i]] += sign * src[i]   (per-sequence log-likelihood: val_lm.py:133-136)
+// Entries of one segment that follow one another inside a block's 256 are added in index order by the thread of the first of
+// them, and that run reaches dst with ONE atomic.  Both callers list a sequence's rows together, at most 256 of them (T <= 256),
+// so a sequence is one or two runs and its score onto a zeroed dst is the same bits in every launch (a + b = b + a); with an
+// atomic per entry the score of a sequence with three or more rows depended on the order in which the threads arrived.
 __global__ void segment_sum_kernel(const float* __restrict__ src, const int32_t* __restrict__ seg, float* __restrict__ dst,
                                    int64_t n, float sign) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) atomicAdd(dst + seg[i], sign * src[i]);
+  if (i >= n) return;
+  const int32_t s = seg[i];
+  if (threadIdx.x != 0 && seg[i - 1] == s) return;                 // not the first of its run
+  int64_t end = ((int64_t)blockIdx.x + 1) * blockDim.x;
+  end = end < n ? end : n;
+  float acc = 0.f;
+  for (int64_t j = i; j < end && seg[j] == s; ++j) acc += sign * src[j];
+  atomicAdd(dst + s, acc);
 }
 
 }  // namespace
